@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of the full DCGAN G+D training step (train/dcgan_trainer.py:155-189 of the
 reference), 64x64x3 synthetic images, batch 256 per GPU, on the MI355X-native HIP path.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,8 +12,12 @@ A "step" = one pass of the hot path over one synthetic batch already resident in
 (instance noise x2, z, GP alpha), four D passes, one G pass, five backward chains, two Adam steps.  Every kernel is
 launched from the host on two HIP streams (JCK_GRAPH=1 replays the step from captured hipGraphs instead: one host call per
 step segment, but a captured step is one stream - `launch_mode` and `host_enqueue_ms_per_step` say which ran).
-With one GPU the same line carries `secondary.cgan`: BASELINE.json configs[3] (CGAN, 10-class labels, batch 256, the
-penalty back-propagated) measured the same way in the same process.
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the result line.  `--full` adds
+the legs that take runs of their own: the per-kernel roofline profile, the data-parallel cost legs (N > 1) and, with one GPU,
+`secondary.cgan` (BASELINE.json configs[3]: CGAN, 10-class labels, batch 256, the penalty back-propagated), `secondary.f32`,
+`secondary.size128` and `cpu_baseline`, each measured the same way in the same process.
+`--dump-outputs DIR` writes what the last timed step computed (step scalars, G / D state, G's images) to DIR as .npy files;
+with the same arguments the inputs are the same in every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -152,8 +156,40 @@ def cpu_baseline(batch, seconds_budget=30.0):
                       f"(oracle/gan_oracle.py), anomaly detection off"}
 
 
-def measure(a, model, world, rank, dev, dist):
-    """Warm-up, the timed region, the per-launch profile of the MFMA kernels; -> dict (rank 0 fills the roofline)."""
+DUMP_LIMIT_BYTES = 60_000_000     # --dump-outputs: the arrays together (64 MB with room for the .npy headers)
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(eng, scal, out_dir):
+    """What the timed step handed its caller in the last timed step, as float32 / float64 .npy files in `out_dir`: the eight step
+    scalars (scalar.<name>), G's and D's state after the step (G.<key> / D.<key>, the reference's state-dict keys; BatchNorm step
+    counts as float64) and G's output images of the step (fake, NCHW).  Past DUMP_LIMIT_BYTES the largest arrays are replaced by a
+    fixed, seeded sample of their flattened elements (the same indices in every run).  -> (files, bytes)."""
+    import numpy as np
+    arrays = [(f"scalar.{k}", np.asarray([v], dtype=np.float32)) for k, v in scal.items()]
+    for tag, sd in zip(("G", "D"), eng.state_dicts()):
+        for k, v in sd.items():
+            arrays.append((f"{tag}.{k}", v.numpy().astype(np.float32 if v.is_floating_point() else np.float64)))
+    S = eng.size
+    fake = eng.tensor("fake_raw").float().view(eng.batch, S, S, -1)[..., :3].permute(0, 3, 1, 2).contiguous()
+    arrays.append(("fake", fake.cpu().numpy()))
+    keep = max(a.size for _, a in arrays)
+    while sum(min(a.size, keep) * a.itemsize for _, a in arrays) > DUMP_LIMIT_BYTES:
+        keep //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, arr in arrays:
+        if arr.size > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(arr.size, keep, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    return len(arrays), total
+
+
+def measure(a, model, world, rank, dev, dist, dump_dir=None):
+    """Warm-up, the timed region, [--dump-outputs: the last timed step's outputs]; with --full also the per-launch profile of
+    the MFMA kernels and the data-parallel legs; -> dict (rank 0 fills the roofline)."""
     import torch
     from hipgan import lib
     from hipgan.dist import GradReducer
@@ -268,6 +304,10 @@ def measure(a, model, world, rank, dev, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     scal = eng.scalars()
+    if dump_dir and rank == 0:
+        # before anything below runs another step: these are the outputs of the last TIMED step
+        files, nbytes = dump_outputs(eng, scal, dump_dir)
+        print(f"bench.py: wrote {files} arrays ({nbytes / 1e6:.1f} MB) to {dump_dir}", file=sys.stderr, flush=True)
     ms = dt / a.steps * 1e3
     fl = step_flops_per_image() * B
     if S == 128:
@@ -281,6 +321,14 @@ def measure(a, model, world, rank, dev, dist):
            "step_mfma": {"flops_per_step": fl, "achieved_tflops": round(fl / (ms * 1e-3) / 1e12, 2),
                          "frac_of_peak": round(fl / (ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)}}
     if red:
+        ddp["rccl_world"] = dist.get_world_size() if dist else 1
+        ddp["backend"] = dist.get_backend() if dist else None
+        # who runs the all-reduce: torch.distributed's ProcessGroupNCCL (default) or the library's own RCCL communicator behind the
+        # C ABI (JCK_RCCL_NATIVE=1: include/jckgan.h jck_comm_*)
+        ddp["collective"] = "jck_comm_* (RCCL behind the C ABI)" if getattr(red, "_comm", None) is not None else "torch.distributed.all_reduce"
+        ddp["message_bytes"] = {"d": int(eng.arenas["d_grads"].numel()) * 4, "g": int(eng.arenas["g_grads"].numel()) * 4}
+        res["ddp"] = ddp
+    if red and a.full:
         # what the collectives cost (every rank runs these legs; after the timed region, which stays exactly K steps):
         #   comm_exposed_ms   HIP events around the waits in front of Adam(D) / Adam(G), mean over 5 steps and max over ranks
         #   n1_equivalent_ms  the same step with the reducers off (what one GPU of this node does alone); DESIGN.md section 6's
@@ -312,13 +360,6 @@ def measure(a, model, world, rank, dev, dist):
             dist.all_reduce(tn1, op=dist.ReduceOp.MAX)
         use_red["on"] = True
         ddp["n1_equivalent_ms"] = round(float(tn1[0]), 4)
-        ddp["rccl_world"] = dist.get_world_size() if dist else 1
-        ddp["backend"] = dist.get_backend() if dist else None
-        # who runs the all-reduce: torch.distributed's ProcessGroupNCCL (default) or the library's own RCCL communicator behind the
-        # C ABI (JCK_RCCL_NATIVE=1: include/jckgan.h jck_comm_*)
-        ddp["collective"] = "jck_comm_* (RCCL behind the C ABI)" if getattr(red, "_comm", None) is not None else "torch.distributed.all_reduce"
-        ddp["message_bytes"] = {"d": int(eng.arenas["d_grads"].numel()) * 4, "g": int(eng.arenas["g_grads"].numel()) * 4}
-        res["ddp"] = ddp
     if not a.no_roofline:
         # every rank runs the three extra steps (they contain the gradient all-reduce); rank 0 times its launches with HIP
         # events on the launch streams - which needs every launch to come from the host, so these steps are not replayed
@@ -441,10 +482,18 @@ def main():
     ap.add_argument("--input", default="tensor", choices=["tensor", "u8"],
                     help="tensor: fp32 NCHW batches resident in HBM (default); u8: index batches into a uint8 32x32 dataset "
                          "resident in HBM, Resize/ToTensor/Normalize done inside the step (the training pipeline's form)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the CGAN (configs[3]) measurement of the one-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the per-kernel roofline profile, the one-GPU run's "
+                         "secondary measurements (CGAN, fp32, 128x128) and CPU baseline, and the data-parallel cost legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (step scalars, G / D state, G's images) as .npy files to DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline profile")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements of the one-GPU run")
     a = ap.parse_args()
+    if not a.full:
+        # a plain run sets up, warms up, times the steps and reports them: nothing else runs
+        a.no_cpu_baseline = a.no_roofline = a.no_secondary = True
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts the N ranks itself and never touches the GPU
@@ -479,7 +528,7 @@ def main():
     dev = torch.device("cuda", local)
     B = a.batch
     cgan = a.model == "cgan"
-    res = measure(a, a.model, world, rank, dev, dist)
+    res = measure(a, a.model, world, rank, dev, dist, dump_dir=a.dump_outputs)
     out = {"metric": "images/sec (G+D step) DCGAN 64x64 bs256" if not cgan else "images/sec (G+D step) CGAN 64x64 bs256",
            "value": res.pop("value"), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
            "host_enqueue_ms_per_step": res.pop("host_enqueue_ms_per_step"), "ms_per_step": res.pop("ms_per_step"),

@@ -11,6 +11,8 @@ Tolerances (relative):
       bf16-storage emulation of the oracle - see tests/test_bf16_envelope.py, which also holds the free-running trajectory
       and the run-to-run determinism; tests/test_trainer_gpu.py holds the bf16 trainer's first step to the fixture recorded
       from the reference's own trainer at 1e-2."""
+import contextlib
+
 import pytest
 import torch
 
@@ -33,7 +35,29 @@ def mnist_shaped(n):
     return (x - 0.5) / 0.5
 
 
+ORACLE_THREADS = 1
+
+
+@contextlib.contextmanager
+def _oracle_threads(n):
+    saved = torch.get_num_threads()
+    torch.set_num_threads(n)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(saved)
+
+
 def _run(B, steps, prec, lr=2e-4, teacher_forced=True, images=None):
+    """The oracle runs free and the engine restarts from its state at every step (teacher forcing), so the state a later step
+    is compared at is the oracle's own trajectory - and the CPU summation order, which follows torch's thread count, moves that
+    trajectory (not one step's arithmetic: ~1e-6).  The oracle runs on ORACLE_THREADS threads whatever the machine offers, so
+    every machine compares the same states."""
+    with _oracle_threads(ORACLE_THREADS):
+        return _run_pinned(B, steps, prec, lr, teacher_forced, images)
+
+
+def _run_pinned(B, steps, prec, lr, teacher_forced, images):
     from hipgan.engine import DcganEngine
     from oracle.gan_oracle import GanOracle
     from util import synth_images
