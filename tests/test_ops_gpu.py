@@ -596,6 +596,3 @@ def test_grouped_forward_statistics(G, cfg):
         r = ref[k * gimg:(k + 1) * gimg].double()
         G.check(rows[k, :, 0].sum(0), r.sum((0, 2, 3)), 2e-3, f"sum, group {k}")
         G.check(rows[k, :, 1].sum(0), (r * r).sum((0, 2, 3)), 2e-3, f"sum of squares, group {k}")
-
-
-# ---- BatchNorm statistics as exact integer-atomic sums (csrc/bnstat.hpp): the `_x` entry points -------------------------------

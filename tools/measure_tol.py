@@ -23,7 +23,8 @@ real = synth_images(B)
 g = torch.Generator().manual_seed(77)
 lab = torch.nn.functional.one_hot(torch.randint(0, 10, (B,), generator=g), 100).to(torch.int64)
 nz = Cg._noise(B, 900, lab)
-ref = orc.step(real, lab, nz)
+with T._oracle_threads(Cg.ORACLE_THREADS):     # as the test runs it
+    ref = orc.step(real, lab, nz)
 got = eng.step(real.cuda(), {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in nz.items()}, lr=2e-4)
 for tag, refs in (("d", orc.d_grads), ("g", orc.g_grads)):
     v = eng.named_views(tag, "grads")
