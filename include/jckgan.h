@@ -398,8 +398,9 @@ int jck_engine_capture_abort(jck_engine*, void* stream);
 int jck_graph_launch(void* graph_exec, void* stream);
 void jck_graph_destroy(void* graph_exec);
 
-/* Kernel-selection knob (same names as the JCK_<KEY> environment presets, lower case: "igemm_256", "wgrad_gt", ...): lets
- * one process A/B two variants on one device and lets a test force a variant at a small shape.  Unknown key -> JCK_E_ARG. */
+/* Kernel-selection knob (same names as the JCK_<KEY> environment presets, lower case): "bn_res", "bn_bwd_fuse",
+ * "igemm_dma_ksplit", "wgrad_ws", "wgrad_dma", "wgrad_wgs".  Lets a test force a variant at a small shape.
+ * Unknown key -> JCK_E_ARG. */
 int jck_tune(const char* key, int value);
 /* per-launch HIP-event timing of the MFMA kernels (bench.py roofline leg).  enable(1) ... run ... collect():
  * per (kernel variant, HIP stream the launches ran on): launches, total milliseconds, total algorithmic FLOPs, total algorithmic
@@ -411,13 +412,6 @@ int jck_prof_collect(int cap, const char** name_out, int* count_out, double* ms_
 /* debug probe: lane l of one wave returns the 8 elements wgrad's transposed LDS read hands it from a
  * [32][ld] 16-bit tile: out[l*8+j] must equal in[(8*(l>>4)+j)*ld + (l&15)] */
 int jck_debug_tr_read(const void* in, int ld, void* out, void* stream);
-/* development aid: the resident BatchNorm launches write [256][8] s_memrealtime stamps (uint64) of their workgroup leaders to buf
- * (device memory; NULL switches it off) */
-int jck_debug_bnres_stamps(void* buf);
-/* development probe: per-wave s_memtime totals {wait+barrier, DMA issue, LDS reads+MFMA, whole kernel} of the last
- * weight-gradient launch made with JCK_WGRAD_STAMP=1 (n = number of 64-bit values to copy, 4 per wave, 8 waves per workgroup
- * slot, first 1024 workgroups); synchronises the device */
-int jck_debug_wgrad_stamps(unsigned long long* out, int n);
 
 /* ---- RCCL gradient all-reduce {init, enqueue, wait} ------------------------------------------------------------------------
  * The reference's multi-GPU form is DistributedDataParallel around G and D: what optimizer_d.step() / optimizer_g.step() consume

@@ -44,7 +44,6 @@ struct BnResParams {
   float* sums; long long sums_stride;   // [groups][stride]: s1 | s2 (2C), then the partial rows (nb * 128 floats)
   float* dgamma; float* dbeta;    // += over groups < grad_groups (may be null)
   unsigned* sync;
-  unsigned long long* stamps;     // debug: [nb][8] s_memrealtime stamps of workgroup leaders (null in production)
   long long rows;                 // per group
   int C, groups, grad_groups, nb, nsl;
   float slope, inv_count;
@@ -94,8 +93,6 @@ __device__ __forceinline__ unsigned bnres_off(unsigned voff0, unsigned kstep, in
   return o < gbytes ? (unsigned)o : JCK_OOB;
 }
 
-#define BNRES_STAMP(i) do { if (p.stamps && threadIdx.x == 0) p.stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-
 template <int NCH, int NG>
 __global__ __launch_bounds__(BNRES_THREADS) void bn_bwd_res_kernel(const BnResParams p) {
   __shared__ __attribute__((aligned(16))) float sm_wave[NG][8][128];   // per-wave partial rows, later the totals in [j][0]
@@ -105,7 +102,6 @@ __global__ __launch_bounds__(BNRES_THREADS) void bn_bwd_res_kernel(const BnResPa
   __shared__ int sm_ok;
   const int C = p.C, nsl = p.nsl, nbs = p.nb / nsl;
   const int slice = blockIdx.x % nsl, wslot = blockIdx.x / nsl;
-  BNRES_STAMP(0);
   unsigned gen0 = 0;
   if (threadIdx.x == 0) {
     gen0 = bnres_ld(p.sync + BNRES_W_GEN * 32);
@@ -190,7 +186,6 @@ __global__ __launch_bounds__(BNRES_THREADS) void bn_bwd_res_kernel(const BnResPa
         for (int i = 0; i < 8; ++i) { sm_wave[j][wave][lane * 8 + i] = s1[i]; sm_wave[j][wave][64 + lane * 8 + i] = s2[i]; }
       }
     }
-    if (g0 == 0) BNRES_STAMP(1);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < NG; ++j) {
@@ -203,10 +198,8 @@ __global__ __launch_bounds__(BNRES_THREADS) void bn_bwd_res_kernel(const BnResPa
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (g0 == 0) BNRES_STAMP(2);
     // ---- grid barrier (a timeout is recorded in the error word; the launch runs on)
     bnres_grid_sync(p.sync, gen0 + (++phase), p.nb, &sm_ok);
-    if (g0 == 0) BNRES_STAMP(3);
     // ---- totals of this slice: nbs rows of 128 floats per group, 16 row lanes x 32 float4 columns, fixed order; the loads of
     // a thread are independent (four rows in flight): a dependent chain of 16 row loads cost 5.8 us at C = 64
 #pragma unroll
@@ -252,7 +245,6 @@ __global__ __launch_bounds__(BNRES_THREADS) void bn_bwd_res_kernel(const BnResPa
       }
     }
     __syncthreads();
-    if (g0 == 0) BNRES_STAMP(4);
     // ---- phase 2: apply to the resident chunks, store, and refill the registers with the next batch of groups
     // (the chunk's registers pass through an asm statement again: otherwise the compiler keeps phase 1's unpacked g_z and
     // y - mean alive across the barrier as fp32 - four times the resident bytes - instead of recomputing them)
@@ -297,7 +289,6 @@ __global__ __launch_bounds__(BNRES_THREADS) void bn_bwd_res_kernel(const BnResPa
       }
     }
   }
-  if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); BNRES_STAMP(5); }
   if (wslot == 0 && threadIdx.x < 64) {
     const int c = slice * 64 + threadIdx.x;
     if (p.dgamma) p.dgamma[c] += sm_grad[0][threadIdx.x];

@@ -59,8 +59,8 @@ Topo make_topo(int S) {
   return T;
 }
 const int N_CLASS = 100, EMB = 200, L1_OUT = 256, L1_FEAT = 8192, L1_K = L1_FEAT + EMB, L1_KPAD = 8448;   // model/CGAN.py:83,104
-// split-K of Linear(8392, 256): 132 k-steps of 64 over L1_KSPLIT workgroups per tile (a divisor of 132; JCK_L1_KSPLIT to A/B)
-static const int L1_KSPLIT = [] { const char* v = getenv("JCK_L1_KSPLIT"); const int k = v ? atoi(v) : 12; return (k > 0 && 132 % k == 0) ? k : 12; }();
+// split-K of Linear(8392, 256): 132 k-steps of 64 over L1_KSPLIT workgroups per tile (a divisor of 132; hipgan/functional.py uses the same)
+constexpr int L1_KSPLIT = 12;
 inline int z_dim(int family) { return family == 1 ? 200 : 100; }      // model/CGAN.py:132: ConvTranspose2d(200, 512)
 inline int z_pad(int family) { return family == 1 ? 256 : 128; }
 
@@ -916,10 +916,8 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
   JCK_TRY(jck_linear_wgrad(e->prec, gh1, L1_OUT, e->cbuf2, L1_KPAD, e->wg_ws, e->wg_ws_bytes, e->gw1p, 1, B, L1_OUT, fork(0)));
   // What the reverse sweep must wait for are the v-chain's products (they read the v_i it overwrites): the weight-gradient stream is
   // marked HERE, behind the last of them - not after the head's parameter gradients, which are forked to it below and which nothing
-  // on the main stream waits for before the optimiser (JCK_GP_NARROW_JOIN=0: the join covers them too)
-  static const bool narrow_join = !(getenv("JCK_GP_NARROW_JOIN") && atoi(getenv("JCK_GP_NARROW_JOIN")) == 0);
-  const bool narrow = side && narrow_join;
-  if (narrow) (void)hipEventRecord(e->evGP, side);
+  // on the main stream waits for before the optimiser
+  if (side) (void)hipEventRecord(e->evGP, side);
   JCK_TRY(jck_linear_fwd(e->prec, e->cbuf2, e->l1_w, nullptr, e->l1_slab, B, L1_KPAD, L1_OUT, L1_OUT, L1_KSPLIT, st));
   const bool fuse = e->head_fuse && L1_OUT == 256;    // the next four launches as one (ops.hip: gp_head_mid_ev)
   if (!fuse) JCK_TRY(jck_linear_finish(e->prec, e->l1_slab, L1_KSPLIT, nullptr, drop_mask, 1.0f / 0.75f, nullptr, e->ughd, B, L1_OUT, st));
@@ -937,7 +935,7 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
     JCK_TRY(gp_head2_ev(e->prec, e->ughd, e->P(e->LD, e->dp, "linear2.weight"), prob1, B, L1_OUT, e->rs,
                         e->P(e->LD, e->dg, "linear2.weight"), e->gp2_ws, st, hs, hs ? e->evHead : nullptr));
   // ---- reverse sweep through the forward pass from the logit adjoint rs, with the extra BatchNorm inputs
-  if (narrow) (void)hipStreamWaitEvent(st, e->evGP, 0); else join();
+  if (side) (void)hipStreamWaitEvent(st, e->evGP, 0); else join();
   JCK_TRY(d_head_backward(e, e->dset[0], e->rs, B, true, drop_mask, e->d_v[TT.NS - 1], st, hs, fuse));
   // the last sum into the permuted Linear gradient is enqueued: back to the reference's layout, on the stream that holds it
   JCK_TRY(jck_unperm_linear_grad(e->gw1p, L1_OUT, L1_K, L1_KPAD, 512, 16, e->P(e->LD, e->dg, "linear1.weight"), 1, hs ? hs : st));
@@ -1437,7 +1435,6 @@ static int set_step_impl(jck_engine* e, int step, float lr, void* stream, bool z
   if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "engine not bound");
   if (e->capturing) JCK_FAIL(JCK_E_ARG, "set_step inside a graph capture would bake one step's scalars into the graph");
   const int q = step & 1;
-  static const bool fold_z = !(getenv("JCK_FOLD_Z") && atoi(getenv("JCK_FOLD_Z")) == 0);      // (=0: pad_rows_kernel in front of G's forward)
   zero_d = zero_d && e->fold_zero && e->LD.n_params % 4 == 0;
   JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, 0.5, 0.999, step, e->noise_seed, (hipStream_t)stream, e->rz[q], (long long)e->B * 100,
                             e->ralpha[q], e->B, e->rmask[q], e->rmask[q] ? (long long)4 * e->B * L1_OUT : 0, 0.75f,
@@ -1445,8 +1442,8 @@ static int set_step_impl(jck_engine* e, int step, float lr, void* stream, bool z
                             zero_d ? e->dg : nullptr, e->LD.n_params, zero_d && e->family == 1 ? e->gw1p : nullptr, (long long)L1_OUT * L1_KPAD,
                             // DCGAN: the drawn z goes straight into G.conv1's operand rows too (no pad_rows launch in front of G's forward
                             // when the step uses the engine's own z)
-                            e->family == 0 && e->fold_zero && fold_z ? e->g_z : nullptr, 100, z_pad(e->family), e->prec == JCK_PREC_F32 ? 1 : 0));
-  e->gz_step = (e->family == 0 && e->fold_zero && fold_z) ? step : -1;
+                            e->family == 0 && e->fold_zero ? e->g_z : nullptr, 100, z_pad(e->family), e->prec == JCK_PREC_F32 ? 1 : 0));
+  e->gz_step = (e->family == 0 && e->fold_zero) ? step : -1;
   if (zero_d) e->dg_clean_step = step;
   e->acc_clean_step = step;
   e->hp_step[step & 1] = step;

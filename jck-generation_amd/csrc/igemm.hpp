@@ -55,7 +55,6 @@ struct IgemmParams {
   // forward statistics accumulated per workgroup and BatchNorm group by the persistent kernels (rows [group][rank][2][cstat])
   // instead of one row per (tile, wave); set by the launcher for the *_grouped entry points
   int stat_accum;
-  int loader_prio;        // persistent kernels: s_setprio of the loader waves (jck_tune "igemm_prio")
   double flops;           // algorithmic FLOPs of this launch (profiling only)
 };
 
@@ -541,7 +540,7 @@ __device__ __forceinline__ void igemm_wg_row(float* sx, unsigned* scnt, int wave
     if (ch < nch_store) row[(r >> 3) * cstat + (ch & (cstat - 1)) + (r & 7)] = t;
   }
 }
-template <int BCH, int BPIX, int FM, int FN, int WPIXN, bool NOSTORE = false>
+template <int BCH, int BPIX, int FM, int FN, int WPIXN>
 __device__ __forceinline__ void igemm_epilogue_perm(const IgemmParams& p, f32x4 (&acc)[FM][FN], int lane, int wch, int wpix, int z,
                                                     int bidx, int bidy, int m0, int ch0, bool tile_stats, float* sx, unsigned* scnt) {
   static_assert(FM % 2 == 0, "fragment pairs");
@@ -559,7 +558,6 @@ __device__ __forceinline__ void igemm_epilogue_perm(const IgemmParams& p, f32x4 
       if (ch >= p.NchStore) continue;
       const float v[8] = {acc[2 * k][j][0], acc[2 * k][j][1], acc[2 * k][j][2], acc[2 * k][j][3],
                           acc[2 * k + 1][j][0], acc[2 * k + 1][j][1], acc[2 * k + 1][j][2], acc[2 * k + 1][j][3]};
-      if constexpr (NOSTORE) asm volatile("" :: "v"(v[0]), "v"(v[7])); else
       st8(outp + off + ch, v);
     }
   }
@@ -589,17 +587,13 @@ __device__ __forceinline__ void igemm_epilogue_perm(const IgemmParams& p, f32x4 
 // the same results.  Forward statistics (p.stat_accum) are accumulated per workgroup and BatchNorm group.
 // Both roles execute exactly (tiles of this workgroup) x (K / 64) barriers.
 // ------------------------------------------------------------------------------------------------------------------
-template <int BCH, int BPIX, int NCW, int ADIV = 1>
+template <int BCH, int BPIX, int NCW>
 __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const IgemmParams p) {
   typedef PrecBf16 P;
   typedef IgemmCfg<P, BCH, BPIX, NCW> C;
   constexpr int FM = C::FM, FN = C::FN, LD = IG_BK;
   constexpr int STG_BYTES = (BCH + BPIX) * LD * 2;
-  // ADIV != 1: TIMING EXPERIMENTS ONLY (wrong results): 2 / 4 = part of the gather skipped; 101 no loads, 102 no MFMAs, 103 no epilogue, 104 barriers only
-  constexpr bool NOLOAD = ADIV == 101 || ADIV == 104 || ADIV == 108, NOMFMA = ADIV == 102 || ADIV == 104, NOEPI = ADIV == 103 || ADIV == 104 || ADIV == 108;
-  constexpr bool NOSTORE = ADIV == 105, NOSTAT = ADIV == 106, NOREAD = ADIV == 107 || ADIV == 108;
-  constexpr int AD = ADIV > 100 ? 1 : ADIV;
-  constexpr int NLD = NOLOAD ? 0 : (BCH + BPIX / AD) / 32;
+  constexpr int NLD = (BCH + BPIX) / 32;                            // DMA wave-instructions per stage and wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned char* lds = smem_raw;
 
@@ -630,7 +624,7 @@ __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const
   if (loader) {
     // the loader waves are the younger half of the workgroup and lose the issue arbitration at equal priority (MI355X guide, "Two
     // waves per SIMD", item 4); the kernel is bound by how fast they issue their pieces: +0.3..3 % per launch alone, neutral in the step
-    if (p.loader_prio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     const int lrow = (tid & 255) >> 3, unit = tid & 7;
     const unsigned src_chunk = (unsigned)(unit ^ ((lrow >> 1) & 7)) * 16u;
     unsigned rowoff[C::APASS], wrowoff[C::WPASS];
@@ -658,7 +652,6 @@ __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const
     const auto rs_a = make_rsrc(p.act, p.act_bytes);
     const auto rs_wt = make_rsrc(p.w, p.w_bytes);
     auto issue = [&](int kc, int stage) {
-      if constexpr (NOLOAD) return;
       const int kbase = kc * IG_BK;
       unsigned char* sb = lds + stage * STG_BYTES + (wave & 3) * (8 * LD * 2);
 #pragma unroll
@@ -670,7 +663,7 @@ __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const
       const int dyv = tp >> 16, dxv = (int)(short)(tp & 0xffff);
       const unsigned toffb = (unsigned)((((dyv * p.W + dxv) << p.logC) + (kbase & (Cc - 1))) * 2);
 #pragma unroll
-      for (int ps = 0; ps < C::APASS / AD; ++ps) {
+      for (int ps = 0; ps < C::APASS; ++ps) {
         const bool ok = (unsigned)(riy[ps] + dyv) < (unsigned)p.H && (unsigned)(rix[ps] + dxv) < (unsigned)p.W;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lptr_t)(sb + (BCH + ps * 32) * (LD * 2)), 16,
                                                  (int)(ok ? rowoff[ps] + toffb + src_chunk : JCK_OOB), 0, 0, 0);
@@ -691,10 +684,6 @@ __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const
       if constexpr (NLD == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else if constexpr (NLD == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
       else if constexpr (NLD == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else if constexpr (NLD == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else if constexpr (NLD == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else if constexpr (NLD == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else if constexpr (NLD == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else static_assert(NLD == 8 || NLD == 6 || NLD == 12, "add the vmcnt literal");
     };
     for (int s = 0; s < steps; ++s) {
@@ -776,13 +765,6 @@ __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const
       bf16x8 a0[FM], b0[FN], a1[FM], b1[FN];
       auto rd = [&](bf16x8 (&a)[FM], bf16x8 (&b)[FN], int sl, int col) __attribute__((always_inline)) {
         const unsigned char* base = lds + sl * STG_BYTES + col;
-        if constexpr (NOREAD) {
-#pragma unroll
-          for (int j = 0; j < FN; ++j) asm volatile("" : "=v"(b[j]));
-#pragma unroll
-          for (int i = 0; i < FM; ++i) asm volatile("" : "=v"(a[i]));
-          return;
-        }
 #pragma unroll
         for (int j = 0; j < FN; ++j) b[j] = lds_frag(reinterpret_cast<const bf16_t*>(base + offB + j * 16 * LD * 2));
 #pragma unroll
@@ -792,10 +774,7 @@ __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
-          for (int j = 0; j < FN; ++j) {
-            if constexpr (NOMFMA) asm volatile("" :: "v"(a[i]), "v"(b[j]));
-            else acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
-          }
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
       };
       // one read, then MFMAs, ... : a burst of 8 reads per wave, issued by all 8 waves at the same moment behind the barrier, fills the
       // LDS queue and the wave sits at its next ds_read instead of issuing the MFMAs behind it
@@ -831,14 +810,8 @@ __global__ __launch_bounds__((NCW + 4) * 64) void igemm_dma_persist_kernel(const
     }
     const int grp = (acc_stats && p.bn_group_rows > 0) ? m0 / p.bn_group_rows : 0;
     if (acc_stats && grp != cur_group) stat_switch(grp);
-    if constexpr (NOEPI) {
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) asm volatile("" :: "v"(acc[i][j]));
-    } else
-    igemm_epilogue_perm<BCH, BPIX, FM, FN, C::WPIX, NOSTORE>(p, acc, lane, wch, wpix, z, bidx, bidy, m0, ch0, !acc_stats && !NOSTAT, sx, scnt);
-    if (acc_stats && !NOEPI && !NOSTAT) {     // rows past M and taps outside the image contributed zeros to acc: no masks needed
+    igemm_epilogue_perm<BCH, BPIX, FM, FN, C::WPIX>(p, acc, lane, wch, wpix, z, bidx, bidy, m0, ch0, !acc_stats, sx, scnt);
+    if (acc_stats) {     // rows past M and taps outside the image contributed zeros to acc: no masks needed
 #pragma unroll
       for (int k = 0; k < NPAIR; ++k) {
         float v[16];

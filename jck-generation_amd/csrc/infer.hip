@@ -300,8 +300,7 @@ extern "C" int jck_conv2d_nhwc_f32(const float* x, const float* w_kc, const floa
   p.M = (int)M;
   if (out_cstride < out_coff + Cout || out_coff < 0) JCK_FAIL(JCK_E_ARG, "conv2d_nhwc_f32: output slice outside the channel stride");
   p.ocs = out_cstride; p.ocoff = out_coff; p.relu = relu;
-  static const bool c16 = !(getenv("JCK_INFER_C16") && atoi(getenv("JCK_INFER_C16")) == 0);
-  if (c16 && Cin % 16 == 0 && Cout % 4 == 0 && (((uintptr_t)x | (uintptr_t)w_kc) & 15) == 0)
+  if (Cin % 16 == 0 && Cout % 4 == 0 && (((uintptr_t)x | (uintptr_t)w_kc) & 15) == 0)
     hipLaunchKernelGGL(conv2d_nhwc_f32_c16_kernel, dim3(cdiv(p.M, CV_M), cdiv(Cout, CV_N)), dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(conv2d_nhwc_f32_kernel, dim3(cdiv(p.M, CB_M), cdiv(Cout, CB_N)), dim3(256), 0, (hipStream_t)stream, p);

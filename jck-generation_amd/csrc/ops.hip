@@ -23,47 +23,19 @@ static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 // ---------------------------------------------------------------------------------------------------------
 // kernel-selection knobs: defaults are the measured-best choices; each can be preset with an environment variable of the
-// same name (JCK_<KEY>) or changed at run time with jck_tune("<key>", value) - which is what lets one process A/B two
-// variants on the same device and lets a test force a variant at a small shape.
+// same name (JCK_<KEY>) or changed at run time with jck_tune("<key>", value) - which is what lets a test force the other
+// variant at a small shape.
 // ---------------------------------------------------------------------------------------------------------
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-static int g_igemm_dma = env_int("JCK_IGEMM_DMA", 1);        // LDS-DMA gather-GEMM for bf16 tiles
-static int g_igemm_ws = env_int("JCK_IGEMM_WS", 1);          // wave-specialised 128x64 tiles when < 512 tiles of 128x128
-static int g_igemm_256 = env_int("JCK_IGEMM_256", 250);      // minimum number of 128x256 tiles to take that kernel (0: never)
-static int g_igemm_eff = env_int("JCK_IGEMM_EFF", 1);        // prefer 128x128 tiles where 128x256 tiles leave the last round of workgroups half empty
-static int g_igemm_128 = env_int("JCK_IGEMM_128", 200);      // minimum number of 128x128 tiles to take the persistent kernel at that tile (0: never)
-static int g_igemm_persist = env_int("JCK_IGEMM_PERSIST", 7);   // persistent wave-specialised gather-GEMMs (igemm.hpp); bit 0: 128x256, 1: 128x64, 2: 64x128 tiles
-// s_setprio 1 for the loader waves of the wave-specialised kernels: the younger half of a workgroup loses the issue arbitration
-// (MI355X guide, "Two waves per SIMD", item 4), and the kernels are bound by how fast the loaders issue their LDS-DMA pieces -
-// +0.3..3 % per gather-GEMM (tools/mb2.py igemm_prio 0 1 ...)
-static int g_igemm_dbg = 0;            // JCK_DIAG builds only: timing-experiment variant of the persistent gather-GEMM
-static int g_igemm_prio = env_int("JCK_IGEMM_PRIO", 1);      // in the step: neutral (1.905 vs 1.907 ms)
-static int g_wgrad_prio = env_int("JCK_WGRAD_PRIO", 0);
-static int g_stat_accum = env_int("JCK_STAT_ACCUM", 1);         // forward statistics accumulated per workgroup (persistent kernels, *_grouped calls)
-static int g_bn_unr = env_int("JCK_BN_UNR", 2);
-static int g_bn_res_mb = env_int("JCK_BN_RES_MB", 120);         // multi-group passes: resident form above this many MB of (g_a, y)
-static int g_bn_fuse = env_int("JCK_BN_FUSE", 1);               // forward BatchNorm finalize + apply as one launch (bn_fwd_fused_kernel) ...
-static int g_bn_fuse_wgs = env_int("JCK_BN_FUSE_WGS", 256);     // ... on about this many workgroups (each re-reads its slice's rows)
-static int g_bn_fuse_rows = env_int("JCK_BN_FUSE_ROWS", 320);   // ... while a group has at most this many statistics rows
-static int g_igemm_dma_ksplit = env_int("JCK_IGEMM_DMA_KSPLIT", 1);
-static int g_bn_bwd_fuse = env_int("JCK_BN_BWD_FUSE", 1);       // three-launch BatchNorm backward as two: the apply sums its slice's partial rows itself (bn_bwd_apply_fused_kernel) ...
-static int g_bn_bwd_fuse_wgs = env_int("JCK_BN_BWD_FUSE_WGS", 256);   // ... on about this many workgroups
-static int g_bn_res_small_mb = env_int("JCK_BN_RES_SMALL_MB", 0);   // multi-group passes: resident form also at or below this many MB (launch-latency-bound layers)
-static int g_bn_res = env_int("JCK_BN_RES", 1);                  // resident one-launch BatchNorm backward (bnres.hpp); 0: reduce + sums + apply, 2: whenever it fits                  // rows in flight per thread in bn_bwd_reduce (1, 2, 4)
-static int g_thin = env_int("JCK_THIN", 1);                  // streaming kernels for the image-side layers
-static int g_wgrad_gt = env_int("JCK_WGRAD_GT", 1);          // 2: 256-column weight-gradient tile (measured: no gain)
+static int g_igemm_dma_ksplit = env_int("JCK_IGEMM_DMA_KSPLIT", 1);   // split-K plain GEMMs on the LDS-DMA gather-GEMM; 0: register-staged
+static int g_bn_bwd_fuse = env_int("JCK_BN_BWD_FUSE", 1);       // three-launch BatchNorm backward as two: the apply sums its slice's partial rows itself (bn_bwd_apply_fused_kernel); 2: fp32 too
+static int g_bn_res = env_int("JCK_BN_RES", 1);                  // resident one-launch BatchNorm backward (bnres.hpp); 0: reduce + sums + apply, 2: whenever it fits
 static int g_wgrad_wgs = env_int("JCK_WGRAD_WGS", 256);      // split-K target workgroups
-static int g_wgrad_small_wgs = env_int("JCK_WGRAD_SMALL_WGS", 512);
-static int g_wgrad_stamp = env_int("JCK_WGRAD_STAMP", 0);
-static int g_wgrad_ws = env_int("JCK_WGRAD_WS", 1);
-static int g_wgrad_dma = env_int("JCK_WGRAD_DMA", 1);
-static int g_wgrad_dbg = 0;             // JCK_DIAG builds only: timing-experiment variant of the weight-gradient kernel (wgrad.hpp WDBG)
-static int g_wgrad_pipe = env_int("JCK_WGRAD_PIPE", 1);      // software-pipelined consumer waves of the wave-specialised weight gradient
+static int g_wgrad_ws = env_int("JCK_WGRAD_WS", 1);          // wave-specialised LDS-DMA weight gradient; 0: the 4-wave, 2-stage form
+static int g_wgrad_dma = env_int("JCK_WGRAD_DMA", 1);        // LDS-DMA weight gradient; 0: register-staged
 extern "C" int jck_tune(const char* key, int value) {
-  struct { const char* k; int* p; } tab[] = {{"igemm_dma", &g_igemm_dma}, {"igemm_ws", &g_igemm_ws}, {"igemm_256", &g_igemm_256}, {"igemm_128", &g_igemm_128}, {"igemm_eff", &g_igemm_eff}, {"igemm_persist", &g_igemm_persist}, {"igemm_dbg", &g_igemm_dbg}, {"igemm_prio", &g_igemm_prio}, {"wgrad_prio", &g_wgrad_prio},  {"stat_accum", &g_stat_accum}, {"bn_unr", &g_bn_unr}, {"bn_res", &g_bn_res}, {"bn_res_mb", &g_bn_res_mb}, {"bn_fuse", &g_bn_fuse}, {"bn_fuse_rows", &g_bn_fuse_rows}, {"bn_fuse_wgs", &g_bn_fuse_wgs}, {"igemm_dma_ksplit", &g_igemm_dma_ksplit}, {"bn_bwd_fuse", &g_bn_bwd_fuse}, {"bn_bwd_fuse_wgs", &g_bn_bwd_fuse_wgs}, {"bn_res_small_mb", &g_bn_res_small_mb},
-                                              {"thin", &g_thin}, {"wgrad_gt", &g_wgrad_gt}, {"wgrad_wgs", &g_wgrad_wgs},
-                                              {"wgrad_small_wgs", &g_wgrad_small_wgs}, {"wgrad_stamp", &g_wgrad_stamp},
-                                              {"wgrad_ws", &g_wgrad_ws}, {"wgrad_dma", &g_wgrad_dma}, {"wgrad_pipe", &g_wgrad_pipe}, {"wgrad_dbg", &g_wgrad_dbg}};
+  struct { const char* k; int* p; } tab[] = {{"bn_res", &g_bn_res}, {"igemm_dma_ksplit", &g_igemm_dma_ksplit}, {"bn_bwd_fuse", &g_bn_bwd_fuse},
+                                              {"wgrad_wgs", &g_wgrad_wgs}, {"wgrad_ws", &g_wgrad_ws}, {"wgrad_dma", &g_wgrad_dma}};
   for (auto& t : tab)
     if (key && !strcmp(t.k, key)) { *t.p = value; return JCK_OK; }
   JCK_FAIL(JCK_E_ARG, std::string("jck_tune: unknown key ") + (key ? key : "(null)"));
@@ -101,11 +73,10 @@ const char* const PROF_NAMES[] = {"igemm<bf16,128,128>", "igemm<bf16,128,64>", "
                                   "igemm<f32,64,128>",   "igemm<f32,16,256>",  "wgrad<bf16,128,128>",    "wgrad<bf16,128,64>",
                                   "wgrad<bf16,64,64,img>", "wgrad<bf16,64,64>", "wgrad<f32,128,128>",    "wgrad<f32,128,64>",
                                   "wgrad<f32,64,64,img>", "wgrad<f32,64,64>",  "img_down<bf16>",         "img_up<bf16>",
-                                  "igemm<bf16,128,256>",  "wgrad<bf16,256,128>", "bn_act_fwd",           "bn_bwd_resident",
-                                  "bn_bwd_3launch"};
-#define PROF_BN_ACT_FWD 22
-#define PROF_BN_BWD_RES 23
-#define PROF_BN_BWD_3L 24
+                                  "igemm<bf16,128,256>",  "bn_act_fwd",           "bn_bwd_resident",      "bn_bwd_3launch"};
+#define PROF_BN_ACT_FWD 21
+#define PROF_BN_BWD_RES 22
+#define PROF_BN_BWD_3L 23
 struct ProfScope {
   ProfRec r; bool on; hipStream_t st;
   ProfScope(int variant, double flops, hipStream_t s, double bytes = 0.0) : on(g_prof_on), st(s) {
@@ -215,38 +186,22 @@ static int launch_igemm_dma_persist(const IgemmParams& p, int nch_pad, int phase
   constexpr int LDSB = 3 * (BCH + BPIX) * IG_BK * 2 + NCW * (BCH >= 128 ? 2 : 1) * 256 + 64;
   constexpr int variant = BCH == 64 ? 3 : BPIX == 256 ? 20 : BPIX == 128 ? 0 : 1;
   ProfScope prof(variant, p.flops, st);
-  // JCK_DIAG builds (hipgan/build.py with JCK_DIAG=1 in the environment) carry the timing-experiment variants of igemm.hpp - part of
-  // the gather skipped, no loads / MFMAs / LDS reads / epilogue / stores / statistics (wrong results; jck_tune("igemm_dbg", code)):
-  // the ablation table of DESIGN.md section 7 comes from them
-#ifdef JCK_DIAG
-#define JCK_DBG_VARIANT(code) g_igemm_dbg == code ? igemm_dma_persist_kernel<BCH, BPIX, NCW, code>
-  auto kern = g_igemm_dbg == 2 ? igemm_dma_persist_kernel<BCH, BPIX, NCW, 2> : g_igemm_dbg == 4 ? igemm_dma_persist_kernel<BCH, BPIX, NCW, (BPIX >= 128 ? 4 : 2)>
-              : JCK_DBG_VARIANT(101) : JCK_DBG_VARIANT(102) : JCK_DBG_VARIANT(103) : JCK_DBG_VARIANT(104) : JCK_DBG_VARIANT(105)
-              : JCK_DBG_VARIANT(106) : JCK_DBG_VARIANT(107) : JCK_DBG_VARIANT(108) : igemm_dma_persist_kernel<BCH, BPIX, NCW>;
-#undef JCK_DBG_VARIANT
-#else
   auto kern = igemm_dma_persist_kernel<BCH, BPIX, NCW>;
-#endif
-  static const void* attr_done[16] = {};                             // the variants of this tile that have their LDS attribute set
-  {
-    int i = 0;
-    while (i < 16 && attr_done[i] && attr_done[i] != reinterpret_cast<const void*>(kern)) ++i;
-    if (i < 16 && !attr_done[i]) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_done[i] = reinterpret_cast<const void*>(kern);
-    }
+  static bool attr_done = false;
+  if (!attr_done) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_done = true;
   }
   dim3 grid(cdiv(p.M, BPIX), nch_pad / BCH, phases);
   IgemmParams q = p;
   q.gx = grid.x; q.gy = grid.y; q.gz = grid.z;
-  q.loader_prio = g_igemm_prio;
   const int ntiles = (int)(grid.x * grid.y * grid.z);
   const int cap = 256 * (160 * 1024 / LDSB);                         // 256 CUs x workgroups that fit their LDS
   const int nwg = std::min(ntiles, cap);
   if (q.stats && q.stat_accum) {
     // accumulated rows need several tiles of ONE channel tile per workgroup and tiles inside one group (igemm.hpp)
     const int gyy = (int)grid.y;
-    if (!(g_stat_accum && ntiles >= cap && ntiles % 8 == 0 && (ntiles / 8) % gyy == 0 && (cap / 8) % gyy == 0 && q.cstat == nch_pad &&
+    if (!(ntiles >= cap && ntiles % 8 == 0 && (ntiles / 8) % gyy == 0 && (cap / 8) % gyy == 0 && q.cstat == nch_pad &&
           (q.bn_group_rows == 0 || q.bn_group_rows % BPIX == 0)))
       q.stat_accum = 0;
   }
@@ -263,44 +218,38 @@ static int launch_igemm_dma_persist(const IgemmParams& p, int nch_pad, int phase
   return JCK_OK;
 }
 
+// 128 x 256 tiles when there are at least this many: about one tile per CU (fewer leave most of the chip idle)
+constexpr int IGEMM_256_MIN_TILES = 250;
+// 128 x 128 tiles on the persistent kernel when there are at least this many: batch-256 layers with 8x8 outputs
+// (D.conv3's forward at 3 x 256 images 60.6 -> 55.3 us against 128 x 256 tiles)
+constexpr int IGEMM_128_MIN_TILES = 200;
+
 template <class P>
 static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st, int* slots) {
-  // bf16 tiles with >= 128 channel rows run on the LDS-DMA kernel with 2 LDS stages (64 / 48 KB -> 2-3 workgroups per CU,
-  // which hide each other's load latency): 128x128 tiles while that still gives >= 512 workgroups, else 128x64.
+  // bf16 tiles with >= 128 channel rows run on the LDS-DMA kernels: 128x128 tiles with 2 LDS stages (64 KB -> 2-3 workgroups per
+  // CU, which hide each other's load latency) while that still gives >= 512 workgroups, else wave-specialised 128x64 tiles.
   // Measured on MI355X at B=256 (tools/micro.py, us): down2 36.2 -> 29.7, down3 43.0 -> 30.3, down4 65.8 -> 40.3,
-  // up2 47.2 -> 30.8, up3 34.5 -> 28.8; 3-4 stages at one workgroup per CU are slower.  JCK_IGEMM_DMA=0 disables.
-  const int use_dma = g_igemm_dma;
-  // (split-K plain GEMMs - CGAN's Linear(8392,256) - take the non-persistent LDS-DMA kernels: round 5, JCK_IGEMM_DMA_KSPLIT=0 the register-staged one)
-  if (use_dma && !P::IS_F32 && nsub == 1 && nch_pad % 128 == 0 && (p.ksplit <= 1 || (g_igemm_dma_ksplit && p.act_row_elems)) && !p.rows_are_phases) {
+  // up2 47.2 -> 30.8, up3 34.5 -> 28.8 against the register-staged kernel.  Split-K plain GEMMs (CGAN's Linear(8392,256)) take
+  // them too unless jck_tune("igemm_dma_ksplit", 0) sends them to the register-staged one.
+  if (!P::IS_F32 && nsub == 1 && nch_pad % 128 == 0 && (p.ksplit <= 1 || (g_igemm_dma_ksplit && p.act_row_elems)) && !p.rows_are_phases) {
     const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
-    // wave-specialised variant for the launches that would run 128x64 tiles (< 512 tiles of 128x128: one or two workgroups
-    // per CU); JCK_IGEMM_WS=0 disables.  128x128 WS (one workgroup per CU) and WS for the 64-channel tile measured slower.
-    const int ws_mode = g_igemm_ws;
-    // 128 x 256 tiles (8 consumer + 4 loader waves, one workgroup per CU) when that still gives about one tile per CU and a
-    // tile cannot straddle two BatchNorm groups: groups are multiples of 8 images, so 8 * OH*OW must be a multiple of 256.
-    // JCK_IGEMM_256 = minimum number of such tiles (0 disables).
-    const int min256 = g_igemm_256;
     const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128) * phases;
     // persistent kernels: plain bf16 conv / dgrad launches only (their epilogue has no bias, tanh, fp32 or split-K output)
-    int persist = (p.bias || p.epi || p.out_f32 || p.rows_are_phases || p.out_split_stride) ? 0 : g_igemm_persist;
+    const bool persist = !(p.bias || p.epi || p.out_f32 || p.out_split_stride);
     // a tile must not straddle two BatchNorm groups: groups are multiples of 8 images (8 * OH*OW % 256 == 0)
     const bool groups_ok = !p.stats || p.logOHW >= 5;
     // ... and the 256 persistent workgroups are not left half idle in their last round: 384 tiles are 1.5 rounds, the same layer in
-    // 128 x 128 tiles is 3 full ones (round 5: D.conv3's forward at 3 x 256 images 60.6 -> 55.3 us)
+    // 128 x 128 tiles is 3 full ones
     const auto round_eff = [](long long t) { return (double)t / (double)(((t + 255) / 256) * 256); };
-    const bool prefer128 = g_igemm_eff && g_igemm_128 > 0 && wgs >= g_igemm_128 && round_eff(wgs256) < 0.85 && round_eff(wgs) > round_eff(wgs256) + 0.1;
-    if (min256 > 0 && wgs256 >= min256 && !prefer128 && !p.act_row_elems && groups_ok && p.M % 256 == 0)
-      return (persist & 1) ? launch_igemm_dma_persist<128, 256, 8>(p, nch_pad, phases, st, slots)
-                           : launch_igemm_dma<128, 256, 3, true, 8>(p, nch_pad, phases, st, slots);
-    // 128 x 128 tiles on the persistent kernel (4 consumer + 4 loader waves, one workgroup per CU) when that gives about one tile
-    // per CU and 128 x 256 tiles would leave half the chip idle: batch-256 layers with 8x8 outputs (round 5; JCK_IGEMM_128 = minimum
-    // number of such tiles, 0 disables)
-    if (g_igemm_128 > 0 && wgs >= g_igemm_128 && (persist & 1) && !p.act_row_elems && (!p.stats || p.logOHW >= 4) && p.M % 128 == 0)
+    const bool prefer128 = wgs >= IGEMM_128_MIN_TILES && round_eff(wgs256) < 0.85 && round_eff(wgs) > round_eff(wgs256) + 0.1;
+    if (wgs256 >= IGEMM_256_MIN_TILES && !prefer128 && !p.act_row_elems && groups_ok && p.M % 256 == 0)
+      return persist ? launch_igemm_dma_persist<128, 256, 8>(p, nch_pad, phases, st, slots)
+                     : launch_igemm_dma<128, 256, 3, true, 8>(p, nch_pad, phases, st, slots);
+    if (wgs >= IGEMM_128_MIN_TILES && persist && !p.act_row_elems && (!p.stats || p.logOHW >= 4) && p.M % 128 == 0)
       return launch_igemm_dma_persist<128, 128, 4>(p, nch_pad, phases, st, slots);
     if (wgs >= 512) return launch_igemm_dma<128, 128, 2>(p, nch_pad, phases, st, slots);
-    if (ws_mode && (persist & 2) && !p.act_row_elems) return launch_igemm_dma_persist<128, 64, 4>(p, nch_pad, phases, st, slots);
-    if (ws_mode) return launch_igemm_dma<128, 64, 3, true>(p, nch_pad, phases, st, slots);
-    return launch_igemm_dma<128, 64, 2>(p, nch_pad, phases, st, slots);
+    if (persist && !p.act_row_elems) return launch_igemm_dma_persist<128, 64, 4>(p, nch_pad, phases, st, slots);
+    return launch_igemm_dma<128, 64, 3, true>(p, nch_pad, phases, st, slots);
   }
   if (nch_pad % 128 == 0) {
     if (nsub != 1) JCK_FAIL(JCK_E_ARG, "igemm: 4-channel gather with >=128 output rows unsupported");
@@ -310,9 +259,8 @@ static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsu
     return launch_igemm_t<P, 128, 64, 1>(p, nch_pad, phases, st, slots);
   }
   if (nch_pad == 64) {
-    if (use_dma && !P::IS_F32 && nsub == 1 && p.ksplit <= 1 && !p.rows_are_phases) {
-      const long long t128 = (long long)cdiv(p.M, 128) * phases;
-      if ((g_igemm_persist & 4) && !p.act_row_elems && !p.bias && !p.epi && !p.out_f32 && !p.rows_are_phases && !p.out_split_stride)
+    if (!P::IS_F32 && nsub == 1 && p.ksplit <= 1 && !p.rows_are_phases) {
+      if (!p.act_row_elems && !p.bias && !p.epi && !p.out_f32 && !p.out_split_stride)
         return launch_igemm_dma_persist<64, 128, 4>(p, nch_pad, phases, st, slots);
       return launch_igemm_dma<64, 128, 2>(p, nch_pad, phases, st, slots);
     }
@@ -358,7 +306,6 @@ extern "C" size_t jck_stats_floats(long long pixels, int C, int nyrep) {
 extern "C" size_t jck_packed_bytes(int prec, long long elems) { return (size_t)elems * (prec == JCK_PREC_F32 ? 4 : 2); }
 
 // image-side layers on the streaming kernels of thin.hpp (bf16, 64 channels on the wide side, row length % 16 == 0)
-#define g_use_thin g_thin
 #define IMG_GPW 8
 static int launch_img_down(const void* x, const void* w, void* out, float* stats, int* slots, int N, int Hb, int Wb, double flops,
                            hipStream_t st) {
@@ -407,7 +354,7 @@ static int conv_down_impl(int prec, const void* big, const void* w, void* small_
   if (stats && !is_pow2(Cs)) JCK_FAIL(JCK_E_ARG, "conv_down: BN statistics need a power-of-two channel count");
   p.flops = 2.0 * p.M * Cs * 16.0 * Cb;
   if (stats && fwd_group_images > 0) { p.bn_group_rows = fwd_group_images * OH * OW; p.stat_accum = 1; }
-  if (g_use_thin && prec == JCK_PREC_BF16 && cbp == 4 && Cs == 64 && OW % 16 == 0 && is_pow2(OH))
+  if (prec == JCK_PREC_BF16 && cbp == 4 && Cs == 64 && OW % 16 == 0 && is_pow2(OH))
     return launch_img_down(big, w, small_out, stats, stats_slots, N, Hb, Wb, p.flops, (hipStream_t)stream);
   return launch_igemm(prec, p, jck_pad_rows(Cs), 1, cbp == 4 ? 2 : 1, (hipStream_t)stream, stats_slots);
 }
@@ -445,7 +392,7 @@ static int conv_up_impl(int prec, const void* small_in, const void* w, void* big
     p.osN = (long long)4 * Hs * Ws * cbp; p.osY = 2 * 2 * Ws * cbp; p.osX = 2 * cbp;
     p.cstat = 4; p.ytiles_per_cset = 1; p.epi = epi_tanh ? 1 : 0; p.w_phase_stride = 0;
     p.flops = 2.0 * p.M * 4.0 * Cb * 4.0 * Cs;
-    if (g_use_thin && prec == JCK_PREC_BF16 && Cs == 64 && Ws % 16 == 0 && Hs % IMG_UP_R == 0)
+    if (prec == JCK_PREC_BF16 && Cs == 64 && Ws % 16 == 0 && Hs % IMG_UP_R == 0)
       return launch_img_up(small_in, w, big_out, epi_tanh ? 1 : 0, N, Hs, Ws, p.flops, (hipStream_t)stream);
     return launch_igemm(prec, p, 16, 1, 1, (hipStream_t)stream, nullptr);
   }
@@ -471,7 +418,7 @@ static int conv_up_impl(int prec, const void* small_in, const void* w, void* big
 // nothing launched) when the layer does not run on the image-side streaming kernel: the caller then issues the two launches.
 int conv_up_tanh_bwd_ev(int prec, const void* small_in, const void* w, const void* tanh_y, float scale, void* out, int N, int Hs, int Ws,
                         int Cs, int Cb, hipStream_t stream, hipEvent_t done, bool* fused) {
-  *fused = g_use_thin && prec == JCK_PREC_BF16 && jck_pad_chan(Cb) == 4 && Cs == 64 && Ws % 16 == 0 && Hs % IMG_UP_R == 0 &&
+  *fused = prec == JCK_PREC_BF16 && jck_pad_chan(Cb) == 4 && Cs == 64 && Ws % 16 == 0 && Hs % IMG_UP_R == 0 &&
            is_pow2(Hs) && is_pow2(Ws) && (long long)N * Hs * Ws * 16 < (1ll << 31);
   if (!*fused) return JCK_OK;
   return launch_img_up(small_in, w, out, 0, N, Hs, Ws, 2.0 * N * Hs * Ws * 4.0 * Cb * 4.0 * Cs, stream, tanh_y, scale, done);
@@ -510,19 +457,18 @@ extern "C" int jck_g1_fwd(int prec, const void* z, const void* w, void* out, flo
 // ---------------------------------------------------------------------------------------------------------
 struct WgradPlan { int BG, BS, gx, gy, Z, mchunk, CsRows, ncols; size_t ws; };
 
-// wide: 256-column gathered tile of the LDS-DMA kernel (bf16, Cs % 128 == 0, ncols % 256 == 0); JCK_WGRAD_GT=1 disables
-static bool wgrad_wide_shape(int ncols, int Cs) { return g_wgrad_gt == 2 && ncols % 256 == 0 && Cs % 128 == 0; }
-static WgradPlan plan_wgrad(long long Mtot, int ncols, int Cs, bool wide = false) {
+// split-K target workgroups of a plan with fewer than 4 tiles
+constexpr int WGRAD_SMALL_WGS = 512;
+static WgradPlan plan_wgrad(long long Mtot, int ncols, int Cs) {
   WgradPlan pl;
   pl.ncols = ncols;
-  pl.BG = wide ? 256 : (ncols % 128 == 0) ? 128 : 64;
+  pl.BG = (ncols % 128 == 0) ? 128 : 64;
   pl.BS = (Cs >= 128) ? 128 : 64;
   pl.gx = cdiv(ncols, pl.BG);
   pl.gy = cdiv(Cs, pl.BS);
   pl.CsRows = pl.gy * pl.BS;
   const int tiles = pl.gx * pl.gy;
-  const int target = g_wgrad_wgs, target_small = g_wgrad_small_wgs;
-  long long Z = std::max(1, (tiles >= 4 ? target : target_small) / tiles);
+  long long Z = std::max(1, (tiles >= 4 ? g_wgrad_wgs : WGRAD_SMALL_WGS) / tiles);
   const long long maxZ = std::max(1ll, Mtot / (WG_BKP * 4));
   Z = std::min(Z, maxZ);
   long long mchunk = (Mtot + Z - 1) / Z;
@@ -549,48 +495,35 @@ static int launch_wgrad_t(const WgradParams& p, const WgradPlan& pl, hipStream_t
   return JCK_OK;
 }
 
-// LDS-DMA weight gradient: wave-specialised (4 loader + 4 consumer waves, 3 stages = 96 KB) by default; JCK_WGRAD_WS=0 selects
-// the 4-wave, 2-stage form (48.4 vs 33.7 us at B=256 on the isolated product; 3-4 stages or 8 symmetric waves: within 7 %).
-// JCK_WGRAD_STAMP=1 (development) launches the instrumented twin read back by jck_debug_wgrad_stamps.
-template <int NSTG, bool STAMP, bool WS, int GT = 1, bool PIPE = false, int WDBG = 0>
+// LDS-DMA weight gradient: wave-specialised (4 loader + 4 software-pipelined consumer waves, 3 stages = 96 KB) by default;
+// jck_tune("wgrad_ws", 0) selects the 4-wave, 2-stage form (48.4 vs 33.7 us at B=256 on the isolated product).
+template <int NSTG, bool WS>
 static int launch_wgrad_dma_t(const WgradParams& q, int grid, hipStream_t st) {
-  constexpr int LDSB = NSTG * (GT + 1) * WGD_BKP * 256;
+  constexpr int LDSB = NSTG * 2 * WGD_BKP * 256;
   static bool attr_done = false;
   if (!attr_done) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<NSTG, 4, STAMP, WS, GT, PIPE, WDBG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<NSTG, 4, WS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
     attr_done = true;
   }
-  hipLaunchKernelGGL((wgrad_dma_kernel<NSTG, 4, STAMP, WS, GT, PIPE, WDBG>), dim3(grid), dim3(WS ? (4 + 4 * GT) * 64 : 256), LDSB, st, q);
+  hipLaunchKernelGGL((wgrad_dma_kernel<NSTG, 4, WS>), dim3(grid), dim3(WS ? 8 * 64 : 256), LDSB, st, q);
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }
 static int launch_wgrad_dma(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
-  ProfScope prof(pl.BG == 256 ? 21 : 10, p.flops, st);
+  ProfScope prof(10, p.flops, st);
   WgradParams q = p;
   q.gx = pl.gx; q.gy = pl.gy; q.gz = pl.Z;
-  q.loader_prio = g_wgrad_prio;
   const int grid = pl.gx * pl.gy * pl.Z;
-  const int stamp = g_wgrad_stamp, wsp = g_wgrad_ws;
-  if (pl.BG == 256) return launch_wgrad_dma_t<3, false, true, 2>(q, grid, st);
-#ifdef JCK_DIAG
-  if (g_wgrad_dbg == 1) return launch_wgrad_dma_t<3, false, true, 1, true, 1>(q, grid, st);
-  if (g_wgrad_dbg == 2) return launch_wgrad_dma_t<3, false, true, 1, true, 2>(q, grid, st);
-  if (g_wgrad_dbg == 3) return launch_wgrad_dma_t<3, false, true, 1, true, 3>(q, grid, st);
-  if (g_wgrad_dbg == 4) return launch_wgrad_dma_t<3, false, true, 1, true, 4>(q, grid, st);
-#endif
-  if (wsp && !stamp && g_wgrad_pipe) return launch_wgrad_dma_t<3, false, true, 1, true>(q, grid, st);
-  if (wsp) return stamp ? launch_wgrad_dma_t<3, true, true>(q, grid, st) : launch_wgrad_dma_t<3, false, true>(q, grid, st);
-  return stamp ? launch_wgrad_dma_t<2, true, false>(q, grid, st) : launch_wgrad_dma_t<2, false, false>(q, grid, st);
+  if (g_wgrad_ws) return launch_wgrad_dma_t<3, true>(q, grid, st);
+  return launch_wgrad_dma_t<2, false>(q, grid, st);
 }
 
 template <class P>
 static int launch_wgrad_p(const WgradParams& p, const WgradPlan& pl, int nsub, hipStream_t st) {
-  const int use_dma = g_wgrad_dma;
-  if (use_dma && p.big_bytes && p.s_bytes && !P::IS_F32 && (pl.BG == 128 || pl.BG == 256) && pl.BS == 128 && nsub == 1 && !p.big_row_elems && p.logCb >= 6 && p.logCb < 30 &&
+  if (g_wgrad_dma && p.big_bytes && p.s_bytes && !P::IS_F32 && pl.BG == 128 && pl.BS == 128 && nsub == 1 && !p.big_row_elems && p.logCb >= 6 && p.logCb < 30 &&
       pl.mchunk % WGD_BKP == 0 && p.logOW <= 6 &&
       ((1 << p.logOHW) <= WGD_BKP || p.H == p.sy * ((1 << p.logOHW) >> p.logOW)))     // constant 64-pixel address step (wgrad.hpp)
     return launch_wgrad_dma(p, pl, st);
-  if (pl.BG == 256) JCK_FAIL(JCK_E_ARG, "wgrad: the 256-column plan is for the LDS-DMA kernel only");
   if (pl.BG == 128 && pl.BS == 128 && nsub == 1) return launch_wgrad_t<P, 128, 128, 1>(p, pl, st);
   if (pl.BG == 128 && pl.BS == 64 && nsub == 1) return launch_wgrad_t<P, 128, 64, 1>(p, pl, st);
   if (pl.BG == 64 && pl.BS == 64 && nsub == 2) return launch_wgrad_t<P, 64, 64, 2>(p, pl, st);
@@ -625,16 +558,9 @@ static int launch_wgrad_reduce(const float* ws, int Z, int CsRows, int ncols, in
   return JCK_OK;
 }
 
-// the 256-column plan applies when the launch takes the LDS-DMA kernel (bf16, >= 64 gathered channels, 128-row S tiles)
-static bool conv_wgrad_wide(int prec, int cbp, int Cs) {
-  return g_wgrad_dma && prec == JCK_PREC_BF16 && cbp >= 64 && wgrad_wide_shape(16 * cbp, Cs);
-}
 extern "C" size_t jck_conv_wgrad_ws_bytes(int N, int Hb, int Wb, int Cb, int Cs) {
   const long long M = (long long)N * (Hb / 2) * (Wb / 2);
-  const int cbp = jck_pad_chan(Cb);
-  // the larger of the two plans, whatever the knobs say right now (a workspace outlives a jck_tune call)
-  const bool wide_shape = cbp >= 64 && (16 * cbp) % 256 == 0 && Cs % 128 == 0;
-  return std::max(plan_wgrad(M, 16 * cbp, Cs).ws, wide_shape ? plan_wgrad(M, 16 * cbp, Cs, true).ws : (size_t)0);
+  return plan_wgrad(M, 16 * jck_pad_chan(Cb), Cs).ws;
 }
 
 extern "C" int jck_conv_wgrad(int prec, const void* small_side, const void* big_side, float* ws, size_t ws_bytes,
@@ -652,7 +578,7 @@ extern "C" int jck_conv_wgrad(int prec, const void* small_side, const void* big_
     const long long bb = (long long)N * Hb * Wb * cbp * esz, sbytes = (long long)p.Mtot * Cs * esz;
     if (bb < (1ll << 31) && sbytes < (1ll << 31)) { p.big_bytes = (unsigned)bb; p.s_bytes = (unsigned)sbytes; }
   }
-  const WgradPlan pl = plan_wgrad(p.Mtot, 16 * cbp, Cs, conv_wgrad_wide(prec, cbp, Cs));
+  const WgradPlan pl = plan_wgrad(p.Mtot, 16 * cbp, Cs);
   JCK_TRY(run_wgrad(prec, p, pl, cbp == 4 ? 2 : 1, ws, ws_bytes, (hipStream_t)stream));
   JCK_TRY(launch_wgrad_reduce(ws, pl.Z, pl.CsRows, pl.ncols, Cs, Cb, p.logCb, grad, accumulate, (hipStream_t)stream));
   return JCK_OK;
@@ -750,16 +676,19 @@ extern "C" int jck_bn_act_fwd(int prec, const void* y, const float* aux, float s
 
 // finalize + apply in one launch (ew.hpp: bn_fwd_fused_kernel).  Taken while the statistics rows are few (every workgroup sums the rows of
 // its channel slice itself); *fused = false and nothing launched otherwise - the caller then issues jck_bn_finalize* + jck_bn_act_fwd*.
+constexpr int BN_FUSE_MAX_ROWS = 320;   // statistics rows per group up to which re-reading them in every workgroup still pays
+// workgroups of the fused BatchNorm launches (forward, and the backward apply): each re-reads its slice's partial rows
+// (L2-resident), so more of them cost more than they hide
+constexpr int BN_FUSE_WGS = 256;
 int bn_fwd_fused(int prec, const void* y, const float* stats, int slots_per_group, float count, const float* gamma, const float* beta,
                  float eps, float slope, void* a, float* aux, float* stat_out, float* running_mean, float* running_var, int64_t* nbt,
                  float momentum, long long rows_per_group, int C, int groups, long long out_row, long long out_pitch, hipStream_t stream,
                  bool* fused) {
-  *fused = g_bn_fuse && C >= 64 && C % 64 == 0 && is_pow2(C) && slots_per_group >= 1 && slots_per_group <= g_bn_fuse_rows && groups >= 1 &&
+  *fused = C >= 64 && C % 64 == 0 && is_pow2(C) && slots_per_group >= 1 && slots_per_group <= BN_FUSE_MAX_ROWS && groups >= 1 &&
            (!out_pitch || (out_row >= 8 && !(out_row & (out_row - 1)) && out_pitch >= out_row && out_pitch % 8 == 0));
   if (!*fused) return JCK_OK;
-  // ~512 workgroups: each re-reads slots x 512 bytes of rows (L2-resident), so more of them cost more than they hide
   const int nsl = C / 64;
-  const long long per = std::max<long long>(1, g_bn_fuse_wgs / ((long long)nsl * groups));
+  const long long per = std::max<long long>(1, BN_FUSE_WGS / ((long long)nsl * groups));
   const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows_per_group + 31) / 32, per));
   ProfScope prof(PROF_BN_ACT_FWD, 0.0, stream, 2.0 * groups * rows_per_group * C * (prec == JCK_PREC_F32 ? 4 : 2));
   DISPATCH_T(prec, hipLaunchKernelGGL(bn_fwd_fused_kernel<T>, dim3(gx, nsl, groups), dim3(BNF_THREADS), 0, stream, (const T*)y, stats,
@@ -847,19 +776,15 @@ static int bn_act_bwd_grouped_ev(int prec, const void* g_a, const void* y, const
   const int blocks = bn_bwd_blocks(rows, rstep, groups);
   const long long gstride = (long long)jck_bn_bwd_ws_floats(C);
   float* partial = sums + 2 * C;
-  if (g_bn_unr >= 4) { DISPATCH_T(prec, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 4>), dim3(blocks, groups), dim3(256), 2 * C * rstep * sizeof(float),
-                                      (hipStream_t)stream, (const T*)g_a, (const T*)y, aux, slope, partial, rows, C, gstride)); }
-  else if (g_bn_unr == 2) { DISPATCH_T(prec, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 2>), dim3(blocks, groups), dim3(256), 2 * C * rstep * sizeof(float),
-                                      (hipStream_t)stream, (const T*)g_a, (const T*)y, aux, slope, partial, rows, C, gstride)); }
-  else { DISPATCH_T(prec, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 1>), dim3(blocks, groups), dim3(256), 2 * C * rstep * sizeof(float),
-                                      (hipStream_t)stream, (const T*)g_a, (const T*)y, aux, slope, partial, rows, C, gstride)); }
+  DISPATCH_T(prec, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 2>), dim3(blocks, groups), dim3(256), 2 * C * rstep * sizeof(float),
+                                      (hipStream_t)stream, (const T*)g_a, (const T*)y, aux, slope, partial, rows, C, gstride));
   HIPCHK(hipGetLastError());
   if (g_bn_bwd_fuse && C >= 64 && C % 64 == 0 && (prec == JCK_PREC_BF16 || g_bn_bwd_fuse > 1)) {
     // two launches: every workgroup of the apply sums the partial rows of its 64-channel slice itself (ew.hpp).  The fast path's
     // form: the fp32 parity path keeps the three launches and with them the summation order its step tolerances were measured
     // with (a free-running second step amplifies a last-bit change of the sums to 1e-3 of D(G(z))); bn_bwd_fuse = 2 takes it there too
     const int nsl = C / 64;
-    const long long per = std::max<long long>(1, g_bn_bwd_fuse_wgs / ((long long)nsl * groups));
+    const long long per = std::max<long long>(1, BN_FUSE_WGS / ((long long)nsl * groups));
     const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows + 31) / 32, per));
     DISPATCH_T(prec, LAUNCH_EV(bn_bwd_apply_fused_kernel<T>, dim3(gx, nsl, groups), dim3(BNF_THREADS), 0, (hipStream_t)stream, done,
                                (const T*)g_a, (const T*)y, (const float*)aux, (const float*)partial, blocks, sums, dgamma, dbeta, slope,
@@ -887,8 +812,6 @@ static int bnres_cus() {
   }();
   return cus;
 }
-static unsigned long long* g_bnres_stamps = nullptr;
-extern "C" int jck_debug_bnres_stamps(void* buf) { g_bnres_stamps = (unsigned long long*)buf; return JCK_OK; }   // [256][8] u64, development aid
 extern "C" size_t jck_grid_sync_bytes(void) { return BNRES_SYNC_BYTES; }
 // 1 if a grid barrier of a resident launch timed out since the state was last zeroed (synchronises the device)
 const unsigned* jck_grid_sync_error_word(const void* sync_ws) { return sync_ws ? (const unsigned*)sync_ws + BNRES_W_ERR * 32 : nullptr; }
@@ -898,6 +821,8 @@ extern "C" int jck_grid_sync_error(const void* sync_ws) {
   if (hipMemcpy(&err, (const unsigned*)sync_ws + BNRES_W_ERR * 32, sizeof(err), hipMemcpyDeviceToHost) != hipSuccess) return 1;
   return err != 0;
 }
+// multi-group passes take the resident form above this many MB of (g_a, y): below it their second read comes out of the Infinity Cache
+constexpr int BN_RES_MIN_MB = 120;
 // nb workgroups (all co-resident), nsl channel slices, chunks per thread; 0 = does not fit
 static int bnres_plan(int prec, long long rows, int C, int groups, int* nb_out, int* nsl_out) {
   if (!g_bn_res || prec != JCK_PREC_BF16 || !is_pow2(C) || C < 64 || groups < 1 || rows < 1) return 0;
@@ -905,8 +830,7 @@ static int bnres_plan(int prec, long long rows, int C, int groups, int* nb_out, 
   // Infinity Cache while all groups fit it, and then it is as fast or faster in the step (measured, DESIGN.md section 5.3:
   // D.conv2's layer at 3 x 256 images 60 vs 70 us alone, the step 1.744 vs 1.733 ms); the resident form wins where they do not
   // fit (D.conv1's layer: 3 x 2 x 33.5 MB, or 2 x 2 x 33.5 MB for its loss groups alone).  bn_res = 2 takes the resident form whenever it fits the registers.
-  if (g_bn_res == 1 && groups > 1 && (long long)groups * rows * C * 4 <= ((long long)g_bn_res_mb << 20) &&
-      (long long)groups * rows * C * 4 > ((long long)g_bn_res_small_mb << 20)) return 0;
+  if (g_bn_res == 1 && groups > 1 && (long long)groups * rows * C * 4 <= ((long long)BN_RES_MIN_MB << 20)) return 0;
   const int nsl = C / 64;
   int nb = std::min(bnres_cus(), 256);
   nb -= nb % std::max(nsl, 8);
@@ -933,7 +857,7 @@ int bn_act_bwd_res_ev(int prec, const void* g_a, const void* y, const float* aux
   BnResParams p;
   p.ga = (const bf16_t*)g_a; p.y = (const bf16_t*)y; p.gy = (bf16_t*)g_y; p.aux = aux;
   p.sums = sums; p.sums_stride = (long long)jck_bn_bwd_ws_floats(C);
-  p.dgamma = dgamma; p.dbeta = dbeta; p.sync = (unsigned*)sync_ws; p.stamps = g_bnres_stamps;
+  p.dgamma = dgamma; p.dbeta = dbeta; p.sync = (unsigned*)sync_ws;
   p.rows = rows_per_group; p.C = C; p.groups = groups; p.grad_groups = grad_groups; p.nb = nb; p.nsl = nsl;
   p.slope = slope; p.inv_count = 1.0f / (float)rows_per_group;
   const dim3 grid(nb), block(BNRES_THREADS);
@@ -1431,7 +1355,7 @@ extern "C" int jck_bn2_vchain(int prec, const void* v, const void* y, const void
   if (g_bn_bwd_fuse && C >= 64 && C % 64 == 0 && (prec == JCK_PREC_BF16 || g_bn_bwd_fuse > 1)) {
     // two launches: the apply sums the partial rows of its own channel slice (ew.hpp: bn2_vchain_apply_fused_kernel)
     const int nsl = C / 64;
-    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows + 31) / 32, std::max(1, g_bn_bwd_fuse_wgs / nsl)));
+    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows + 31) / 32, std::max(1, BN_FUSE_WGS / nsl)));
     DISPATCH_T(prec, hipLaunchKernelGGL(bn2_vchain_apply_fused_kernel<T>, dim3(gx, nsl), dim3(256), 0, (hipStream_t)stream, (const T*)v, (const T*)y,
                                         (const T*)gy, aux, s1, (const float*)partial, blocks, ws, gamma, dgamma, slope, 1.0f / (float)rows,
                                         (T*)u, (T*)xdir, rows, C));
@@ -1460,7 +1384,7 @@ extern "C" int jck_bn2_reverse(int prec, const void* ua, const void* y, const vo
   HIPCHK(hipGetLastError());
   if (g_bn_bwd_fuse && C >= 64 && C % 64 == 0 && (prec == JCK_PREC_BF16 || g_bn_bwd_fuse > 1)) {
     const int nsl = C / 64;
-    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows + 31) / 32, std::max(1, g_bn_bwd_fuse_wgs / nsl)));
+    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows + 31) / 32, std::max(1, BN_FUSE_WGS / nsl)));
     DISPATCH_T(prec, hipLaunchKernelGGL(bn2_reverse_apply_fused_kernel<T>, dim3(gx, nsl), dim3(256), 0, (hipStream_t)stream, (const T*)ua,
                                         (const T*)y, (const T*)xdir, aux, gamma, (const float*)partial, blocks, ws, vsums + 2 * C,
                                         (dgamma && dbeta) ? dgamma : nullptr, (dgamma && dbeta) ? dbeta : nullptr, slope,
@@ -1489,12 +1413,5 @@ extern "C" int jck_cgan_z(int prec, const float* z, const int64_t* labels, int B
   DISPATCH_T(prec, hipLaunchKernelGGL(cgan_z_kernel<T>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, z,
                                       (const long long*)labels, B, NZ, NL, CiPad, (T*)out));
   HIPCHK(hipGetLastError());
-  return JCK_OK;
-}
-
-// development probe: copies the per-wave stamp totals of the last stamped wgrad_dma launch (see wgrad.hpp) to the host
-extern "C" int jck_debug_wgrad_stamps(unsigned long long* out, int n) {
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgd_stamps), (size_t)n * sizeof(unsigned long long)));
   return JCK_OK;
 }

@@ -37,7 +37,6 @@ struct WgradParams {
   int big_row_elems;      // > 0: the gathered side is a plain [Mtot][big_row_elems] matrix (Linear layers), 1 tap
   int gx, gy, gz;         // logical grid of the LDS-DMA kernel (launched 1-D): column tiles, row tiles, pixel chunks
   unsigned big_bytes, s_bytes;   // sizes of the two operands (buffer descriptors of the LDS-DMA kernels; 0: use the register-staged kernel)
-  int loader_prio;        // wave-specialised kernels: s_setprio of the loader waves (jck_tune "wgrad_prio")
   double flops;           // algorithmic FLOPs of this launch (profiling only)
 };
 
@@ -299,30 +298,21 @@ static __device__ __attribute__((aligned(16))) unsigned int g_jck_zero_page_w[64
 // NW = 4 or 8 waves per workgroup.  The fill rate of a CU scales with the number of waves that issue LDS-DMA (an issuing wave
 // stalls ~0.1 us per 1 KiB piece and cannot feed the MFMA meanwhile): 8 waves each issue half the pieces and own a 64x32
 // part of the tile, without the extra split-K slabs that a second 4-wave workgroup per CU would cost.
-// STAMP (development): per-wave s_memtime totals of the three parts of a k-step - [0] wait + barrier, [1] DMA issue,
-// [2] LDS reads + MFMA - and [3] the whole kernel, read back with jck_debug_wgrad_stamps
-static __device__ unsigned long long g_wgd_stamps[1024 * 8 * 4];
-// WS (wave-specialised, 8 waves, NW = 4, NSTG = 3): the stamps show a 4-wave workgroup spending 38 % of a k-step stalled in the
+// WS (wave-specialised, 8 waves, NW = 4, NSTG = 3): timestamps showed a 4-wave workgroup spending 38 % of a k-step stalled in the
 // issue of its 8 LDS-DMA pieces (the fill path pushes back at ~35 B/clk/CU - its hardware rate) and 45 % in LDS reads + MFMA,
 // one after the other in each wave's instruction stream, while waiting for data takes 2 %.  With WS waves 4-7 only issue the
 // DMA (two stages ahead) and waves 0-3 only read fragments and feed the MFMA, one loader and one consumer per SIMD, so the
 // two halves of a k-step overlap; one s_barrier per k-step hands a landed stage over and frees the stage read last.
-// GT (wave-specialised form only): gathered-side tiles of 128 columns per workgroup.  GT = 2 gives a 256 x 128 output tile:
-// 8 consumer waves (4 per gathered tile) + 4 loader waves = 768 threads, three 48 KB stages.  The S tile is filled once for
-// twice the columns, 87 instead of 64 FLOP per filled byte - the kernels are bound by the LDS fill rate (~24 B/clk/CU), so
-// bytes per FLOP is what sets their speed.
-template <int NSTG, int NW, bool STAMP = false, bool WS = false, int GT = 1, bool PIPE = false, int WDBG = 0>
-static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad_dma_kernel(const WgradParams p) {
-  static_assert(!PIPE || (WS && !STAMP), "the software-pipelined consumer exists in the wave-specialised form");
-  static_assert(!WS || (NW == 4 && NSTG == 3), "wave specialisation: 4 loader + 4*GT consumer waves, 3 LDS stages");
-  static_assert(GT == 1 || (WS && !STAMP && GT == 2), "the 256-column tile exists in the wave-specialised form only");
-  constexpr int BG = 128 * GT, BS = 128, FM = 4, FN = NW == 8 ? 2 : 4;
+template <int NSTG, int NW, bool WS = false>
+static __global__ __launch_bounds__(WS ? 8 * 64 : NW * 64) void wgrad_dma_kernel(const WgradParams p) {
+  static_assert(!WS || (NW == 4 && NSTG == 3), "wave specialisation: 4 loader + 4 consumer waves, 3 LDS stages");
+  constexpr int BG = 128, BS = 128, FM = 4, FN = NW == 8 ? 2 : 4;
   constexpr int NQ = 16 / NW;                                        // DMA rounds per operand tile: 4 rows per wave and round
   constexpr int SW = 128 / (NW / 2);                                 // small-side columns per wave: 64 (4 waves) or 32 (8 waves)
   constexpr int ROWB = 256;                                          // bytes per tile row (128 bf16)
   constexpr int TILE_BYTES = WGD_BKP * ROWB;                         // 16 KB per operand tile
-  constexpr int STG_BYTES = (GT + 1) * TILE_BYTES;                   // GT gathered tiles, then the S tile
-  constexpr int NCW = WS ? 4 * GT : NW;                              // consumer waves
+  constexpr int STG_BYTES = 2 * TILE_BYTES;                          // the gathered tile, then the S tile
+  constexpr int NCW = WS ? 4 : NW;                                   // consumer waves
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned char* lds = smem_raw;
 
@@ -360,9 +350,9 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
   const unsigned binc = (unsigned)((small_img ? (WGD_BKP / OHW) * p.H * p.W : (WGD_BKP / OW) * p.sy * p.W) << p.logCb) * 2u;
   const unsigned sinc = (unsigned)(WGD_BKP * p.CsStride) * 2u;
   const int doy = small_img ? 0 : WGD_BKP / OW;
-  unsigned boff[GT][NQ], soff[NQ];
-  int oyq[NQ], mq[NQ], dyq[GT][NQ];
-  bool bokx[GT][NQ], sokc[NQ];
+  unsigned boff[NQ], soff[NQ];
+  int oyq[NQ], mq[NQ], dyq[NQ];
+  bool bokx[NQ], sokc[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int row = q * (4 * NW) + wave * 4 + r4;                      // 0..63 inside the tile
@@ -371,23 +361,19 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
     const int n = m >> p.logOHW;
     const int rem = m & (OHW - 1);
     const int oy = rem >> p.logOW, ox = rem & (OW - 1);
-#pragma unroll
-    for (int g = 0; g < GT; ++g) {
-      // gathered side: column g0 + 128*g + lc*8 -> (tap, cb); a 128-column tile spans at most two taps (Cb >= 64)
-      const int gcol0 = g0 + 128 * g;
-      const int t_base = gcol0 >> p.logCb;
-      const int col = (gcol0 & (Cb - 1)) + lc * 8;
-      const bool second = col >= Cb;                                   // only when Cb == 64
-      const int t = t_base + (second ? 1 : 0);
-      const bool tv = t < p.ntaps;
-      const int tc = min(t, p.ntaps - 1);
-      const int dyv = p.dy[tc], dxv = p.dx[tc];
-      const int cb = second ? col - Cb : col;
-      const int ix = ox * p.sx + dxv;
-      boff[g][q] = (unsigned)(((((n * p.H + oy * p.sy + dyv) * p.W + ix) << p.logCb) + cb) * 2);
-      bokx[g][q] = tv && (unsigned)ix < (unsigned)p.W;
-      dyq[g][q] = dyv;
-    }
+    // gathered side: column g0 + lc*8 -> (tap, cb); a 128-column tile spans at most two taps (Cb >= 64)
+    const int t_base = g0 >> p.logCb;
+    const int col = (g0 & (Cb - 1)) + lc * 8;
+    const bool second = col >= Cb;                                     // only when Cb == 64
+    const int t = t_base + (second ? 1 : 0);
+    const bool tv = t < p.ntaps;
+    const int tc = min(t, p.ntaps - 1);
+    const int dyv = p.dy[tc], dxv = p.dx[tc];
+    const int cb = second ? col - Cb : col;
+    const int ix = ox * p.sx + dxv;
+    boff[q] = (unsigned)(((((n * p.H + oy * p.sy + dyv) * p.W + ix) << p.logCb) + cb) * 2);
+    bokx[q] = tv && (unsigned)ix < (unsigned)p.W;
+    dyq[q] = dyv;
     oyq[q] = oy; mq[q] = m;
     soff[q] = (unsigned)((m * p.CsStride + s0 + lc * 8) * 2);
     sokc[q] = s0 + lc * 8 < p.CsStride;
@@ -396,21 +382,16 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
   // zeros - no zero page): the issue of a piece costs less than with a 64-bit address pair per lane (round 3: +4-14 %)
   const auto rs_big = make_rsrc(p.big, p.big_bytes);
   const auto rs_s = make_rsrc(p.sside, p.s_bytes);
-  // WDBG (JCK_DIAG builds, timing experiments with wrong results): 1 no loads, 2 no MFMAs, 3 no slab stores, 4 no transposed reads
   auto issue = [&](int stage) {
-    if constexpr (WDBG == 1) return;
     unsigned char* gt = lds + stage * STG_BYTES;
-    unsigned char* st = gt + GT * TILE_BYTES;
+    unsigned char* st = gt + TILE_BYTES;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const bool rok = mq[q] < mz1;
-#pragma unroll
-      for (int g = 0; g < GT; ++g) {
-        const bool ok = rok && bokx[g][q] && (unsigned)(oyq[q] * p.sy + dyq[g][q]) < (unsigned)p.H;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_big, (lptr_t)(gt + g * TILE_BYTES + (q * (4 * NW) + wave * 4) * ROWB), 16,
-                                                 (int)(ok ? boff[g][q] : JCK_OOB), 0, 0, 0);
-        boff[g][q] += binc;
-      }
+      const bool ok = rok && bokx[q] && (unsigned)(oyq[q] * p.sy + dyq[q]) < (unsigned)p.H;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_big, (lptr_t)(gt + (q * (4 * NW) + wave * 4) * ROWB), 16,
+                                               (int)(ok ? boff[q] : JCK_OOB), 0, 0, 0);
+      boff[q] += binc;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_s, (lptr_t)(st + (q * (4 * NW) + wave * 4) * ROWB), 16,
                                                (int)((rok && sokc[q]) ? soff[q] : JCK_OOB), 0, 0, 0);
       soff[q] += sinc; mq[q] += WGD_BKP;
@@ -418,7 +399,7 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
     }
   };
 
-  // consumer wave -> 64 x SW part of the output tile: wg = 64-column block of the gathered side (GT*2 of them), ws = S part
+  // consumer wave -> 64 x SW part of the output tile: wg = 64-column block of the gathered side (2 of them), ws = S part
   const int wg = NW == 8 ? wave >> 2 : wave >> 1, ws = NW == 8 ? wave & 3 : wave & 1;
   f32x4 acc[FM][FN];
 #pragma unroll
@@ -436,7 +417,7 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
   };
   auto compute = [&](int stage) {
     const unsigned char* gt = lds + stage * STG_BYTES + (wg >> 1) * TILE_BYTES;      // this wave's gathered tile
-    const unsigned char* st = lds + stage * STG_BYTES + GT * TILE_BYTES;
+    const unsigned char* st = lds + stage * STG_BYTES + TILE_BYTES;
 #pragma unroll
     for (int kk = 0; kk < WGD_BKP / 32; ++kk) {
       const int row = kk * 32 + (lane >> 4) * 8 + (il >> 2);
@@ -462,44 +443,29 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
   // NSTG LDS stages (2: two workgroups share a CU; 3-4: one workgroup per CU keeps 2-3 k-steps of loads in flight - the
   // split-K plan launches ~one workgroup per CU).  8 DMA pieces per stage and wave: the counted wait leaves the NSTG-2
   // youngest stages in flight; stages past the end read the zero page and are never consumed.
-  unsigned long long tw = 0, ti = 0, tc = 0, t0 = 0, tk0 = 0;
-  if constexpr (STAMP) tk0 = __builtin_amdgcn_s_memtime();
   if constexpr (WS) {
     if (loader) {
-      if (p.loader_prio) __builtin_amdgcn_s_setprio(1);
       issue(0); issue(1);                                             // stages 0, 1 in flight
       int slot = 2;
       for (int k = 0; k < nk; ++k) {
-        if constexpr (STAMP) t0 = __builtin_amdgcn_s_memtime();
-        // stage k has landed (this wave's pieces): (GT + 1) * NQ = 8 or 12 younger pieces may stay in flight
-        if constexpr (WDBG == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if constexpr (GT == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        // stage k has landed (this wave's pieces): 2 * NQ = 8 younger pieces may stay in flight
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                 // consumers may read stage k; stage k-1 is free
-        if constexpr (STAMP) { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); tw += t1 - t0; t0 = t1; }
         issue(slot);                                                  // stage k+2 (past the end: zero page, never read)
-        if constexpr (STAMP) { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); ti += t1 - t0; }
         slot = slot == 2 ? 0 : slot + 1;
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if constexpr (PIPE) {
-      // software-pipelined consumer (round 5, as igemm_dma_persist_kernel): the transposed reads of the next 32-pixel half-step are
+    } else {
+      // software-pipelined consumer (as igemm_dma_persist_kernel): the transposed reads of the next 32-pixel half-step are
       // issued under the MFMAs of this one, one read per MFMA, across the k-step border too; lgkmcnt(0) in front of the barrier
       // says every read of the stage the loaders refill next has completed.  Same products in the same order: the same bits.
       const unsigned char* gt0 = lds + (wg >> 1) * TILE_BYTES;
-      const unsigned char* st0 = lds + GT * TILE_BYTES;
+      const unsigned char* st0 = lds + TILE_BYTES;
       bf16x8 a0[FM], b0[FN], a1[FM], b1[FN];
       auto rdh = [&](bf16x8 (&a)[FM], bf16x8 (&b)[FN], int slot, int kk) __attribute__((always_inline)) {
         const unsigned char* gt = gt0 + slot * STG_BYTES;
         const unsigned char* st = st0 + slot * STG_BYTES;
         const int row = kk * 32 + (lane >> 4) * 8 + (il >> 2);
-        if constexpr (WDBG == 4) {
-#pragma unroll
-          for (int j = 0; j < FN; ++j) asm volatile("" : "=v"(b[j]));
-#pragma unroll
-          for (int i = 0; i < FM; ++i) asm volatile("" : "=v"(a[i]));
-          return;
-        }
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           const int c0 = ws * SW + j * 16;
@@ -515,7 +481,7 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
-          for (int j = 0; j < FN; ++j) { if constexpr (WDBG == 2) asm volatile("" :: "v"(a[i]), "v"(b[j])); else acc[i][j] = mfma16(a[i], b[j], acc[i][j]); }
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
       };
       auto interleave = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -548,25 +514,6 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
         __builtin_amdgcn_sched_barrier(0);
         mm(a1, b1);
       }
-    } else {
-      int slot = 0;
-      for (int k = 0; k < nk; ++k) {
-        if constexpr (STAMP) t0 = __builtin_amdgcn_s_memtime();
-        __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); tw += t1 - t0; t0 = t1; }
-        compute(slot);
-        if constexpr (STAMP) {
-          asm volatile("s_nop 0" ::: "memory");
-          const unsigned long long t1 = __builtin_amdgcn_s_memtime(); tc += t1 - t0;
-        }
-        slot = slot == 2 ? 0 : slot + 1;
-      }
-    }
-    if constexpr (STAMP) {
-      if (lane == 0 && wgid < 1024) {
-        unsigned long long* d = g_wgd_stamps + ((long long)wgid * 8 + wave_raw) * 4;
-        d[0] = tw; d[1] = ti; d[2] = tc; d[3] = __builtin_amdgcn_s_memtime() - tk0;
-      }
     }
     if (loader) return;
   } else {
@@ -574,31 +521,18 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
   for (int s0_ = 0; s0_ < NSTG - 1; ++s0_) issue(s0_);
   int st_c = 0, st_i = NSTG - 1;
   for (int k = 0; k < nk; ++k) {
-    if constexpr (STAMP) t0 = __builtin_amdgcn_s_memtime();
     if constexpr (NSTG == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if constexpr (2 * NQ * (NSTG - 2) == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else if constexpr (2 * NQ * (NSTG - 2) == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if constexpr (2 * NQ * (NSTG - 2) == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else static_assert(NSTG == 2, "add the vmcnt literal");
     __builtin_amdgcn_s_barrier();
-    if constexpr (STAMP) { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); tw += t1 - t0; t0 = t1; }
     issue(st_i);
-    if constexpr (STAMP) { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); ti += t1 - t0; t0 = t1; }
     compute(st_c);
-    if constexpr (STAMP) {
-      asm volatile("s_nop 0" ::: "memory");
-      const unsigned long long t1 = __builtin_amdgcn_s_memtime(); tc += t1 - t0;
-    }
     st_c = (st_c + 1 == NSTG) ? 0 : st_c + 1;
     st_i = (st_i + 1 == NSTG) ? 0 : st_i + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (STAMP) {
-    if (lane == 0 && wgid < 1024) {
-      unsigned long long* d = g_wgd_stamps + ((long long)wgid * 8 + wave) * 4;
-      d[0] = tw; d[1] = ti; d[2] = tc; d[3] = __builtin_amdgcn_s_memtime() - tk0;
-    }
-  }
   }   // !WS
 
   float* part = p.part + (long long)bz * p.CsRows * p.ncols;
@@ -610,7 +544,6 @@ static __global__ __launch_bounds__(WS ? (4 + 4 * GT) * 64 : NW * 64) void wgrad
     for (int i = 0; i < FM; ++i) {
       const int col = g0 + wg * 64 + i * 16 + (lane >> 4) * 4;
       if (col >= p.ncols) continue;
-      if constexpr (WDBG == 3) asm volatile("" :: "v"(acc[i][j])); else
       *reinterpret_cast<f32x4*>(part + (long long)cs * p.ncols + col) = acc[i][j];
     }
   }

@@ -47,7 +47,6 @@ PROTOS = {
     "jck_conv_up_grouped": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "jck_bn_act_bwd_grouped": (i32, [i32, vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "jck_grid_sync_bytes": (sz, []),
-    "jck_debug_bnres_stamps": (i32, [vp]),
     "jck_grid_sync_error": (i32, [vp]),
     "jck_bn_act_bwd_res": (i32, [i32, vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]),
     "jck_img_prep": (i32, [i32, vp, vp, f32, f32, vp, i32, i32, vp]),
@@ -113,7 +112,6 @@ PROTOS = {
     "jck_engine_sample": (i32, [vp, vp, vp, i32, vp, vp]),
     "jck_engine_tensor": (vp, [vp, C.c_char_p, C.POINTER(i64)]),
     "jck_debug_tr_read": (i32, [vp, i32, vp, vp]),
-    "jck_debug_wgrad_stamps": (i32, [vp, i32]),
     "jck_tune": (i32, [C.c_char_p, i32]),
     "jck_conv2d_nhwc_f32": (i32, [vp, vp, vp, vp, vp] + [i32] * 14 + [vp]),
     "jck_pool2d_nhwc_f32": (i32, [vp, vp] + [i32] * 10 + [vp]),

@@ -600,10 +600,9 @@ class DcganEngine:
         handle = reduce_g(self.arenas["g_grads"]) if reduce_g else None
         # the forward half of the next step's D(real) pass, announced by the caller: under G's all-reduce when data parallel, and on
         # one GPU beside this step's Adam(G) + repack and the next step's set-step launch, which leave the second stream idle
-        # (round 5: -0.4 % of the step; JCK_PREFETCH_SINGLE=0 keeps it for the data-parallel step only)
+        # (-0.4 % of the step)
         if (next_real is not None and self.family == 0 and self.ddp_overlap and getattr(self, "_prefetch_ok", True)
-                and not (self.graphs if graph is None else graph)
-                and (handle is not None or os.environ.get("JCK_PREFETCH_SINGLE", "1") != "0")):
+                and not (self.graphs if graph is None else graph)):
             keep += self._prefetch_real(next_real, next_noise, lr, grad_scale, st)
         if handle is not None:
             handle()
