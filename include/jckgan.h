@@ -16,7 +16,9 @@
  *   - `prec` selects storage / arithmetic:
  *       JCK_PREC_BF16  activations, gradients, GEMM operands bf16 in HBM; v_mfma_f32_16x16x32_bf16, fp32 accumulate (fast)
  *       JCK_PREC_F32   everything fp32 in HBM; v_mfma_f32_16x16x4_f32 = exact fp32 products + accumulation      (parity)
- *     "T" below means bf16 (2 bytes) or float according to `prec`
+ *       JCK_PREC_BF16X3 storage and kernels of JCK_PREC_F32; the GEMM operands are split x = hi + lo (two bf16) and
+ *                      each product is lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x32_bf16, fp32 accumulate   (tracking)
+ *     "T" below means bf16 (2 bytes) or float (JCK_PREC_F32, JCK_PREC_BF16X3) according to `prec`
  *   - activations are NHWC; 3-channel images are stored with 4 channels (4th = 0)
  *   - a stride-2 stage is described by its BIG side [N,Hb,Wb,Cb] and SMALL side [N,Hb/2,Wb/2,Cs];
  *     Conv2d (D) maps big->small, ConvTranspose2d (G) maps small->big; both keep the weight as
@@ -32,6 +34,7 @@ extern "C" {
 
 #define JCK_PREC_BF16 0
 #define JCK_PREC_F32 1
+#define JCK_PREC_BF16X3 2
 
 #define JCK_OK 0
 #define JCK_E_ARG (-1)      /* bad argument / unsupported shape */

@@ -17,8 +17,14 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 // Bf16 : activations, gradients and GEMM operands bf16 in HBM/LDS, v_mfma_f32_16x16x32_bf16, fp32 accumulate (fast)
 // F32  : everything fp32 in HBM/LDS, v_mfma_f32_16x16x4_f32 = exact fp32 products and accumulation (parity;
 //        1/16 of the bf16 MFMA rate)
-struct PrecBf16 { typedef bf16_t T; typedef bf16_t W; static constexpr bool IS_F32 = false; };
-struct PrecF32  { typedef float  T; typedef float  W; static constexpr bool IS_F32 = true; };
+// Bf16x3: the F32 path in every storage and scheduling decision (IS_F32: fp32 in HBM, fp32 packed weights); only the GEMM
+//        core differs.  Each staged fp32 operand is split once into hi = bf16(x), lo = bf16(x - hi) (split_bf16x3), the
+//        two halves go to LDS as two bf16 tiles, and every product is lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x32_bf16
+//        with fp32 accumulation (3 bf16 MFMAs = 3/16 of the F32 path's MFMA time; ~1e-5 relative GEMM error)
+// SPLIT: the kernels' `if constexpr` flag for the split-bf16 core (LDS holds bf16 although T and W are float)
+struct PrecBf16   { typedef bf16_t T; typedef bf16_t W; static constexpr bool IS_F32 = false; static constexpr bool SPLIT = false; };
+struct PrecF32    { typedef float  T; typedef float  W; static constexpr bool IS_F32 = true;  static constexpr bool SPLIT = false; };
+struct PrecBf16x3 { typedef float  T; typedef float  W; static constexpr bool IS_F32 = true;  static constexpr bool SPLIT = true; };
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {                  // RNE, NaN stays NaN (v_cvt_pk_bf16_f32)
@@ -34,6 +40,18 @@ __device__ __forceinline__ unsigned pack2bf_pk(float lo, float hi) {
   typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
   const f32x2_t v = {lo, hi};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+}
+
+// x = hi + lo + O(2^-16 |x|) for 8 staged fp32 elements: hi = bf16_rne(x), lo = bf16_rne(x - hi) (x - hi is exact in fp32);
+// both roundings are v_cvt_pk_bf16_f32.  A non-finite x gives a NaN lo (inf - inf): the product is non-finite either way.
+__device__ __forceinline__ void split_bf16x3(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float x0 = i < 2 ? a[2 * i] : b[2 * i - 4], x1 = i < 2 ? a[2 * i + 1] : b[2 * i - 3];
+    const unsigned h = pack2bf_pk(x0, x1);
+    hi[i] = h;
+    lo[i] = pack2bf_pk(x0 - __uint_as_float(h << 16), x1 - __uint_as_float(h & 0xffff0000u));
+  }
 }
 
 template <typename T> __device__ __forceinline__ float ldf(const T* p);

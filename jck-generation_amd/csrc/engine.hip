@@ -340,10 +340,10 @@ extern "C" int jck_engine_create_sized(jck_engine** out, int family, int prec, i
   if (image_size != 64 && image_size != 128) JCK_FAIL(JCK_E_ARG, "image_size must be 64 or 128");
   if (image_size != 64 && family != 0) JCK_FAIL(JCK_E_ARG, "the 128x128 topology exists for DCGAN only (CGAN's Linear(8392,256) fixes 64x64)");
   if (family != 0 && family != 1) JCK_FAIL(JCK_E_ARG, "family must be 0 (DCGAN) or 1 (CGAN)");
-  if (prec != JCK_PREC_BF16 && prec != JCK_PREC_F32) JCK_FAIL(JCK_E_ARG, "bad prec");
+  if (prec != JCK_PREC_BF16 && !prec_f32_storage(prec)) JCK_FAIL(JCK_E_ARG, "bad prec");
   if (batch < 1 || batch > 8192) JCK_FAIL(JCK_E_ARG, "batch must be in [1, 8192]");
   jck_engine* e = new jck_engine();
-  e->family = family; e->prec = prec; e->B = batch; e->esz = prec == JCK_PREC_BF16 ? 2 : 4;
+  e->family = family; e->prec = prec; e->B = batch; e->esz = prec_f32_storage(prec) ? 4 : 2;
   e->T = make_topo(image_size);
   e->LG = make_layout(family, 0, image_size); e->LD = make_layout(family, 1, image_size);
   e->overlap = !(getenv("JCK_OVERLAP") && atoi(getenv("JCK_OVERLAP")) == 0);
@@ -1442,7 +1442,7 @@ static int set_step_impl(jck_engine* e, int step, float lr, void* stream, bool z
                             zero_d ? e->dg : nullptr, e->LD.n_params, zero_d && e->family == 1 ? e->gw1p : nullptr, (long long)L1_OUT * L1_KPAD,
                             // DCGAN: the drawn z goes straight into G.conv1's operand rows too (no pad_rows launch in front of G's forward
                             // when the step uses the engine's own z)
-                            e->family == 0 && e->fold_zero ? e->g_z : nullptr, 100, z_pad(e->family), e->prec == JCK_PREC_F32 ? 1 : 0));
+                            e->family == 0 && e->fold_zero ? e->g_z : nullptr, 100, z_pad(e->family), prec_f32_storage(e->prec) ? 1 : 0));
   e->gz_step = (e->family == 0 && e->fold_zero) ? step : -1;
   if (zero_d) e->dg_clean_step = step;
   e->acc_clean_step = step;

@@ -14,10 +14,14 @@
 // (double-buffered LDS, one barrier per k-step).
 //   PrecBf16: bf16 tiles, v_mfma_f32_16x16x32_bf16          (fast path)
 //   PrecF32 : fp32 tiles, v_mfma_f32_16x16x4_f32 - exact fp32 products and accumulation (parity path)
+//   PrecBf16x3: fp32 global loads as PrecF32; store_tiles splits every staged element into hi/lo bf16 and writes two bf16
+//             tiles in the bf16 layout (the same LDS bytes as one fp32 tile); 3 x v_mfma_f32_16x16x32_bf16 per fragment pair
 // Optional epilogue: per-channel sum / sum-of-squares of the fp32 accumulators for the BatchNorm that
 // follows - reduced over the 16 pixel lanes with wavefront shuffles and stored (no atomics) into a
 // per-(tile, wave) slot that jck_bn_finalize sums - and tanh.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 struct IgemmParams {
@@ -61,7 +65,7 @@ struct IgemmParams {
 #define IG_BK 64
 
 template <class P, int BCH, int BPIX, int NW = 4> struct IgemmCfg {      // NW: waves that own accumulators (4, or 8 consumers)
-  static constexpr bool F32 = P::IS_F32;
+  static constexpr bool F32 = P::IS_F32 && !P::SPLIT;                   // fp32 LDS tiles (else bf16: one plane, or hi + lo)
   static constexpr int WCH = (BCH >= 64) ? 2 : 1;
   static constexpr int WPIX = NW / WCH;
   static constexpr int FM = BCH / WCH / 16;
@@ -72,7 +76,8 @@ template <class P, int BCH, int BPIX, int NW = 4> struct IgemmCfg {      // NW: 
   // and for the 8-lane ds_write_b128 groups.  fp32: rows padded by 16 bytes.
   static constexpr int LD = F32 ? (IG_BK + 4) : IG_BK;
   static constexpr int ESZ = F32 ? 4 : 2;
-  static constexpr int BUF_BYTES = (BCH + BPIX) * LD * ESZ;
+  static constexpr int PLANE = (BCH + BPIX) * LD;                         // elements of one operand plane (weights, then pixels)
+  static constexpr int BUF_BYTES = PLANE * ESZ * (P::SPLIT ? 2 : 1);     // bf16x3: hi plane, then lo plane
   static constexpr int LDS_BYTES = 2 * BUF_BYTES + 128;
   // slots of partial statistics written by one launch = gridDim.x * gridDim.z * (gridDim.y / ytiles_per_cset) * WPIX
 };
@@ -151,9 +156,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
 template <class P, int BCH, int BPIX, int NSUB, int NST = 2>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   typedef typename P::T T;        // activation storage type
-  typedef typename P::W W;        // LDS / packed-weight element type (bf16_t or float)
+  typedef typename P::W W;        // packed-weight element type (bf16_t or float)
   typedef IgemmCfg<P, BCH, BPIX> C;
-  constexpr bool F32 = C::F32;
+  constexpr bool F32 = C::F32, SPLIT = P::SPLIT;
+  typedef typename std::conditional<F32, float, bf16_t>::type L;   // LDS element type
   constexpr int FM = C::FM, FN = C::FN, LD = C::LD;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   int* toff = reinterpret_cast<int*>(smem_raw);                    // 16 ints: element offset of each tap
@@ -248,6 +254,24 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   // LDS column (elements) of this thread's 8-element unit; rows ps*32 + lrow share ((row >> 1) & 7) because 32 % 16 == 0
   const int wcol = F32 ? unit * 8 : ((unit ^ ((lrow >> 1) & 7)) * 8);
   auto store_tiles = [&](int buf, const Stage& sg) {
+    if constexpr (SPLIT) {
+      bf16_t* wt = reinterpret_cast<bf16_t*>(lds + buf * C::BUF_BYTES);   // hi plane [BCH][LD], [BPIX][LD]; lo plane PLANE later
+      bf16_t* at = wt + BCH * LD;
+      auto put = [&](bf16_t* q, const Raw8<float>& r) __attribute__((always_inline)) {
+        u32x4 hi, lo;
+        split_bf16x3(r.a, r.b, hi, lo);
+        *reinterpret_cast<u32x4*>(q) = hi;
+        *reinterpret_cast<u32x4*>(q + C::PLANE) = lo;
+      };
+#pragma unroll
+      for (int ps = 0; ps < C::WPASS; ++ps) {
+        const int r = ps * 32 + lrow;
+        if (BCH >= 32 || r < BCH) put(wt + r * LD + wcol, sg.w[ps]);
+      }
+#pragma unroll
+      for (int ps = 0; ps < C::APASS; ++ps) put(at + (ps * 32 + lrow) * LD + wcol, sg.a[ps]);
+      return;
+    }
     W* wt = reinterpret_cast<W*>(lds + buf * C::BUF_BYTES);      // [BCH][LD]
     W* at = wt + BCH * LD;                                        // [BPIX][LD]
 #pragma unroll
@@ -270,9 +294,36 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   const int nk = p.ksplit > 1 ? p.ksteps : p.K / IG_BK;
   const int sw = ((lane & 15) >> 1) & 7;                           // read-side swizzle of this lane's rows
   auto compute = [&](int buf) {
-    const W* wt0 = reinterpret_cast<const W*>(lds + buf * C::BUF_BYTES);
-    const W* at0 = wt0 + BCH * LD;
-    if constexpr (!F32) {
+    const L* wt0 = reinterpret_cast<const L*>(lds + buf * C::BUF_BYTES);
+    const L* at0 = wt0 + BCH * LD;
+    if constexpr (SPLIT) {
+      // three bf16 products per fragment pair into the same accumulator, small terms first: lo*hi, hi*lo, then hi*hi (lo*lo,
+      // ~2^-16 relative, is dropped).  Each term runs over all (i, j) before the next, so consecutive MFMAs are independent;
+      // the order per accumulator is fixed: bitwise deterministic.
+      const bf16_t* wt = wt0 + (wch * FM * 16 + (lane & 15)) * LD;
+      const bf16_t* at = at0 + (wpix * FN * 16 + (lane & 15)) * LD;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const int col = (((lane >> 4) + ks * 4) ^ sw) * 8;
+        bf16x8 ah[FM], al[FM], bh[FN], bl[FN];
+#pragma unroll
+        for (int i = 0; i < FM; ++i) { ah[i] = lds_frag(wt + i * 16 * LD + col); al[i] = lds_frag(wt + C::PLANE + i * 16 * LD + col); }
+#pragma unroll
+        for (int j = 0; j < FN; ++j) { bh[j] = lds_frag(at + j * 16 * LD + col); bl[j] = lds_frag(at + C::PLANE + j * 16 * LD + col); }
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(al[i], bh[j], acc[i][j]);
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(ah[i], bl[j], acc[i][j]);
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(ah[i], bh[j], acc[i][j]);
+      }
+    } else if constexpr (!F32) {
       const bf16_t* wt = wt0 + (wch * FM * 16 + (lane & 15)) * LD;
       const bf16_t* at = at0 + (wpix * FN * 16 + (lane & 15)) * LD;
 #pragma unroll

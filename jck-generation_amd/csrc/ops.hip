@@ -54,7 +54,7 @@ extern "C" int jck_tune(const char* key, int value) {
 #define DISPATCH_T(prec, CALL)                                  \
   do {                                                          \
     if ((prec) == JCK_PREC_BF16) { typedef bf16_t T; CALL; }    \
-    else if ((prec) == JCK_PREC_F32) { typedef float T; CALL; } \
+    else if (prec_f32_storage(prec)) { typedef float T; CALL; } \
     else JCK_FAIL(JCK_E_ARG, "bad prec");                       \
   } while (0)
 
@@ -73,10 +73,15 @@ const char* const PROF_NAMES[] = {"igemm<bf16,128,128>", "igemm<bf16,128,64>", "
                                   "igemm<f32,64,128>",   "igemm<f32,16,256>",  "wgrad<bf16,128,128>",    "wgrad<bf16,128,64>",
                                   "wgrad<bf16,64,64,img>", "wgrad<bf16,64,64>", "wgrad<f32,128,128>",    "wgrad<f32,128,64>",
                                   "wgrad<f32,64,64,img>", "wgrad<f32,64,64>",  "img_down<bf16>",         "img_up<bf16>",
-                                  "igemm<bf16,128,256>",  "bn_act_fwd",           "bn_bwd_resident",      "bn_bwd_3launch"};
+                                  "igemm<bf16,128,256>",  "bn_act_fwd",           "bn_bwd_resident",      "bn_bwd_3launch",
+                                  "igemm<bf16x3,128,128>", "igemm<bf16x3,128,64>", "igemm<bf16x3,64,128,img>", "igemm<bf16x3,64,128>",
+                                  "igemm<bf16x3,16,256>", "wgrad<bf16x3,128,128>", "wgrad<bf16x3,128,64>", "wgrad<bf16x3,64,64,img>",
+                                  "wgrad<bf16x3,64,64>"};
 #define PROF_BN_ACT_FWD 21
 #define PROF_BN_BWD_RES 22
 #define PROF_BN_BWD_3L 23
+#define PROF_IGEMM_BF16X3 24     // + the igemm offset of the tile (0..4)
+#define PROF_WGRAD_BF16X3 29     // + the wgrad offset of the tile (0..3)
 struct ProfScope {
   ProfRec r; bool on; hipStream_t st;
   ProfScope(int variant, double flops, hipStream_t s, double bytes = 0.0) : on(g_prof_on), st(s) {
@@ -135,7 +140,8 @@ extern "C" int jck_prof_collect(int cap, const char** name_out, int* count_out, 
 template <class P, int BCH, int BPIX, int NSUB>
 static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   typedef IgemmCfg<P, BCH, BPIX> C;
-  constexpr int variant = (P::IS_F32 ? 5 : 0) + (BCH == 128 ? (BPIX == 128 ? 0 : 1) : (BCH == 64 ? (NSUB == 2 ? 2 : 3) : 4));
+  constexpr int tile = BCH == 128 ? (BPIX == 128 ? 0 : 1) : (BCH == 64 ? (NSUB == 2 ? 2 : 3) : 4);
+  constexpr int variant = (P::SPLIT ? PROF_IGEMM_BF16X3 : P::IS_F32 ? 5 : 0) + tile;
   ProfScope prof(variant, p.flops, st);
   auto kern = igemm_kernel<P, BCH, BPIX, NSUB, 2>;
   static bool attr_done = false;
@@ -280,7 +286,7 @@ int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int n
   IgemmParams p = p0;
   for (int zz = 0; zz < 4; ++zz)
     for (int t = 0; t < 16; ++t) p.tap[zz][t] = ((int)p.dy[zz][t] << 16) | ((int)p.dx[zz][t] & 0xffff);
-  const long long esz = prec == JCK_PREC_F32 ? 4 : 2;
+  const long long esz = prec_f32_storage(prec) ? 4 : 2;
   if (nsub == 1 && p.logC < 6 && !p.act_row_elems) JCK_FAIL(JCK_E_ARG, "igemm: the gathered tensor needs >= 64 channels (or exactly 4)");
   {
     // extent of the gathered tensor: rows (n, oy, ox) span N = M / (OH*OW) images of H x W x C
@@ -295,6 +301,7 @@ int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int n
   if (p.stats && !slots) JCK_FAIL(JCK_E_ARG, "igemm: stats requested without a slot-count output");
   if (prec == JCK_PREC_BF16) return launch_igemm_p<PrecBf16>(p, nch_pad, phases, nsub, st, slots);
   if (prec == JCK_PREC_F32) return launch_igemm_p<PrecF32>(p, nch_pad, phases, nsub, st, slots);
+  if (prec == JCK_PREC_BF16X3) return launch_igemm_p<PrecBf16x3>(p, nch_pad, phases, nsub, st, slots);
   JCK_FAIL(JCK_E_ARG, "bad prec");
 }
 
@@ -303,7 +310,7 @@ int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int n
 extern "C" size_t jck_stats_floats(long long pixels, int C, int nyrep) {
   return (size_t)std::max<long long>(pixels / 32 + 16, 4096) * (size_t)std::max(1, nyrep) * 2 * (size_t)C;
 }
-extern "C" size_t jck_packed_bytes(int prec, long long elems) { return (size_t)elems * (prec == JCK_PREC_F32 ? 4 : 2); }
+extern "C" size_t jck_packed_bytes(int prec, long long elems) { return (size_t)elems * (prec_f32_storage(prec) ? 4 : 2); }
 
 // image-side layers on the streaming kernels of thin.hpp (bf16, 64 channels on the wide side, row length % 16 == 0)
 #define IMG_GPW 8
@@ -481,7 +488,8 @@ static WgradPlan plan_wgrad(long long Mtot, int ncols, int Cs) {
 
 template <class P, int BG, int BS, int NSUB>
 static int launch_wgrad_t(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
-  constexpr int variant = 10 + (P::IS_F32 ? 4 : 0) + (BG == 128 ? (BS == 128 ? 0 : 1) : (NSUB == 2 ? 2 : 3));
+  constexpr int tile = BG == 128 ? (BS == 128 ? 0 : 1) : (NSUB == 2 ? 2 : 3);
+  constexpr int variant = (P::SPLIT ? PROF_WGRAD_BF16X3 : 10 + (P::IS_F32 ? 4 : 0)) + tile;
   ProfScope prof(variant, p.flops, st);
   constexpr int LDSB = WgradCfg<P, BG, BS>::LDS_BYTES;
   auto kern = wgrad_kernel<P, BG, BS, NSUB>;
@@ -536,6 +544,7 @@ static int run_wgrad(int prec, WgradParams& p, const WgradPlan& pl, int nsub, fl
   p.part = ws; p.CsRows = pl.CsRows; p.ncols = pl.ncols; p.mchunk = pl.mchunk;
   if (prec == JCK_PREC_BF16) return launch_wgrad_p<PrecBf16>(p, pl, nsub, st);
   if (prec == JCK_PREC_F32) return launch_wgrad_p<PrecF32>(p, pl, nsub, st);
+  if (prec == JCK_PREC_BF16X3) return launch_wgrad_p<PrecBf16x3>(p, pl, nsub, st);
   JCK_FAIL(JCK_E_ARG, "bad prec");
 }
 
@@ -574,7 +583,7 @@ extern "C" int jck_conv_wgrad(int prec, const void* small_side, const void* big_
   for (int t = 0; t < 16; ++t) { p.dy[t] = (signed char)(t / 4 - 1); p.dx[t] = (signed char)(t % 4 - 1); }
   p.flops = 2.0 * p.Mtot * Cs * 16.0 * Cb;
   {   // operand sizes for the buffer descriptors of the LDS-DMA kernels (32-bit byte offsets: < 2 GiB each)
-    const long long esz = prec == JCK_PREC_F32 ? 4 : 2;
+    const long long esz = prec_f32_storage(prec) ? 4 : 2;
     const long long bb = (long long)N * Hb * Wb * cbp * esz, sbytes = (long long)p.Mtot * Cs * esz;
     if (bb < (1ll << 31) && sbytes < (1ll << 31)) { p.big_bytes = (unsigned)bb; p.s_bytes = (unsigned)sbytes; }
   }
@@ -596,7 +605,7 @@ extern "C" int jck_g1_wgrad(int prec, const void* z, const void* dy, float* ws, 
   const WgradPlan pl = plan_wgrad(B, 16 * Co, CiPad);
   p.flops = 2.0 * B * Ci * 16.0 * Co;
   {
-    const long long esz = prec == JCK_PREC_F32 ? 4 : 2;
+    const long long esz = prec_f32_storage(prec) ? 4 : 2;
     p.big_bytes = (unsigned)((long long)B * 16 * Co * esz); p.s_bytes = (unsigned)((long long)B * CiPad * esz);
   }
   int rc = run_wgrad(prec, p, pl, 1, ws, ws_bytes, (hipStream_t)stream);
@@ -667,7 +676,7 @@ extern "C" int jck_bn_act_fwd(int prec, const void* y, const float* aux, float s
                               void* stream) {
   if (!is_pow2(C) || C < 8) JCK_FAIL(JCK_E_ARG, "bn_act_fwd: C must be a power of two >= 8");
   const long long total8 = rows * C / 8;
-  ProfScope prof(PROF_BN_ACT_FWD, 0.0, (hipStream_t)stream, 2.0 * rows * C * (prec == JCK_PREC_F32 ? 4 : 2));
+  ProfScope prof(PROF_BN_ACT_FWD, 0.0, (hipStream_t)stream, 2.0 * rows * C * (prec_f32_storage(prec) ? 4 : 2));
   DISPATCH_T(prec, hipLaunchKernelGGL(bn_act_fwd_kernel<T>, dim3(ew_grid(total8)), dim3(256), 0, (hipStream_t)stream,
                                       (const T*)y, aux, slope, (T*)a, total8, C));
   HIPCHK(hipGetLastError());
@@ -690,7 +699,7 @@ int bn_fwd_fused(int prec, const void* y, const float* stats, int slots_per_grou
   const int nsl = C / 64;
   const long long per = std::max<long long>(1, BN_FUSE_WGS / ((long long)nsl * groups));
   const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows_per_group + 31) / 32, per));
-  ProfScope prof(PROF_BN_ACT_FWD, 0.0, stream, 2.0 * groups * rows_per_group * C * (prec == JCK_PREC_F32 ? 4 : 2));
+  ProfScope prof(PROF_BN_ACT_FWD, 0.0, stream, 2.0 * groups * rows_per_group * C * (prec_f32_storage(prec) ? 4 : 2));
   DISPATCH_T(prec, hipLaunchKernelGGL(bn_fwd_fused_kernel<T>, dim3(gx, nsl, groups), dim3(BNF_THREADS), 0, stream, (const T*)y, stats,
                                       slots_per_group, count, gamma, beta, eps, slope, (T*)a, aux, stat_out, running_mean, running_var,
                                       (long long*)nbt, momentum, rows_per_group, C, out_pitch ? ilog2((int)out_row) : 0, out_pitch));
@@ -752,7 +761,7 @@ int bn_act_fwd_pitched(int prec, const void* y, const float* aux, float slope, v
   if (out_pitch && (out_row < 8 || (out_row & (out_row - 1)) || out_pitch < out_row || out_pitch % 8))
     JCK_FAIL(JCK_E_ARG, "bn_act_fwd: a pitched output needs rows of a power of two >= 8 elements, pitch >= row, pitch % 8 == 0");
   const long long total8 = rows_per_group * C / 8;
-  ProfScope prof(PROF_BN_ACT_FWD, 0.0, stream, 2.0 * groups * rows_per_group * C * (prec == JCK_PREC_F32 ? 4 : 2));
+  ProfScope prof(PROF_BN_ACT_FWD, 0.0, stream, 2.0 * groups * rows_per_group * C * (prec_f32_storage(prec) ? 4 : 2));
   DISPATCH_T(prec, hipLaunchKernelGGL(bn_act_fwd_kernel<T>, dim3(ew_grid(total8), groups), dim3(256), 0, stream,
                                       (const T*)y, aux, slope, (T*)a, total8, C, out_pitch ? ilog2((int)out_row) : 0, out_pitch));
   HIPCHK(hipGetLastError());
@@ -772,7 +781,7 @@ static int bn_act_bwd_grouped_ev(int prec, const void* g_a, const void* y, const
   const int rstep = 256 / (C / 8);
   if (rstep < 1) JCK_FAIL(JCK_E_ARG, "bn_act_bwd_grouped: C too large");
   // algorithmic bytes of the backward: read g_a and y once, write g_y (what the resident form moves; this form reads twice)
-  ProfScope prof(PROF_BN_BWD_3L, 0.0, (hipStream_t)stream, 3.0 * groups * rows * C * (prec == JCK_PREC_F32 ? 4 : 2));
+  ProfScope prof(PROF_BN_BWD_3L, 0.0, (hipStream_t)stream, 3.0 * groups * rows * C * (prec_f32_storage(prec) ? 4 : 2));
   const int blocks = bn_bwd_blocks(rows, rstep, groups);
   const long long gstride = (long long)jck_bn_bwd_ws_floats(C);
   float* partial = sums + 2 * C;

@@ -12,6 +12,10 @@
 
 void jck_set_error(const std::string& s);
 
+// fp32 storage (HBM tensors, packed weights) and the f32 path's kernel choices: JCK_PREC_F32 and JCK_PREC_BF16X3, which differ
+// only in the MFMA core of the register-staged GEMM kernels
+static inline bool prec_f32_storage(int prec) { return prec == JCK_PREC_F32 || prec == JCK_PREC_BF16X3; }
+
 #define JCK_FAIL(code, msg)                                   \
   do {                                                        \
     jck_set_error(std::string(__func__) + ": " + (msg));     \

@@ -12,6 +12,9 @@
 //             v_mfma_f32_16x16x32_bf16
 //   PrecF32 : v_mfma_f32_16x16x4_f32 takes ONE element per lane (A[row l&15][k l>>4]), which is a plain
 //             row read of the [pixel][channel] tile - exact fp32
+//   PrecBf16x3: fp32 loads as PrecF32; every staged element is split into hi/lo bf16 (split_bf16x3) and written to two bf16
+//             [pixel][channel] tiles in the bf16 layout; four transposed reads per fragment pair (hi and lo of both
+//             operands) and three v_mfma_f32_16x16x32_bf16 (lo*hi, hi*lo, hi*hi) into the same accumulator
 // MFMA A = gathered side (rows = (tap, cb) columns of dW), B = S side (cols = cs): a lane then owns
 // 4 consecutive (tap, cb) entries of one cs row -> one float4 store into a split-K partial slab
 // part[z][cs][ncols].  `wgrad_reduce_kernel` sums the slabs and transposes into the PyTorch weight
@@ -43,11 +46,12 @@ struct WgradParams {
 #define WG_BKP 32
 
 template <class P, int BG, int BS> struct WgradCfg {
-  static constexpr bool F32 = P::IS_F32;
+  static constexpr bool F32 = P::IS_F32 && !P::SPLIT;                   // fp32 LDS tiles (else bf16: one plane, or hi + lo)
   static constexpr int PAD = F32 ? 4 : 16;
   static constexpr int LDG = BG + PAD, LDSS = BS + PAD;            // padded rows (elements)
   static constexpr int ESZ = F32 ? 4 : 2;
-  static constexpr int BUF_BYTES = WG_BKP * (LDG + LDSS) * ESZ;
+  static constexpr int PLANE = WG_BKP * (LDG + LDSS);                     // elements of one plane (gathered tile, then S tile)
+  static constexpr int BUF_BYTES = PLANE * ESZ * (P::SPLIT ? 2 : 1);     // bf16x3: hi plane, then lo plane
   static constexpr int LDS_BYTES = 2 * BUF_BYTES;
 };
 
@@ -55,7 +59,7 @@ template <class P, int BG, int BS, int NSUB>
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   typedef typename P::T T;
   typedef WgradCfg<P, BG, BS> C;
-  constexpr bool F32 = C::F32;
+  constexpr bool F32 = C::F32, SPLIT = P::SPLIT;
   constexpr int LDG = C::LDG, LDSS = C::LDSS;
   constexpr int WG_ = (BG >= 64) ? 2 : 1, WS_ = 4 / WG_;
   constexpr int FM = BG / WG_ / 16, FN = BS / WS_ / 16;
@@ -118,6 +122,27 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   };
 
   auto store_tiles = [&](int buf) {
+    if constexpr (SPLIT) {
+      bf16_t* gt = reinterpret_cast<bf16_t*>(smem_raw + buf * C::BUF_BYTES);   // hi plane [WG_BKP][LDG], [WG_BKP][LDSS]
+      bf16_t* st = gt + WG_BKP * LDG;                                          // lo plane PLANE elements later
+      auto put = [&](bf16_t* q, const Raw8<float>& r) __attribute__((always_inline)) {
+        u32x4 hi, lo;
+        split_bf16x3(r.a, r.b, hi, lo);
+        *reinterpret_cast<u32x4*>(q) = hi;
+        *reinterpret_cast<u32x4*>(q + C::PLANE) = lo;
+      };
+#pragma unroll
+      for (int ps = 0; ps < PG; ++ps) {
+        const int r = ps * RG + gr;
+        if (r < WG_BKP) put(gt + r * LDG + gu * 8, greg[ps]);
+      }
+#pragma unroll
+      for (int ps = 0; ps < PS; ++ps) {
+        const int r = ps * RS + sr;
+        if (r < WG_BKP) put(st + r * LDSS + su * 8, sreg[ps]);
+      }
+      return;
+    }
     T* gt = reinterpret_cast<T*>(smem_raw + buf * C::BUF_BYTES);   // [WG_BKP][LDG]
     T* st = gt + WG_BKP * LDG;                                     // [WG_BKP][LDSS]
 #pragma unroll
@@ -152,9 +177,38 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   for (int kc = 0; kc < nk; ++kc) {
     const bool more = kc + 1 < nk;
     if (more) load_tiles(mz0 + (kc + 1) * WG_BKP);
-    const T* gt = reinterpret_cast<const T*>(smem_raw + (kc & 1) * C::BUF_BYTES);
-    const T* st = gt + WG_BKP * LDG;
-    if constexpr (!F32) {
+    if constexpr (SPLIT) {
+      // lo*hi, hi*lo, then hi*hi per accumulator, each term over all (i, j) before the next (fixed order: deterministic)
+      const bf16_t* gt = reinterpret_cast<const bf16_t*>(smem_raw + (kc & 1) * C::BUF_BYTES);
+      const bf16_t* st = gt + WG_BKP * LDG;
+      bf16x8 ah[FM], al[FM], bh[FN], bl[FN];
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+        const bf16_t* q = gt + trow * LDG + wg * FM * 16 + i * 16 + tcol;
+        ah[i] = join_tr(lds_tr4(q), lds_tr4(q + 4 * LDG));
+        al[i] = join_tr(lds_tr4(q + C::PLANE), lds_tr4(q + C::PLANE + 4 * LDG));
+      }
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const bf16_t* q = st + trow * LDSS + ws * FN * 16 + j * 16 + tcol;
+        bh[j] = join_tr(lds_tr4(q), lds_tr4(q + 4 * LDSS));
+        bl[j] = join_tr(lds_tr4(q + C::PLANE), lds_tr4(q + C::PLANE + 4 * LDSS));
+      }
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(al[i], bh[j], acc[i][j]);
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(ah[i], bl[j], acc[i][j]);
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(ah[i], bh[j], acc[i][j]);
+    } else if constexpr (!F32) {
+      const T* gt = reinterpret_cast<const T*>(smem_raw + (kc & 1) * C::BUF_BYTES);
+      const T* st = gt + WG_BKP * LDG;
       bf16x8 a[FM], b[FN];
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
@@ -171,6 +225,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
     } else {
+      const T* gt = reinterpret_cast<const T*>(smem_raw + (kc & 1) * C::BUF_BYTES);
+      const T* st = gt + WG_BKP * LDG;
       const float* ga = gt + (lane >> 4) * LDG + wg * FM * 16 + (lane & 15);
       const float* sb = st + (lane >> 4) * LDSS + ws * FN * 16 + (lane & 15);
 #pragma unroll 4

@@ -6,7 +6,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(HERE), "lib", "libjckgan_hip.so")
-PREC_BF16, PREC_F32 = 0, 1
+PREC_BF16, PREC_F32, PREC_BF16X3 = 0, 1, 2
 
 vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_size_t
 

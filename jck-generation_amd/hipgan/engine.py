@@ -10,14 +10,15 @@ import os
 
 import torch
 
-from ._lib import PREC_BF16, PREC_F32, JckError, StepInputs, cur_stream, lib, load_library
+from ._lib import PREC_BF16, PREC_BF16X3, PREC_F32, JckError, StepInputs, cur_stream, lib, load_library
 
 (PHASE_D_LOSS, PHASE_D_GP, PHASE_D_STEP, PHASE_G_LOSS, PHASE_G_STEP, PHASE_D_REAL, PHASE_D_FAKE, PHASE_D_REAL_FWD, PHASE_D_LOSS_A,
  PHASE_D_LOSS_B) = range(10)
 PHASE_LAZY_JOIN = 0x100
 PHASE_GP_ONLY = 10                 # include/jckgan.h: the gradient penalty alone (module path)
 PHASE_NO_RESIDENT = 0x200          # include/jckgan.h: no grid-barrier launch in this phase call (a collective may be holding CUs)
-_PREC = {"bf16": PREC_BF16, "f32": PREC_F32, PREC_BF16: PREC_BF16, PREC_F32: PREC_F32}
+_PREC = {"bf16": PREC_BF16, "f32": PREC_F32, "bf16x3": PREC_BF16X3, PREC_BF16: PREC_BF16, PREC_F32: PREC_F32,
+         PREC_BF16X3: PREC_BF16X3}
 SCALAR_NAMES = ("loss_d", "loss_g", "d_x", "d_gz1", "d_gz2", "gp", "loss_real", "loss_fake")
 
 
@@ -743,7 +744,7 @@ class DcganEngine:
         if not p:
             raise KeyError(name)
         f32 = name in ("prob", "ds", "norms", "acc", "rs", "prob_gp")
-        dt = torch.float32 if (f32 or self.prec == PREC_F32) else torch.bfloat16
+        dt = torch.bfloat16 if (self.prec == PREC_BF16 and not f32) else torch.float32
         return self._ws_view(p, n.value, dt).clone()
 
 

@@ -13,10 +13,10 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import PREC_BF16, PREC_F32, JckError, cur_stream, lib
+from ._lib import PREC_BF16, PREC_BF16X3, PREC_F32, JckError, cur_stream, lib
 
-_PREC = {"bf16": PREC_BF16, "f32": PREC_F32}
-_DT = {PREC_BF16: torch.bfloat16, PREC_F32: torch.float32}
+_PREC = {"bf16": PREC_BF16, "f32": PREC_F32, "bf16x3": PREC_BF16X3}
+_DT = {PREC_BF16: torch.bfloat16, PREC_F32: torch.float32, PREC_BF16X3: torch.float32}
 BN_MOMENTUM, BN_EPS = 0.1, 1e-5
 
 

@@ -24,6 +24,7 @@ from utils import require_gpu
 
 class CGANTrainer(DCGANTrainer):
     def __init__(self, args, model_g, model_d, data_pre, prec=None, host_rng=None):
+        """prec: "bf16" (default), "f32" or "bf16x3", as DCGANTrainer; env JCKGAN_PREC."""
         Trainer.__init__(self)
         self.logger = MainLogger(args)
         self.device = require_gpu("CGANTrainer")

@@ -85,7 +85,8 @@ def _save_png(path, chw, title=None):
 
 class DCGANTrainer(Trainer):
     def __init__(self, args: argparse.Namespace, model_g: nn.Module, model_d: nn.Module, data_pre, prec=None, host_rng=None):
-        """prec: "bf16" (fast, default) or "f32" (exact-fp32 parity path); env JCKGAN_PREC.
+        """prec: "bf16" (fast, default), "f32" (exact-fp32 parity path) or "bf16x3" (fp32 storage, split-bf16 GEMMs: tracks
+        the reference within 1e-3 per step at several times the f32 path's speed); env JCKGAN_PREC.
         host_rng: draw every random tensor from the CPU generator in the reference's order and upload it (bit-identical
         noise to a CPU run of the reference; env JCKGAN_HOST_RNG=1).  Default: Philox on the device."""
         self.logger = MainLogger(args)
