@@ -232,6 +232,15 @@ int jck_gp_grad(int prec, const void* g, const float* norms, float coef, int N, 
 /* ws: float[B + jck_head_bwd_ws_floats(K)] */
 int jck_gp_head2(int prec, const void* ughd, const float* w2, const float* prob, int B, int K, float* rs, float* dw2, float* ws,
                  void* stream);
+/* DCGAN's head step of the back-propagated penalty (conv5 = one dot product per image over K = 16*C, packed (h,w,c) order; the
+ * closed form is checked in tests/test_dcgan_gp_math.py), with v4 the adjoint at a4 from the v-chain and prob the penalty pass's
+ * probabilities:  rs[n] = <v4[n], wp> (1-2p) p(1-p);  g_a4[n][k] = rs[n] wp[k] in the storage type (skipped when NULL; may alias v4,
+ * not a4);  grad[c][t] += sum_n p(1-p) v4[n][t*C+c] + rs[n] a4[n][t*C+c] into the PyTorch-layout gradient of conv5.weight
+ * [1][C][4][4] (skipped when NULL; always accumulates; rows summed in a fixed order, no float atomics).  Two launches;
+ * ws: jck_gp_head2_conv_ws_floats(B) floats. */
+size_t jck_gp_head2_conv_ws_floats(int B);
+int jck_gp_head2_conv(int prec, const void* v4, const void* a4, const float* wp, const float* prob, int B, int C, float* rs,
+                      void* g_a4, float* grad, float* ws, void* stream);
 size_t jck_bn2_ws_floats(int C);
 int jck_bn2_vchain(int prec, const void* v, const void* y, const void* gy, const float* aux, const float* s1, const float* gamma,
                    float slope, float* ws, void* u, void* xdir, float* dgamma, long long rows, int C, void* stream);
@@ -250,6 +259,13 @@ int jck_engine_create(jck_engine** out, int family, int prec, int batch);
 /* image_size 64 = the reference's nets (model/DCGAN.py:10-27,42-59); 128 = one more stride-2 stage at the deep end (D 3-64-128-
  * 256-512-1024-1, G 100-1024-...-64-3; DCGAN only) for BASELINE.json configs[4] - no reference behaviour exists for it. */
 int jck_engine_create_sized(jck_engine** out, int family, int prec, int batch, int image_size);
+/* flags (OR-ed; 0 = jck_engine_create_sized):
+ *   JCK_ENGINE_GP_BACKWARD - DCGAN: back-propagate the gradient penalty as CGAN does (the reference only logs it,
+ *     train/dcgan_trainer.py:178-179): PHASE_D_GP adds 10 * d(penalty)/d(theta_D) to D's gradient arena and PHASE_GP_ONLY leaves
+ *     d(penalty)/d(theta_D) there; D's gradients are final only after PHASE_D_GP (no PHASE_D_LOSS_A / _B split, grad_tail -1).
+ *     The workspace grows by the second-order buffers.  CGAN ignores the flag. */
+#define JCK_ENGINE_GP_BACKWARD 1u
+int jck_engine_create_ex(jck_engine** out, int family, int prec, int batch, int image_size, unsigned flags);
 int jck_engine_image_size(const jck_engine*);
 /* layout queries of a created engine (its own image size); same meaning as the family-keyed ones below */
 int jck_engine_num_tensors_of(const jck_engine*, int net);

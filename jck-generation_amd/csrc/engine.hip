@@ -193,6 +193,7 @@ struct jck_engine {
   // launch of the step's first D phase, G's by D's Adam launch; the step whose arena is clean (consumed by the phase that would memset)
   int dg_clean_step = -1, gg_clean_step = -1;
   bool capturing = false;
+  bool gp_bwd = false;                  // DCGAN created with JCK_ENGINE_GP_BACKWARD: PHASE_D_GP back-propagates the penalty as CGAN's does
   float* g1_ws = nullptr; size_t g1_ws_bytes = 0;
   float* wg_ws; size_t wg_ws_bytes;
   long long gz_step = -1;               // the step whose set-step launch wrote its own z into g_z (G.conv1's operand) as well
@@ -304,13 +305,17 @@ struct jck_engine {
       gh_b1 = c.take<unsigned char>(bytes((size_t)B * L1_OUT)); ughd = c.take<unsigned char>(bytes((size_t)B * L1_OUT));
       gc = c.take<unsigned char>(bytes(HR * B * L1_KPAD));
       pre_e = c.take<float>(HR * B * EMB); l1_slab = c.take<float>((size_t)L1_KSPLIT * HR * B * L1_OUT);
-      gw1p = c.take<float>((size_t)L1_OUT * L1_KPAD); rs = c.take<float>(B); prob_gp = c.take<float>(B);
+      gw1p = c.take<float>((size_t)L1_OUT * L1_KPAD);
+    }
+    // second-order penalty buffers: CGAN, and DCGAN with JCK_ENGINE_GP_BACKWARD (a default DCGAN engine carves none of them)
+    if (family == 1 || gp_bwd) {
+      rs = c.take<float>(B); prob_gp = c.take<float>(B);
       for (int i = 0; i < TT.NS; ++i) {
         const size_t n = (size_t)B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i];
         d_v[i] = c.take<unsigned char>(bytes(n)); d_xdir[i] = c.take<unsigned char>(bytes(n));
         bn2_ws[i] = c.take<float>(jck_bn2_ws_floats(TT.D_CS[i]));
       }
-      bn2_ws_rev = c.take<float>(jck_bn2_ws_floats(512));
+      bn2_ws_rev = c.take<float>(jck_bn2_ws_floats(TT.G_C1));          // the widest D stage: 512, 1024 on the 128x128 plan
       d_u0 = c.take<unsigned char>(bytes(img));
     }
     ws_bytes = c.off;
@@ -336,7 +341,12 @@ extern "C" int jck_engine_create(jck_engine** out, int family, int prec, int bat
 }
 // image_size 64 = the reference's topology; 128 = one more stride-2 stage (DCGAN only; BASELINE.json configs[4])
 extern "C" int jck_engine_create_sized(jck_engine** out, int family, int prec, int batch, int image_size) {
+  return jck_engine_create_ex(out, family, prec, batch, image_size, 0);
+}
+// flags: JCK_ENGINE_GP_BACKWARD (include/jckgan.h)
+extern "C" int jck_engine_create_ex(jck_engine** out, int family, int prec, int batch, int image_size, unsigned flags) {
   if (!out) JCK_FAIL(JCK_E_ARG, "null out");
+  if (flags & ~JCK_ENGINE_GP_BACKWARD) JCK_FAIL(JCK_E_ARG, "unknown engine flags");
   if (image_size != 64 && image_size != 128) JCK_FAIL(JCK_E_ARG, "image_size must be 64 or 128");
   if (image_size != 64 && family != 0) JCK_FAIL(JCK_E_ARG, "the 128x128 topology exists for DCGAN only (CGAN's Linear(8392,256) fixes 64x64)");
   if (family != 0 && family != 1) JCK_FAIL(JCK_E_ARG, "family must be 0 (DCGAN) or 1 (CGAN)");
@@ -350,6 +360,7 @@ extern "C" int jck_engine_create_sized(jck_engine** out, int family, int prec, i
   // batched D passes need whole tiles per group: 16*B rows at the last layer, tiles of up to 128 rows
   e->batched = getenv("JCK_BATCHED") ? atoi(getenv("JCK_BATCHED")) : JCK_BATCHED_DEFAULT;
   if (!e->overlap || batch % 8 != 0 || e->batched != 3) e->batched = 0;
+  e->gp_bwd = family == 0 && (flags & JCK_ENGINE_GP_BACKWARD);        // CGAN back-propagates its penalty anyway
   e->carve(nullptr);
   e->ext_events = !(getenv("JCK_EXT_EVENTS") && atoi(getenv("JCK_EXT_EVENTS")) == 0);
   e->bn_res = !(getenv("JCK_BN_RES") && atoi(getenv("JCK_BN_RES")) == 0);
@@ -840,7 +851,7 @@ static int d_batched_pass(jck_engine* e, const void* x_in, int B, int G, int pas
   return JCK_OK;
 }
 
-// The back-propagated gradient penalty (train/cgan_trainer.py:200-203).  Precondition: the GP forward and first backward
+// The back-propagated gradient penalty (train/cgan_trainer.py:200-203; DCGAN with JCK_ENGINE_GP_BACKWARD).  Precondition: the GP forward and first backward
 // have run (d_forward(xhat), d_head(mode 1), d_backward(wgrad=false, xgrad=true)), so d_g[i] = gy_i, d_bn[i].sums = first-
 // backward sums, g_h = gradient at the Linear(8392,256) output, d_gx = g_x, norms = ||g_x[n]||.  Accumulates
 // lambda * dGP/dtheta into D's gradient arena.  Derivation + fp64 check: tests/test_gp_double_backward_math.py.
@@ -849,11 +860,13 @@ static int d_batched_pass(jck_engine* e, const void* x_in, int B, int G, int pas
 // (which overwrites the v_i the v-chain products read and runs the Linear weight gradient on the main stream) and at the end.
 // where the penalty pass left its forward / first-backward tensors: activation set 0 (per-pass schedule) or the last group
 // of the batched set
-struct GpSrc { const void *y[JCK_MAX_STAGES], *a[JCK_MAX_STAGES], *g[JCK_MAX_STAGES]; const float *aux[JCK_MAX_STAGES], *sums[JCK_MAX_STAGES], *prob; };
-static GpSrc gp_src_dset0(jck_engine* e) {
+// (activation set 1: DCGAN's per-pass penalty pass on its own stream; gx / norms: the image gradient and its per-image norms)
+struct GpSrc { const void *y[JCK_MAX_STAGES], *a[JCK_MAX_STAGES], *g[JCK_MAX_STAGES], *gx; const float *aux[JCK_MAX_STAGES], *sums[JCK_MAX_STAGES], *prob, *norms; };
+static GpSrc gp_src_dset(jck_engine* e, int s) {
   GpSrc r;
-  for (int i = 0; i < TT.NS; ++i) { r.y[i] = e->d_y[i]; r.a[i] = e->d_a[i]; r.g[i] = e->d_g[i]; r.aux[i] = e->d_bn[i].aux; r.sums[i] = e->d_bn[i].sums; }
-  r.prob = e->prob;
+  DSet& D = e->dset[s];
+  for (int i = 0; i < TT.NS; ++i) { r.y[i] = D.y[i]; r.a[i] = D.a[i]; r.g[i] = D.g[i]; r.aux[i] = D.bn[i].aux; r.sums[i] = D.bn[i].sums; }
+  r.prob = D.prob; r.gx = D.gx; r.norms = D.norms;
   return r;
 }
 static GpSrc gp_src_group(jck_engine* e, int g, int B) {
@@ -865,7 +878,7 @@ static GpSrc gp_src_group(jck_engine* e, int g, int B) {
     r.aux[i] = S.aux[i] + (size_t)g * 4 * TT.D_CS[i];
     r.sums[i] = S.sums[i] + (size_t)g * jck_bn_bwd_ws_floats(TT.D_CS[i]);
   }
-  r.prob = S.prob + (size_t)g * B;
+  r.prob = S.prob + (size_t)g * B; r.gx = e->d_gx; r.norms = e->norms;
   return r;
 }
 
@@ -888,17 +901,20 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
   // otherwise (the per-pass head backward below overwrites g_h)
   // the head's parameter gradients of PHASE_D_LOSS may still be queued on the weight-gradient stream (cg_head_backward_batched, no
   // join in between under JCK_PHASE_LAZY_JOIN): this pass adds to the same tensors from the main stream
-  if (side) (void)hipStreamWaitEvent(st, e->evHead, 0);
+  const bool cg = e->family == 1;
   const void* gh1 = e->gh_b1;
   const float* prob1 = e->prob_gp;
-  if (e->head_row0 > 0) {
-    gh1 = (const unsigned char*)e->g_h + (size_t)e->head_row0 * L1_OUT * esz;
-    prob1 = P.prob;
-  } else {
-    HIPCHK(hipMemcpyAsync(e->gh_b1, e->g_h, (size_t)B * L1_OUT * esz, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->prob_gp, P.prob, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (cg) {
+    if (side) (void)hipStreamWaitEvent(st, e->evHead, 0);
+    if (e->head_row0 > 0) {
+      gh1 = (const unsigned char*)e->g_h + (size_t)e->head_row0 * L1_OUT * esz;
+      prob1 = P.prob;
+    } else {
+      HIPCHK(hipMemcpyAsync(e->gh_b1, e->g_h, (size_t)B * L1_OUT * esz, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(e->prob_gp, P.prob, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
   }
-  JCK_TRY(jck_gp_grad(e->prec, e->d_gx, e->norms, 2.0f * lambda / (float)B, B, TT.HW, e->d_u0, st));
+  JCK_TRY(jck_gp_grad(e->prec, P.gx, P.norms, 2.0f * lambda / (float)B, B, TT.HW, e->d_u0, st));
   // ---- v-chain: adjoint of the first backward, swept forward through D
   const void* u = e->d_u0;
   for (int i = 0; i < TT.NS; ++i) {
@@ -911,34 +927,44 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
                            LRELU, e->bn2_ws[i], e->d_v[i], e->d_xdir[i], e->P(e->LD, e->dg, NWN[i]), rows, cs, st));
     u = e->d_v[i];
   }
-  // head: gc[:, :8192] = gh W1 -> adj(gh) = [u4 | 0] W1^T, dW1 += gh^T [u4 | 0]; gh = gh' * m/(1-p); gh' = ds w2; ds = p(1-p)
-  JCK_TRY(jck_concat_rows(e->prec, e->d_v[TT.NS - 1], TT.FEAT, e->cbuf2, L1_KPAD, B, st));          // tail columns of cbuf2 stay zero
-  JCK_TRY(jck_linear_wgrad(e->prec, gh1, L1_OUT, e->cbuf2, L1_KPAD, e->wg_ws, e->wg_ws_bytes, e->gw1p, 1, B, L1_OUT, fork(0)));
-  // What the reverse sweep must wait for are the v-chain's products (they read the v_i it overwrites): the weight-gradient stream is
-  // marked HERE, behind the last of them - not after the head's parameter gradients, which are forked to it below and which nothing
-  // on the main stream waits for before the optimiser
-  if (side) (void)hipEventRecord(e->evGP, side);
-  JCK_TRY(jck_linear_fwd(e->prec, e->cbuf2, e->l1_w, nullptr, e->l1_slab, B, L1_KPAD, L1_OUT, L1_OUT, L1_KSPLIT, st));
-  const bool fuse = e->head_fuse && L1_OUT == 256;    // the next four launches as one (ops.hip: gp_head_mid_ev)
-  if (!fuse) JCK_TRY(jck_linear_finish(e->prec, e->l1_slab, L1_KSPLIT, nullptr, drop_mask, 1.0f / 0.75f, nullptr, e->ughd, B, L1_OUT, st));
-  // (the head's parameter gradients - the dw2 sum here, linear2 / linear1 / the label embedding in d_head_backward below: ~75 us of
-  // launches that only the optimiser waits for - go to the weight-gradient stream; JCK_HEAD_SIDE=0 keeps them on the main one)
-  static const bool head_side = !(getenv("JCK_HEAD_SIDE") && atoi(getenv("JCK_HEAD_SIDE")) == 0);
-  hipStream_t hs = head_side && e->ext_events ? side : nullptr;
-  if (fuse) {
-    // g_hd / g_h rows [head_wrow0, + B): not the rows the v-chain's Linear weight gradient reads (the penalty group's, or the copy)
-    const size_t w0 = (size_t)e->head_wrow0 * L1_OUT * esz;
-    JCK_TRY(gp_head_mid_ev(e->prec, e->l1_slab, L1_KSPLIT, drop_mask, 1.0f / 0.75f, e->ughd, e->P(e->LD, e->dp, "linear2.weight"), prob1, B, e->rs,
-                           e->P(e->LD, e->dg, "linear2.weight"), e->gp2_ws, (unsigned char*)e->g_hd + w0, (unsigned char*)e->g_h + w0, st, hs,
-                           hs ? e->evHead : nullptr));
-  } else
-    JCK_TRY(gp_head2_ev(e->prec, e->ughd, e->P(e->LD, e->dp, "linear2.weight"), prob1, B, L1_OUT, e->rs,
-                        e->P(e->LD, e->dg, "linear2.weight"), e->gp2_ws, st, hs, hs ? e->evHead : nullptr));
-  // ---- reverse sweep through the forward pass from the logit adjoint rs, with the extra BatchNorm inputs
-  if (side) (void)hipStreamWaitEvent(st, e->evGP, 0); else join();
-  JCK_TRY(d_head_backward(e, e->dset[0], e->rs, B, true, drop_mask, e->d_v[TT.NS - 1], st, hs, fuse));
-  // the last sum into the permuted Linear gradient is enqueued: back to the reference's layout, on the stream that holds it
-  JCK_TRY(jck_unperm_linear_grad(e->gw1p, L1_OUT, L1_K, L1_KPAD, 512, 16, e->P(e->LD, e->dg, "linear1.weight"), 1, hs ? hs : st));
+  if (!cg) {
+    // DCGAN's head (conv5 + sigmoid) in one step (ops.hip: jck_gp_head2_conv): rs, conv5.weight's gradient and the reverse sweep's
+    // input g_a4 = rs * w5 written over v4.  The v-chain's products on the weight-gradient stream read v_0 .. v_{NS-2}, which the
+    // reverse sweep overwrites: it waits for the mark behind the last of them.
+    if (side) (void)hipEventRecord(e->evGP, side);
+    JCK_TRY(jck_gp_head2_conv(e->prec, e->d_v[TT.NS - 1], P.a[TT.NS - 1], e->d_head_wp, P.prob, B, TT.G_C1, e->rs, e->d_v[TT.NS - 1],
+                              e->P(e->LD, e->dg, CWN[TT.NS]), e->gp2_ws, st));
+    if (side) (void)hipStreamWaitEvent(st, e->evGP, 0);
+  } else {
+    // head: gc[:, :8192] = gh W1 -> adj(gh) = [u4 | 0] W1^T, dW1 += gh^T [u4 | 0]; gh = gh' * m/(1-p); gh' = ds w2; ds = p(1-p)
+    JCK_TRY(jck_concat_rows(e->prec, e->d_v[TT.NS - 1], TT.FEAT, e->cbuf2, L1_KPAD, B, st));          // tail columns of cbuf2 stay zero
+    JCK_TRY(jck_linear_wgrad(e->prec, gh1, L1_OUT, e->cbuf2, L1_KPAD, e->wg_ws, e->wg_ws_bytes, e->gw1p, 1, B, L1_OUT, fork(0)));
+    // What the reverse sweep must wait for are the v-chain's products (they read the v_i it overwrites): the weight-gradient stream is
+    // marked HERE, behind the last of them - not after the head's parameter gradients, which are forked to it below and which nothing
+    // on the main stream waits for before the optimiser
+    if (side) (void)hipEventRecord(e->evGP, side);
+    JCK_TRY(jck_linear_fwd(e->prec, e->cbuf2, e->l1_w, nullptr, e->l1_slab, B, L1_KPAD, L1_OUT, L1_OUT, L1_KSPLIT, st));
+    const bool fuse = e->head_fuse && L1_OUT == 256;    // the next four launches as one (ops.hip: gp_head_mid_ev)
+    if (!fuse) JCK_TRY(jck_linear_finish(e->prec, e->l1_slab, L1_KSPLIT, nullptr, drop_mask, 1.0f / 0.75f, nullptr, e->ughd, B, L1_OUT, st));
+    // (the head's parameter gradients - the dw2 sum here, linear2 / linear1 / the label embedding in d_head_backward below: ~75 us of
+    // launches that only the optimiser waits for - go to the weight-gradient stream; JCK_HEAD_SIDE=0 keeps them on the main one)
+    static const bool head_side = !(getenv("JCK_HEAD_SIDE") && atoi(getenv("JCK_HEAD_SIDE")) == 0);
+    hipStream_t hs = head_side && e->ext_events ? side : nullptr;
+    if (fuse) {
+      // g_hd / g_h rows [head_wrow0, + B): not the rows the v-chain's Linear weight gradient reads (the penalty group's, or the copy)
+      const size_t w0 = (size_t)e->head_wrow0 * L1_OUT * esz;
+      JCK_TRY(gp_head_mid_ev(e->prec, e->l1_slab, L1_KSPLIT, drop_mask, 1.0f / 0.75f, e->ughd, e->P(e->LD, e->dp, "linear2.weight"), prob1, B, e->rs,
+                             e->P(e->LD, e->dg, "linear2.weight"), e->gp2_ws, (unsigned char*)e->g_hd + w0, (unsigned char*)e->g_h + w0, st, hs,
+                             hs ? e->evHead : nullptr));
+    } else
+      JCK_TRY(gp_head2_ev(e->prec, e->ughd, e->P(e->LD, e->dp, "linear2.weight"), prob1, B, L1_OUT, e->rs,
+                          e->P(e->LD, e->dg, "linear2.weight"), e->gp2_ws, st, hs, hs ? e->evHead : nullptr));
+    // ---- reverse sweep through the forward pass from the logit adjoint rs, with the extra BatchNorm inputs
+    if (side) (void)hipStreamWaitEvent(st, e->evGP, 0); else join();
+    JCK_TRY(d_head_backward(e, e->dset[0], e->rs, B, true, drop_mask, e->d_v[TT.NS - 1], st, hs, fuse));
+    // the last sum into the permuted Linear gradient is enqueued: back to the reference's layout, on the stream that holds it
+    JCK_TRY(jck_unperm_linear_grad(e->gw1p, L1_OUT, L1_K, L1_KPAD, 512, 16, e->P(e->LD, e->dg, "linear1.weight"), 1, hs ? hs : st));
+  }
   for (int i = TT.NS - 1; i >= 0; --i) {
     const int hb = TT.D_HB[i], cs = TT.D_CS[i], cb = TT.D_CB[i];
     const long long rows = (long long)B * (hb / 2) * (hb / 2);
@@ -1158,7 +1184,9 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
   switch (phase) {
     case JCK_PHASE_D_LOSS_A:
     case JCK_PHASE_D_LOSS_B:
-      if (cg || e->batched != 3 || e->capturing) JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS_A / _B: only with the batched DCGAN schedule, outside a capture");
+      if (cg || e->batched != 3 || e->capturing || e->gp_bwd)
+        JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS_A / _B: only with the batched DCGAN schedule, outside a capture, without JCK_ENGINE_GP_BACKWARD "
+                            "(D's gradients are final only after PHASE_D_GP then)");
       [[fallthrough]];
     case JCK_PHASE_D_LOSS:
       if (cg && e->batched) {
@@ -1322,8 +1350,9 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
     case JCK_PHASE_GP_ONLY: {
       // The stand-alone gradient penalty of the module path (train/dcgan_trainer.py:110-127, train/cgan_trainer.py:114-131 called
       // outside this engine's step): real_nchw = real_data, noise_real = fake_data - both [B,3,S,S] fp32, taken as they are -, alpha
-      // (CGAN: labels, drop_mask[2]).  Leaves the per-image gradient norms in "norms" (the caller forms mean((n - 1)^2)) and, CGAN,
-      // d(penalty)/d(theta_D) with lambda = 1 in D's gradient arena, which is cleared first: the double backward in closed form.
+      // (CGAN: labels, drop_mask[2]).  Leaves the per-image gradient norms in "norms" (the caller forms mean((n - 1)^2)) and, CGAN
+      // and DCGAN with JCK_ENGINE_GP_BACKWARD, d(penalty)/d(theta_D) with lambda = 1 in D's gradient arena, which is cleared first: the
+      // double backward in closed form.
       if (!in->real_nchw || !in->noise_real || !in_->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY needs real_nchw (real), noise_real (fake) and alpha");
       if (e->capturing) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY: not inside a capture");
       if (cg && !in_->drop_mask[2]) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY (CGAN) needs drop_mask[2]");
@@ -1336,12 +1365,12 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
       JCK_TRY(jck_img_prep(e->prec, in->real_nchw, nullptr, 1.0f, 0.0f, e->real_noisy, B, HW, st));
       JCK_TRY(jck_img_prep(e->prec, in->noise_real, nullptr, 1.0f, 0.0f, e->fake, B, HW, st));
       JCK_TRY(penalty_pass(D0, st));
-      if (cg) JCK_TRY(gp_double_backward(e, gp_src_dset0(e), e->xhat, B, 1.0f, in->drop_mask[2], st, nullptr));
+      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, gp_src_dset(e, 0), e->xhat, B, 1.0f, in->drop_mask[2], st, nullptr));
       return JCK_OK;
     }
     case JCK_PHASE_D_GP: {
       if (!in->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP needs alpha");
-      if (e->gp_done && cg) {                         // forward and first backward ran as group 2 of the batched pass
+      if (e->gp_done && (cg || e->gp_bwd)) {          // forward and first backward ran as group 2 of the batched pass
         e->gp_done = false;
         JCK_TRY(gp_double_backward(e, gp_src_group(e, 2, B), e->xhat, B, 10.0f, in->drop_mask[2], st, sA, lazy));
         if (!(lazy && sA)) e->join_pending = e->mid_recorded = false;      // it joined the stream itself
@@ -1349,19 +1378,19 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
         return JCK_OK;
       }
       if (e->gp_done) { e->gp_done = false; return JCK_OK; }    // computed inside the batched pass of PHASE_D_LOSS
-      if (e->gp_inflight) {                           // started in PHASE_D_LOSS: just join
+      if (e->gp_inflight) {                           // started in PHASE_D_LOSS: join (JCK_ENGINE_GP_BACKWARD: and back-propagate it)
         HIPCHK(hipStreamWaitEvent(st, e->evGP, 0));
         e->gp_inflight = false;
+        if (e->gp_bwd) JCK_TRY(gp_double_backward(e, gp_src_dset(e, 1), e->xhat, B, 10.0f, nullptr, st, sA));
         return JCK_OK;
       }
       JCK_TRY(penalty_pass(D0, st));
-      if (cg) {                                      // CGAN back-propagates the penalty (train/cgan_trainer.py:200-203)
-        JCK_TRY(gp_double_backward(e, gp_src_dset0(e), e->xhat, B, 10.0f, in->drop_mask[2], st, sA));
-      }
+      // CGAN back-propagates the penalty (train/cgan_trainer.py:200-203); DCGAN when created with JCK_ENGINE_GP_BACKWARD
+      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, gp_src_dset(e, 0), e->xhat, B, 10.0f, in->drop_mask[2], st, sA));
       return JCK_OK;
     }
     case JCK_PHASE_D_STEP: {                                                                      // :180
-      if (e->gp_inflight) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP must be called before PHASE_D_STEP");
+      if (e->gp_inflight || (e->gp_bwd && e->gp_done)) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP must be called before PHASE_D_STEP");
       if (!e->hp_holds(in->step, in->lr) && !e->capturing) JCK_TRY(refresh_adam_scalars(e, in->step, in->lr, st));   // (eager callers)
       const float* hp = e->hp2 + 8 * e->parity;
       // G.zero_grad() (:182) rides on D's Adam launch: G's gradient arena is dead between G's optimiser step and PHASE_G_LOSS
@@ -1572,7 +1601,7 @@ extern "C" int jck_engine_drop_prefetch(jck_engine* e, void* stream) {
   return JCK_OK;
 }
 extern "C" long long jck_engine_grad_tail(const jck_engine* e, int net) {
-  if (!e || !e->bound || net != 1 || e->family != 0 || e->batched != 3) return -1;
+  if (!e || !e->bound || net != 1 || e->family != 0 || e->batched != 3 || e->gp_bwd) return -1;
   return (long long)find(e->LD, CWN[e->T.NS - 1])->offset;
 }
 

@@ -1462,6 +1462,81 @@ __global__ __launch_bounds__(256) void gp_head2_kernel(const T* __restrict__ ugh
   }
 }
 
+// DCGAN head step of the penalty's double backward (conv5 = one dot product per image, K = 16*C; tests/test_dcgan_gp_math.py):
+//   rows:    rs[n] = <v4[n,:], w5> * (1-2p) * p(1-p),  sn[n] = p(1-p)          (one workgroup per row, as head_fwd_kernel)
+//   columns: g_a4[n][k] = rs[n] * w5[k]  and  grad[c][t] += sum_n sn[n] v4[n][k] + rs[n] a4[n][k]   (k = t*C + c)
+// The column launch reads v4[n][k] before it writes g_a4[n][k] from the same thread: g_a4 may BE v4 (the engine's reverse sweep
+// starts in place from the v-chain's last buffer).
+template <typename T>
+__global__ __launch_bounds__(256) void dcgan_gp_head_rows_kernel(const T* __restrict__ v4, const float* __restrict__ w, int K,
+                                                                 const float* __restrict__ prob, float* __restrict__ rs,
+                                                                 float* __restrict__ sn) {
+  __shared__ float sm[4];
+  const T* x = v4 + (long long)blockIdx.x * K;
+  float s = 0.f;
+  for (int i = threadIdx.x * 8; i < K; i += 256 * 8) {
+    float v[8];
+    ld8(x + i, v);
+    const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + i), w1 = *reinterpret_cast<const f32x4*>(w + i + 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += v[k] * w0[k] + v[4 + k] * w1[k];
+  }
+  s = block_sum256(s, sm);
+  if (threadIdx.x == 0) {
+    const float p = prob[blockIdx.x], pq = p * (1.f - p);
+    rs[blockIdx.x] = s * (1.f - 2.f * p) * pq;
+    sn[blockIdx.x] = pq;
+  }
+}
+
+// grid (cdiv(K/8, GP_HEAD_CU)): GP_HEAD_CU column units of 8 columns x GP_HEAD_RL row lanes per workgroup; a workgroup owns its
+// columns over ALL rows, so the weight term needs no cross-workgroup sum: the row lanes' partial sums are added in lane order
+// (deterministic, no atomics).  grad == nullptr: g_a4 only.
+#define GP_HEAD_CU 8
+#define GP_HEAD_RL 32
+template <typename T>
+__global__ __launch_bounds__(256) void dcgan_gp_head_cols_kernel(const T* v4, const T* __restrict__ a4, const float* __restrict__ w,
+                                                                 const float* __restrict__ rs, const float* __restrict__ sn, int B,
+                                                                 int K, int C, T* g_a4, float* __restrict__ grad) {
+  __shared__ float red[GP_HEAD_RL][GP_HEAD_CU * 8 + 1];
+  const int u = threadIdx.x % GP_HEAD_CU, ln = threadIdx.x / GP_HEAD_CU;
+  const int k = (blockIdx.x * GP_HEAD_CU + u) * 8;
+  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (k < K) {
+    float wv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wv[j] = w[k + j];
+    for (int n = ln; n < B; n += GP_HEAD_RL) {
+      const long long o = (long long)n * K + k;
+      float v[8], a[8];
+      ld8(v4 + o, v);
+      ld8(a4 + o, a);
+      const float r = rs[n], q = sn[n];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s[j] += q * v[j] + r * a[j];
+      if (g_a4) {
+        float g[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g[j] = r * wv[j];
+        st8(g_a4 + o, g);
+      }
+    }
+  }
+  if (!grad) return;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) red[ln][u * 8 + j] = s[j];
+  __syncthreads();
+  if (threadIdx.x < GP_HEAD_CU * 8) {
+    const int kk = blockIdx.x * GP_HEAD_CU * 8 + threadIdx.x;
+    if (kk < K) {
+      float t = 0.f;
+      for (int l = 0; l < GP_HEAD_RL; ++l) t += red[l][threadIdx.x];
+      const int tt = kk / C, c = kk - tt * C;
+      grad[c * 16 + tt] += t;
+    }
+  }
+}
+
 // The same stretch of the penalty's double backward as ONE launch, one workgroup per row of 256 columns (thread = column):
 // linear_finish_kernel (split-K sum of the v-chain's Linear product, Dropout) -> ughd, gp_head2_kernel (rs, pq), head_dgrad_kernel
 // (g_hd = rs * w2) and the Dropout backward (g_h) - the arithmetic and the rounding points of the four launches.

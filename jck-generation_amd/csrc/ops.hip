@@ -1328,6 +1328,25 @@ int gp_head2_ev(int prec, const void* ughd, const float* w2, const float* prob, 
   return JCK_OK;
 }
 
+// DCGAN head step of the penalty's double backward (ew.hpp: dcgan_gp_head_rows_kernel, dcgan_gp_head_cols_kernel): two launches
+// where gp_head2_ev + jck_head_bwd_conv + jck_head_unpack_grad would take five.  ws: sn[n] = p(1-p) between the two.
+extern "C" size_t jck_gp_head2_conv_ws_floats(int B) { return (size_t)(B + 63) / 64 * 64; }
+extern "C" int jck_gp_head2_conv(int prec, const void* v4, const void* a4, const float* wp, const float* prob, int B, int C, float* rs,
+                                 void* g_a4, float* grad, float* ws, void* stream) {
+  if (B < 1 || C < 8 || C % 8) JCK_FAIL(JCK_E_ARG, "gp_head2_conv: B >= 1 and C % 8 == 0 required");
+  if (!v4 || !a4 || !wp || !prob || !rs || !ws) JCK_FAIL(JCK_E_ARG, "gp_head2_conv: null operand or workspace");
+  if (g_a4 && g_a4 == a4) JCK_FAIL(JCK_E_ARG, "gp_head2_conv: g_a4 may alias v4, not a4");
+  const int K = 16 * C;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_T(prec, hipLaunchKernelGGL(dcgan_gp_head_rows_kernel<T>, dim3(B), dim3(256), 0, st, (const T*)v4, wp, K, prob, rs, ws));
+  HIPCHK(hipGetLastError());
+  if (!g_a4 && !grad) return JCK_OK;
+  DISPATCH_T(prec, hipLaunchKernelGGL(dcgan_gp_head_cols_kernel<T>, dim3(cdiv(K / 8, GP_HEAD_CU)), dim3(256), 0, st, (const T*)v4,
+                                      (const T*)a4, wp, rs, ws, B, K, C, (T*)g_a4, grad));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+
 // jck_linear_finish(bias = NULL, h = NULL) + gp_head2_ev + the input-gradient half of jck_head_bwd(ds = rs) + jck_dropout in one launch
 // (ew.hpp: cg_gp_head_mid_kernel; 256 columns), then the dw2 sum as in gp_head2_ev (on `side` behind `handover` when given)
 int gp_head_mid_ev(int prec, const float* slab, int ksplit, const float* mask, float scale, void* ughd, const float* w2, const float* prob, int B,

@@ -79,6 +79,8 @@ PROTOS = {
     "jck_cgan_z": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "jck_gp_grad": (i32, [i32, vp, vp, f32, i32, i32, vp, vp]),
     "jck_gp_head2": (i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "jck_gp_head2_conv_ws_floats": (sz, [i32]),
+    "jck_gp_head2_conv": (i32, [i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "jck_bn2_ws_floats": (sz, [i32]),
     "jck_bn2_vchain": (i32, [i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, vp]),
     "jck_bn2_reverse": (i32, [i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, vp]),
@@ -89,6 +91,7 @@ PROTOS = {
     "jck_adam": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, i32, f32, vp]),
     "jck_engine_create": (i32, [C.POINTER(vp), i32, i32, i32]),
     "jck_engine_create_sized": (i32, [C.POINTER(vp), i32, i32, i32, i32]),
+    "jck_engine_create_ex": (i32, [C.POINTER(vp), i32, i32, i32, i32, C.c_uint]),
     "jck_engine_image_size": (i32, [vp]),
     "jck_engine_num_tensors_of": (i32, [vp, i32]),
     "jck_engine_tensor_info_of": (i32, [vp, i32, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),

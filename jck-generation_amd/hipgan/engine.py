@@ -17,6 +17,7 @@ from ._lib import PREC_BF16, PREC_BF16X3, PREC_F32, JckError, StepInputs, cur_st
 PHASE_LAZY_JOIN = 0x100
 PHASE_GP_ONLY = 10                 # include/jckgan.h: the gradient penalty alone (module path)
 PHASE_NO_RESIDENT = 0x200          # include/jckgan.h: no grid-barrier launch in this phase call (a collective may be holding CUs)
+ENGINE_GP_BACKWARD = 1             # include/jckgan.h: JCK_ENGINE_GP_BACKWARD
 _PREC = {"bf16": PREC_BF16, "f32": PREC_F32, "bf16x3": PREC_BF16X3, PREC_BF16: PREC_BF16, PREC_F32: PREC_F32,
          PREC_BF16X3: PREC_BF16X3}
 SCALAR_NAMES = ("loss_d", "loss_g", "d_x", "d_gz1", "d_gz2", "gp", "loss_real", "loss_fake")
@@ -97,10 +98,13 @@ class DcganEngine:
 
     family = 0
 
-    def __init__(self, batch, prec="bf16", device="cuda:0", share=None, image_size=64):
+    def __init__(self, batch, prec="bf16", device="cuda:0", share=None, image_size=64, gp_backward=False):
         """share: another DcganEngine whose arenas (weights, gradients, Adam moments, BN statistics) this one binds
         too - used for the ragged last batch of an epoch, which needs its own workspace geometry but the same state.
-        image_size: 64 = the reference's nets; 128 = one more stride-2 stage (DCGAN only, BASELINE.json configs[4])."""
+        image_size: 64 = the reference's nets; 128 = one more stride-2 stage (DCGAN only, BASELINE.json configs[4]).
+        gp_backward (DCGAN; a `share=` engine inherits it): back-propagate the gradient penalty into D as the CGAN step does -
+        D's step then descends on error_real + error_fake + 10 * gp.  Default False = the reference, which only logs the penalty
+        (train/dcgan_trainer.py:178-179).  CGAN engines always back-propagate it."""
         if not torch.cuda.is_available():
             raise JckError("DcganEngine needs a GPU: the HIP path has no CPU fallback")
         self.device = torch.device(device) if share is None else share.device
@@ -110,6 +114,7 @@ class DcganEngine:
         self.prec = _PREC[prec] if share is None else share.prec
         self.batch = batch
         self.size = image_size if share is None else share.size
+        self.gp_backward = (bool(gp_backward) if share is None else share.gp_backward) or self.family == 1
         self._shared = share._shared if share is not None else {"t": 0, "version": 0, "last_step": 0}
         self._packed_version = -1
         # hipGraph replay of the step (JCK_GRAPH=1 enables): one captured graph per (segment, step parity, input kind).
@@ -131,7 +136,8 @@ class DcganEngine:
         self._graph_cache, self._sbuf, self._st, self._eager_steps = {}, None, None, 0
         h = C.c_void_p()
         dll = load_library()
-        if dll.jck_engine_create_sized(C.byref(h), self.family, self.prec, batch, self.size) != 0:
+        flags = ENGINE_GP_BACKWARD if (self.gp_backward and self.family == 0) else 0
+        if dll.jck_engine_create_ex(C.byref(h), self.family, self.prec, batch, self.size, flags) != 0:
             raise JckError(dll.jck_last_error().decode())
         self._h = h
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -586,10 +592,10 @@ class DcganEngine:
             # with the weight-gradient stream itself (include/jckgan.h: JCK_PHASE_LAZY_JOIN)
             lazy = PHASE_LAZY_JOIN if (self.family == 1 and not reduce_d and self.lazy_join) else 0
             lib.jck_engine_phase(h, PHASE_D_LOSS | lazy, C.byref(si), st)
-            if self.family == 0:
+            if not self.gp_backward:
                 handle = reduce_d(self.arenas["d_grads"]) if reduce_d else None
                 lib.jck_engine_phase(h, PHASE_D_GP | (nores if handle is not None else 0), C.byref(si), st)   # the penalty pass overlaps the D all-reduce (no gradients)
-            else:                                                      # CGAN back-propagates the penalty: reduce after it
+            else:                                                      # the penalty is back-propagated: reduce after it
                 lib.jck_engine_phase(h, PHASE_D_GP | lazy, C.byref(si), st)
                 handle = reduce_d(self.arenas["d_grads"]) if reduce_d else None
             if handle is not None:
@@ -657,7 +663,8 @@ class DcganEngine:
 
     def gradient_penalty_pass(self, real, fake, alpha, labels=None, drop_mask=None):
         """PHASE_GP_ONLY on this engine's D weights: -> per-image gradient norms [B] (device fp32 view, valid until the next
-        call).  CGAN engines also leave d(penalty)/d(theta_D) in arenas["d_grads"] (cleared first).  real / fake: [B,3,S,S]
+        call).  CGAN engines and DCGAN engines created with gp_backward=True also leave d(penalty)/d(theta_D) in
+        arenas["d_grads"] (cleared first).  real / fake: [B,3,S,S]
         fp32 device tensors taken as they are, alpha [B]; CGAN: labels int64 one-hot [B,100], drop_mask float keep-mask [B,256]."""
         B, S = self.batch, self.size
         self.join()

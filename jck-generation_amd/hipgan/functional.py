@@ -432,8 +432,8 @@ class _GradientPenalty(Function):
     D's parameters: forward and backward are one PHASE_GP_ONLY call of a step engine that holds D's weights - the forward pass,
     the first backward to the image, and (CGAN) the closed-form double backward through conv, train-mode BatchNorm, LeakyReLU,
     Linear, Dropout and the sigmoid (derivation checked against autograd(create_graph=True) in
-    tests/test_gp_double_backward_math.py).  DCGAN never back-propagates its penalty (train/dcgan_trainer.py:178-179 only logs
-    it): its engine forms the value and the Function returns zero gradients."""
+    tests/test_gp_double_backward_math.py).  DCGAN: the same on an engine created with gp_backward=True (the conv5 + sigmoid head
+    in closed form, tests/test_dcgan_gp_math.py); a value formed on a default DCGAN engine has no gradient path."""
 
     @staticmethod
     def forward(ctx, eng, real, fake, alpha, labels, mask, names, *params):
@@ -446,7 +446,7 @@ class _GradientPenalty(Function):
             norms = eng.gradient_penalty_pass(real, fake, alpha, labels, mask)
             gp = ((norms - 1.0) ** 2).mean()
             gviews = eng.named_views("d", "grads")
-            ctx.grads = [gviews[k].detach().clone().view_as(p) for k, p in zip(names, params)] if eng.family == 1 else None
+            ctx.grads = [gviews[k].detach().clone().view_as(p) for k, p in zip(names, params)] if eng.gp_backward else None
             ctx.shapes = [p.shape for p in params]
         return gp.clone()
 
@@ -454,16 +454,20 @@ class _GradientPenalty(Function):
     @once_differentiable
     def backward(ctx, g):
         if ctx.grads is None:
-            raise JckError("the DCGAN penalty is a logged value only (train/dcgan_trainer.py:178-179): it has no gradient path")
+            raise JckError("this DCGAN penalty was formed without its double backward (no D parameter required grad, grad mode was "
+                           "off, or the engine passed in was not created with gp_backward=True): it has no gradient path")
         return (None,) * 7 + tuple(g * t for t in ctx.grads)
 
 
 def gradient_penalty(model_d, real_data, fake_data, labels=None, alpha=None, drop_mask=None, prec=None, engine=None):
     """`compute_gradient_penalty` of the reference's trainers for the HIP modules, as a tensor that can be back-propagated
-    (CGAN: `error_d = error_real + error_fake + 10 * gp; error_d.backward()`, train/cgan_trainer.py:200-203).
-    model_d: model.CGAN.Discriminator (labels required) or model.DCGAN.Discriminator of this package.  alpha ~ U[0,1) [B,1,1,1]
-    and the Dropout keep-mask (CGAN, p = 0.25) are drawn here when not given.  engine: a step engine to run on (default: one per
-    (module, batch), cached on the module; its D arena is overwritten with the module's weights on every call).
+    (`error_d = error_real + error_fake + 10 * gp; error_d.backward()`: train/cgan_trainer.py:200-203, and the usual WGAN-GP loop
+    around a DCGAN discriminator, whose reference trainer only logs the value).
+    model_d: model.CGAN.Discriminator (labels required) or model.DCGAN.Discriminator of this package (64 or 128).  DCGAN: the
+    double backward runs only when grad mode is on and some parameter of model_d requires grad; otherwise the call is the
+    value-only pass (same launches, same value) and its result has no gradient path.  alpha ~ U[0,1) [B,1,1,1] and the Dropout
+    keep-mask (CGAN, p = 0.25) are drawn here when not given.  engine: a step engine to run on (default: one per (module, batch,
+    whether gradients are formed), cached on the module; its D arena is overwritten with the module's weights on every call).
     BatchNorm running statistics of the module are not moved by this pass (the reference's D(interpolates) call moves them once)."""
     from .engine import CganEngine, DcganEngine
     _need_cuda(real_data, "gradient_penalty")
@@ -472,11 +476,13 @@ def gradient_penalty(model_d, real_data, fake_data, labels=None, alpha=None, dro
     p_ = prec or getattr(model_d, "prec", None) or __import__("os").environ.get("JCKGAN_PREC", "bf16")
     if engine is None:
         cache = model_d.__dict__.setdefault("_jck_gp_engines", {})
-        key = (B, p_, real_data.device.index)
+        back = not cg and torch.is_grad_enabled() and any(p.requires_grad for p in model_d.parameters())
+        key = (B, p_, real_data.device.index) + ((back,) if not cg else ())
         if key not in cache:
             size = getattr(model_d, "image_size", 64)
             cache[key] = (CganEngine(batch=B, prec=p_, device=real_data.device) if cg else
-                          DcganEngine(batch=B, prec=p_, device=real_data.device, **({"image_size": size} if size != 64 else {})))
+                          DcganEngine(batch=B, prec=p_, device=real_data.device, gp_backward=back,
+                                      **({"image_size": size} if size != 64 else {})))
         engine = cache[key]
     if alpha is None:
         alpha = torch.rand(B, 1, 1, 1, device=real_data.device)

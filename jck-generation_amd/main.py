@@ -42,6 +42,9 @@ def get_arg_parse(argv=None):
     p.add_argument("-milr", "--min_learning_rate", type=float, default=1e-4, help="unused, kept for compatibility")
     p.add_argument("-wd", "--weight_decay", type=float, default=5e-4, help="unused, kept for compatibility")
     p.add_argument("-snt", "--nesterov", type=int, default=1, help="unused, kept for compatibility")
+    # not in the namespace unless given (default 0, read by the trainer): the reference's flag set stays as it is
+    p.add_argument("-gpb", "--gp_backward", type=int, choices=(0, 1), default=argparse.SUPPRESS,
+                   help="DCGAN: back-propagate the gradient penalty into D (1); 0 (default) = the reference, which only logs it")
     return p.parse_args(argv)
 
 

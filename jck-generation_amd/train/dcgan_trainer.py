@@ -84,16 +84,20 @@ def _save_png(path, chw, title=None):
 
 
 class DCGANTrainer(Trainer):
-    def __init__(self, args: argparse.Namespace, model_g: nn.Module, model_d: nn.Module, data_pre, prec=None, host_rng=None):
+    def __init__(self, args: argparse.Namespace, model_g: nn.Module, model_d: nn.Module, data_pre, prec=None, host_rng=None,
+                 gp_backward=None):
         """prec: "bf16" (fast, default), "f32" (exact-fp32 parity path) or "bf16x3" (fp32 storage, split-bf16 GEMMs: tracks
         the reference within 1e-3 per step at several times the f32 path's speed); env JCKGAN_PREC.
         host_rng: draw every random tensor from the CPU generator in the reference's order and upload it (bit-identical
-        noise to a CPU run of the reference; env JCKGAN_HOST_RNG=1).  Default: Philox on the device."""
+        noise to a CPU run of the reference; env JCKGAN_HOST_RNG=1).  Default: Philox on the device.
+        gp_backward (default: args.gp_backward, 0): 1 back-propagates the gradient penalty into D (error_d = error_real + error_fake
+        + 10 * gp is what D descends on); 0 is the reference, which computes error_d but never calls backward on it (:178-179)."""
         self.logger = MainLogger(args)
         self.device = require_gpu("DCGANTrainer")
         self.epoch = args.epoch
         self.max_lr = args.max_learning_rate
         self.lambda_gp = 10.0
+        self.gp_backward = bool(int(getattr(args, "gp_backward", 0) if gp_backward is None else gp_backward))
         self.prec = prec or os.environ.get("JCKGAN_PREC", "bf16")
 
         self.host_rng = bool(int(os.environ.get("JCKGAN_HOST_RNG", "0"))) if host_rng is None else host_rng
@@ -121,7 +125,8 @@ class DCGANTrainer(Trainer):
             self.world, self.rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
         self.batch_size = int(getattr(args, "batch_size", 128))
         self.engine = DcganEngine(batch=self.batch_size, prec=self.prec, device=self.device,
-                                  image_size=getattr(self.model_g, "image_size", 64))     # 128: the configs[4] topology
+                                  image_size=getattr(self.model_g, "image_size", 64),     # 128: the configs[4] topology
+                                  gp_backward=self.gp_backward)                           # the tail-batch engines share it
         self.engine.adopt_modules(self.model_g, self.model_d)
         if self.world > 1:
             for key in ("g_params", "d_params", "g_bn", "d_bn"):
