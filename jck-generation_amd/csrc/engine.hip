@@ -7,6 +7,7 @@
 
 #include "ops_internal.hpp"
 #define JCK_BATCHED_DEFAULT 3
+struct jck_engine;
 #define TT (e->T)        /* the engine's channel plan; `e` is the engine in every function below (this inside its members) */
 
 namespace {
@@ -117,7 +118,18 @@ struct Carver {
   }
 };
 
-struct BnBuf { float *stats, *sums, *aux; int slots; };
+struct BnBuf { float *stats, *sums, *aux; int slots; };      // G's BatchNorm buffers of one stage
+
+// D's activations for `cap` batches of B images stored back to back (cap = 1: the set of one pass, 3: the batched schedule's
+// [real | fake | penalty]), or a view of `groups` of them from group `g0` on.  Per stage: conv output y, activation a, gradient g,
+// BatchNorm statistic slots / scale-shift table / backward sums.  Per set: probabilities and logit gradients, and - the penalty
+// pass - the gradient w.r.t. its input image and that gradient's per-image norms.
+struct DActs {
+  void *y[JCK_MAX_STAGES], *a[JCK_MAX_STAGES], *g[JCK_MAX_STAGES], *gx;
+  float *stats[JCK_MAX_STAGES], *aux[JCK_MAX_STAGES], *sums[JCK_MAX_STAGES], *prob, *ds, *norms;
+  int cap, g0, groups;
+  DActs group(const jck_engine* e, int first, int n) const;      // groups [first, first + n) of this set or view
+};
 
 }  // namespace
 
@@ -140,13 +152,10 @@ struct jck_engine {
   float *d_head_wp, *d_head_dwp;
   void *g1_w, *g_up[JCK_MAX_STAGES], *g_down[JCK_MAX_STAGES];
   // activations: three B-image D sets for the per-pass schedules (each pass that may run concurrently has its own)
-  struct DSet { void *y[JCK_MAX_STAGES], *a[JCK_MAX_STAGES], *g[JCK_MAX_STAGES], *gx; BnBuf bn[JCK_MAX_STAGES]; float *prob, *ds, *norms; } dset[3];      // 0: D(fake) and the G-phase pass, 1: penalty pass, 2: D(real) (may overlap the previous step's G phase)
-  void **d_y = dset[0].y, **d_a = dset[0].a, **d_g = dset[0].g;
-  void*& d_gx = dset[0].gx;
-  BnBuf* d_bn = dset[0].bn;
-  float*& prob = dset[0].prob; float*& ds = dset[0].ds; float*& norms = dset[0].norms;
-  // batched D passes (DCGAN): up to 3 batches that share D's weights go through ONE launch per layer, BatchNorm grouped
-  struct BSet { void *y[JCK_MAX_STAGES], *a[JCK_MAX_STAGES], *g[JCK_MAX_STAGES]; float *stats[JCK_MAX_STAGES], *aux[JCK_MAX_STAGES], *sums[JCK_MAX_STAGES]; float *prob, *ds; } bset;
+  DActs dset[3] = {};                   // 0: D(fake) and the G-phase pass, 1: penalty pass, 2: D(real) (may overlap the previous step's G phase)
+  // batched D passes: up to 3 batches that share D's weights go through ONE launch per layer, BatchNorm grouped.  The penalty
+  // group's image gradient and norms go where the per-pass schedule leaves them: bset.gx / .norms are dset[0]'s
+  DActs bset = {};
   int batched = 0;                      // 0: one D pass per batch (batch % 8 != 0, JCK_BATCHED=0), 3: [real | fake | penalty] as ONE 3B pass
   bool gp_done = false;
   long long real_fwd_step = -1;         // step whose D(real) forward already ran (PHASE_D_REAL_FWD), -1: none
@@ -157,7 +166,14 @@ struct jck_engine {
   // side streams: A = weight gradients beside the dgrad chain, B = G forward beside D(real), C = penalty pass beside D(fake)
   hipStream_t sA = nullptr, sB = nullptr, sC = nullptr;
   hipEvent_t evW[JCK_MAX_STAGES] = {}, evWdone = nullptr, evWmid = nullptr, evHead = nullptr, evTail = nullptr, ev0 = nullptr, evF = nullptr, evReal = nullptr, evGP = nullptr;
+  template <typename F> void for_each_side_stream(F f) { for (hipStream_t* p : {&sA, &sB, &sC}) f(*p); }
+  template <typename F> void for_each_event(F f) {
+    for (hipEvent_t* p : {&evWdone, &evWmid, &evHead, &evTail, &ev0, &evF, &evReal, &evGP}) f(*p);
+    for (hipEvent_t& p : evW) f(p);
+  }
   bool overlap = true, gp_inflight = false, defer_join = true;
+  bool wgrad_side = true;               // weight gradients beside the dgrad chain on sA (JCK_WGRAD_SIDE=0: on the main stream)
+  bool head_side = true;                // the head's parameter gradients on sA as well (JCK_HEAD_SIDE=0: on the main stream)
   bool tail_on_side = false, pre_on_side = false;       // PHASE_D_LOSS_A's tail marker sits on sA; PHASE_D_REAL_FWD ran on sA (evReal)
   bool join_pending = false, mid_recorded = false;    // PHASE_LAZY_JOIN: evWdone (and evWmid) recorded on sA, not yet waited for
   // cross-stream hand-overs of the backward: the producing launch completes the event itself (the `done` argument of
@@ -175,8 +191,6 @@ struct jck_engine {
   void *g_z, *g_y[JCK_MAX_STAGES], *g_a[JCK_MAX_STAGES], *g_gr[JCK_MAX_STAGES], *fake_raw, *fake, *g_raw;
   void *real_noisy, *xhat;
   // small buffers
-  unsigned char* zero_d; size_t zero_d_bytes;      // stats + sums of D's 4 layers
-  unsigned char* zero_g; size_t zero_g_bytes;
   BnBuf g_bn[JCK_MAX_STAGES];
   float *acc, *scal_out;                // current-parity views into acc2 / scal2
   float *acc2, *scal2;                  // acc2: [2 parities][8 rows][acc_ld] per-image scalar table (summed by the step tail)
@@ -221,18 +235,20 @@ struct jck_engine {
       g_down[i] = c.take<unsigned char>(bytes((size_t)jck_pad_rows(TT.G_CS[i]) * 16 * jck_pad_chan(TT.G_CB[i])));
     }
     const size_t img = (size_t)B * TT.HW * 4;
-    for (int sI = 0; sI < 3; ++sI) {
-      DSet& D = dset[sI];
+    auto take_set = [&](DActs& D, int cap, bool penalty_out) {
+      D.cap = D.groups = cap; D.g0 = 0;
       for (int i = 0; i < TT.NS; ++i) {
-        const size_t n = (size_t)B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i];
+        const size_t n = (size_t)cap * B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i];
         D.y[i] = c.take<unsigned char>(bytes(n)); D.a[i] = c.take<unsigned char>(bytes(n)); D.g[i] = c.take<unsigned char>(bytes(n));
-        D.bn[i].sums = c.take<float>(jck_bn_bwd_ws_floats(TT.D_CS[i]));
-        D.bn[i].aux = c.take<float>(4 * TT.D_CS[i]);
-        D.bn[i].stats = c.take<float>(jck_stats_floats((long long)B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2), TT.D_CS[i], 1));
+        D.sums[i] = c.take<float>(cap * jck_bn_bwd_ws_floats(TT.D_CS[i]));
+        D.aux[i] = c.take<float>(cap * 4 * TT.D_CS[i]);
+        D.stats[i] = c.take<float>(jck_stats_floats((long long)cap * B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2), TT.D_CS[i], 1));
       }
-      D.gx = c.take<unsigned char>(bytes(img));
-      D.prob = c.take<float>(B); D.ds = c.take<float>(B); D.norms = c.take<float>(B);
-    }
+      if (penalty_out) D.gx = c.take<unsigned char>(bytes(img));
+      D.prob = c.take<float>((size_t)cap * B); D.ds = c.take<float>((size_t)cap * B);
+      if (penalty_out) D.norms = c.take<float>(B);
+    };
+    for (DActs& D : dset) take_set(D, 1, true);
     for (int i = 0; i < TT.NS; ++i) d_rs[i] = c.take<float>(2 * 4 * 2 * TT.D_CS[i]);
     g_z = c.take<unsigned char>(bytes((size_t)B * z_pad(family)));
     // G layer i (0..3): output of conv(i+1) = [B, h, h, C] with (h, C) = (4,512), (8,256), (16,128), (32,64)
@@ -245,28 +261,14 @@ struct jck_engine {
     // real_noisy | fake | xhat are consecutive (img bytes % 256 == 0): the batched D pass reads them as one 3B-image tensor
     real_noisy = c.take<unsigned char>(bytes(img)); fake = c.take<unsigned char>(bytes(img)); xhat = c.take<unsigned char>(bytes(img));
     if (batched) {
-      for (int i = 0; i < TT.NS; ++i) {
-        const size_t n = (size_t)3 * B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i];
-        bset.y[i] = c.take<unsigned char>(bytes(n)); bset.a[i] = c.take<unsigned char>(bytes(n)); bset.g[i] = c.take<unsigned char>(bytes(n));
-        bset.sums[i] = c.take<float>(3 * jck_bn_bwd_ws_floats(TT.D_CS[i]));
-        bset.aux[i] = c.take<float>(3 * 4 * TT.D_CS[i]);
-        bset.stats[i] = c.take<float>(jck_stats_floats((long long)3 * B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2), TT.D_CS[i], 1));
-      }
-      bset.prob = c.take<float>(3 * B); bset.ds = c.take<float>(3 * B);
+      take_set(bset, 3, false);
+      bset.gx = dset[0].gx; bset.norms = dset[0].norms;
     }
-    // zeroed-per-pass regions
-    {
-      size_t start = c.off;
-      zero_d = nullptr; zero_d_bytes = 0;
-      start = c.off;
-      zero_g = base ? base + start : nullptr;
-      for (int i = 0; i < TT.NS; ++i) g_bn[i].sums = c.take<float>(jck_bn_bwd_ws_floats(TT.G_C1 >> i));
-      zero_g_bytes = c.off - start;
-      for (int i = 0; i < TT.NS; ++i) {
-        const int C = TT.G_C1 >> i, h = 4 << i;
-        g_bn[i].aux = c.take<float>(4 * C);
-        g_bn[i].stats = c.take<float>(jck_stats_floats((long long)B * h * h, C, i == 0 ? 16 : 1));
-      }
+    for (int i = 0; i < TT.NS; ++i) g_bn[i].sums = c.take<float>(jck_bn_bwd_ws_floats(TT.G_C1 >> i));
+    for (int i = 0; i < TT.NS; ++i) {
+      const int C = TT.G_C1 >> i, h = 4 << i;
+      g_bn[i].aux = c.take<float>(4 * C);
+      g_bn[i].stats = c.take<float>(jck_stats_floats((long long)B * h * h, C, i == 0 ? 16 : 1));
     }
     acc_ld = (B + 63) / 64 * 64;
     acc2 = c.take<float>((size_t)2 * 8 * acc_ld); scal2 = c.take<float>(16);
@@ -336,6 +338,45 @@ struct jck_engine {
 };
 
 
+DActs DActs::group(const jck_engine* e, int first, int n) const {
+  DActs v = *this;
+  v.g0 = g0 + first; v.groups = n;
+  const size_t B = (size_t)e->B;
+  auto at = [&](void* p, size_t elems) { return (void*)((unsigned char*)p + elems * e->esz); };
+  for (int i = 0; i < TT.NS; ++i) {
+    const int cs = TT.D_CS[i];
+    const size_t px = (size_t)(TT.D_HB[i] / 2) * (TT.D_HB[i] / 2), off = first * B * px * cs;
+    v.y[i] = at(y[i], off); v.a[i] = at(a[i], off); v.g[i] = at(g[i], off);
+    v.aux[i] = aux[i] + (size_t)first * 4 * cs;
+    v.sums[i] = sums[i] + (size_t)first * jck_bn_bwd_ws_floats(cs);
+    // statistic slots of a group start at its 1/cap point of the buffer (sized for cap * B images at one slot per 32 pixels)
+    v.stats[i] = stats[i] + (size_t)first * (jck_stats_floats((long long)(cap * B * px), cs, 1) / cap / (2 * cs)) * (2 * cs);
+  }
+  v.prob = prob + first * B; v.ds = ds + first * B;
+  return v;
+}
+
+// a schedule switch: on unless the variable is set to 0
+static bool env_on(const char* name) {
+  const char* v = getenv(name);
+  return !(v && atoi(v) == 0);
+}
+// the side streams and events of an overlapping engine (at creation, and again after an aborted capture)
+static int create_side_streams(jck_engine* e) {
+  hipError_t rc = hipSuccess;
+  e->for_each_side_stream([&](hipStream_t& s) { if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&s, hipStreamNonBlocking); });      // queue priorities measured neutral (r1-r4)
+  e->for_each_event([&](hipEvent_t& ev) { if (rc == hipSuccess) rc = hipEventCreateWithFlags(&ev, jck_event_flags()); });
+  HIPCHK(rc);
+  return JCK_OK;
+}
+static void destroy_side_streams(jck_engine* e, bool sync) {
+  e->for_each_side_stream([&](hipStream_t& s) {
+    if (s) { if (sync) (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    s = nullptr;
+  });
+  e->for_each_event([](hipEvent_t& ev) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; });
+}
+
 extern "C" int jck_engine_create(jck_engine** out, int family, int prec, int batch) {
   return jck_engine_create_sized(out, family, prec, batch, 64);
 }
@@ -356,44 +397,32 @@ extern "C" int jck_engine_create_ex(jck_engine** out, int family, int prec, int 
   e->family = family; e->prec = prec; e->B = batch; e->esz = prec_f32_storage(prec) ? 4 : 2;
   e->T = make_topo(image_size);
   e->LG = make_layout(family, 0, image_size); e->LD = make_layout(family, 1, image_size);
-  e->overlap = !(getenv("JCK_OVERLAP") && atoi(getenv("JCK_OVERLAP")) == 0);
+  e->overlap = env_on("JCK_OVERLAP");
   // batched D passes need whole tiles per group: 16*B rows at the last layer, tiles of up to 128 rows
   e->batched = getenv("JCK_BATCHED") ? atoi(getenv("JCK_BATCHED")) : JCK_BATCHED_DEFAULT;
   if (!e->overlap || batch % 8 != 0 || e->batched != 3) e->batched = 0;
   e->gp_bwd = family == 0 && (flags & JCK_ENGINE_GP_BACKWARD);        // CGAN back-propagates its penalty anyway
   e->carve(nullptr);
-  e->ext_events = !(getenv("JCK_EXT_EVENTS") && atoi(getenv("JCK_EXT_EVENTS")) == 0);
-  e->bn_res = !(getenv("JCK_BN_RES") && atoi(getenv("JCK_BN_RES")) == 0);
-  e->cbuf_direct = family == 1 && !(getenv("JCK_CBUF_DIRECT") && atoi(getenv("JCK_CBUF_DIRECT")) == 0);
-  e->head_fuse = !(getenv("JCK_HEAD_FUSE") && atoi(getenv("JCK_HEAD_FUSE")) == 0);
-  e->real_side = !(getenv("JCK_REAL_SIDE") && atoi(getenv("JCK_REAL_SIDE")) == 0);
-  e->fold_zero = !(getenv("JCK_FOLD_ZERO") && atoi(getenv("JCK_FOLD_ZERO")) == 0);
-  e->fuse_tanh = !(getenv("JCK_FUSE_TANH") && atoi(getenv("JCK_FUSE_TANH")) == 0);
-  if (e->overlap) {
-    hipStream_t* ss[3] = {&e->sA, &e->sB, &e->sC};
-    for (auto pp : ss) HIPCHK(hipStreamCreateWithFlags(pp, hipStreamNonBlocking));      // queue priorities measured neutral (r1-r4)
-    hipEvent_t* ev[8 + JCK_MAX_STAGES] = {&e->evWdone, &e->evWmid, &e->evHead, &e->evTail, &e->ev0, &e->evF, &e->evReal, &e->evGP};
-    for (int i = 0; i < JCK_MAX_STAGES; ++i) ev[8 + i] = &e->evW[i];
-    for (auto p : ev) HIPCHK(hipEventCreateWithFlags(p, jck_event_flags()));
-  }
+  e->wgrad_side = env_on("JCK_WGRAD_SIDE");
+  e->head_side = env_on("JCK_HEAD_SIDE");
+  e->ext_events = env_on("JCK_EXT_EVENTS");
+  e->bn_res = env_on("JCK_BN_RES");
+  e->cbuf_direct = family == 1 && env_on("JCK_CBUF_DIRECT");
+  e->head_fuse = env_on("JCK_HEAD_FUSE");
+  e->real_side = env_on("JCK_REAL_SIDE");
+  e->fold_zero = env_on("JCK_FOLD_ZERO");
+  e->fuse_tanh = env_on("JCK_FUSE_TANH");
+  if (e->overlap) JCK_TRY(create_side_streams(e));
   *out = e;
   return JCK_OK;
 }
 extern "C" void jck_engine_destroy(jck_engine* e) {
   if (!e) return;
-  if (e->overlap) {
-    hipStream_t ss[3] = {e->sA, e->sB, e->sC};
-    for (auto p : ss) if (p) { (void)hipStreamSynchronize(p); (void)hipStreamDestroy(p); }
-    hipEvent_t ev[8 + JCK_MAX_STAGES] = {e->evWdone, e->evWmid, e->evHead, e->evTail, e->ev0, e->evF, e->evReal, e->evGP};
-    for (int i = 0; i < JCK_MAX_STAGES; ++i) ev[8 + i] = e->evW[i];
-    for (auto p : ev) if (p) (void)hipEventDestroy(p);
-  }
+  if (e->overlap) destroy_side_streams(e, true);
   delete e;
 }
 extern "C" int jck_engine_num_tensors(int family, int net) { return (int)make_layout(family, net).t.size(); }
-extern "C" int jck_engine_tensor_info(int family, int net, int idx, char* name, int name_cap, int* kind, long long* offset,
-                                      long long* numel, int* shape4) {
-  NetLayout L = make_layout(family, net);
+static int tensor_info(const NetLayout& L, int idx, char* name, int name_cap, int* kind, long long* offset, long long* numel, int* shape4) {
   if (idx < 0 || idx >= (int)L.t.size()) JCK_FAIL(JCK_E_ARG, "index out of range");
   const TensorInfo& t = L.t[idx];
   if (name && name_cap > 0) { strncpy(name, t.name, name_cap - 1); name[name_cap - 1] = 0; }
@@ -403,29 +432,21 @@ extern "C" int jck_engine_tensor_info(int family, int net, int idx, char* name, 
   if (shape4) for (int q_ = 0; q_ < 4; ++q_) shape4[q_] = t.shape[q_];
   return JCK_OK;
 }
-extern "C" long long jck_engine_arena_numel(int family, int net, int which) {
-  NetLayout L = make_layout(family, net);
-  return which == 0 ? L.n_params : L.n_bn;
+static long long arena_numel(const NetLayout& L, int which) { return which == 0 ? L.n_params : L.n_bn; }
+extern "C" int jck_engine_tensor_info(int family, int net, int idx, char* name, int name_cap, int* kind, long long* offset,
+                                      long long* numel, int* shape4) {
+  return tensor_info(make_layout(family, net), idx, name, name_cap, kind, offset, numel, shape4);
 }
+extern "C" long long jck_engine_arena_numel(int family, int net, int which) { return arena_numel(make_layout(family, net), which); }
 // the same three queries for a created engine (its own image size)
 extern "C" int jck_engine_num_tensors_of(const jck_engine* e, int net) { return e ? (int)(net == 0 ? e->LG : e->LD).t.size() : 0; }
 extern "C" int jck_engine_tensor_info_of(const jck_engine* e, int net, int idx, char* name, int name_cap, int* kind, long long* offset,
                                          long long* numel, int* shape4) {
   if (!e) JCK_FAIL(JCK_E_ARG, "null engine");
-  const NetLayout& L = net == 0 ? e->LG : e->LD;
-  if (idx < 0 || idx >= (int)L.t.size()) JCK_FAIL(JCK_E_ARG, "index out of range");
-  const TensorInfo& t = L.t[idx];
-  if (name && name_cap > 0) { strncpy(name, t.name, name_cap - 1); name[name_cap - 1] = 0; }
-  if (kind) *kind = t.kind;
-  if (offset) *offset = t.offset;
-  if (numel) *numel = t.numel;
-  if (shape4) for (int q_ = 0; q_ < 4; ++q_) shape4[q_] = t.shape[q_];
-  return JCK_OK;
+  return tensor_info(net == 0 ? e->LG : e->LD, idx, name, name_cap, kind, offset, numel, shape4);
 }
 extern "C" long long jck_engine_arena_numel_of(const jck_engine* e, int net, int which) {
-  if (!e) return 0;
-  const NetLayout& L = net == 0 ? e->LG : e->LD;
-  return which == 0 ? L.n_params : L.n_bn;
+  return e ? arena_numel(net == 0 ? e->LG : e->LD, which) : 0;
 }
 extern "C" int jck_engine_image_size(const jck_engine* e) { return e ? e->T.S : 0; }
 extern "C" size_t jck_engine_workspace_bytes(const jck_engine* e) { return e ? e->ws_bytes : 0; }
@@ -512,33 +533,45 @@ extern "C" int jck_engine_repack(jck_engine* e, int net, void* stream) {
 static const float BN_MOM = 0.1f, BN_EPS = 1e-5f, LRELU = 0.2f;
 
 
-typedef jck_engine::DSet DSet;
+// `ws` work enqueued after this starts behind everything on `st` so far: on `side` when there is one (the hand-over goes through
+// evW[k]; record = false: the last launch on st completes that event itself), else on st
+static int fork_side(jck_engine* e, int k, hipStream_t st, hipStream_t side, hipStream_t* ws, bool record = true) {
+  *ws = st;
+  if (!side) return JCK_OK;
+  if (record) HIPCHK(hipEventRecord(e->evW[k], st));
+  HIPCHK(hipStreamWaitEvent(side, e->evW[k], 0));
+  *ws = side;
+  return JCK_OK;
+}
 
-// conv stack of D on activation set `D`; BatchNorm running statistics are NOT touched here: (mean, unbiased var) go to the
-// deferred record of `pass` (0 real, 1 fake, 2 penalty, 3 G phase) and are applied in that order at the end of the step,
-// which keeps the result bitwise independent of how the passes overlap on streams.
-// to_cbuf (CGAN): the last layer's activation goes to rows [0, B) of the head's concat buffer instead of D.a (cg_head_forward then
-// has nothing to copy)
-static int d_convs_forward(jck_engine* e, DSet& D, const void* x_in, int B, int pass, hipStream_t st, bool to_cbuf = false) {
+// conv stack of D for the groups of view `S` (x_in = first image of its first group): ONE launch per layer for all of them,
+// BatchNorm statistics per group (= per batch, train/dcgan_trainer.py:162,173,118).  BatchNorm running statistics are NOT touched
+// here: (mean, unbiased var) of group g go to the deferred record of pass `pass0 + g` (g counted in the set: 0 real, 1 fake,
+// 2 penalty; 3 G phase) and are applied in that order at the end of the step, which keeps the result bitwise independent of how the
+// passes overlap on streams.
+// to_cbuf (CGAN): the last layer's activation goes to the groups' rows of the head's concat buffer instead of S.a (cg_head_forward
+// then has nothing to copy)
+static int d_convs_forward(jck_engine* e, const DActs& S, const void* x_in, int B, int pass0, hipStream_t st, bool to_cbuf = false) {
+  const int n = S.groups;
   const void* in = x_in;
   for (int i = 0; i < TT.NS; ++i) {
     const int hb = TT.D_HB[i], cs = TT.D_CS[i];
     const long long rows = (long long)B * (hb / 2) * (hb / 2);
-    JCK_TRY(jck_conv_down_grouped(e->prec, in, e->d_down[i], D.y[i], D.bn[i].stats, &D.bn[i].slots, B, hb, hb, TT.D_CB[i], cs, B, st));
+    float* rec = e->d_rs[i] + ((size_t)e->parity * 4 + pass0 + S.g0) * 2 * cs;
+    int slots = 0;
+    JCK_TRY(jck_conv_down_grouped(e->prec, in, e->d_down[i], S.y[i], S.stats[i], &slots, n * B, hb, hb, TT.D_CB[i], cs, B, st));
+    if (slots % n) JCK_FAIL(JCK_E_ARG, "batched D pass: statistic slots do not split by group");
     const bool cb = to_cbuf && i == TT.NS - 1;
+    void* out = cb ? (unsigned char*)e->cbuf + (size_t)S.g0 * B * L1_KPAD * e->esz : S.a[i];
     bool fused = false;                           // finalize + apply as one launch where the statistics rows are few (ops.hip)
-    JCK_TRY(bn_fwd_fused(e->prec, D.y[i], D.bn[i].stats, D.bn[i].slots, (float)rows, e->P(e->LD, e->dp, NWN[i]), e->P(e->LD, e->dp, NBN[i]), BN_EPS,
-                         LRELU, cb ? e->cbuf : D.a[i], D.bn[i].aux, e->d_rs[i] + ((size_t)e->parity * 4 + pass) * 2 * cs, nullptr, nullptr, nullptr,
-                         BN_MOM, rows, cs, 1, cb ? TT.FEAT : 0, cb ? L1_KPAD : 0, st, &fused));
+    JCK_TRY(bn_fwd_fused(e->prec, S.y[i], S.stats[i], slots / n, (float)rows, e->P(e->LD, e->dp, NWN[i]), e->P(e->LD, e->dp, NBN[i]), BN_EPS, LRELU, out,
+                         S.aux[i], rec, nullptr, nullptr, nullptr, BN_MOM, rows, cs, n, cb ? TT.FEAT : 0, cb ? L1_KPAD : 0, st, &fused));
     if (!fused) {
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(cs / 4), dim3(256), 0, st, D.bn[i].stats, D.bn[i].slots, (float)rows,
-                       e->P(e->LD, e->dp, NWN[i]), e->P(e->LD, e->dp, NBN[i]), (float*)nullptr, (float*)nullptr,
-                       (long long*)nullptr, BN_MOM, BN_EPS, D.bn[i].aux, cs, e->d_rs[i] + ((size_t)e->parity * 4 + pass) * 2 * cs);
-    HIPCHK(hipGetLastError());
-    if (cb) JCK_TRY(bn_act_fwd_pitched(e->prec, D.y[i], D.bn[i].aux, LRELU, e->cbuf, rows, cs, 1, TT.FEAT, L1_KPAD, st));
-    else JCK_TRY(jck_bn_act_fwd(e->prec, D.y[i], D.bn[i].aux, LRELU, D.a[i], rows, cs, st));
+      JCK_TRY(jck_bn_finalize_grouped(S.stats[i], slots / n, (float)rows, e->P(e->LD, e->dp, NWN[i]), e->P(e->LD, e->dp, NBN[i]), BN_EPS, S.aux[i], rec,
+                                      cs, n, st));
+      JCK_TRY(bn_act_fwd_pitched(e->prec, S.y[i], S.aux[i], LRELU, out, rows, cs, n, cb ? TT.FEAT : 0, cb ? L1_KPAD : 0, st));
     }
-    in = D.a[i];
+    in = S.a[i];
   }
   return JCK_OK;
 }
@@ -569,16 +602,16 @@ static int cg_head_middle(jck_engine* e, int B, int G, const float* targets, con
                      slot_p, e->acc_ld, e->g_hd, e->g_h, st);
 }
 
-static int d_forward(jck_engine* e, DSet& D, const void* x_in, int B, int pass, const float* drop_mask, hipStream_t st, bool head_finish = true) {
+static int d_forward(jck_engine* e, DActs& D, const void* x_in, int B, int pass, const float* drop_mask, hipStream_t st, bool head_finish = true) {
   const bool direct = e->family == 1 && e->cbuf_direct;
   JCK_TRY(d_convs_forward(e, D, x_in, B, pass, st, direct));
-  if (e->family == 1) return cg_head_forward(e, direct ? nullptr : e->d_a[TT.NS - 1], B, drop_mask, st, 0, head_finish);
+  if (e->family == 1) return cg_head_forward(e, direct ? nullptr : D.a[TT.NS - 1], B, drop_mask, st, 0, head_finish);
   return JCK_OK;
 }
 
-// sigmoid head + loss (mode 0) or + d(sum p)/dlogit (mode 1); fills e->prob / e->ds
+// sigmoid head + loss (mode 0) or + d(sum p)/dlogit (mode 1); fills D.prob / D.ds
 // g_out (family 0, optional): conv5's input gradient ds[n] * w from the same launch
-static int d_head(jck_engine* e, DSet& D, int B, float target, int mode, int slot_loss, int slot_p, hipStream_t st, void* g_out = nullptr) {
+static int d_head(jck_engine* e, DActs& D, int B, float target, int mode, int slot_loss, int slot_p, hipStream_t st, void* g_out = nullptr) {
   if (e->family == 0)
     return head_fwd_grouped_ev(e->prec, D.a[TT.NS - 1], e->d_head_wp, nullptr, B, TT.FEAT, 1, &target, &mode, D.prob, D.ds, e->acc, &slot_loss,
                                &slot_p, e->acc_ld, g_out, st, nullptr);
@@ -586,10 +619,10 @@ static int d_head(jck_engine* e, DSet& D, int B, float target, int mode, int slo
                       mode, D.prob, D.ds, e->acc, slot_loss, slot_p, e->acc_ld, st);
 }
 
-// head backward from ds (device float[B]) down to the gradient w.r.t. a4 in e->d_g[3] (or `ga4_out`).
+// head backward from ds (device float[B]) down to the gradient w.r.t. a4 in `ga4_out`.
 // side (family 1, optional): the parameter gradients run there (see cg_head_backward_batched)
 // mid_done: g_hd and g_h are in place (cg_head_middle)
-static int d_head_backward(jck_engine* e, DSet& D, const float* ds, int B, bool want_wgrad, const float* drop_mask, void* ga4_out, hipStream_t st,
+static int d_head_backward(jck_engine* e, DActs& D, const float* ds, int B, bool want_wgrad, const float* drop_mask, void* ga4_out, hipStream_t st,
                            hipStream_t side = nullptr, bool mid_done = false) {
   if (e->family == 0)       // mid_done: the input gradient is in place (d_head with g_out)
     return jck_head_bwd_conv(e->prec, ds, e->d_head_wp, D.a[TT.NS - 1], B, TT.G_C1, mid_done ? nullptr : ga4_out,
@@ -602,13 +635,7 @@ static int d_head_backward(jck_engine* e, DSet& D, const float* ds, int B, bool 
   void *g_hd = hb(e->g_hd, w0, L1_OUT), *g_h = hb(e->g_h, w0, L1_OUT), *gc = hb(e->gc, w0, L1_KPAD);
   const float* pre_e = e->pre_e + r0 * EMB;
   hipStream_t ws = st;
-  auto fork = [&](int k) -> int {                     // `ws` work enqueued from here on starts behind everything on st so far
-    if (!side || !want_wgrad) return JCK_OK;
-    HIPCHK(hipEventRecord(e->evW[k], st));
-    HIPCHK(hipStreamWaitEvent(side, e->evW[k], 0));
-    ws = side;
-    return JCK_OK;
-  };
+  auto fork = [&](int k) { return fork_side(e, k, st, side, &ws); };
   const float* w2 = e->P(e->LD, e->dp, "linear2.weight");
   if (!mid_done) JCK_TRY(jck_head_bwd(e->prec, ds, w2, h_drop, B, L1_OUT, g_hd, nullptr, 1, e->head_ws, st));
   if (want_wgrad) {
@@ -643,13 +670,7 @@ static int cg_head_backward_batched(jck_engine* e, const float* ds, int B, const
   const int R3 = 3 * B, R2 = 2 * B;
   const float* w2 = e->P(e->LD, e->dp, "linear2.weight");
   hipStream_t ws = st;
-  auto fork = [&](int k) -> int {                     // `ws` work enqueued from here on starts behind everything on st so far
-    if (!side) return JCK_OK;
-    HIPCHK(hipEventRecord(e->evW[k], st));
-    HIPCHK(hipStreamWaitEvent(side, e->evW[k], 0));
-    ws = side;
-    return JCK_OK;
-  };
+  auto fork = [&](int k) { return fork_side(e, k, st, side, &ws); };
   if (!mid_done) JCK_TRY(jck_head_bwd(e->prec, ds, w2, e->h_drop, R3, L1_OUT, e->g_hd, nullptr, 1, e->head_ws, st));
   if (!mid_done) {        // (with the middle in one launch both forks start at the same point: one hand-over)
     JCK_TRY(fork(0));
@@ -672,102 +693,40 @@ static int cg_head_backward_batched(jck_engine* e, const float* ds, int B, const
   return jck_split_rows(e->prec, e->gc, L1_KPAD, TT.FEAT, ga4_out, R3, st);
 }
 
-// D backward on set `D`.  With `side` != nullptr the weight-gradient products run on that stream beside the dgrad chain
-// (both only READ gy_i and the saved activations); the main stream waits for them before returning.
-// resident = false: the pass runs beside another pass of the step on a second stream.  Two resident BatchNorm launches in flight
-// at once would share the engine's barrier words and could each hold CUs the other's missing workgroups need: such a pass takes
-// the three-launch form.
 // xe (G's loss pass): the input gradient is wanted only as the operand of the tanh + noise-mix backward of G's output - that
 // product rides in the epilogue of the launch that computes it (conv_up_tanh_bwd_ev) when the layer runs on the image-side kernel
 struct XgradEpi { const void* tanh_y; float scale; void* out; hipEvent_t done; bool fused; };
-static int d_backward(jck_engine* e, DSet& D, const void* x_in, int B, bool want_wgrad, bool want_xgrad, const float* drop_mask,
-                      hipStream_t st, hipStream_t side, bool join = true, bool resident = true, XgradEpi* xe = nullptr, bool head_mid_done = false) {
-  JCK_TRY(d_head_backward(e, D, D.ds, B, want_wgrad, drop_mask, D.g[TT.NS - 1], st, nullptr, head_mid_done));
-  const bool par = want_wgrad && side != nullptr;
+// What a backward pass through D's conv stack does beside the dgrad chain
+struct DBackward {
+  int gw = 1;                   // the first gw groups contribute weight gradients (0: no parameter gradient is wanted)
+  hipStream_t side = nullptr;   // the weight-gradient products run on this stream beside the dgrad chain (both only READ gy_i and the
+                                // saved activations)
+  // join = false: the caller's NEXT backward with a side stream (or its own join) orders the main stream behind these weight
+  // gradients - nothing on the main stream reads them before the optimiser step.  lazy_join (JCK_PHASE_LAZY_JOIN): the side stream
+  // is marked, whoever comes next waits
+  bool join = true, lazy_join = false;
+  // part 0: the whole pass.  part 1 / 2 (data parallel, PHASE_D_LOSS_A / _B): up to and including the weight gradient of the LAST
+  // layer (joined into `st`: the tail of D's gradient arena - conv4.weight, norm4.*, conv5.weight - is then final in `st` order and
+  // its all-reduce can start) / everything after it
+  int part = 0;
+  // resident = false: the pass runs beside another pass of the step on a second stream.  Two resident BatchNorm launches in flight
+  // at once would share the engine's barrier words and could each hold CUs the other's missing workgroups need: such a pass takes
+  // the three-launch form
+  bool resident = true;
+  bool xgrad = false;           // the gradient w.r.t. the input image of the LAST group -> S.gx ...
+  XgradEpi* xe = nullptr;       // ... or into the epilogue above
+  bool gp_norm = false;         // ... and its per-image norms -> S.norms (the penalty pass)
+};
+// Backward of D's conv stack for the groups of `S` whose gradients w.r.t. the top activation are in S.g[NS - 1] (x_in = first image
+// of the first group): BatchNorm backward grouped, ONE dgrad launch per layer over all groups, ONE weight-gradient launch per
+// layer over the first o.gw groups.
+static int d_convs_backward(jck_engine* e, const DActs& S, const void* x_in, int B, hipStream_t st, const DBackward& o) {
+  const int G = S.groups, gw = o.gw;
+  hipStream_t side = gw > 0 ? o.side : nullptr;
   for (int i = TT.NS - 1; i >= 0; --i) {
     const int hb = TT.D_HB[i], cs = TT.D_CS[i], cb = TT.D_CB[i];
     const long long rows = (long long)B * (hb / 2) * (hb / 2);
-    float* dgam = want_wgrad ? e->P(e->LD, e->dg, NWN[i]) : nullptr;
-    float* dbet = want_wgrad ? e->P(e->LD, e->dg, NBN[i]) : nullptr;
-    // the launch that writes g_y hands it to the weight-gradient stream by completing evW[i] itself
-    hipEvent_t done = par && e->ext_events ? e->evW[i] : nullptr;
-    JCK_TRY(bn_act_bwd_res_ev(e->prec, D.g[i], D.y[i], D.bn[i].aux, LRELU, D.bn[i].sums, D.g[i], dgam, dbet, rows, cs, 1, 1,
-                              e->bn_res && resident ? e->gsync : nullptr, st, done));
-    const void* big = i == 0 ? x_in : D.a[i - 1];
-    if (want_wgrad) {
-      hipStream_t ws = st;
-      if (par) { if (!done) HIPCHK(hipEventRecord(e->evW[i], st)); HIPCHK(hipStreamWaitEvent(side, e->evW[i], 0)); ws = side; }
-      JCK_TRY(jck_conv_wgrad(e->prec, D.g[i], big, e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, B, hb, hb, cb, cs, ws));
-    }
-    if (i > 0)
-      JCK_TRY(jck_conv_up(e->prec, D.g[i], e->d_up[i], D.g[i - 1], nullptr, nullptr, 0, B, hb / 2, hb / 2, cs, cb, st));
-    else if (want_xgrad) {
-      if (xe) JCK_TRY(conv_up_tanh_bwd_ev(e->prec, D.g[0], e->d_up[0], xe->tanh_y, xe->scale, xe->out, B, hb / 2, hb / 2, cs, cb, st, xe->done, &xe->fused));
-      if (!xe || !xe->fused)
-        JCK_TRY(jck_conv_up(e->prec, D.g[0], e->d_up[0], D.gx, nullptr, nullptr, 0, B, hb / 2, hb / 2, cs, cb, st));
-    }
-  }
-  // join = false: the caller's NEXT d_backward/g_backward with a side stream (or its own join) orders the main stream
-  // behind these weight gradients - nothing on the main stream reads them before the optimiser step
-  if (par && join) { HIPCHK(hipEventRecord(e->evWdone, side)); HIPCHK(hipStreamWaitEvent(st, e->evWdone, 0)); }
-  return JCK_OK;
-}
-
-// D forward + backward on G batches stored back to back from `x_in` (real_noisy | fake | xhat are consecutive): ONE launch
-// per layer and direction instead of G, BatchNorm statistics per group (= per batch, as in the separate passes,
-// train/dcgan_trainer.py:162,173,118).  Groups [0, G-1) are loss passes (targets / accumulator slots given per group) and
-// contribute weight gradients; the LAST group is the penalty pass (head mode 1, gradient w.r.t. its input image -> dset[0].gx,
-// norms -> dset[0].norms).  Group g writes BatchNorm record pass0 + g.  Weight gradients run on `side`.
-// forward of the conv stack for groups [g0, g0 + n) of the batched set (x_in = first image of group g0); own slot range
-static int d_batched_forward(jck_engine* e, const void* x_in, int B, int g0, int n, int pass0, hipStream_t st, bool to_cbuf = false) {
-  auto& S = e->bset;
-  const size_t esz = e->esz;
-  auto at = [&](void* p, size_t elems) { return (void*)((unsigned char*)p + elems * esz); };
-  const void* in = x_in;
-  for (int i = 0; i < TT.NS; ++i) {
-    const int hb = TT.D_HB[i], cs = TT.D_CS[i];
-    const long long rows = (long long)B * (hb / 2) * (hb / 2);
-    // statistic slots of group g0 start at the g0/3 point of the buffer (sized for 3B pixels at one slot per 32 pixels)
-    float* stats = S.stats[i] + (size_t)g0 * (jck_stats_floats((long long)3 * B * (hb / 2) * (hb / 2), cs, 1) / 3 / (2 * cs)) * (2 * cs);
-    int slots = 0;
-    JCK_TRY(jck_conv_down_grouped(e->prec, in, e->d_down[i], at(S.y[i], (size_t)g0 * rows * cs), stats, &slots, n * B, hb, hb, TT.D_CB[i], cs, B, st));
-    if (slots % n) JCK_FAIL(JCK_E_ARG, "batched D pass: statistic slots do not split by group");
-    const bool cb = to_cbuf && i == TT.NS - 1;      // CGAN: rows [g0 * B, (g0 + n) * B) of the head's concat buffer
-    bool fused = false;
-    JCK_TRY(bn_fwd_fused(e->prec, at(S.y[i], (size_t)g0 * rows * cs), stats, slots / n, (float)rows, e->P(e->LD, e->dp, NWN[i]), e->P(e->LD, e->dp, NBN[i]),
-                         BN_EPS, LRELU, cb ? at(e->cbuf, (size_t)g0 * B * L1_KPAD) : at(S.a[i], (size_t)g0 * rows * cs), S.aux[i] + (size_t)g0 * 4 * cs,
-                         e->d_rs[i] + ((size_t)e->parity * 4 + pass0 + g0) * 2 * cs, nullptr, nullptr, nullptr, BN_MOM, rows, cs, n, cb ? TT.FEAT : 0,
-                         cb ? L1_KPAD : 0, st, &fused));
-    if (!fused) {
-    JCK_TRY(jck_bn_finalize_grouped(stats, slots / n, (float)rows, e->P(e->LD, e->dp, NWN[i]), e->P(e->LD, e->dp, NBN[i]),
-                                    BN_EPS, S.aux[i] + (size_t)g0 * 4 * cs, e->d_rs[i] + ((size_t)e->parity * 4 + pass0 + g0) * 2 * cs, cs, n, st));
-    if (cb)
-      JCK_TRY(bn_act_fwd_pitched(e->prec, at(S.y[i], (size_t)g0 * rows * cs), S.aux[i] + (size_t)g0 * 4 * cs, LRELU,
-                                 at(e->cbuf, (size_t)g0 * B * L1_KPAD), rows, cs, n, TT.FEAT, L1_KPAD, st));
-    else
-      JCK_TRY(jck_bn_act_fwd_grouped(e->prec, at(S.y[i], (size_t)g0 * rows * cs), S.aux[i] + (size_t)g0 * 4 * cs, LRELU,
-                                     at(S.a[i], (size_t)g0 * rows * cs), rows, cs, n, st));
-    }
-    in = at(S.a[i], (size_t)g0 * rows * cs);
-  }
-  return JCK_OK;
-}
-
-// Backward of the conv stack for G groups whose gradients w.r.t. a4 are in bset.g[3]: BatchNorm backward grouped, ONE dgrad
-// launch per layer over all groups, ONE weight-gradient launch per layer over the first gw groups (on `side` when given),
-// and - xgrad_last - the gradient w.r.t. the input image of the LAST group -> dset[0].gx.  Joins `side` before returning.
-// part 0: the whole pass.  part 1 / 2 (data parallel, PHASE_D_LOSS_A / _B): up to and including the weight gradient of the LAST
-// layer (joined into `st`: the tail of D's gradient arena - conv4.weight, norm4.*, conv5.weight - is then final in `st` order and
-// its all-reduce can start) / everything after it.
-static int d_batched_backward(jck_engine* e, const void* x_in, int B, int G, int gw, bool xgrad_last, hipStream_t st, hipStream_t side,
-                              bool with_gp_norm = false, int part = 0, bool lazy_join = false) {
-  auto& S = e->bset;
-  const size_t esz = e->esz;
-  auto at = [&](void* p, size_t elems) { return (void*)((unsigned char*)p + elems * esz); };
-  for (int i = TT.NS - 1; i >= 0; --i) {
-    const int hb = TT.D_HB[i], cs = TT.D_CS[i], cb = TT.D_CB[i];
-    const long long rows = (long long)B * (hb / 2) * (hb / 2);
-    const bool resume = part == 2 && i == TT.NS - 1;      // part 2 starts at this layer's dgrad
+    const bool resume = o.part == 2 && i == TT.NS - 1;      // part 2 starts at this layer's dgrad
     // The bottom layer's weight gradient is the last product of the pass and nothing but the penalty's image gradient runs
     // beside it (37 us of the main stream waiting for it in round 3).  Its operand is the gradient of the LOSS groups only:
     // their BatchNorm backward goes first, the weight gradient starts behind it on the second stream, and the penalty
@@ -777,53 +736,63 @@ static int d_batched_backward(jck_engine* e, const void* x_in, int B, int G, int
     const bool split0 = !resume && i == 0 && e->bn_res && e->prec == JCK_PREC_BF16 && gw > 0 && gw < G;
     hipEvent_t done = side && e->ext_events && !resume ? e->evW[i] : nullptr;    // the launch that writes g_y completes evW[i] itself
     if (!resume)
-      JCK_TRY(bn_act_bwd_res_ev(e->prec, S.g[i], S.y[i], S.aux[i], LRELU, S.sums[i], S.g[i], e->P(e->LD, e->dg, NWN[i]),
-                                e->P(e->LD, e->dg, NBN[i]), rows, cs, split0 ? gw : G, gw, e->bn_res ? e->gsync : nullptr, st, done));
-    const void* big = i == 0 ? x_in : S.a[i - 1];
-    if (!resume) {
-      hipStream_t ws = st;
-      if (side) { if (!done) HIPCHK(hipEventRecord(e->evW[i], st)); HIPCHK(hipStreamWaitEvent(side, e->evW[i], 0)); ws = side; }
-      JCK_TRY(jck_conv_wgrad(e->prec, S.g[i], big, e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, gw * B, hb, hb, cb, cs, ws));
+      JCK_TRY(bn_act_bwd_res_ev(e->prec, S.g[i], S.y[i], S.aux[i], LRELU, S.sums[i], S.g[i], gw ? e->P(e->LD, e->dg, NWN[i]) : nullptr,
+                                gw ? e->P(e->LD, e->dg, NBN[i]) : nullptr, rows, cs, split0 ? gw : G, gw,
+                                e->bn_res && o.resident ? e->gsync : nullptr, st, done));
+    if (!resume && gw) {
+      hipStream_t ws;
+      JCK_TRY(fork_side(e, i, st, side, &ws, !done));
+      JCK_TRY(jck_conv_wgrad(e->prec, S.g[i], i == 0 ? x_in : S.a[i - 1], e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, gw * B, hb, hb, cb,
+                             cs, ws));
     }
-    if (split0)
-      JCK_TRY(bn_act_bwd_res_ev(e->prec, at(S.g[i], (size_t)gw * rows * cs), at(S.y[i], (size_t)gw * rows * cs), S.aux[i] + (size_t)gw * 4 * cs, LRELU,
-                                S.sums[i] + (size_t)gw * jck_bn_bwd_ws_floats(cs), at(S.g[i], (size_t)gw * rows * cs), nullptr, nullptr, rows, cs,
-                                G - gw, 0, e->gsync, st, nullptr));
-    if (part == 1) {
+    if (split0) {
+      const DActs P = S.group(e, gw, G - gw);
+      JCK_TRY(bn_act_bwd_res_ev(e->prec, P.g[i], P.y[i], P.aux[i], LRELU, P.sums[i], P.g[i], nullptr, nullptr, rows, cs, G - gw, 0, e->gsync, st, nullptr));
+    }
+    if (o.part == 1) {
       // evTail: the tail of D's gradient arena is final behind it (jck_engine_order_after_tail); lazy_join: st does not wait
       HIPCHK(hipEventRecord(e->evTail, side ? side : st));
       e->tail_on_side = side != nullptr;
-      if (side && !lazy_join) HIPCHK(hipStreamWaitEvent(st, e->evTail, 0));
+      if (side && !o.lazy_join) HIPCHK(hipStreamWaitEvent(st, e->evTail, 0));
       return JCK_OK;
     }
     if (i > 0)
       JCK_TRY(jck_conv_up(e->prec, S.g[i], e->d_up[i], S.g[i - 1], nullptr, nullptr, 0, G * B, hb / 2, hb / 2, cs, cb, st));
-    else if (xgrad_last)
-      JCK_TRY(jck_conv_up(e->prec, at(S.g[0], (size_t)(G - 1) * rows * cs), e->d_up[0], e->d_gx, nullptr, nullptr, 0, B, hb / 2, hb / 2, cs, cb, st));
+    else if (o.xgrad) {
+      const void* g0 = S.group(e, G - 1, 1).g[0];
+      if (o.xe) JCK_TRY(conv_up_tanh_bwd_ev(e->prec, g0, e->d_up[0], o.xe->tanh_y, o.xe->scale, o.xe->out, B, hb / 2, hb / 2, cs, cb, st, o.xe->done, &o.xe->fused));
+      if (!o.xe || !o.xe->fused) JCK_TRY(jck_conv_up(e->prec, g0, e->d_up[0], S.gx, nullptr, nullptr, 0, B, hb / 2, hb / 2, cs, cb, st));
+    }
   }
   // the penalty's norm does not need the weight gradients: it runs while the side stream finishes the last of them
-  if (with_gp_norm) JCK_TRY(jck_gp_norm(e->prec, e->d_gx, B, TT.HW, e->acc, 6, e->acc_ld, e->norms, st));
-  if (side) {
+  if (o.gp_norm) JCK_TRY(jck_gp_norm(e->prec, S.gx, B, TT.HW, e->acc, 6, e->acc_ld, S.norms, st));
+  if (side && o.join) {
     HIPCHK(hipEventRecord(e->evWdone, side));
-    if (lazy_join) { e->join_pending = true; e->mid_recorded = false; }      // JCK_PHASE_LAZY_JOIN: whoever comes next waits
+    if (o.lazy_join) { e->join_pending = true; e->mid_recorded = false; }
     else HIPCHK(hipStreamWaitEvent(st, e->evWdone, 0));
   }
   return JCK_OK;
 }
+// one pass's backward on its set `D`: the head from D.ds down to the gradient w.r.t. a4, then the conv stack
+static int d_backward(jck_engine* e, DActs& D, const void* x_in, int B, const float* drop_mask, hipStream_t st, const DBackward& o,
+                      bool head_mid_done = false) {
+  JCK_TRY(d_head_backward(e, D, D.ds, B, o.gw > 0, drop_mask, D.g[TT.NS - 1], st, nullptr, head_mid_done));
+  return d_convs_backward(e, D, x_in, B, st, o);
+}
 
-// Heads + backward of G batches stored back to back from `x_in` (real_noisy | fake | xhat are consecutive) after
-// d_batched_forward has filled every group: ONE launch per layer and direction instead of G, BatchNorm statistics per
-// group (= per batch, as in the separate passes, train/dcgan_trainer.py:162,173,118).  Groups [0, G-1) are loss passes
-// (targets / accumulator slots given per group) and contribute weight gradients; the LAST group is the penalty pass (head
-// mode 1, gradient w.r.t. its input image -> dset[0].gx, norms -> dset[0].norms).  Weight gradients run on `side`.
+// DCGAN's D forward (unless forward_done: d_convs_forward has filled every group), heads and backward on the G batches stored
+// back to back from `x_in` (real_noisy | fake | xhat are consecutive): ONE launch per layer and direction instead of G.  Groups
+// [0, G-1) are loss passes (targets / accumulator slots given per group) and contribute weight gradients; the LAST group is the
+// penalty pass (head mode 1, gradient w.r.t. its input image -> dset[0].gx, norms -> dset[0].norms).  Group g writes BatchNorm
+// record pass0 + g.  Weight gradients run on `side`.
 static int d_batched_pass(jck_engine* e, const void* x_in, int B, int G, int pass0, const float* targets, const int* slot_loss,
                           const int* slot_p, hipStream_t st, hipStream_t side, bool forward_done = false, int part = 0, bool lazy_tail = false) {
-  auto& S = e->bset;
-  const size_t esz = e->esz;
+  const DActs S = e->bset.group(e, 0, G);
   const int gw = G - 1;
-  if (part == 2) return d_batched_backward(e, x_in, B, G, gw, true, st, side, true, 2);
-  auto at = [&](void* p, size_t elems) { return (void*)((unsigned char*)p + elems * esz); };
-  if (!forward_done) JCK_TRY(d_batched_forward(e, x_in, B, 0, G, pass0, st));
+  DBackward bw;
+  bw.gw = gw; bw.side = side; bw.xgrad = bw.gp_norm = true; bw.part = part; bw.lazy_join = part == 1 && lazy_tail;
+  if (part == 2) return d_convs_backward(e, S, x_in, B, st, bw);
+  if (!forward_done) JCK_TRY(d_convs_forward(e, S, x_in, B, pass0, st));
   {
     float tg[4] = {0.f, 0.f, 0.f, 0.f};
     int md[4] = {0, 0, 0, 0}, sl[4] = {-1, -1, -1, -1}, sp[4] = {-1, -1, -1, -1};
@@ -838,8 +807,7 @@ static int d_batched_pass(jck_engine* e, const void* x_in, int B, int G, int pas
   }
   // loss groups (input + weight gradient) and the penalty group (input gradient only), one launch
   // (the ordered sum of conv5's weight-gradient rows is wanted by the optimiser only: weight-gradient stream, 10 us off the main one)
-  static const bool head_side = !(getenv("JCK_HEAD_SIDE") && atoi(getenv("JCK_HEAD_SIDE")) == 0);
-  const bool hs = side && e->ext_events && head_side;
+  const bool hs = side && e->ext_events && e->head_side;
   if (e->head_fuse) {
     const bool hf = side && e->ext_events;
     JCK_TRY(head_bwd_conv2_ev(e->prec, S.ds, e->d_head_wp, S.a[TT.NS - 1], gw * B, 0, TT.G_C1, nullptr, e->P(e->LD, e->dg, CWN[TT.NS]),
@@ -847,50 +815,23 @@ static int d_batched_pass(jck_engine* e, const void* x_in, int B, int G, int pas
   } else
     JCK_TRY(head_bwd_conv2_ev(e->prec, S.ds, e->d_head_wp, S.a[TT.NS - 1], gw * B, B, TT.G_C1, S.g[TT.NS - 1], e->P(e->LD, e->dg, CWN[TT.NS]),
                               e->head_ws, st, hs ? side : nullptr, hs ? e->evHead : nullptr));
-  JCK_TRY(d_batched_backward(e, x_in, B, G, gw, true, st, side, true, part, part == 1 && lazy_tail));
-  return JCK_OK;
+  return d_convs_backward(e, S, x_in, B, st, bw);
 }
 
 // The back-propagated gradient penalty (train/cgan_trainer.py:200-203; DCGAN with JCK_ENGINE_GP_BACKWARD).  Precondition: the GP forward and first backward
-// have run (d_forward(xhat), d_head(mode 1), d_backward(wgrad=false, xgrad=true)), so d_g[i] = gy_i, d_bn[i].sums = first-
-// backward sums, g_h = gradient at the Linear(8392,256) output, d_gx = g_x, norms = ||g_x[n]||.  Accumulates
+// have run (d_forward(xhat), d_head(mode 1), d_backward(gw = 0, xgrad)), so P.g[i] = gy_i, P.sums[i] = first-
+// backward sums, g_h = gradient at the Linear(8392,256) output, P.gx = g_x, P.norms = ||g_x[n]||.  Accumulates
 // lambda * dGP/dtheta into D's gradient arena.  Derivation + fp64 check: tests/test_gp_double_backward_math.py.
 // `side` (optional): the weight-gradient products run there beside the v-chain / reverse sweep; they share the split-K
 // workspace, so everything that uses it is ordered on that one stream, and the main stream joins it before the reverse sweep
 // (which overwrites the v_i the v-chain products read and runs the Linear weight gradient on the main stream) and at the end.
-// where the penalty pass left its forward / first-backward tensors: activation set 0 (per-pass schedule) or the last group
-// of the batched set
-// (activation set 1: DCGAN's per-pass penalty pass on its own stream; gx / norms: the image gradient and its per-image norms)
-struct GpSrc { const void *y[JCK_MAX_STAGES], *a[JCK_MAX_STAGES], *g[JCK_MAX_STAGES], *gx; const float *aux[JCK_MAX_STAGES], *sums[JCK_MAX_STAGES], *prob, *norms; };
-static GpSrc gp_src_dset(jck_engine* e, int s) {
-  GpSrc r;
-  DSet& D = e->dset[s];
-  for (int i = 0; i < TT.NS; ++i) { r.y[i] = D.y[i]; r.a[i] = D.a[i]; r.g[i] = D.g[i]; r.aux[i] = D.bn[i].aux; r.sums[i] = D.bn[i].sums; }
-  r.prob = D.prob; r.gx = D.gx; r.norms = D.norms;
-  return r;
-}
-static GpSrc gp_src_group(jck_engine* e, int g, int B) {
-  GpSrc r;
-  auto& S = e->bset;
-  for (int i = 0; i < TT.NS; ++i) {
-    const size_t off = (size_t)g * B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i] * e->esz;
-    r.y[i] = (const unsigned char*)S.y[i] + off; r.a[i] = (const unsigned char*)S.a[i] + off; r.g[i] = (const unsigned char*)S.g[i] + off;
-    r.aux[i] = S.aux[i] + (size_t)g * 4 * TT.D_CS[i];
-    r.sums[i] = S.sums[i] + (size_t)g * jck_bn_bwd_ws_floats(TT.D_CS[i]);
-  }
-  r.prob = S.prob + (size_t)g * B; r.gx = e->d_gx; r.norms = e->norms;
-  return r;
-}
-
-static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, int B, float lambda, const float* drop_mask, hipStream_t st,
+// P: where the penalty pass left its forward / first-backward tensors, image gradient and norms - the set of a per-pass penalty
+// pass (set 1: DCGAN's on its own stream), or the last group of the batched set
+static int gp_double_backward(jck_engine* e, const DActs& P, const void* xhat, int B, float lambda, const float* drop_mask, hipStream_t st,
                               hipStream_t side = nullptr, bool lazy_join = false) {
   const size_t esz = e->esz;
-  auto fork = [&](int k) -> hipStream_t {            // work enqueued on the returned stream starts after everything on st so far
-    if (!side) return st;
-    (void)hipEventRecord(e->evW[k], st);
-    (void)hipStreamWaitEvent(side, e->evW[k], 0);
-    return side;
-  };
+  hipStream_t ws = st;
+  auto fork = [&](int k) { return fork_side(e, k, st, side, &ws); };
   auto join = [&]() {
     if (!side) return;
     (void)hipEventRecord(e->evWdone, side);
@@ -921,7 +862,8 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
     const int hb = TT.D_HB[i], cs = TT.D_CS[i], cb = TT.D_CB[i];
     const long long rows = (long long)B * (hb / 2) * (hb / 2);
     // g_{a_{i-1}} = convT(gy_i; W_i):  dW_i += wgrad(gy_i, u_{i-1}),  v_i = conv(u_{i-1}; W_i)
-    JCK_TRY(jck_conv_wgrad(e->prec, P.g[i], u, e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, B, hb, hb, cb, cs, fork(i)));
+    JCK_TRY(fork(i));
+    JCK_TRY(jck_conv_wgrad(e->prec, P.g[i], u, e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, B, hb, hb, cb, cs, ws));
     JCK_TRY(jck_conv_down(e->prec, u, e->d_down[i], e->d_v[i], nullptr, nullptr, B, hb, hb, cb, cs, st));
     JCK_TRY(jck_bn2_vchain(e->prec, e->d_v[i], P.y[i], P.g[i], P.aux[i], P.sums[i], e->P(e->LD, e->dp, NWN[i]),
                            LRELU, e->bn2_ws[i], e->d_v[i], e->d_xdir[i], e->P(e->LD, e->dg, NWN[i]), rows, cs, st));
@@ -938,7 +880,8 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
   } else {
     // head: gc[:, :8192] = gh W1 -> adj(gh) = [u4 | 0] W1^T, dW1 += gh^T [u4 | 0]; gh = gh' * m/(1-p); gh' = ds w2; ds = p(1-p)
     JCK_TRY(jck_concat_rows(e->prec, e->d_v[TT.NS - 1], TT.FEAT, e->cbuf2, L1_KPAD, B, st));          // tail columns of cbuf2 stay zero
-    JCK_TRY(jck_linear_wgrad(e->prec, gh1, L1_OUT, e->cbuf2, L1_KPAD, e->wg_ws, e->wg_ws_bytes, e->gw1p, 1, B, L1_OUT, fork(0)));
+    JCK_TRY(fork(0));
+    JCK_TRY(jck_linear_wgrad(e->prec, gh1, L1_OUT, e->cbuf2, L1_KPAD, e->wg_ws, e->wg_ws_bytes, e->gw1p, 1, B, L1_OUT, ws));
     // What the reverse sweep must wait for are the v-chain's products (they read the v_i it overwrites): the weight-gradient stream is
     // marked HERE, behind the last of them - not after the head's parameter gradients, which are forked to it below and which nothing
     // on the main stream waits for before the optimiser
@@ -948,8 +891,7 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
     if (!fuse) JCK_TRY(jck_linear_finish(e->prec, e->l1_slab, L1_KSPLIT, nullptr, drop_mask, 1.0f / 0.75f, nullptr, e->ughd, B, L1_OUT, st));
     // (the head's parameter gradients - the dw2 sum here, linear2 / linear1 / the label embedding in d_head_backward below: ~75 us of
     // launches that only the optimiser waits for - go to the weight-gradient stream; JCK_HEAD_SIDE=0 keeps them on the main one)
-    static const bool head_side = !(getenv("JCK_HEAD_SIDE") && atoi(getenv("JCK_HEAD_SIDE")) == 0);
-    hipStream_t hs = head_side && e->ext_events ? side : nullptr;
+    hipStream_t hs = e->head_side && e->ext_events ? side : nullptr;
     if (fuse) {
       // g_hd / g_h rows [head_wrow0, + B): not the rows the v-chain's Linear weight gradient reads (the penalty group's, or the copy)
       const size_t w0 = (size_t)e->head_wrow0 * L1_OUT * esz;
@@ -971,7 +913,8 @@ static int gp_double_backward(jck_engine* e, const GpSrc& P, const void* xhat, i
     JCK_TRY(jck_bn2_reverse(e->prec, e->d_v[i], P.y[i], e->d_xdir[i], P.aux[i], e->P(e->LD, e->dp, NWN[i]), e->bn2_ws[i],
                             LRELU, e->bn2_ws_rev, e->d_v[i], e->P(e->LD, e->dg, NWN[i]), e->P(e->LD, e->dg, NBN[i]), rows, cs, st));
     const void* big = i == 0 ? xhat : P.a[i - 1];
-    JCK_TRY(jck_conv_wgrad(e->prec, e->d_v[i], big, e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, B, hb, hb, cb, cs, fork(i)));
+    JCK_TRY(fork(i));
+    JCK_TRY(jck_conv_wgrad(e->prec, e->d_v[i], big, e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, B, hb, hb, cb, cs, ws));
     // everything but the bottom conv weight's gradient is final on the side stream here (lazy join: the optimiser phase starts
     // behind this point and takes that one tensor last)
     if (side && lazy_join && i == 1) { (void)hipEventRecord(e->evWmid, side); e->mid_recorded = true; }
@@ -1140,9 +1083,9 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
     if (!in->labels) JCK_FAIL(JCK_E_ARG, "CGAN phases need labels");
     e->cur_labels = in->labels;
   }
-  DSet& D0 = e->dset[0];
-  DSet& D1 = e->dset[1];
-  DSet& DR = cg ? e->dset[0] : e->dset[2];          // D(real): own set so it may run beside the previous step's G phase
+  DActs& D0 = e->dset[0];
+  DActs& D1 = e->dset[1];
+  DActs& DR = cg ? e->dset[0] : e->dset[2];          // D(real): own set so it may run beside the previous step's G phase
   e->parity = in->step & 1;
   // eager callers that did not call jck_engine_set_step: the step's scalars / Philox words are written by its first phase
   // (a phase called with another learning rate than the step's earlier phases - separate G and D rates - rewrites the Adam
@@ -1162,24 +1105,23 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
   // weight gradients beside the dgrad chain on a second stream: +8 % for DCGAN in round 1, +1.5 % now; CGAN +1.4 % (2.886 vs
   // 2.929 ms eager, round 3).  JCK_WGRAD_SIDE=0 keeps them on the main stream.  A captured step keeps everything on one stream
   // either way (below).
-  static const bool wgrad_side = !(getenv("JCK_WGRAD_SIDE") && atoi(getenv("JCK_WGRAD_SIDE")) == 0);
   // Under a stream capture everything stays on the capturing stream: a hipGraph with parallel branches makes the ROCm 7.2
   // runtime keep per-graph side streams, costs ~7 us of host time per node at launch, ran slower than the linear graph for
   // CGAN, and its hipGraphLaunch reads past the end of the graph's stream pool whenever two of those streams share the launch
   // stream's hardware queue (hip::Graph::UpdateStreams; cause and frame in DESIGN.md section 5.6; jck_engine_capture_end refuses
   // any non-linear graph).  Same kernels, same order per stream as the eager schedule - bitwise the same results.
   const bool par = e->overlap && !e->capturing;
-  hipStream_t sA = (par && wgrad_side) ? e->sA : nullptr;
+  hipStream_t sA = (par && e->wgrad_side) ? e->sA : nullptr;
   const bool ov_g = par, ov_gp = par && !cg;
-  auto penalty_pass = [&](DSet& D, hipStream_t s) -> int {                                      // :110-127, 178
+  auto penalty_pass = [&](DActs& D, hipStream_t s) -> int {                                      // :110-127, 178
     JCK_TRY(jck_interp(e->prec, e->real_noisy, e->fake, in->alpha, e->xhat, B, HW, s));
     JCK_TRY(d_forward(e, D, e->xhat, B, 2, in->drop_mask[2], s));
     JCK_TRY(d_head(e, D, B, 0.f, 1, -1, -1, s));
-    // DCGAN's per-pass schedule runs this pass on its own stream beside D(fake): three-launch BatchNorm backward (d_backward),
+    // DCGAN's per-pass schedule runs this pass on its own stream beside D(fake): three-launch BatchNorm backward (DBackward),
     // whatever the stream layout of this call (a captured one-stream step stays launch for launch the eager one)
-    JCK_TRY(d_backward(e, D, e->xhat, B, false, true, in->drop_mask[2], s, nullptr, true, cg));
-    JCK_TRY(jck_gp_norm(e->prec, D.gx, B, HW, e->acc, 6, e->acc_ld, D.norms, s));
-    return JCK_OK;
+    DBackward bw;
+    bw.gw = 0; bw.resident = cg; bw.xgrad = bw.gp_norm = true;
+    return d_backward(e, D, e->xhat, B, in->drop_mask[2], s, bw);
   };
   switch (phase) {
     case JCK_PHASE_D_LOSS_A:
@@ -1203,17 +1145,17 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
         const bool direct = head3 && e->cbuf_direct;
         // D(real)'s conv stack beside G's forward, [fake | penalty] as a 2B forward behind it (see the DCGAN branch below)
         const bool split = e->real_side, beside = split && sA;
+        const DActs& S = e->bset;
         hipStream_t sr = beside ? sA : st;
         if (beside) { HIPCHK(hipEventRecord(e->ev0, st)); HIPCHK(hipStreamWaitEvent(sA, e->ev0, 0)); }
         JCK_TRY(prep_real(e, in, B, sr));
-        if (split) JCK_TRY(d_batched_forward(e, e->real_noisy, B, 0, 1, 0, sr, direct));
+        if (split) JCK_TRY(d_convs_forward(e, S.group(e, 0, 1), e->real_noisy, B, 0, sr, direct));
         if (beside) HIPCHK(hipEventRecord(e->evReal, sA));
         JCK_TRY(g_forward(e, in->z, in->labels, B, st, in->z == e->rz[in->step & 1] && e->gz_step == (long long)in->step));
         if (beside) HIPCHK(hipStreamWaitEvent(st, e->evReal, 0));
         JCK_TRY(e->mix_fake_noise_interp(in, B, st));     // :171, :111-113
-        if (split) JCK_TRY(d_batched_forward(e, e->fake, B, 1, 2, 0, st, direct));
-        else JCK_TRY(d_batched_forward(e, e->real_noisy, B, 0, 3, 0, st, direct));
-        auto& S = e->bset;
+        if (split) JCK_TRY(d_convs_forward(e, S.group(e, 1, 2), e->fake, B, 0, st, direct));
+        else JCK_TRY(d_convs_forward(e, S, e->real_noisy, B, 0, st, direct));
         const float tg[2] = {0.9f, 0.1f};
         e->head_row0 = 0;
         const bool fuse = head3 && e->head_fuse;
@@ -1228,21 +1170,22 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
         }
         for (int g = 0; g < 3 && !head3; ++g) {
           const bool pen = g == 2;
-          void* a4 = (unsigned char*)S.a[TT.NS - 1] + (size_t)g * B * TT.FEAT * e->esz;
-          void* g4 = (unsigned char*)S.g[TT.NS - 1] + (size_t)g * B * TT.FEAT * e->esz;
+          const DActs Sg = S.group(e, g, 1);
+          void *a4 = Sg.a[TT.NS - 1], *g4 = Sg.g[TT.NS - 1];
           if (!head3) JCK_TRY(cg_head_forward(e, a4, B, in->drop_mask[g], st));
           const void* hd = (const unsigned char*)e->h_drop + (head3 ? (size_t)g * B * L1_OUT * e->esz : 0);
           JCK_TRY(jck_head_fwd(e->prec, hd, e->P(e->LD, e->dp, "linear2.weight"), e->P(e->LD, e->dp, "linear2.bias"), B, L1_OUT,
-                               pen ? 0.f : tg[g], pen ? 1 : 0, S.prob + g * B, S.ds + g * B, e->acc, pen ? -1 : g, pen ? -1 : 3 + g, e->acc_ld, st));
-          if (!head3) JCK_TRY(d_head_backward(e, e->dset[0], S.ds + g * B, B, !pen, in->drop_mask[g], g4, st));
+                               pen ? 0.f : tg[g], pen ? 1 : 0, Sg.prob, Sg.ds, e->acc, pen ? -1 : g, pen ? -1 : 3 + g, e->acc_ld, st));
+          if (!head3) JCK_TRY(d_head_backward(e, e->dset[0], Sg.ds, B, !pen, in->drop_mask[g], g4, st));
         }
         if (head3) {
-          static const bool head_side = !(getenv("JCK_HEAD_SIDE") && atoi(getenv("JCK_HEAD_SIDE")) == 0);
-          JCK_TRY(cg_head_backward_batched(e, S.ds, B, in->drop_mask[0], S.g[TT.NS - 1], st, head_side ? sA : nullptr, fuse));
+          JCK_TRY(cg_head_backward_batched(e, S.ds, B, in->drop_mask[0], S.g[TT.NS - 1], st, e->head_side ? sA : nullptr, fuse));
           e->head_row0 = 2 * B;                        // where PHASE_D_GP finds the penalty group's head state
           e->head_wrow0 = 0;
         }
-        JCK_TRY(d_batched_backward(e, e->real_noisy, B, 3, 2, true, st, sA, true, 0, lazy));
+        DBackward bw;
+        bw.gw = 2; bw.side = sA; bw.xgrad = bw.gp_norm = true; bw.lazy_join = lazy;
+        JCK_TRY(d_convs_backward(e, S, e->real_noisy, B, st, bw));
         e->gp_done = true;
         return JCK_OK;
       }
@@ -1274,14 +1217,14 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
         hipStream_t sr = beside ? sA : st;
         if (beside) { HIPCHK(hipEventRecord(e->ev0, st)); HIPCHK(hipStreamWaitEvent(sA, e->ev0, 0)); }
         if (!pre) JCK_TRY(prep_real(e, in, B, sr));                                               // :160
-        if (!pre && split) JCK_TRY(d_batched_forward(e, e->real_noisy, B, 0, 1, 0, sr));          // :162
+        if (!pre && split) JCK_TRY(d_convs_forward(e, e->bset.group(e, 0, 1), e->real_noisy, B, 0, sr));      // :162
         if (beside) HIPCHK(hipEventRecord(e->evReal, sA));
         JCK_TRY(g_forward(e, in->z, in->labels, B, st, in->z == e->rz[in->step & 1] && e->gz_step == (long long)in->step));                                          // :168-169
         if (beside || pre_side) HIPCHK(hipStreamWaitEvent(st, e->evReal, 0));
         JCK_TRY(e->mix_fake_noise_interp(in, B, st));                                             // :171, :111-113
         const float tg[2] = {0.9f, 0.1f};
         const int sl[2] = {0, 1}, sp[2] = {3, 4};
-        if (split) JCK_TRY(d_batched_forward(e, e->fake, B, 1, 2, 0, st));                        // :173, 118 as one 2B forward
+        if (split) JCK_TRY(d_convs_forward(e, e->bset.group(e, 1, 2), e->fake, B, 0, st));          // :173, 118 as one 2B forward
         JCK_TRY(d_batched_pass(e, e->real_noisy, B, 3, 0, tg, sl, sp, st, sA, split, part, lazy_tail));      // :162-176, 178
         if (part == 0) e->gp_done = true;
         return JCK_OK;
@@ -1311,8 +1254,9 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
         JCK_TRY(d_head(e, DR, B, 0.9f, 0, 0, 3, st));                                             // :163,165
         // D(real)'s weight gradients stay in flight on sA while D(fake) starts (own activation set); D(fake)'s backward
         // queues behind them on sA and joins.  PHASE_D_REAL alone (pipeline mode) and CGAN (shared set) join here.
-        JCK_TRY(d_backward(e, DR, e->real_noisy, B, true, false, in->drop_mask[0], st, sA,
-                           phase == JCK_PHASE_D_REAL || cg || !e->defer_join));                                     // :164 (cgan :203)
+        DBackward bw;
+        bw.side = sA; bw.join = phase == JCK_PHASE_D_REAL || cg || !e->defer_join;
+        JCK_TRY(d_backward(e, DR, e->real_noisy, B, in->drop_mask[0], st, bw));                   // :164 (cgan :203)
         if (phase == JCK_PHASE_D_REAL) return JCK_OK;
       }
       // ---- D on the fake batch (:170-176) with the penalty pass (:178) beside it
@@ -1327,8 +1271,9 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
       }
       JCK_TRY(d_forward(e, D0, e->fake, B, 1, in->drop_mask[1], st));                             // :173
       JCK_TRY(d_head(e, D0, B, 0.1f, 0, 1, 4, st));                                               // :174,176
-      JCK_TRY(d_backward(e, D0, e->fake, B, true, false, in->drop_mask[1], st, sA));              // :175
-      return JCK_OK;
+      DBackward bw;
+      bw.side = sA;
+      return d_backward(e, D0, e->fake, B, in->drop_mask[1], st, bw);                             // :175
     }
     case JCK_PHASE_D_REAL_FWD: {
       // forward half of D(real) of step in->step, ahead of its PHASE_D_LOSS: touches only real_noisy and group 0 of the batched
@@ -1341,7 +1286,7 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
       hipStream_t sr = (e->real_side && sA) ? sA : st;
       if (sr != st) { HIPCHK(hipEventRecord(e->ev0, st)); HIPCHK(hipStreamWaitEvent(sr, e->ev0, 0)); }
       JCK_TRY(prep_real(e, in, B, sr));                                                           // :160
-      JCK_TRY(d_batched_forward(e, e->real_noisy, B, 0, 1, 0, sr));                               // :162
+      JCK_TRY(d_convs_forward(e, e->bset.group(e, 0, 1), e->real_noisy, B, 0, sr));             // :162
       if (sr != st) HIPCHK(hipEventRecord(e->evReal, sr));
       e->pre_on_side = sr != st;
       e->real_fwd_step = in->step;
@@ -1365,14 +1310,14 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
       JCK_TRY(jck_img_prep(e->prec, in->real_nchw, nullptr, 1.0f, 0.0f, e->real_noisy, B, HW, st));
       JCK_TRY(jck_img_prep(e->prec, in->noise_real, nullptr, 1.0f, 0.0f, e->fake, B, HW, st));
       JCK_TRY(penalty_pass(D0, st));
-      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, gp_src_dset(e, 0), e->xhat, B, 1.0f, in->drop_mask[2], st, nullptr));
+      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, D0, e->xhat, B, 1.0f, in->drop_mask[2], st, nullptr));
       return JCK_OK;
     }
     case JCK_PHASE_D_GP: {
       if (!in->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP needs alpha");
       if (e->gp_done && (cg || e->gp_bwd)) {          // forward and first backward ran as group 2 of the batched pass
         e->gp_done = false;
-        JCK_TRY(gp_double_backward(e, gp_src_group(e, 2, B), e->xhat, B, 10.0f, in->drop_mask[2], st, sA, lazy));
+        JCK_TRY(gp_double_backward(e, e->bset.group(e, 2, 1), e->xhat, B, 10.0f, in->drop_mask[2], st, sA, lazy));
         if (!(lazy && sA)) e->join_pending = e->mid_recorded = false;      // it joined the stream itself
         e->head_row0 = 0;
         return JCK_OK;
@@ -1381,12 +1326,12 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
       if (e->gp_inflight) {                           // started in PHASE_D_LOSS: join (JCK_ENGINE_GP_BACKWARD: and back-propagate it)
         HIPCHK(hipStreamWaitEvent(st, e->evGP, 0));
         e->gp_inflight = false;
-        if (e->gp_bwd) JCK_TRY(gp_double_backward(e, gp_src_dset(e, 1), e->xhat, B, 10.0f, nullptr, st, sA));
+        if (e->gp_bwd) JCK_TRY(gp_double_backward(e, D1, e->xhat, B, 10.0f, nullptr, st, sA));
         return JCK_OK;
       }
       JCK_TRY(penalty_pass(D0, st));
       // CGAN back-propagates the penalty (train/cgan_trainer.py:200-203); DCGAN when created with JCK_ENGINE_GP_BACKWARD
-      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, gp_src_dset(e, 0), e->xhat, B, 10.0f, in->drop_mask[2], st, sA));
+      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, D0, e->xhat, B, 10.0f, in->drop_mask[2], st, sA));
       return JCK_OK;
     }
     case JCK_PHASE_D_STEP: {                                                                      // :180
@@ -1428,7 +1373,9 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
       } else JCK_TRY(d_head(e, D0, B, 0.9f, 0, 2, 5, st));
       // D's own weight gradients from this pass are dead (zeroed at :155 before they are read): skipped
       XgradEpi xe = {e->fake_raw, 0.9f, e->g_raw, (sA && e->ext_events) ? e->evW[TT.NS - 1] : nullptr, false};
-      JCK_TRY(d_backward(e, D0, e->fake, B, false, true, in->drop_mask[3], st, nullptr, true, true, e->fuse_tanh ? &xe : nullptr, fuse));
+      DBackward bw;
+      bw.gw = 0; bw.xgrad = true; bw.xe = e->fuse_tanh ? &xe : nullptr;
+      JCK_TRY(d_backward(e, D0, e->fake, B, in->drop_mask[3], st, bw, fuse));
       JCK_TRY(g_backward(e, D0.gx, B, st, sA, xe.fused));
       return JCK_OK;
     }
@@ -1550,21 +1497,10 @@ extern "C" int jck_engine_capture_abort(jck_engine* e, void* stream) {
   if (g) (void)hipGraphDestroy(g);
   (void)hipGetLastError();
   // side streams that joined the broken capture may be left invalidated: replace them
+  // ... and so may the events recorded inside it
   if (e && e->overlap) {
-    hipStream_t* ss[3] = {&e->sA, &e->sB, &e->sC};
-    for (auto pp : ss) {
-      if (*pp) (void)hipStreamDestroy(*pp);
-      *pp = nullptr;
-      HIPCHK(hipStreamCreateWithFlags(pp, hipStreamNonBlocking));
-    }
-    // ... and so may the events recorded inside it
-    hipEvent_t* ev[8 + JCK_MAX_STAGES] = {&e->evWdone, &e->evWmid, &e->evHead, &e->evTail, &e->ev0, &e->evF, &e->evReal, &e->evGP};
-    for (int i = 0; i < JCK_MAX_STAGES; ++i) ev[8 + i] = &e->evW[i];
-    for (auto p : ev) {
-      if (*p) (void)hipEventDestroy(*p);
-      *p = nullptr;
-      HIPCHK(hipEventCreateWithFlags(p, jck_event_flags()));
-    }
+    destroy_side_streams(e, false);
+    JCK_TRY(create_side_streams(e));
     e->gp_inflight = false;
     e->join_pending = e->mid_recorded = false;
     (void)hipGetLastError();
@@ -1629,10 +1565,11 @@ extern "C" int jck_engine_sample(jck_engine* e, const float* z, const int64_t* l
 extern "C" const void* jck_engine_tensor(const jck_engine* e, const char* name, long long* numel) {
   if (!e || !e->bound || !name) return nullptr;
   const long long img = (long long)e->B * TT.HW * 4;
+  const DActs& D = e->dset[0];
   struct { const char* n; const void* p; long long c; } tab[] = {
       {"fake", e->fake, img}, {"fake_raw", e->fake_raw, img}, {"real_noisy", e->real_noisy, img}, {"xhat", e->xhat, img},
-      {"d_gx", e->d_gx, img}, {"prob", e->prob, e->B}, {"ds", e->ds, e->B}, {"norms", e->norms, e->B}, {"acc", e->acc, (long long)8 * e->acc_ld},
-      {"d_y1", e->d_y[0], (long long)e->B * (TT.S / 2) * (TT.S / 2) * 64}, {"d_a4", e->d_a[TT.NS - 1], (long long)e->B * TT.FEAT},
+      {"d_gx", D.gx, img}, {"prob", D.prob, e->B}, {"ds", D.ds, e->B}, {"norms", D.norms, e->B}, {"acc", e->acc, (long long)8 * e->acc_ld},
+      {"d_y1", D.y[0], (long long)e->B * (TT.S / 2) * (TT.S / 2) * 64}, {"d_a4", D.a[TT.NS - 1], (long long)e->B * TT.FEAT},
       {"g_y1", e->g_y[0], (long long)e->B * TT.FEAT}, {"g_a4", e->g_a[TT.NS - 1], (long long)e->B * (TT.S / 2) * (TT.S / 2) * 64}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) { if (numel) *numel = t.c; return t.p; }
