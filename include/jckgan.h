@@ -42,6 +42,11 @@ extern "C" {
 #define JCK_E_WS (-3)       /* workspace too small */
 
 const char* jck_last_error(void);
+/* Name of the kernel that the calling thread's last gather-GEMM, weight-gradient or image-side launch ran on ("" before the
+ * first), e.g. "igemm_dma_persist<128,256,8>", "wgrad_dma<3,ws>", "wgrad<bf16x3,128,64>", "img_up".  A report only: it selects
+ * nothing.  jck_launch_name(i) enumerates every name the library can report, NULL past the end. */
+const char* jck_last_launch(void);
+const char* jck_launch_name(int i);
 int jck_version(void);
 /* rows of a packed weight matrix for `c` output channels (tile padding): 16, 64 or a multiple of 128 */
 int jck_pad_rows(int c);

@@ -16,6 +16,45 @@ extern "C" const char* jck_last_error(void) { return g_err.c_str(); }
 #define JCK_BUILD_ID 100
 #endif
 extern "C" int jck_version(void) { return JCK_BUILD_ID; }
+
+// ---------------------------------------------------------------------------------------------------------
+// which kernel ran: every launch_* function below records the name of the kernel it chose for the calling thread.  A read-only
+// report (tests assert that a case still lands on the kernel it was written for); it selects nothing.  Unlike PROF_NAMES
+// further down - which bench.py reads and which merges the persistent and the non-persistent forms - one name per kernel.
+// ---------------------------------------------------------------------------------------------------------
+enum {
+  LN_PRECS = 3,                                   // bf16, f32, bf16x3
+  LN_IGEMM_TILES = 5,                             // 128x128, 128x64, 64x128 img, 64x128, 16x256
+  LN_DMA_TILES = 4,                               // 128x256, 128x128, 128x64, 64x128
+  LN_WGRAD_TILES = 4,                             // 128x128, 128x64, 64x64 img, 64x64
+  LN_IGEMM = 0,                                   // + LN_IGEMM_TILES * precision + tile
+  LN_PERSIST = LN_IGEMM + LN_PRECS * LN_IGEMM_TILES,
+  LN_DMA = LN_PERSIST + LN_DMA_TILES,
+  LN_IMG_DOWN = LN_DMA + LN_DMA_TILES, LN_IMG_UP,
+  LN_WGRAD_DMA_WS, LN_WGRAD_DMA,
+  LN_WGRAD,                                       // + LN_WGRAD_TILES * precision + tile
+  LN_COUNT = LN_WGRAD + LN_PRECS * LN_WGRAD_TILES
+};
+static const char* const LAUNCH_NAMES[] = {
+    "igemm<bf16,128,128>",   "igemm<bf16,128,64>",   "igemm<bf16,64,128,img>",   nullptr,                "igemm<bf16,16,256>",
+    "igemm<f32,128,128>",    "igemm<f32,128,64>",    "igemm<f32,64,128,img>",    "igemm<f32,64,128>",    "igemm<f32,16,256>",
+    "igemm<bf16x3,128,128>", "igemm<bf16x3,128,64>", "igemm<bf16x3,64,128,img>", "igemm<bf16x3,64,128>", "igemm<bf16x3,16,256>",
+    "igemm_dma_persist<128,256,8>", "igemm_dma_persist<128,128,4>", "igemm_dma_persist<128,64,4>", "igemm_dma_persist<64,128,4>",
+    "igemm_dma<128,256,3,ws,8>", "igemm_dma<128,128,2>", "igemm_dma<128,64,3,ws>", "igemm_dma<64,128,2>",
+    "img_down", "img_up",
+    "wgrad_dma<3,ws>", "wgrad_dma<2>",
+    "wgrad<bf16,128,128>",   "wgrad<bf16,128,64>",   "wgrad<bf16,64,64,img>",   "wgrad<bf16,64,64>",
+    "wgrad<f32,128,128>",    "wgrad<f32,128,64>",    "wgrad<f32,64,64,img>",    "wgrad<f32,64,64>",
+    "wgrad<bf16x3,128,128>", "wgrad<bf16x3,128,64>", "wgrad<bf16x3,64,64,img>", "wgrad<bf16x3,64,64>"};
+static_assert(sizeof(LAUNCH_NAMES) / sizeof(LAUNCH_NAMES[0]) == LN_COUNT, "LAUNCH_NAMES and the LN_* offsets disagree");
+static thread_local const char* g_last_launch = "";
+static inline void note_launch(int name) { g_last_launch = LAUNCH_NAMES[name]; }
+extern "C" const char* jck_last_launch(void) { return g_last_launch; }
+extern "C" const char* jck_launch_name(int i) {       // (a null entry: a kernel that is not built - bf16's register-staged 64 x 128 tile)
+  for (int k = 0; k < LN_COUNT; ++k)
+    if (LAUNCH_NAMES[k] && i-- == 0) return LAUNCH_NAMES[k];
+  return nullptr;
+}
 extern "C" int jck_pad_rows(int c) { return c <= 16 ? 16 : (c <= 64 ? 64 : (c + 127) / 128 * 128); }
 extern "C" int jck_pad_chan(int c) { return c == 3 ? 4 : c; }
 
@@ -143,6 +182,8 @@ static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStre
   constexpr int tile = BCH == 128 ? (BPIX == 128 ? 0 : 1) : (BCH == 64 ? (NSUB == 2 ? 2 : 3) : 4);
   constexpr int variant = (P::SPLIT ? PROF_IGEMM_BF16X3 : P::IS_F32 ? 5 : 0) + tile;
   ProfScope prof(variant, p.flops, st);
+  static_assert(P::IS_F32 || !(BCH == 64 && NSUB == 1), "bf16 has no register-staged 64 x 128 tile (and no name for one)");
+  note_launch(LN_IGEMM + LN_IGEMM_TILES * (P::SPLIT ? 2 : P::IS_F32 ? 1 : 0) + tile);
   auto kern = igemm_kernel<P, BCH, BPIX, NSUB, 2>;
   static bool attr_done = false;
   if (!attr_done) {
@@ -167,6 +208,7 @@ static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipSt
   constexpr int LDSB = NSTG * (BCH + BPIX) * IG_BK * 2;
   constexpr int variant = BPIX == 256 ? 20 : BCH == 64 ? 3 : (BPIX == 128 ? 0 : 1);
   ProfScope prof(variant, p.flops, st);
+  note_launch(LN_DMA + (BPIX == 256 ? 0 : BCH == 64 ? 3 : BPIX == 128 ? 1 : 2));
   auto kern = igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW>;
   static bool attr_done = false;
   if (!attr_done) {
@@ -192,6 +234,7 @@ static int launch_igemm_dma_persist(const IgemmParams& p, int nch_pad, int phase
   constexpr int LDSB = 3 * (BCH + BPIX) * IG_BK * 2 + NCW * (BCH >= 128 ? 2 : 1) * 256 + 64;
   constexpr int variant = BCH == 64 ? 3 : BPIX == 256 ? 20 : BPIX == 128 ? 0 : 1;
   ProfScope prof(variant, p.flops, st);
+  note_launch(LN_PERSIST + (BPIX == 256 ? 0 : BCH == 64 ? 3 : BPIX == 128 ? 1 : 2));
   auto kern = igemm_dma_persist_kernel<BCH, BPIX, NCW>;
   static bool attr_done = false;
   if (!attr_done) {
@@ -265,13 +308,17 @@ static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsu
     return launch_igemm_t<P, 128, 64, 1>(p, nch_pad, phases, st, slots);
   }
   if (nch_pad == 64) {
-    if (!P::IS_F32 && nsub == 1 && p.ksplit <= 1 && !p.rows_are_phases) {
+    if (nsub == 2) return launch_igemm_t<P, 64, 128, 2>(p, nch_pad, phases, st, slots);
+    if constexpr (!P::IS_F32) {
+      // bf16: always the LDS-DMA kernels, so the register-staged 64 x 128 tile is not built for it.  (Split-K comes from
+      // jck_linear_fwd alone, which needs a multiple of 128 rows, and rows-as-phases from the 16-row image layer alone: neither
+      // gets here.)
       if (!p.act_row_elems && !p.bias && !p.epi && !p.out_f32 && !p.out_split_stride)
         return launch_igemm_dma_persist<64, 128, 4>(p, nch_pad, phases, st, slots);
       return launch_igemm_dma<64, 128, 2>(p, nch_pad, phases, st, slots);
+    } else {
+      return launch_igemm_t<P, 64, 128, 1>(p, nch_pad, phases, st, slots);
     }
-    if (nsub == 2) return launch_igemm_t<P, 64, 128, 2>(p, nch_pad, phases, st, slots);
-    return launch_igemm_t<P, 64, 128, 1>(p, nch_pad, phases, st, slots);
   }
   if (nch_pad == 16) {
     if (nsub != 1) JCK_FAIL(JCK_E_ARG, "igemm: 4->4 channel product unsupported");
@@ -327,6 +374,7 @@ static int launch_img_down(const void* x, const void* w, void* out, float* stats
     *slots = grid;
   }
   ProfScope prof(18, flops, st);
+  note_launch(LN_IMG_DOWN);
   hipLaunchKernelGGL(img_down_kernel<IMG_GPW>, dim3(grid), dim3(256), 0, st, q);
   HIPCHK(hipGetLastError());
   return JCK_OK;
@@ -339,6 +387,7 @@ static int launch_img_up(const void* a, const void* w, void* out, int epi_tanh, 
   q.nunits = N * (Hs / IMG_UP_R) * (Ws / 16); q.Hs = Hs; q.Ws = Ws; q.logYB = ilog2(Hs / IMG_UP_R); q.logG = ilog2(Ws / 16);
   q.a_bytes = (unsigned)((long long)N * Hs * Ws * 64 * 2);
   ProfScope prof(19, flops, st);
+  note_launch(LN_IMG_UP);
   LAUNCH_EV(img_up_kernel<IMG_UP_R>, dim3(cdiv(q.nunits, 4)), dim3(256), 0, st, done, q);
   HIPCHK(hipGetLastError());
   return JCK_OK;
@@ -491,6 +540,7 @@ static int launch_wgrad_t(const WgradParams& p, const WgradPlan& pl, hipStream_t
   constexpr int tile = BG == 128 ? (BS == 128 ? 0 : 1) : (NSUB == 2 ? 2 : 3);
   constexpr int variant = (P::SPLIT ? PROF_WGRAD_BF16X3 : 10 + (P::IS_F32 ? 4 : 0)) + tile;
   ProfScope prof(variant, p.flops, st);
+  note_launch(LN_WGRAD + LN_WGRAD_TILES * (P::SPLIT ? 2 : P::IS_F32 ? 1 : 0) + tile);
   constexpr int LDSB = WgradCfg<P, BG, BS>::LDS_BYTES;
   auto kern = wgrad_kernel<P, BG, BS, NSUB>;
   static bool attr_done = false;
@@ -508,6 +558,7 @@ static int launch_wgrad_t(const WgradParams& p, const WgradPlan& pl, hipStream_t
 template <int NSTG, bool WS>
 static int launch_wgrad_dma_t(const WgradParams& q, int grid, hipStream_t st) {
   constexpr int LDSB = NSTG * 2 * WGD_BKP * 256;
+  note_launch(WS ? LN_WGRAD_DMA_WS : LN_WGRAD_DMA);
   static bool attr_done = false;
   if (!attr_done) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma_kernel<NSTG, 4, WS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));

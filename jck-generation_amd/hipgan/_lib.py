@@ -20,6 +20,8 @@ class StepInputs(C.Structure):
 # name -> (restype, argtypes)      (keep in sync with include/jckgan.h; tests/test_abi.py checks the symbol list)
 PROTOS = {
     "jck_last_error": (C.c_char_p, []),
+    "jck_last_launch": (C.c_char_p, []),
+    "jck_launch_name": (C.c_char_p, [i32]),
     "jck_version": (i32, []),
     "jck_pad_rows": (i32, [i32]),
     "jck_pad_chan": (i32, [i32]),
