@@ -256,6 +256,13 @@ int jck_bn2_reverse(int prec, const void* ua, const void* y, const void* xdir, c
 /* ---- optimiser (torch.optim.Adam as built at train/dcgan_trainer.py:61-62) over a flat fp32 arena ---------- */
 int jck_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,
              int step, float grad_scale, void* stream);
+/* The same update with an exponential moving average of the parameters advanced in the same launch.  The reference samples and
+ * checkpoints the raw generator (train/dcgan_trainer.py:199-200,86-91); the averaged generator is the usual remedy for its
+ * oscillation against D and an opt-in addition here.  ema [n]: e <- lerp(e, p_new, ema_weight) with ATen's two lerp branches
+ * (ema_weight = 1 - decay in [0, 1]; 1 gives e = p_new exactly).  skip_if: device word or NULL; non-zero leaves p, m, v and ema
+ * untouched.  p, m, v come out bitwise as jck_adam leaves them. */
+int jck_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, double lr, double beta1, double beta2,
+                 double eps, int step, float grad_scale, float ema_weight, const unsigned* skip_if, void* stream);
 
 /* ---- whole-step engine (train/dcgan_trainer.py:155-189 as one native schedule) --------------------------- */
 typedef struct jck_engine jck_engine;
@@ -401,6 +408,15 @@ int jck_mean_cov_f64(const float* x, double* mean, double* cov, int N, int D, vo
  * returns an executable graph; launch replays it.  The jck_step_inputs pointers are baked: keep the buffers in place,
  * refresh their contents, keep one graph per step parity, call jck_engine_set_step before every launch. */
 int jck_engine_set_step(jck_engine*, int step, float lr, void* stream);
+/* Moving average of G's weights inside the step (optimizer_g.step(), train/dcgan_trainer.py:189, train/cgan_trainer.py:212, is
+ * where it advances; the reference keeps none).  bind_ema attaches an arena of jck_engine_arena_numel_of(e, 0, 0) floats, 16-byte
+ * aligned, to a bound engine (NULL detaches): JCK_PHASE_G_STEP's Adam launch then updates it as jck_adam_ema does - no further
+ * launch, workspace and every other launch unchanged; D has no average.  set_ema: the weight of optimiser step s is 1 for
+ * s < start_step (the average tracks the weights during warm-up) and (float)(1.0 - decay) from there on (decay is a double so that this is the one rounding, as for jck_adam's scalars).  It reaches the launch
+ * through the step's scalars in device memory (jck_engine_set_step), so a captured graph bakes no weight.  An engine bound with
+ * the EMA arena AS its g_params samples the averaged generator through jck_engine_sample. */
+int jck_engine_bind_ema(jck_engine*, float* g_ema);
+int jck_engine_set_ema(jck_engine*, double decay, int start_step);
 /* Instance noise drawn INSIDE the image kernels (steps whose jck_step_inputs.noise_real / noise_fake are NULL): Philox4x32-10
  * keyed by `seed`, counter = (pixel, tensor, optimiser step), Box-Muller normals - no 25 MB noise tensor per step.  The *_rng
  * entry points are the per-op forms (rng: device uint32[4] = {seed lo, seed hi, step, 0}; tensor_id separates real / fake). */
@@ -419,6 +435,9 @@ int jck_axpy_noise_rng(int prec, const void* x, const unsigned* rng, int tensor_
 int jck_engine_capture_begin(jck_engine*, void* stream);
 int jck_engine_capture_end(jck_engine*, void* stream, void** graph_exec);
 int jck_engine_capture_abort(jck_engine*, void* stream);
+/* nodes (kernel launches, memsets) of the graph this engine's last jck_engine_capture_end instantiated: the launch count of the
+ * captured phases (one optimizer step = train/dcgan_trainer.py:155-189 when all five phases are captured) */
+int jck_engine_graph_nodes(const jck_engine*);
 int jck_graph_launch(void* graph_exec, void* stream);
 void jck_graph_destroy(void* graph_exec);
 

@@ -147,6 +147,12 @@ struct jck_engine {
   float *gp = nullptr, *gg = nullptr, *gm = nullptr, *gv = nullptr, *gbn = nullptr;
   float *dp = nullptr, *dg = nullptr, *dm = nullptr, *dv = nullptr, *dbn = nullptr;
   int64_t *gnbt = nullptr, *dnbt = nullptr;
+  // exponential moving average of G's parameters (jck_engine_bind_ema; null: none): advanced by Adam(G)'s launch with the weight
+  // jck_engine_set_ema configures - 1 below ema_start (the average tracks the weights), 1 - decay from there on
+  float* gema = nullptr;
+  double ema_decay = 0.0; int ema_start = 0;
+  float ema_w(int step) const { return !gema ? 0.f : (step < ema_start ? 1.f : (float)(1.0 - ema_decay)); }
+  int graph_nodes = 0;                  // nodes of the graph jck_engine_capture_end instantiated last
   // packed weights
   void *d_down[JCK_MAX_STAGES], *d_up[JCK_MAX_STAGES];
   float *d_head_wp, *d_head_dwp;
@@ -196,7 +202,7 @@ struct jck_engine {
   float *acc2, *scal2;                  // acc2: [2 parities][8 rows][acc_ld] per-image scalar table (summed by the step tail)
   int acc_ld = 0;
   float *head_ws, *gp2_ws;              // partial rows of the head weight gradients (deterministic two-stage sums)
-  float* hp2;                           // [2 parities][8]: {step_size, bc2_sqrt, -, -, noise seed lo, hi, step, 0} of the step in flight (jck_engine_set_step)
+  float* hp2;                           // [2 parities][8]: {step_size, bc2_sqrt, EMA weight, -, noise seed lo, hi, step, 0} of the step in flight (jck_engine_set_step)
   unsigned long long noise_seed = 0x6a636b67616e0001ull;      // in-kernel instance noise (jck_engine_set_noise_seed)
   float *rz[2] = {nullptr, nullptr}, *ralpha[2] = {nullptr, nullptr}, *rmask[2] = {nullptr, nullptr};
   int hp_step[2] = {0, 0};              // which step's scalars each parity holds (checked by the optimiser phases) ...
@@ -1015,7 +1021,7 @@ static int prep_real(jck_engine* e, const jck_step_inputs* in, int B, hipStream_
 // them) and not the step's random inputs (jck_engine_set_step here logged loss_d = loss_g = gp = 0).
 static int refresh_adam_scalars(jck_engine* e, int step, float lr, hipStream_t st) {
   const int q = step & 1;
-  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, 0.5, 0.999, step, e->noise_seed, st));
+  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, 0.5, 0.999, step, e->noise_seed, e->ema_w(step), st));
   e->hp_step[q] = step;
   e->hp_lr[q] = lr;
   return JCK_OK;
@@ -1381,8 +1387,9 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
     }
     case JCK_PHASE_G_STEP: {                                                                      // :189
       if (!e->hp_holds(in->step, in->lr) && !e->capturing) JCK_TRY(refresh_adam_scalars(e, in->step, in->lr, st));
+      // ... and the moving average of G's weights, when one is bound, in the same launch (its weight is hp[2] of the step)
       JCK_TRY(jck_adam_hp(e->gp, e->gg, e->gm, e->gv, e->LG.n_params, 0.5, 0.999, 1e-8, in->grad_scale, e->hp2 + 8 * e->parity, st, nullptr, 0,
-                          jck_grid_sync_error_word(e->gsync)));
+                          jck_grid_sync_error_word(e->gsync), e->gema));
       {   // G's repack, the four D passes' BatchNorm records in the reference's order and the logged scalars: one launch
         TailJobs t = {};
         for (int i = 0; i < TT.NS; ++i) {
@@ -1412,7 +1419,7 @@ static int set_step_impl(jck_engine* e, int step, float lr, void* stream, bool z
   if (e->capturing) JCK_FAIL(JCK_E_ARG, "set_step inside a graph capture would bake one step's scalars into the graph");
   const int q = step & 1;
   zero_d = zero_d && e->fold_zero && e->LD.n_params % 4 == 0;
-  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, 0.5, 0.999, step, e->noise_seed, (hipStream_t)stream, e->rz[q], (long long)e->B * 100,
+  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, 0.5, 0.999, step, e->noise_seed, e->ema_w(step), (hipStream_t)stream, e->rz[q], (long long)e->B * 100,
                             e->ralpha[q], e->B, e->rmask[q], e->rmask[q] ? (long long)4 * e->B * L1_OUT : 0, 0.75f,
                             e->acc2 + (size_t)8 * e->acc_ld * q, (long long)8 * e->acc_ld,
                             zero_d ? e->dg : nullptr, e->LD.n_params, zero_d && e->family == 1 ? e->gw1p : nullptr, (long long)L1_OUT * L1_KPAD,
@@ -1427,6 +1434,26 @@ static int set_step_impl(jck_engine* e, int step, float lr, void* stream, bool z
   return JCK_OK;
 }
 extern "C" int jck_engine_set_step(jck_engine* e, int step, float lr, void* stream) { return set_step_impl(e, step, lr, stream, false); }
+// Exponential moving average of G's weights (the averaged generator a GAN trainer samples, scores and ships; the reference has
+// none).  bind: `g_ema` = LG.n_params floats, 16-byte aligned, NULL detaches; PHASE_G_STEP's Adam launch then advances it.  set:
+// the weight of step s is 1 for s < start_step and (float)(1 - decay) from there on; it travels in the step's hp block.
+extern "C" int jck_engine_bind_ema(jck_engine* e, float* g_ema) {
+  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "engine not bound");
+  if (e->capturing) JCK_FAIL(JCK_E_ARG, "bind_ema inside a graph capture");
+  if ((uintptr_t)g_ema & 15) JCK_FAIL(JCK_E_ARG, "bind_ema: the EMA arena must be 16-byte aligned");
+  e->gema = g_ema;
+  e->hp_step[0] = e->hp_step[1] = 0;      // the next step rewrites the device copy of its scalars (the weight slot among them)
+  e->hp_lr[0] = e->hp_lr[1] = -1.f;
+  return JCK_OK;
+}
+extern "C" int jck_engine_set_ema(jck_engine* e, double decay, int start_step) {
+  if (!e) JCK_FAIL(JCK_E_ARG, "null engine");
+  if (!(decay >= 0.0 && decay <= 1.0)) JCK_FAIL(JCK_E_ARG, "set_ema: decay must lie in [0, 1]");
+  e->ema_decay = decay; e->ema_start = start_step;
+  e->hp_step[0] = e->hp_step[1] = 0;
+  e->hp_lr[0] = e->hp_lr[1] = -1.f;
+  return JCK_OK;
+}
 // Seed of the in-kernel instance noise (steps whose jck_step_inputs carry no noise tensors draw 0.1*N(0,1) inside the image
 // kernels: Philox4x32-10 keyed by this seed, counter = pixel | tensor | optimiser step).  Data-parallel ranks pass seed + rank.
 extern "C" int jck_engine_set_noise_seed(jck_engine* e, unsigned long long seed) {
@@ -1468,6 +1495,7 @@ extern "C" int jck_engine_capture_end(jck_engine* e, void* stream, void** graph_
     hipError_t q = hipGraphGetNodes(g, nullptr, &nn);
     if (q == hipSuccess) q = hipGraphGetEdges(g, nullptr, nullptr, &ne);
     bool linear = q == hipSuccess && nn > 0 && ne == nn - 1;
+    e->graph_nodes = (int)nn;
     if (linear && ne > 0) {
       std::vector<hipGraphNode_t> from(ne), to(ne);
       q = hipGraphGetEdges(g, from.data(), to.data(), &ne);
@@ -1507,6 +1535,9 @@ extern "C" int jck_engine_capture_abort(jck_engine* e, void* stream) {
   }
   return JCK_OK;
 }
+// nodes (kernel launches and memsets) of the graph the last jck_engine_capture_end of this engine instantiated: the launch count
+// of the captured phases
+extern "C" int jck_engine_graph_nodes(const jck_engine* e) { return e ? e->graph_nodes : 0; }
 extern "C" int jck_graph_launch(void* graph_exec, void* stream) {
   if (!graph_exec) JCK_FAIL(JCK_E_ARG, "null graph");
   HIPCHK(hipGraphLaunch((hipGraphExec_t)graph_exec, (hipStream_t)stream));

@@ -885,7 +885,8 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(const float* __rest
 // hp (optional): device float[2] = {step_size, bc2_sqrt} of THIS step, written by adam_hp_kernel before the step is enqueued
 // - the whole-step engine passes its per-step scalars this way so that a captured hipGraph of the step carries no
 // per-step kernel argument; the values are the same host-computed floats either way.
-// hp[0..1] = Adam's per-step scalars; hp[4..7] (as uint32) = {noise seed lo, hi, step, 0} for the in-kernel Philox noise.
+// hp[0..1] = Adam's per-step scalars; hp[2] = the generator EMA's weight 1 - decay of this step (0 when no EMA is configured; read
+// by adam_kernel only when it is handed an EMA arena); hp[3] unused; hp[4..7] (as uint32) = {noise seed lo, hi, step, 0} for the in-kernel Philox noise.
 // The same launch draws the step's SMALL random inputs when the caller hands over none (perf mode): z [nz] ~ N(0,1)
 // (train/dcgan_trainer.py:168), alpha [nalpha] ~ U[0,1) (:111), CGAN's Dropout keep masks [nmask] in {0,1} with P(keep) = keep_p
 // (model/CGAN.py:105) - Philox4x32-10, counter = (index/4, tensor id 8 / 9 / 10, step), key = seed.  No ATen launch is left
@@ -898,9 +899,9 @@ struct StepRng { float* z; long long nz; float* alpha; long long nalpha; float* 
 // D.zero_grad() (train/dcgan_trainer.py:155) would clear with a launch of its own a few microseconds later)
 __device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 static __global__ void adam_hp_kernel(float* __restrict__ hp, float step_size, float bc2_sqrt, unsigned seed_lo, unsigned seed_hi,
-                                      unsigned step, const StepRng r) {
+                                      unsigned step, const StepRng r, float ema_w) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    hp[0] = step_size; hp[1] = bc2_sqrt;
+    hp[0] = step_size; hp[1] = bc2_sqrt; hp[2] = ema_w;
     unsigned* w = reinterpret_cast<unsigned*>(hp + 4);
     w[0] = seed_lo; w[1] = seed_hi; w[2] = step; w[3] = 0u;
   }
@@ -955,13 +956,20 @@ __device__ __forceinline__ void adam_one(float& pi, float gi_raw, float& mi_io, 
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
   pi = pi - step_size * (mi / denom);
 }
+// Exponential moving average of the parameters, updated from the new parameter while it is still in a register: ATen's lerp
+// (the same two branches adam_one takes for exp_avg), so w = 1 gives e = p exactly
+__device__ __forceinline__ float ema_one(float e, float pn, float w) { return (w < 0.5f) ? e + w * (pn - e) : pn - (pn - e) * (1.f - w); }
 // four elements per thread (16-byte loads and stores: the arenas are 16-byte aligned); the last n % 4 elements one by one
+// EMA = true: `ema` is a fifth arena of n floats (16-byte aligned like the others when vec = 1), weight ema_w - or hp[2] when the
+// per-step scalars come from device memory; EMA = false is the kernel without any of it
+template <bool EMA>
 static __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long long n, float w1 /*1-beta1*/, float beta2, float omb2 /*1-beta2*/,
                             float eps, float step_size, float bc2_sqrt, float grad_scale, const float* __restrict__ hp = nullptr,
                             int vec = 1, float* __restrict__ zero = nullptr, long long nzero4 = 0,
-                            const unsigned* __restrict__ skip_if = nullptr) {
+                            const unsigned* __restrict__ skip_if = nullptr, float* __restrict__ ema = nullptr, float ema_w = 1.f) {
   if (hp) { step_size = hp[0]; bc2_sqrt = hp[1]; }
+  if (EMA && hp) ema_w = hp[2];
   // skip_if (the engine's grid-barrier error word): a resident launch of this step went on with incomplete sums - the gradients
   // are invalid, so parameters and moments stay as they are (the host learns of it at jck_engine_check); the zero range below is
   // still cleared: the next pass accumulates into it
@@ -975,16 +983,22 @@ static __global__ void adam_kernel(float* __restrict__ p, const float* __restric
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
     const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 ev;
+    if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float pk = pv[k], mk = mv[k], vk = vv[k];
       adam_one(pk, gv[k], mk, vk, w1, beta2, omb2, eps, step_size, bc2_sqrt, grad_scale);
       pv[k] = pk; mv[k] = mk; vv[k] = vk;
+      if (EMA) ev[k] = ema_one(ev[k], pk, ema_w);
     }
     reinterpret_cast<f32x4*>(p)[i] = pv; reinterpret_cast<f32x4*>(m)[i] = mv; reinterpret_cast<f32x4*>(v)[i] = vv;
+    if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
   }
-  for (long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+  for (long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     adam_one(p[i], g[i], m[i], v[i], w1, beta2, omb2, eps, step_size, bc2_sqrt, grad_scale);
+    if (EMA) ema[i] = ema_one(ema[i], p[i], ema_w);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -1158,14 +1158,30 @@ extern "C" int jck_adam(float* p, const float* g, float* m, float* v, long long 
   const double bc1 = 1.0 - std::pow(beta1, step), bc2 = 1.0 - std::pow(beta2, step);
   const float step_size = (float)(lr / bc1), bc2s = (float)std::sqrt(bc2);
   const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-  hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - beta1),
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(ew_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - beta1),
                      (float)beta2, (float)(1.0 - beta2), (float)eps, step_size, bc2s, grad_scale, (const float*)nullptr, vec);
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// jck_adam that advances an exponential moving average of the parameters in the same launch (the averaged generator that GAN
+// trainers sample and checkpoint): ema <- lerp(ema, p_new, ema_weight), ema_weight = 1 - decay; skip_if as in jck_adam_hp
+extern "C" int jck_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, double lr, double beta1, double beta2,
+                            double eps, int step, float grad_scale, float ema_weight, const unsigned* skip_if, void* stream) {
+  if (step < 1) JCK_FAIL(JCK_E_ARG, "adam: step is 1-based");
+  if (!ema) JCK_FAIL(JCK_E_ARG, "adam_ema: null EMA arena (jck_adam is the form without one)");
+  if (!(ema_weight >= 0.f && ema_weight <= 1.f)) JCK_FAIL(JCK_E_ARG, "adam_ema: ema_weight = 1 - decay must lie in [0, 1]");
+  const double bc1 = 1.0 - std::pow(beta1, step), bc2 = 1.0 - std::pow(beta2, step);
+  const float step_size = (float)(lr / bc1), bc2s = (float)std::sqrt(bc2);
+  const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0;
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(ew_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), (float)eps, step_size, bc2s, grad_scale, (const float*)nullptr, vec, (float*)nullptr,
+                     0ll, skip_if, ema, ema_weight);
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }
 // the same update with {step_size, bc2_sqrt} read from device memory: jck_adam_set_step writes them (same host arithmetic)
 // ... and (rz / ralpha / rmasks, each optional) the step's small random inputs, drawn by the same launch (ew.hpp: adam_hp_kernel)
-int jck_adam_set_step(float* hp, double lr, double beta1, double beta2, int step, unsigned long long seed, hipStream_t st, float* rz,
+int jck_adam_set_step(float* hp, double lr, double beta1, double beta2, int step, unsigned long long seed, float ema_w, hipStream_t st, float* rz,
                       long long nz, float* ralpha, long long nalpha, float* rmasks, long long nmask, float keep_p, float* zero,
                       long long nzero, float* zbig0, long long nzbig0, float* zbig1, long long nzbig1, void* zpad, int zd, int zp, int zpad_f32) {
   if (step < 1) JCK_FAIL(JCK_E_ARG, "adam: step is 1-based");
@@ -1176,7 +1192,7 @@ int jck_adam_set_step(float* hp, double lr, double beta1, double beta2, int step
   const long long quads = std::max((r.nz + 3) / 4 + (r.nalpha + 3) / 4 + (r.nmask + 3) / 4, std::max(r.nzbig[0], r.nzbig[1]) / 16);
   const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((quads + 255) / 256, 1024));
   hipLaunchKernelGGL(adam_hp_kernel, dim3(blocks), dim3(256), 0, st, hp, (float)(lr / bc1), (float)std::sqrt(bc2), (unsigned)seed,
-                     (unsigned)(seed >> 32), (unsigned)step, r);
+                     (unsigned)(seed >> 32), (unsigned)step, r, ema_w);
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }
@@ -1185,13 +1201,17 @@ int jck_adam_set_step(float* hp, double lr, double beta1, double beta2, int step
 extern "C" int jck_step_rng(float* hp, int step, unsigned long long seed, float* z, long long nz, float* alpha, long long nalpha,
                             float* masks, long long nmask, float keep_p, void* stream) {
   if (!hp) JCK_FAIL(JCK_E_ARG, "step_rng: hp scratch (8 floats) is required");
-  return jck_adam_set_step(hp, 2e-4, 0.5, 0.999, step, seed, (hipStream_t)stream, z, nz, alpha, nalpha, masks, nmask, keep_p);
+  return jck_adam_set_step(hp, 2e-4, 0.5, 0.999, step, seed, 0.f, (hipStream_t)stream, z, nz, alpha, nalpha, masks, nmask, keep_p);
 }
 int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, double beta1, double beta2, double eps,
-                float grad_scale, const float* hp, hipStream_t st, float* zero, long long nzero, const unsigned* skip_if) {
-  const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+                float grad_scale, const float* hp, hipStream_t st, float* zero, long long nzero, const unsigned* skip_if, float* ema) {
+  const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0;
   if (zero && (((uintptr_t)zero & 15) || (nzero & 3))) JCK_FAIL(JCK_E_ARG, "adam: the zero range must be 16-byte aligned, count % 4 == 0");
-  hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, st, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
+  if (ema)
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(ew_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, st, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
+                       (float)(1.0 - beta2), (float)eps, 0.f, 1.f, grad_scale, hp, vec, zero, zero ? nzero / 4 : 0, skip_if, ema, 1.f);
+  else
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(ew_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, st, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps, 0.f, 1.f, grad_scale, hp, vec, zero, zero ? nzero / 4 : 0, skip_if);
   HIPCHK(hipGetLastError());
   return JCK_OK;

@@ -39,14 +39,16 @@ static inline bool prec_f32_storage(int prec) { return prec == JCK_PREC_F32 || p
 
 int launch_igemm(int prec, const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st, int* slots);
 // Adam with {step_size, bc2_sqrt} in device memory (ops.hip): the engine's step has no per-step kernel argument
-int jck_adam_set_step(float* hp, double lr, double beta1, double beta2, int step, unsigned long long seed, hipStream_t st,
+// ema_w: the generator EMA's weight of this step, written to hp[2] (0: no EMA configured)
+int jck_adam_set_step(float* hp, double lr, double beta1, double beta2, int step, unsigned long long seed, float ema_w, hipStream_t st,
                       float* rz = nullptr, long long nz = 0, float* ralpha = nullptr, long long nalpha = 0, float* rmasks = nullptr,
                       long long nmask = 0, float keep_p = 0.75f, float* zero = nullptr, long long nzero = 0, float* zbig0 = nullptr,
                       long long nzbig0 = 0, float* zbig1 = nullptr, long long nzbig1 = 0, void* zpad = nullptr, int zd = 0, int zp = 0,
                       int zpad_f32 = 0);      // zpad: the drawn z also as rows [nz / zd][zp] of type T (G.conv1's operand; padding columns untouched)
 int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, double beta1, double beta2, double eps,
                 float grad_scale, const float* hp, hipStream_t st, float* zero = nullptr, long long nzero = 0,
-                const unsigned* skip_if = nullptr);      // skip_if: device word; non-zero = leave p, m, v untouched (a grid barrier of the step timed out)
+                const unsigned* skip_if = nullptr,       // skip_if: device word; non-zero = leave p, m, v untouched (a grid barrier of the step timed out)
+                float* ema = nullptr);                   // ema: moving average of p, advanced in the same launch with the weight in hp[2]
 const unsigned* jck_grid_sync_error_word(const void* sync_ws);
 bool jck_prof_is_on();
 // BatchNorm finalize + apply as one launch where the statistics rows are few (ops.hip); *fused = false: nothing was launched

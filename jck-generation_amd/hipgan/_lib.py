@@ -91,6 +91,7 @@ PROTOS = {
     "jck_head_bwd_conv": (i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "jck_head_bwd_conv2": (i32, [i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "jck_adam": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, i32, f32, vp]),
+    "jck_adam_ema": (i32, [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, i32, f32, f32, vp, vp]),
     "jck_engine_create": (i32, [C.POINTER(vp), i32, i32, i32]),
     "jck_engine_create_sized": (i32, [C.POINTER(vp), i32, i32, i32, i32]),
     "jck_engine_create_ex": (i32, [C.POINTER(vp), i32, i32, i32, i32, C.c_uint]),
@@ -124,6 +125,9 @@ PROTOS = {
     "jck_nchw_to_nhwc_f32": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "jck_mean_cov_f64": (i32, [vp, vp, vp, i32, i32, vp]),
     "jck_engine_set_step": (i32, [vp, i32, f32, vp]),
+    "jck_engine_bind_ema": (i32, [vp, vp]),
+    "jck_engine_set_ema": (i32, [vp, f64, i32]),
+    "jck_engine_graph_nodes": (i32, [vp]),
     "jck_engine_set_noise_seed": (i32, [vp, C.c_ulonglong]),
     "jck_step_rng": (i32, [vp, i32, C.c_ulonglong, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, f32, vp]),
     "jck_img_prep_rng": (i32, [i32, vp, vp, i32, f32, f32, vp, i32, i32, vp]),
@@ -201,7 +205,7 @@ class _Lib:
                     if not a.is_contiguous():
                         raise JckError(f"{name}: non-contiguous tensor argument")
             r = fn(*[_arg(a) for a in args])
-            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_comm_world") \
+            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_comm_world", "jck_engine_graph_nodes") \
                     and r != 0:
                 raise JckError(f"{name} failed ({r}): {dll.jck_last_error().decode()}")
             return r

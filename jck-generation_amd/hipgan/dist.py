@@ -82,7 +82,7 @@ class ReplicaGuard:
     BatchNorm buffers) is broadcast again, the engines fall back to the plain schedule (one all-reduce per network, waited for
     before its Adam: engine.ddp_overlap = False) and the event is logged once per occurrence - the run continues on consistent
     replicas instead of training on diverged ones."""
-    KEYS = ("g_params", "d_params", "g_m", "g_v", "d_m", "d_v", "g_bn", "d_bn")
+    KEYS = ("g_params", "d_params", "g_m", "g_v", "d_m", "d_v", "g_bn", "d_bn", "g_ema")      # g_ema: engines that average G's weights
 
     def __init__(self, engines, world, group=None, log=None):
         self.engines = engines if callable(engines) else (lambda e=engines: [e])      # callable -> the engines in use (one per batch size)

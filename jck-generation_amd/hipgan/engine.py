@@ -98,13 +98,19 @@ class DcganEngine:
 
     family = 0
 
-    def __init__(self, batch, prec="bf16", device="cuda:0", share=None, image_size=64, gp_backward=False):
+    def __init__(self, batch, prec="bf16", device="cuda:0", share=None, image_size=64, gp_backward=False, ema_decay=None, ema_start=0,
+                 ema=False):
         """share: another DcganEngine whose arenas (weights, gradients, Adam moments, BN statistics) this one binds
         too - used for the ragged last batch of an epoch, which needs its own workspace geometry but the same state.
         image_size: 64 = the reference's nets; 128 = one more stride-2 stage (DCGAN only, BASELINE.json configs[4]).
         gp_backward (DCGAN; a `share=` engine inherits it): back-propagate the gradient penalty into D as the CGAN step does -
         D's step then descends on error_real + error_fake + 10 * gp.  Default False = the reference, which only logs the penalty
-        (train/dcgan_trainer.py:178-179).  CGAN engines always back-propagate it."""
+        (train/dcgan_trainer.py:178-179).  CGAN engines always back-propagate it.
+        ema_decay (a `share=` engine inherits it and ema_start): keep an exponential moving average of G's parameters in
+        arenas["g_ema"], advanced inside Adam(G)'s launch: e <- e + (1 - decay) * (p - e) from optimiser step ema_start on, e = p
+        before it.  None reads JCKGAN_EMA_DECAY; unset or 0 = off = the reference, which has no average (nothing is allocated).
+        ema=True (with share= an engine that keeps an average): a SAMPLING engine - its generator is the average, with BatchNorm
+        running statistics of its own, so sample() never moves the live generator's; it refuses the training phases."""
         if not torch.cuda.is_available():
             raise JckError("DcganEngine needs a GPU: the HIP path has no CPU fallback")
         self.device = torch.device(device) if share is None else share.device
@@ -116,6 +122,16 @@ class DcganEngine:
         self.size = image_size if share is None else share.size
         self.gp_backward = (bool(gp_backward) if share is None else share.gp_backward) or self.family == 1
         self._shared = share._shared if share is not None else {"t": 0, "version": 0, "last_step": 0}
+        if share is not None:
+            self.ema_decay, self.ema_start = share.ema_decay, share.ema_start
+        else:
+            d = float(os.environ.get("JCKGAN_EMA_DECAY", "0") or 0) if ema_decay is None else float(ema_decay)
+            if not 0.0 <= d <= 1.0:
+                raise JckError(f"ema_decay must lie in [0, 1], got {d}")
+            self.ema_decay, self.ema_start = (d if d > 0.0 else None), int(ema_start)
+        self.ema_sampler = bool(ema)
+        if self.ema_sampler and (share is None or share.ema_decay is None):
+            raise JckError("ema=True needs share= an engine created with ema_decay")
         self._packed_version = -1
         # hipGraph replay of the step (JCK_GRAPH=1 enables): one captured graph per (segment, step parity, input kind).
         # Default: off.  A captured step is linear (see jck_engine_phase), so it gives up the second stream that runs the weight
@@ -150,11 +166,29 @@ class DcganEngine:
                 self.arenas[f"{tag}_{what}"] = torch.zeros(n, **f32)
             self.arenas[f"{tag}_bn"] = torch.zeros(nb, **f32)
             self.arenas[f"{tag}_nbt"] = torch.zeros(8, dtype=torch.int64, device=self.device)
+            if tag == "g" and self.ema_decay is not None:
+                # the average and the BatchNorm buffers its sampling engines move (seeded from the live ones: reset_ema)
+                self.arenas["g_ema"] = torch.zeros(n, **f32)
+                self.arenas["g_ema_bn"] = torch.zeros(nb, **f32)
+                self.arenas["g_ema_nbt"] = torch.zeros(8, dtype=torch.int64, device=self.device)
         self.ws_bytes = dll.jck_engine_workspace_bytes(h)
         self.workspace = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=self.device)
         a = self.arenas
-        lib.jck_engine_bind(h, self.workspace, self.ws_bytes, a["g_params"], a["g_grads"], a["g_m"], a["g_v"], a["g_bn"],
-                            a["g_nbt"], a["d_params"], a["d_grads"], a["d_m"], a["d_v"], a["d_bn"], a["d_nbt"])
+        if self.ema_sampler:
+            # G's forward reads the average where a training engine reads the parameters; everything else is the same engine
+            if not self._shared.get("ema_bn_seeded"):
+                share.join()
+                a["g_ema_bn"].copy_(a["g_bn"])
+                a["g_ema_nbt"].copy_(a["g_nbt"])
+                self._shared["ema_bn_seeded"] = True
+            lib.jck_engine_bind(h, self.workspace, self.ws_bytes, a["g_ema"], a["g_grads"], a["g_m"], a["g_v"], a["g_ema_bn"],
+                                a["g_ema_nbt"], a["d_params"], a["d_grads"], a["d_m"], a["d_v"], a["d_bn"], a["d_nbt"])
+        else:
+            lib.jck_engine_bind(h, self.workspace, self.ws_bytes, a["g_params"], a["g_grads"], a["g_m"], a["g_v"], a["g_bn"],
+                                a["g_nbt"], a["d_params"], a["d_grads"], a["d_m"], a["d_v"], a["d_bn"], a["d_nbt"])
+            if self.ema_decay is not None:
+                lib.jck_engine_bind_ema(h, a["g_ema"])
+                lib.jck_engine_set_ema(h, self.ema_decay, self.ema_start)
         self.layout = {"g": _layout(h, 0), "d": _layout(h, 1)}
         # the step's own draws (Philox: z, alpha, instance noise, dropout masks) follow torch's seed unless the caller sets one
         self.set_noise_seed(int(torch.initial_seed()) + 0x6a636b67)
@@ -163,6 +197,8 @@ class DcganEngine:
             for name, kind, off, numel, shp in self.layout[tag]:
                 if kind == 2 and share is None:
                     a[f"{tag}_bn"][off:off + numel].fill_(1.0)
+        if share is None and self.ema_decay is not None:
+            self.reset_ema()
 
     # optimiser step count and weight version are shared by engines bound to the same arenas
     @property
@@ -186,19 +222,47 @@ class DcganEngine:
 
     # ---- state ------------------------------------------------------------------------------------------
     def named_views(self, tag, what="params"):
-        """{state-dict key: view}. what: 'params' (incl. BN buffers), 'grads', 'm', 'v'.  (Call join() first when a step
+        """{state-dict key: view}. what: 'params' (incl. BN buffers), 'grads', 'm', 'v', and for tag 'g' of an engine that keeps
+        one 'ema': the averaged generator with the BatchNorm buffers its sampling engines move.  (Call join() first when a step
         may still be in flight and the views are about to be read.)"""
+        if what == "ema" and (tag != "g" or "g_ema" not in self.arenas):
+            raise JckError("named_views: only the generator of an engine created with ema_decay has an average")
         out = {}
         bn_i = 0
+        bn, nbt = (f"{tag}_ema_bn", f"{tag}_ema_nbt") if what == "ema" else (f"{tag}_bn", f"{tag}_nbt")
         for name, kind, off, numel, shp in self.layout[tag]:
             if kind == 0:
                 out[name] = self.arenas[f"{tag}_{what}"][off:off + numel].view(shp)
-            elif what == "params":
-                out[name] = self.arenas[f"{tag}_bn"][off:off + numel].view(shp)
+            elif what in ("params", "ema"):
+                out[name] = self.arenas[bn][off:off + numel].view(shp)
                 if kind == 2:
-                    out[name.replace("running_var", "num_batches_tracked")] = self.arenas[f"{tag}_nbt"][bn_i]
+                    out[name.replace("running_var", "num_batches_tracked")] = self.arenas[nbt][bn_i]
                     bn_i += 1
         return out
+
+    def reset_ema(self):
+        """average := parameters, its BatchNorm buffers := the live ones (a fresh or freshly loaded generator is its own average)."""
+        self.join()
+        a = self.arenas
+        a["g_ema"].copy_(a["g_params"])
+        a["g_ema_bn"].copy_(a["g_bn"])
+        a["g_ema_nbt"].copy_(a["g_nbt"])
+
+    def ema_state_dict(self):
+        """The averaged generator under the reference's state-dict keys (CPU copies, model_g's keys and shapes)."""
+        self.join()
+        return {k: v.detach().cpu().clone() for k, v in self._ordered("g", "ema")}
+
+    def load_ema_state(self, sd):
+        """Restores an average saved by ema_state_dict() (a checkpoint's "model_g_ema")."""
+        self.join()
+        views = self.named_views("g", "ema")
+        for k, v in sd.items():
+            if k not in views:
+                raise JckError(f"unexpected key {k}")
+            views[k].copy_(v.detach().to(self.device).view(views[k].shape))
+        self._shared["ema_bn_seeded"] = True    # a sampling engine created later keeps the restored buffers
+        self.mark_weights_changed()             # sampling engines re-derive their operands before their next use
 
     def load_state(self, g_state, d_state):
         """Copies reference-keyed state dicts (CPU or device tensors) into the arenas and re-derives the bf16 operands."""
@@ -209,6 +273,8 @@ class DcganEngine:
                 if k not in views:
                     raise JckError(f"unexpected key {k}")
                 views[k].copy_(v.detach().to(self.device).view(views[k].shape))
+        if "g_ema" in self.arenas:
+            self.reset_ema()
         self.mark_weights_changed()
         self.repack()
 
@@ -217,9 +283,9 @@ class DcganEngine:
         order = lambda tag: {k: v.detach().cpu().clone() for k, v in self._ordered(tag)}
         return order("g"), order("d")
 
-    def _ordered(self, tag):
+    def _ordered(self, tag, what="params"):
         """reference state_dict order: per layer weight, [bias, running_mean, running_var, num_batches_tracked]."""
-        v = self.named_views(tag)
+        v = self.named_views(tag, what)
         keys = [k for k in ("label_embedding.weight", "label_embedding.bias") if k in v]
         for i in range(1, 8):
             if f"conv{i}.weight" in v:
@@ -261,10 +327,16 @@ class DcganEngine:
                     for part in path:
                         owner = getattr(owner, part)
                     owner._buffers[leaf] = views[name]
+        if "g_ema" in self.arenas:
+            self.reset_ema()
         self.mark_weights_changed()
         self.repack()
 
     # ---- the step ---------------------------------------------------------------------------------------
+    def _training_only(self, what):
+        if self.ema_sampler:
+            raise JckError(f"{what}: this engine samples the averaged generator (ema=True); train on the engine it shares its state with")
+
     def _inputs(self, real, noise, lr, grad_scale):
         B, S = self.batch, self.size
         si = StepInputs()
@@ -532,6 +604,7 @@ class DcganEngine:
         stack + BatchNorm statistics) is then enqueued right behind the start of G's gradient all-reduce, so the collective
         runs under ~0.13 ms of compute that needs no G weights, instead of being waited for at once; the next step_async call
         must be given that same batch.  Results are bitwise those of the plain order (PHASE_D_REAL_FWD, include/jckgan.h)."""
+        self._training_only("step_async")
         if self._packed_version != self._shared["version"]:
             self.join()
             self.repack()
@@ -667,6 +740,7 @@ class DcganEngine:
         arenas["d_grads"] (cleared first).  real / fake: [B,3,S,S]
         fp32 device tensors taken as they are, alpha [B]; CGAN: labels int64 one-hot [B,100], drop_mask float keep-mask [B,256]."""
         B, S = self.batch, self.size
+        self._training_only("gradient_penalty_pass")
         self.join()
         if self._packed_version != self._shared["version"]:
             self.repack()

@@ -48,8 +48,14 @@ class EngineAdam:
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         p = a[f"{self.tag}_params"]
-        lib.jck_adam(p, a[f"{self.tag}_grads"], a[f"{self.tag}_m"], a[f"{self.tag}_v"], p.numel(), float(g["lr"]), float(b1), float(b2),
-                     float(g["eps"]), t, 1.0, cur_stream())
+        if self.tag == "g" and "g_ema" in a:
+            # the engine keeps an average of G's weights: advanced by the same launch, with the weight PHASE_G_STEP gives step t
+            w = 1.0 if t < eng.ema_start else 1.0 - eng.ema_decay
+            lib.jck_adam_ema(p, a["g_grads"], a["g_m"], a["g_v"], a["g_ema"], p.numel(), float(g["lr"]), float(b1), float(b2),
+                             float(g["eps"]), t, 1.0, w, None, cur_stream())
+        else:
+            lib.jck_adam(p, a[f"{self.tag}_grads"], a[f"{self.tag}_m"], a[f"{self.tag}_v"], p.numel(), float(g["lr"]), float(b1), float(b2),
+                         float(g["eps"]), t, 1.0, cur_stream())
         self._own_t = t
         eng.t = max(eng.t, t)                   # what state_dict() writes as "step"
         eng.mark_weights_changed()              # the packed GEMM operands are rebuilt before their next use

@@ -45,6 +45,11 @@ def get_arg_parse(argv=None):
     # not in the namespace unless given (default 0, read by the trainer): the reference's flag set stays as it is
     p.add_argument("-gpb", "--gp_backward", type=int, choices=(0, 1), default=argparse.SUPPRESS,
                    help="DCGAN: back-propagate the gradient penalty into D (1); 0 (default) = the reference, which only logs it")
+    p.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS,
+                   help="keep an exponential moving average of G's weights with this decay (e.g. 0.999): evaluation samples it and "
+                        "checkpoints gain 'model_g_ema'; absent or 0 = the reference, which has none")
+    p.add_argument("--ema_start", type=int, default=argparse.SUPPRESS,
+                   help="first optimiser step that averages; before it the average equals the weights (default 0)")
     return p.parse_args(argv)
 
 

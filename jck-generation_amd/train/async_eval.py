@@ -5,7 +5,8 @@ The reference stops training every 500 iterations: G(fixed_noise), resize to 299
 scipy on the host, torch.save.  Here the device part - sampling (ONE train-mode BatchNorm batch, as in the reference), the
 fused resize + normalise, the metric network, the copies to pinned host memory - is enqueued on a second stream, and the
 training stream waits only for the SAMPLING kernels and the checkpoint snapshot's device copies (they read G's weights and move
-its BatchNorm running statistics, so the next step must come after them, exactly where the reference has them).  The host part (softmax / KL, fp64 mean-cov read-back,
+its BatchNorm running statistics, so the next step must come after them, exactly where the reference has them; with --ema_decay
+the sampled generator is the average of G's weights, whose own running statistics move instead, and the snapshot gains it).  The host part (softmax / KL, fp64 mean-cov read-back,
 scipy sqrtm, log line, checkpoint) runs when the copies have landed - checked at the next log points, forced before the next
 evaluation and at the end of training.  What is written is a snapshot taken at the evaluation iteration, so the checkpoint
 holds the same state the reference would have saved."""
@@ -24,14 +25,20 @@ def to_host_async(t):
 def checkpoint_snapshot(trainer):
     """What save_model writes (train/dcgan_trainer.py:86-91), copied on the device NOW: the live state moves on while the
     scores of this evaluation are still being computed."""
-    return {"model_g": {k: v.detach().clone() for k, v in trainer.model_g.state_dict().items()},
+    snap = {"model_g": {k: v.detach().clone() for k, v in trainer.model_g.state_dict().items()},
             "model_d": {k: v.detach().clone() for k, v in trainer.model_d.state_dict().items()},
             "optimizer_g": trainer.optimizer_g.state_dict(), "optimizer_d": trainer.optimizer_d.state_dict()}
+    if "g_ema" in trainer.engine.arenas:        # the averaged generator the images of this evaluation came from (--ema_decay)
+        snap["model_g_ema"] = {k: v.detach().clone() for k, v in trainer.engine._ordered("g", "ema")}
+    return snap
 
 
 def snapshot_to_cpu(snap):
-    return {"model_g": {k: v.cpu() for k, v in snap["model_g"].items()}, "model_d": {k: v.cpu() for k, v in snap["model_d"].items()},
-            "optimizer_g": snap["optimizer_g"], "optimizer_d": snap["optimizer_d"]}
+    out = {"model_g": {k: v.cpu() for k, v in snap["model_g"].items()}, "model_d": {k: v.cpu() for k, v in snap["model_d"].items()},
+           "optimizer_g": snap["optimizer_g"], "optimizer_d": snap["optimizer_d"]}
+    if "model_g_ema" in snap:
+        out["model_g_ema"] = {k: v.cpu() for k, v in snap["model_g_ema"].items()}
+    return out
 
 
 class AsyncEval:

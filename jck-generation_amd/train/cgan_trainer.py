@@ -48,13 +48,14 @@ class CGANTrainer(DCGANTrainer):
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world, self.rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
         self.batch_size = int(getattr(args, "batch_size", 128))
-        self.engine = CganEngine(batch=self.batch_size, prec=self.prec, device=self.device)
+        self.engine = CganEngine(batch=self.batch_size, prec=self.prec, device=self.device,
+                                 ema_decay=getattr(args, "ema_decay", None), ema_start=int(getattr(args, "ema_start", 0)))
         self.engine.adopt_modules(self.model_g, self.model_d)
         if self.world > 1:
             for key in ("g_params", "d_params", "g_bn", "d_bn"):
                 torch.distributed.broadcast(self.engine.arenas[key], src=0)
             self.engine.mark_weights_changed()
-        self._tail_engines = {}
+        self._tail_engines, self._ema_samplers = {}, {}
         self.reducer = GradReducer(self.world) if self.world > 1 else None
         self.guard = (ReplicaGuard(lambda: [self.engine] + list(self._tail_engines.values()), self.world, log=self.logger.debug)
                       if self.world > 1 else None)         # replicas must stay identical: hipgan/dist.py
@@ -97,6 +98,8 @@ class CGANTrainer(DCGANTrainer):
             "model_g": {k: v.detach().cpu().clone() for k, v in self.model_g.state_dict().items()},
             "model_d": {k: v.detach().cpu().clone() for k, v in self.model_d.state_dict().items()},
             "optimizer_g": self.optimizer_g.state_dict(), "optimizer_d": self.optimizer_d.state_dict()}
+        if snapshot is None and self.engine.ema_decay is not None:
+            state["model_g_ema"] = self.engine.ema_state_dict()
         self.engine.check()                     # (the copies above synchronised) never checkpoint a step whose grid barrier timed out
         torch.save(state, os.path.join(save_path, f"{iters}_{inception_score:.04f}_{fid:.04f}_{intra_fid:.04f}.pt"))
         self.save_image(save_path, iters, images)
@@ -132,7 +135,7 @@ class CGANTrainer(DCGANTrainer):
         BatchNorm batch as in the reference, the fused 299x299 resize + normalise, ONE pass of the metric network, fp64 mean /
         covariance of the logits (all 1000 and per superclass) - training resumes behind the sampling kernels only."""
         self._finish_eval(best, wait=True)
-        eng = self._engine_for(fixed_noise.size(0))
+        eng = self._sampler_for(fixed_noise.size(0))
         self._image_save_path = image_save_path
 
         def device_part(fake):

@@ -126,13 +126,14 @@ class DCGANTrainer(Trainer):
         self.batch_size = int(getattr(args, "batch_size", 128))
         self.engine = DcganEngine(batch=self.batch_size, prec=self.prec, device=self.device,
                                   image_size=getattr(self.model_g, "image_size", 64),     # 128: the configs[4] topology
-                                  gp_backward=self.gp_backward)                           # the tail-batch engines share it
+                                  gp_backward=self.gp_backward,                           # the tail-batch engines share it
+                                  ema_decay=getattr(args, "ema_decay", None), ema_start=int(getattr(args, "ema_start", 0)))
         self.engine.adopt_modules(self.model_g, self.model_d)
         if self.world > 1:
             for key in ("g_params", "d_params", "g_bn", "d_bn"):
                 torch.distributed.broadcast(self.engine.arenas[key], src=0)
             self.engine.mark_weights_changed()
-        self._tail_engines = {}
+        self._tail_engines, self._ema_samplers = {}, {}
         self.reducer = GradReducer(self.world) if self.world > 1 else None
         # every rank must hold the same parameters after a step: checked after the first steps and at every evaluation point; on a
         # mismatch the state is re-broadcast and the engines fall back to the plain all-reduce schedule (hipgan/dist.py)
@@ -179,6 +180,15 @@ class DCGANTrainer(Trainer):
             self._tail_engines[b].set_noise_seed(self._noise_seed)
         return self._tail_engines[b]
 
+    def _sampler_for(self, n):
+        """The engine evaluation samples n images from: the averaged generator when the engine keeps one (--ema_decay; its own
+        BatchNorm running statistics, the live generator's stay where training left them), else the live one as the reference does."""
+        if self.engine.ema_decay is None:
+            return self._engine_for(n)
+        if n not in self._ema_samplers:
+            self._ema_samplers[n] = type(self.engine)(batch=n, share=self.engine, ema=True)
+        return self._ema_samplers[n]
+
     # ------------------------------------------------------------------------------------------------------
     def save_model(self, typ, iters, value, images, snapshot=None):
         """snapshot: the state captured at the evaluation iteration (train/async_eval.py); None = the live state."""
@@ -195,6 +205,8 @@ class DCGANTrainer(Trainer):
             "model_g": {k: v.detach().cpu().clone() for k, v in self.model_g.state_dict().items()},
             "model_d": {k: v.detach().cpu().clone() for k, v in self.model_d.state_dict().items()},
             "optimizer_g": self.optimizer_g.state_dict(), "optimizer_d": self.optimizer_d.state_dict()}
+        if snapshot is None and self.engine.ema_decay is not None:
+            state["model_g_ema"] = self.engine.ema_state_dict()
         self.engine.check()                     # (the copies above synchronised) never checkpoint a step whose grid barrier timed out
         torch.save(state, os.path.join(save_path, f"{iters}_{value:.04f}.pt"))
         _save_png(os.path.join(save_path, f"{iters}_fake_image.png"), _make_grid(images, padding=2, normalize=True), "fake images")
@@ -207,6 +219,11 @@ class DCGANTrainer(Trainer):
         self.model_d.load_state_dict(saved["model_d"])
         self.optimizer_g.load_state_dict(saved["optimizer_g"])
         self.optimizer_d.load_state_dict(saved["optimizer_d"])
+        if self.engine.ema_decay is not None:       # a checkpoint written without --ema_decay: the average starts at its weights
+            if "model_g_ema" in saved:
+                self.engine.load_ema_state(saved["model_g_ema"])
+            else:
+                self.engine.reset_ema()
         self.engine.mark_weights_changed()
 
     def compute_gradient_penalty(self, real_data, fake_data):
@@ -223,7 +240,7 @@ class DCGANTrainer(Trainer):
         """Device part of the evaluation (reference :198-212) on a side stream; training resumes behind the sampling kernels
         only (train/async_eval.py).  The host part runs in _finish_eval."""
         self._finish_eval(best, wait=True)          # the evaluation of 500 iterations ago, if its host part is still owed
-        eng = self._engine_for(fixed_noise.size(0))
+        eng = self._sampler_for(fixed_noise.size(0))
 
         def device_part(fake):
             if self.metric is None:
