@@ -14,6 +14,11 @@
 // rate - accuracy, not speed, is what a metric network needs): 64 pixels x 64 channels per workgroup, k = (kh, kw, ci) in
 // steps of 16; the activation tile is gathered with ci fastest across lanes (64-byte runs), the weight tile [k][co] with co
 // fastest, both through padded LDS rows.
+//
+// Non-finite values pass through every kernel as they do through torch's operators (a NaN or infinite image must give NaN
+// scores, not finite ones): the ReLU keeps NaN, the max pool starts from -inf and keeps a NaN tap, the sums carry the rest.
+// tests/test_infer_exact_gpu.py holds this, kernel by kernel and through the whole chain, next to the bit-exact integer-data
+// cases of every kernel here.
 #include <cstdlib>
 
 #include "ops_internal.hpp"
@@ -102,7 +107,7 @@ __global__ __launch_bounds__(256) void conv2d_nhwc_f32_kernel(const ConvP p) {
         const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
         if (m >= p.M) continue;
         float v = acc[i][j][r] * sc + sh;
-        if (p.relu) v = v > 0.f ? v : 0.f;
+        if (p.relu) v = v <= 0.f ? 0.f : v;                           // NaN stays NaN (torch's relu)
         p.out[(long long)m * p.ocs + p.ocoff + co] = v;
       }
   }
@@ -113,7 +118,8 @@ __global__ __launch_bounds__(256) void conv2d_nhwc_f32_kernel(const ConvP p) {
 // 16-byte loads per thread and k-step (4 consecutive input channels of a pixel) instead of eight scalar loads behind an integer
 // division.  128 pixels x 64 channels per workgroup (each weight value is used by twice the pixels), register double buffering:
 // the loads of k-step i+1 are in flight while step i is multiplied, one barrier per step.  Same k order and the same exact-fp32
-// MFMA as the generic kernel above - the results are bitwise the same.  Measured (tools/eval_prof.py, 64 images): see DESIGN.md.
+// MFMA as the generic kernel above - the results are bitwise the same (tests/test_infer_exact_gpu.py runs every case through both
+// kernels and compares with torch.equal; keep the two epilogues identical).  Measured (tools/eval_prof.py, 64 images): see DESIGN.md.
 constexpr int CV_M = 128, CV_N = 64, CV_K = 16, CV_LDA = 20, CV_LDB = 80;
 __global__ __launch_bounds__(256) void conv2d_nhwc_f32_c16_kernel(const ConvP p) {
   __shared__ __attribute__((aligned(16))) float As[2][CV_M][CV_LDA];       // [pixel][k]: 16-byte rows; (20 m + k) % 64 is conflict-free
@@ -194,7 +200,7 @@ __global__ __launch_bounds__(256) void conv2d_nhwc_f32_c16_kernel(const ConvP p)
         const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
         if (m >= p.M) continue;
         float v = acc[i][j][r] * sc + sh;
-        if (p.relu) v = v > 0.f ? v : 0.f;
+        if (p.relu) v = v <= 0.f ? 0.f : v;                           // NaN stays NaN (torch's relu)
         p.out[(long long)m * p.ocs + p.ocoff + co] = v;
       }
   }
@@ -210,13 +216,13 @@ __global__ void pool2d_nhwc_f32_kernel(const float* __restrict__ x, float* __res
     const int ox = (int)(t % OW); t /= OW;
     const int oy = (int)(t % OH);
     const long long n = t / OH;
-    float v = mode == 0 ? -3.402823466e38f : 0.f;
+    float v = mode == 0 ? -__builtin_huge_valf() : 0.f;
     for (int dy = 0; dy < k; ++dy)
       for (int dx = 0; dx < k; ++dx) {
         const int iy = oy * stride - pad + dy, ix = ox * stride - pad + dx;
         if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) continue;
         const float u = x[((n * H + iy) * W + ix) * C + c];
-        v = mode == 0 ? fmaxf(v, u) : v + u;
+        v = mode == 0 ? ((u > v || u != u) ? u : v) : v + u;           // a NaN tap wins and stays (torch's max_pool2d)
       }
     if (mode == 1) v /= (float)(k * k);
     out[((n * OH + oy) * OW + ox) * ocs + ocoff + c] = v;
@@ -293,7 +299,8 @@ extern "C" int jck_conv2d_nhwc_f32(const float* x, const float* w_kc, const floa
   p.x = x; p.w = w_kc; p.scale = scale; p.shift = shift; p.out = out;
   p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
   p.OH = (H + 2 * PH - KH) / SH + 1; p.OW = (W + 2 * PW - KW) / SW + 1;
-  if (p.OH < 1 || p.OW < 1) JCK_FAIL(JCK_E_ARG, "conv2d_nhwc_f32: kernel larger than the padded input");
+  // (a negative numerator above truncates towards zero: with a stride > 1 the quotient alone does not show it)
+  if (H + 2 * PH < KH || W + 2 * PW < KW || p.OH < 1 || p.OW < 1) JCK_FAIL(JCK_E_ARG, "conv2d_nhwc_f32: kernel larger than the padded input");
   p.Cout = Cout; p.K = KH * KW * Cin;
   const long long M = (long long)N * p.OH * p.OW;
   if (M >= (1ll << 31) || (long long)N * H * W * Cin >= (1ll << 40)) JCK_FAIL(JCK_E_ARG, "conv2d_nhwc_f32: tensor too large");
@@ -312,7 +319,8 @@ extern "C" int jck_pool2d_nhwc_f32(const float* x, float* out, int N, int H, int
                                    int out_cstride, int out_coff, void* stream) {
   if (!x || !out || N < 1 || C < 1 || k < 1 || stride < 1 || pad < 0 || (mode != 0 && mode != 1)) JCK_FAIL(JCK_E_ARG, "pool2d: bad arguments");
   const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
-  if (OH < 1 || OW < 1 || out_cstride < out_coff + C) JCK_FAIL(JCK_E_ARG, "pool2d: bad geometry");
+  if (H + 2 * pad < k || W + 2 * pad < k || OH < 1 || OW < 1 || out_cstride < out_coff + C || out_coff < 0)
+    JCK_FAIL(JCK_E_ARG, "pool2d: bad geometry");                       // window larger than the padded input (as in conv2d) / slice
   hipLaunchKernelGGL(pool2d_nhwc_f32_kernel, dim3(grid1d((long long)N * OH * OW * C)), dim3(256), 0, (hipStream_t)stream, x, out, N, H,
                      W, C, k, stride, pad, OH, OW, mode, out_cstride, out_coff);
   HIPCHK(hipGetLastError());

@@ -61,8 +61,11 @@ def mean_cov(x):
 
 
 def fid_from_stats(mu1, sigma1, mu2, sigma2):
-    """reference metrics.py:127-129 from the two Gaussians' parameters"""
+    """reference metrics.py:127-129 from the two Gaussians' parameters.  Non-finite statistics (a NaN or infinite feature)
+    give NaN: scipy's sqrtm refuses such a matrix with a ValueError, which would end the run the score is reported to."""
     mu1, sigma1, mu2, sigma2 = (np.asarray(v, dtype=np.float64) for v in (mu1, sigma1, mu2, sigma2))
+    if not all(np.isfinite(v).all() for v in (mu1, sigma1, mu2, sigma2)):
+        return float("nan")
     covmean = sqrtm(sigma1.dot(sigma2))
     if np.iscomplexobj(covmean):
         covmean = covmean.real
@@ -71,11 +74,7 @@ def fid_from_stats(mu1, sigma1, mu2, sigma2):
 
 def fid_from_features(real, fake):
     """Frechet distance between the Gaussians fitted to two feature matrices (reference metrics.py:120-129)."""
-    (mu1, sigma1), (mu2, sigma2) = mean_cov(real), mean_cov(fake)
-    covmean = sqrtm(sigma1.dot(sigma2))
-    if np.iscomplexobj(covmean):
-        covmean = covmean.real
-    return float(np.sum((mu1 - mu2) ** 2.0) + np.trace(sigma1 + sigma2 - 2.0 * covmean))
+    return fid_from_stats(*mean_cov(real), *mean_cov(fake))
 
 
 def inception_score_from_probs(preds, splits=10):

@@ -72,6 +72,23 @@ def test_metrics_arithmetic_matches_reference_golden():
     M.Metrics(object(), real_features=real).fid(dl)
 
 
+def test_non_finite_features_give_nan_scores():
+    """One NaN or infinite feature row makes every score NaN - not a finite number, and not scipy's ValueError from sqrtm."""
+    import metrics as M
+    rng = np.random.default_rng(3)
+    real, fake = rng.standard_normal((40, 6)), rng.standard_normal((30, 6))
+    assert np.isfinite(M.fid_from_features(real, fake))
+    for bad in (np.nan, np.inf, -np.inf):
+        f = fake.copy()
+        f[7, 2] = bad
+        with np.errstate(invalid="ignore"):
+            assert np.isnan(M.fid_from_features(real, f)) and np.isnan(M.fid_from_features(f, real))
+            assert np.isnan(M.fid_from_stats(*M.mean_cov(real), *M.mean_cov(f)))
+    logits = torch.from_numpy(fake).float()
+    logits[7] = float("nan")
+    assert np.isnan(M.inception_score_from_probs(torch.softmax(logits, 1).numpy(), splits=1))
+
+
 def test_metrics_unavailable_without_weights():
     import metrics as M
     with pytest.raises(M.MetricsUnavailable):
