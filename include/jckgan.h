@@ -403,6 +403,22 @@ int jck_global_avgpool_nhwc_f32(const float* x, float* out, int N, int HW, int C
 int jck_nchw_to_nhwc_f32(const float* x, float* out, int N, int C, int H, int W, void* stream);
 int jck_mean_cov_f64(const float* x, double* mean, double* cov, int N, int D, void* stream);
 
+/* Pairwise statistics over feature matrices x[M][D], y[N][D] (row-major fp32, any D, any alignment) for KID and improved
+ * precision / recall (jck-generation_amd/metrics.py): one Gram-tile core on the exact-fp32 MFMA, never an M x N matrix in
+ * memory.  Squared distances are d2 = max(0, (|a|^2 + |b|^2) - 2 <a, b>) in fp32 with fmaf-chain norms. */
+/* bytes of workspace jck_poly3_sum_f64 needs for M x N pairs (host only; grows with the launch grid, not with M * N; 0 for
+ * sizes the entry points refuse) */
+size_t jck_pairstat_ws_bytes(int M, int N);
+/* out[0] = sum_{i,j} (gamma * <x_i, y_j> + coef0)^3, the polynomial in fp64; skip_diag != 0 leaves out the pairs i == j (by
+ * index).  Partials per workgroup go to ws, a second launch adds them in a fixed order: deterministic, no atomics. */
+int jck_poly3_sum_f64(const float* x, int M, const float* y, int N, int D, double gamma, double coef0, int skip_diag, double* out,
+                      double* ws, void* stream);
+/* r2[i] = the k-th smallest d2(x_i, x_j) over j != i (by index), 1 <= k <= 8, k < N; NaN for a row with a non-finite norm */
+int jck_knn_radius2_f32(const float* x, int N, int D, int k, float* r2, void* stream);
+/* hit[i] = 1 when d2(q_i, ref_j) <= r2[j] for some j (a tie is a hit), else 0; 255 for a query row with a non-finite norm.
+ * A reference row whose radius is NaN never hits. */
+int jck_manifold_hit_u8(const float* q, int M, const float* ref, const float* r2, int N, int D, unsigned char* hit, void* stream);
+
 /* Per-step optimiser scalars into device memory (so that a captured graph of the step has no per-step kernel argument), and
  * hipGraph capture of a sequence of jck_engine_phase calls: begin -> phases on `stream` (not the default stream) -> end
  * returns an executable graph; launch replays it.  The jck_step_inputs pointers are baked: keep the buffers in place,

@@ -50,6 +50,9 @@ def get_arg_parse(argv=None):
                         "checkpoints gain 'model_g_ema'; absent or 0 = the reference, which has none")
     p.add_argument("--ema_start", type=int, default=argparse.SUPPRESS,
                    help="first optimiser step that averages; before it the average equals the weights (default 0)")
+    p.add_argument("--extra_metrics", type=int, choices=(0, 1), default=argparse.SUPPRESS,
+                   help="1: every evaluation also reports KID, improved precision / recall (CGAN: intra-KID too) on one more log "
+                        "line and keeps 'kid' (CGAN: 'intra_kid') best checkpoints; absent or 0 = the reference's scores only")
     return p.parse_args(argv)
 
 

@@ -7,7 +7,8 @@ reference's network (inception_v3 with a Linear(2048,100) head, weights from ./s
 46-51) run by the hand-written HIP chain of `inception.InceptionV3Hip` - no torchvision needed; when the weights file is
 missing, construction raises MetricsUnavailable and the trainer carries on without scores.  Feature means and covariances are
 formed in fp64 on the device (jck_mean_cov_f64) when the features live there; the matrix square root stays on the host
-(scipy), as in the reference.  Fixes the reference's `.targets` defect for DCGAN (its loader has none): targets are optional."""
+(scipy), as in the reference.  Beyond the reference (opt-in in the trainers): KID, intra-KID and improved precision / recall
+from pairwise kernels over the feature matrices (csrc/pairstat.hip; numpy fp64 for host arrays).  Fixes the reference's `.targets` defect for DCGAN (its loader has none): targets are optional."""
 import os
 import pickle
 
@@ -90,6 +91,149 @@ def inception_score_from_probs(preds, splits=10):
             kl = np.where(pk > 0, pk * np.log(pk / qk), 0.0).sum(axis=1)
         out.append(np.exp(np.mean(kl)))
     return float(np.mean(out))
+
+
+# ---- KID and improved precision / recall: pairwise statistics over feature matrices -------------------------------------
+# KID (Binkowski et al. 2018) is the unbiased MMD^2 with k(a, b) = (a.b / D + 1)^3 over the FULL sets: unbiased at any
+# sample size, no matrix square root.  Improved precision / recall (Kynkaanniemi et al. 2019): a set's manifold is the union
+# of the balls around its points that reach the k-th nearest other point; precision = share of fake points inside real's
+# manifold (fidelity), recall = share of real points inside fake's (coverage).  CUDA tensors go through the kernels of
+# csrc/pairstat.hip (never an M x N matrix in memory), anything else through blocked numpy fp64 of the same formulas.
+_HOST_BLOCK = 2048          # rows per Gram block of the numpy paths: 2048 x 2048 fp64 = 32 MiB, whatever the set sizes
+
+
+def _np64(x):
+    x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return np.ascontiguousarray(x, dtype=np.float64)
+
+
+def _pair_device(*xs):
+    """the CUDA device the pairwise statistics run on: that of the first CUDA tensor among xs (None: numpy)"""
+    for x in xs:
+        if torch.is_tensor(x) and x.is_cuda:
+            return x.device
+    return None
+
+
+def _dev32(x, device):
+    x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+    return x.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def poly3_sum(x, y, skip_diag=False):
+    """sum_{i,j} (x_i.y_j / D + 1)^3, without the pairs i == j (by index) when skip_diag.  CUDA: a fp64 device tensor [1]
+    (jck_poly3_sum_f64: fp32 dot product, fp64 polynomial and sums, fixed order; no host sync); else a Python float."""
+    dev = _pair_device(x, y)
+    if dev is not None:
+        from hipgan._lib import cur_stream, lib, load_library
+        x, y = _dev32(x, dev), _dev32(y, dev)
+        (m, d), n = x.shape, y.shape[0]
+        out = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = torch.empty(max(1, load_library().jck_pairstat_ws_bytes(m, n) // 8), dtype=torch.float64, device=dev)
+        lib.jck_poly3_sum_f64(x, m, y, n, d, 1.0 / d, 1.0, int(bool(skip_diag)), out, ws, cur_stream())
+        return out
+    x, y = _np64(x), _np64(y)
+    d, total = x.shape[1], 0.0
+    with np.errstate(all="ignore"):
+        for i in range(0, x.shape[0], _HOST_BLOCK):
+            for j in range(0, y.shape[0], _HOST_BLOCK):
+                total += float(((x[i:i + _HOST_BLOCK] @ y[j:j + _HOST_BLOCK].T / d + 1.0) ** 3).sum())
+        if skip_diag:
+            r = min(x.shape[0], y.shape[0])
+            total -= float((((x[:r] * y[:r]).sum(axis=1) / d + 1.0) ** 3).sum())
+    return total
+
+
+def knn_radius2(x, k):
+    """r2[i] = the k-th smallest squared distance from x_i to the OTHER rows of x (by index: a duplicate row is a neighbour at
+    distance 0); NaN for a non-finite row.  CUDA: float32 device tensor (jck_knn_radius2_f32, 1 <= k <= 8); else float64 numpy."""
+    if not 1 <= k < x.shape[0]:
+        raise ValueError(f"knn_radius2: k = {k} needs 1 <= k < rows = {x.shape[0]}")
+    dev = _pair_device(x)
+    if dev is not None:
+        from hipgan._lib import cur_stream, lib
+        x = _dev32(x, dev)
+        r2 = torch.empty(x.shape[0], dtype=torch.float32, device=dev)
+        lib.jck_knn_radius2_f32(x, x.shape[0], x.shape[1], k, r2, cur_stream())
+        return r2
+    x = _np64(x)
+    n = x.shape[0]
+    r2 = np.empty(n)
+    with np.errstate(all="ignore"):
+        nrm = (x * x).sum(axis=1)
+        step = max(1, min(_HOST_BLOCK, (_HOST_BLOCK * _HOST_BLOCK) // n))
+        for i in range(0, n, step):
+            d2 = np.maximum((nrm[i:i + step, None] + nrm[None, :]) - 2.0 * (x[i:i + step] @ x.T), 0.0)
+            rows = np.arange(d2.shape[0])
+            d2[rows, i + rows] = np.inf
+            d2[np.isnan(d2)] = np.inf                       # a non-finite row is nobody's neighbour
+            r2[i:i + step] = np.partition(d2, k - 1, axis=1)[:, k - 1]
+    r2[~np.isfinite(nrm)] = np.nan
+    return r2
+
+
+def manifold_hit(q, ref, r2):
+    """hit[i] = 1 when q_i lies within sqrt(r2[j]) of some ref_j (a tie is a hit), else 0; 255 for a non-finite q_i.  uint8:
+    a CUDA tensor (jck_manifold_hit_u8) when any argument is one, else numpy."""
+    dev = _pair_device(q, ref, r2)
+    if dev is not None:
+        from hipgan._lib import cur_stream, lib
+        q, ref, r2 = _dev32(q, dev), _dev32(ref, dev), _dev32(r2, dev)
+        hit = torch.empty(q.shape[0], dtype=torch.uint8, device=dev)
+        lib.jck_manifold_hit_u8(q, q.shape[0], ref, r2, ref.shape[0], q.shape[1], hit, cur_stream())
+        return hit
+    q, ref, r2 = _np64(q), _np64(ref), _np64(r2)
+    hit = np.zeros(q.shape[0], dtype=np.uint8)
+    with np.errstate(all="ignore"):
+        nq, nr = (q * q).sum(axis=1), (ref * ref).sum(axis=1)
+        for i in range(0, q.shape[0], _HOST_BLOCK):
+            for j in range(0, ref.shape[0], _HOST_BLOCK):
+                d2 = np.maximum((nq[i:i + _HOST_BLOCK, None] + nr[None, j:j + _HOST_BLOCK]) - 2.0 * (q[i:i + _HOST_BLOCK] @ ref[j:j + _HOST_BLOCK].T), 0.0)
+                hit[i:i + _HOST_BLOCK] |= (d2 <= r2[None, j:j + _HOST_BLOCK]).any(axis=1).astype(np.uint8)
+    hit[~np.isfinite(nq)] = 255
+    return hit
+
+
+def _scalar(v):
+    v = v.detach().cpu().numpy() if torch.is_tensor(v) else v
+    return float(np.asarray(v, dtype=np.float64).reshape(-1)[0])
+
+
+def _host(v):
+    return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+
+
+def kid_from_sums(rr, ff, rf, m, n):
+    """the unbiased MMD^2 from the three kernel sums (real x real and fake x fake without their diagonals) of m real and n fake rows"""
+    return _scalar(rr) / (m * (m - 1)) + _scalar(ff) / (n * (n - 1)) - 2.0 * _scalar(rf) / (m * n)
+
+
+def kid_from_features(real, fake):
+    """Kernel Inception Distance of two feature matrices: sum_{i!=j} k(x_i,x_j) / (m(m-1)) + sum_{i!=j} k(y_i,y_j) / (n(n-1))
+    - 2 sum k(x_i,y_j) / (mn) with k(a,b) = (a.b/D + 1)^3, over the full sets.  Non-finite features give NaN."""
+    dev = _pair_device(real, fake)
+    if dev is not None:
+        real, fake = _dev32(real, dev), _dev32(fake, dev)
+    small, big = (fake, real) if fake.shape[0] <= real.shape[0] else (real, fake)      # the kernel's grid runs over its second operand
+    return kid_from_sums(poly3_sum(real, real, True), poly3_sum(fake, fake, True), poly3_sum(small, big), real.shape[0], fake.shape[0])
+
+
+def precision_recall_from_hits(hit_fake, hit_real):
+    """(precision, recall) from the hit vectors of fake in real's manifold and of real in fake's; a 255 marker (a non-finite row
+    in either set) gives (nan, nan)"""
+    hit_fake, hit_real = _host(hit_fake), _host(hit_real)
+    if (hit_fake == 255).any() or (hit_real == 255).any():
+        return float("nan"), float("nan")
+    return float(hit_fake.mean()), float(hit_real.mean())
+
+
+def precision_recall_from_features(real, fake, k=3):
+    """Improved precision / recall: (mean hit of fake in real's k-NN manifold, mean hit of real in fake's).  A non-finite row in
+    either set gives (nan, nan)."""
+    dev = _pair_device(real, fake)
+    if dev is not None:
+        real, fake = _dev32(real, dev), _dev32(fake, dev)
+    return precision_recall_from_hits(manifold_hit(fake, real, knn_radius2(real, k)), manifold_hit(real, fake, knn_radius2(fake, k)))
 
 
 class Metrics:
@@ -237,3 +381,79 @@ class Metrics:
             sub = generated_images[self.fake_superclass_idx[s]]
             total += self.fid(torch.utils.data.DataLoader(sub, 128, shuffle=False), intra_fid=True, label=s)
         return total / 100
+
+    # ---- KID, intra-KID, precision / recall (not in the reference; the trainers report them with --extra_metrics 1)
+    def _real_pair_stats(self, label=None, on_device=False):
+        """Real-side terms of KID for all real features (label None) or one superclass, computed once per Metrics object:
+        {'feats', 'n', 'rr' = sum_{i!=j} k(x_i, x_j)} - device tensors when on_device, else numpy / float."""
+        cache = self.__dict__.setdefault("_real_pair_cache", {})
+        key = (label, bool(on_device))
+        if key not in cache:
+            feats = self._real_on_device() if on_device else np.asarray(self.real_features, dtype=np.float32)
+            if label is not None:
+                idx = self.real_superclass_idx[label]
+                feats = feats[torch.as_tensor(idx, device=feats.device)].contiguous() if on_device else feats[idx]
+            cache[key] = {"feats": feats, "n": int(feats.shape[0]), "rr": poly3_sum(feats, feats, True)}
+        return cache[key]
+
+    def _real_radii(self, k=3, on_device=False):
+        """squared k-NN radii of the real features (real's manifold), computed once per k"""
+        cache = self.__dict__.setdefault("_real_radii_cache", {})
+        key = (int(k), bool(on_device))
+        if key not in cache:
+            cache[key] = knn_radius2(self._real_pair_stats(None, on_device)["feats"], k)
+        return cache[key]
+
+    def fake_pair_stats_device(self, logits, intra=False, k=3):
+        """Device part of KID / precision / recall of generated logits (CUDA), enqueued on the current stream without a host sync;
+        finish with extra_scores_from_stats().  {'kid_rr', 'kid_ff', 'kid_rf'} fp64 sums [1], {'hit_fake', 'hit_real'} uint8 hit
+        vectors (fake in real's manifold, real in fake's) and, with intra, 'kid_rr_s<k>', 'kid_ff_s<k>', 'kid_rf_s<k>' per superclass."""
+        x = logits.detach().to(torch.float32).contiguous()
+        real = self._real_pair_stats(None, True)
+        out = {"kid_rr": real["rr"], "kid_ff": poly3_sum(x, x, True), "kid_rf": poly3_sum(x, real["feats"]),
+               "hit_fake": manifold_hit(x, real["feats"], self._real_radii(k, True)),
+               "hit_real": manifold_hit(real["feats"], x, knn_radius2(x, k))}
+        if intra:
+            for s_ in range(20):
+                xs = x[torch.as_tensor(self.fake_superclass_idx[s_], device=x.device)].contiguous()
+                rs = self._real_pair_stats(s_, True)
+                out[f"kid_rr_s{s_}"], out[f"kid_ff_s{s_}"], out[f"kid_rf_s{s_}"] = rs["rr"], poly3_sum(xs, xs, True), poly3_sum(xs, rs["feats"])
+        return out
+
+    def extra_scores_from_stats(self, stats, intra=False):
+        """Host part: host copies of fake_pair_stats_device -> {'kid', 'precision', 'recall'[, 'intra_kid']}."""
+        m, n = int(np.asarray(self.real_features).shape[0]), int(stats["hit_fake"].shape[0])
+        precision, recall = precision_recall_from_hits(stats["hit_fake"], stats["hit_real"])
+        out = {"kid": kid_from_sums(stats["kid_rr"], stats["kid_ff"], stats["kid_rf"], m, n), "precision": precision, "recall": recall}
+        if intra:
+            out["intra_kid"] = float(np.mean([kid_from_sums(stats[f"kid_rr_s{s_}"], stats[f"kid_ff_s{s_}"], stats[f"kid_rf_s{s_}"],
+                                                            len(self.real_superclass_idx[s_]), len(self.fake_superclass_idx[s_]))
+                                              for s_ in range(20)]))
+        return out
+
+    def _kid_of(self, gen, label=None):
+        on_dev = torch.is_tensor(gen) and gen.is_cuda and self._real_on_device() is not None
+        real = self._real_pair_stats(label, on_dev)
+        gen = _dev32(gen, real["feats"].device) if on_dev else _np64(gen)
+        return kid_from_sums(real["rr"], poly3_sum(gen, gen, True), poly3_sum(gen, real["feats"]), real["n"], gen.shape[0])
+
+    def kid(self, generated_images, intra_kid=False, label=0):
+        """Kernel Inception Distance of the generated images against the cached real features (of superclass `label` with
+        intra_kid), in the style of fid(); the real x real term is computed once and kept."""
+        return self._kid_of(self._extract(generated_images, keep_on_device=True), label if intra_kid else None)
+
+    def intra_kid(self, generated_images):
+        """The MEAN of the 20 per-superclass KIDs.  Deliberately not the reference's intra-FID normalisation (20 values summed
+        and divided by 100, metrics.py:141): a mean of 20 is what the name says, and KID has no reference value to stay
+        comparable with."""
+        return float(np.mean([self.kid(torch.utils.data.DataLoader(generated_images[self.fake_superclass_idx[s]], 128, shuffle=False),
+                                       intra_kid=True, label=s) for s in range(20)]))
+
+    def precision_recall(self, generated_images, k=3):
+        """(precision, recall) of the generated images against real's k-NN manifold and of the real features against theirs;
+        real's radii are computed once per k and kept."""
+        gen = self._extract(generated_images, keep_on_device=True)
+        on_dev = torch.is_tensor(gen) and gen.is_cuda and self._real_on_device() is not None
+        real = self._real_pair_stats(None, on_dev)["feats"]
+        gen = _dev32(gen, real.device) if on_dev else _np64(gen)
+        return precision_recall_from_hits(manifold_hit(gen, real, self._real_radii(k, on_dev)), manifold_hit(real, gen, knn_radius2(gen, k)))

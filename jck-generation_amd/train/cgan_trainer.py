@@ -30,6 +30,7 @@ class CGANTrainer(DCGANTrainer):
         self.device = require_gpu("CGANTrainer")
         self.epoch, self.max_lr, self.lambda_gp = args.epoch, args.max_learning_rate, 10.0
         self.prec = prec or os.environ.get("JCKGAN_PREC", "bf16")
+        self.extra_metrics = bool(int(getattr(args, "extra_metrics", 0)))      # --extra_metrics 1: KID, intra-KID, precision / recall
         self.host_rng = bool(int(os.environ.get("JCKGAN_HOST_RNG", "0"))) if host_rng is None else host_rng
         if self.host_rng:
             model_g.apply(weights_init)
@@ -145,6 +146,8 @@ class CGANTrainer(DCGANTrainer):
                 out["logits"] = logits
                 if logits.is_cuda:
                     out.update(self.metric.fake_stats_device(logits, intra=True))
+                    if self.extra_metrics:
+                        out.update(self.metric.fake_pair_stats_device(logits, intra=True))
             return out
         self._eval.launch(iters, lambda: eng.sample(fixed_noise, fixed_labels), device_part)
 
@@ -160,6 +163,9 @@ class CGANTrainer(DCGANTrainer):
             else:
                 inception_score, fid, intra = self.metric.scores_from_logits(host["logits"], intra=True)
             self.logger.debug(f"inception score: {inception_score}\tfid: {fid}\tintra fid: {intra}")
+            extra = self.metric.extra_scores_from_stats(host, intra=True) if "kid_rr" in host else None
+            if extra is not None:
+                self.logger.debug(f"kid: {extra['kid']}\tprecision: {extra['precision']}\trecall: {extra['recall']}\tintra kid: {extra['intra_kid']}")
             if best["fid"] > fid:
                 best["fid"] = fid
                 self.logger.debug(f"{iters} lowest fid")
@@ -172,6 +178,14 @@ class CGANTrainer(DCGANTrainer):
                 best["is"] = inception_score
                 self.logger.debug(f"{iters} highest is")
                 self.save_model("is", iters, inception_score, fid, intra, denorm, snap)
+            if extra is not None and best.setdefault("kid", 1e10) > extra["kid"]:
+                best["kid"] = extra["kid"]
+                self.logger.debug(f"{iters} lowest kid")
+                self.save_model("kid", iters, inception_score, fid, intra, denorm, snap)
+            if extra is not None and best.setdefault("intra_kid", 1e10) > extra["intra_kid"]:
+                best["intra_kid"] = extra["intra_kid"]
+                self.logger.debug(f"{iters} lowest intra kid")
+                self.save_model("intra_kid", iters, inception_score, fid, intra, denorm, snap)
         else:
             self.save_model("latest", iters, 0.0, 0.0, 0.0, denorm, snap)
         if self.rank == 0:

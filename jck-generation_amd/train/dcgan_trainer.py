@@ -98,6 +98,7 @@ class DCGANTrainer(Trainer):
         self.max_lr = args.max_learning_rate
         self.lambda_gp = 10.0
         self.gp_backward = bool(int(getattr(args, "gp_backward", 0) if gp_backward is None else gp_backward))
+        self.extra_metrics = bool(int(getattr(args, "extra_metrics", 0)))      # --extra_metrics 1: KID, precision / recall beside IS / FID
         self.prec = prec or os.environ.get("JCKGAN_PREC", "bf16")
 
         self.host_rng = bool(int(os.environ.get("JCKGAN_HOST_RNG", "0"))) if host_rng is None else host_rng
@@ -250,6 +251,8 @@ class DCGANTrainer(Trainer):
             out = {"images": x, "logits": logits}
             if logits.is_cuda:
                 out.update(self.metric.fake_stats_device(logits))      # fp64 mean / covariance on the device
+                if self.extra_metrics:
+                    out.update(self.metric.fake_pair_stats_device(logits))     # KID sums, manifold hits (csrc/pairstat.hip)
             return out
         self._eval.launch(iters, lambda: eng.sample(fixed_noise), device_part)      # sample: one train-mode BN batch (:199-200)
 
@@ -266,6 +269,9 @@ class DCGANTrainer(Trainer):
         else:
             inception_score, fid = self.metric.scores_from_logits(host["logits"])
         self.logger.debug(f"inception score: {inception_score}\tfid: {fid}")
+        extra = self.metric.extra_scores_from_stats(host) if "kid_rr" in host else None
+        if extra is not None:
+            self.logger.debug(f"kid: {extra['kid']}\tprecision: {extra['precision']}\trecall: {extra['recall']}")
         if best["fid"] > fid:
             best["fid"] = fid
             self.logger.debug(f"{iters} lowest fid")
@@ -274,6 +280,10 @@ class DCGANTrainer(Trainer):
             best["is"] = inception_score
             self.logger.debug(f"{iters} highest is")
             self.save_model("is", iters, inception_score, host["images"], snap)
+        if extra is not None and best.setdefault("kid", 1e10) > extra["kid"]:
+            best["kid"] = extra["kid"]
+            self.logger.debug(f"{iters} lowest kid")
+            self.save_model("kid", iters, extra["kid"], host["images"], snap)
 
     def train(self):
         loader = self.train_loader
