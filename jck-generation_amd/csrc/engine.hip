@@ -136,6 +136,27 @@ struct DActs {
 // the engine's events order kernels of ONE device across its streams: no system-scope fence (cache write-back for the host's sake)
 // when they are recorded
 static unsigned jck_event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
+// What one phase call leaves behind for a later one - the state of the step in flight.  Everything else in jck_engine is
+// configuration, buffers, streams or the per-call selection (parity, acc, scal_out, cur_labels) that every phase call makes anew.
+struct StepState {
+  bool gp_done = false;                 // the penalty's forward and first backward ran as group 2 of the batched pass (PHASE_D_LOSS / _B; consumed by PHASE_D_GP)
+  bool gp_inflight = false;             // the penalty pass runs on sC, evGP behind it (per-pass PHASE_D_LOSS / PHASE_D_FAKE; joined by PHASE_D_GP)
+  bool join_pending = false, mid_recorded = false;    // PHASE_LAZY_JOIN: evWdone (and evWmid) recorded on sA, not yet waited for
+  long long real_fwd_step = -1;         // step whose D(real) forward already ran (PHASE_D_REAL_FWD), -1: none
+  bool tail_on_side = false, pre_on_side = false;       // PHASE_D_LOSS_A's tail marker sits on sA; PHASE_D_REAL_FWD ran on sA (evReal)
+  int head_row0 = 0;                    // CGAN: first row of the head state (h_drop, cbuf, pre_e) the pass in hand READS (2B: penalty group of a batched head)
+  int head_wrow0 = 0;                   //       first row of the head buffers it WRITES (g_hd, g_h, gc)
+  int acc_clean_step = -1;              // the step whose accumulator rows jck_engine_set_step has just cleared (consumed by its first D phase)
+  // zero_grad() without a launch of its own: D's gradient arena (+ CGAN's permuted Linear gradient) is cleared by the set-step
+  // launch of the step's first D phase, G's by D's Adam launch; the step whose arena is clean (consumed by the phase that would memset)
+  int dg_clean_step = -1, gg_clean_step = -1;
+  long long gz_step = -1;               // the step whose set-step launch wrote its own z into g_z (G.conv1's operand) as well
+  // a phase that failed half way leaves no promise behind: the next D phase clears its arenas itself and joins the
+  // weight-gradient stream before anything else (state armed before a failing call must not outlive it)
+  void drop_promises() { acc_clean_step = dg_clean_step = gg_clean_step = -1; join_pending = mid_recorded = false; }
+  // PHASE_GP_ONLY clears the accumulator rows and D's gradient arena itself and runs the penalty as a pass of its own on set 0
+  void begin_gp_only() { acc_clean_step = dg_clean_step = -1; gp_done = gp_inflight = false; head_row0 = head_wrow0 = 0; }
+};
 struct jck_engine {
   int family, prec, B;
   Topo T;
@@ -163,10 +184,7 @@ struct jck_engine {
   // group's image gradient and norms go where the per-pass schedule leaves them: bset.gx / .norms are dset[0]'s
   DActs bset = {};
   int batched = 0;                      // 0: one D pass per batch (batch % 8 != 0, JCK_BATCHED=0), 3: [real | fake | penalty] as ONE 3B pass
-  bool gp_done = false;
-  long long real_fwd_step = -1;         // step whose D(real) forward already ran (PHASE_D_REAL_FWD), -1: none
-  int head_row0 = 0;                    // CGAN: first row of the head state (h_drop, cbuf, pre_e) the pass in hand READS (2B: penalty group of a batched head)
-  int head_wrow0 = 0;                   //       first row of the head buffers it WRITES (g_hd, g_h, gc)
+  StepState ss;                         // what the phases of a step hand to one another
   float* d_rs[JCK_MAX_STAGES];                       // deferred BatchNorm running-stat records of D: [step parity][pass 0..3][2*C] per layer
   int parity = 0;                       // step & 1: selects the scalar accumulators and the BN records of the step in flight
   // side streams: A = weight gradients beside the dgrad chain, B = G forward beside D(real), C = penalty pass beside D(fake)
@@ -177,11 +195,9 @@ struct jck_engine {
     for (hipEvent_t* p : {&evWdone, &evWmid, &evHead, &evTail, &ev0, &evF, &evReal, &evGP}) f(*p);
     for (hipEvent_t& p : evW) f(p);
   }
-  bool overlap = true, gp_inflight = false, defer_join = true;
+  bool overlap = true, defer_join = true;
   bool wgrad_side = true;               // weight gradients beside the dgrad chain on sA (JCK_WGRAD_SIDE=0: on the main stream)
   bool head_side = true;                // the head's parameter gradients on sA as well (JCK_HEAD_SIDE=0: on the main stream)
-  bool tail_on_side = false, pre_on_side = false;       // PHASE_D_LOSS_A's tail marker sits on sA; PHASE_D_REAL_FWD ran on sA (evReal)
-  bool join_pending = false, mid_recorded = false;    // PHASE_LAZY_JOIN: evWdone (and evWmid) recorded on sA, not yet waited for
   // cross-stream hand-overs of the backward: the producing launch completes the event itself (the `done` argument of
   // bn_act_bwd_res_ev / tanh_bwd_ev: hipExtLaunchKernel's stop event) instead of a
   // hipEventRecord behind it; JCK_EXT_EVENTS=0 restores the records
@@ -208,15 +224,10 @@ struct jck_engine {
   int hp_step[2] = {0, 0};              // which step's scalars each parity holds (checked by the optimiser phases) ...
   float hp_lr[2] = {-1.f, -1.f};        // ... and at which learning rate they were computed (a scheduler may change it between steps)
   bool hp_holds(int step, float lr) const { return hp_step[step & 1] == step && hp_lr[step & 1] == lr; }
-  int acc_clean_step = -1;              // the step whose accumulator rows jck_engine_set_step has just cleared (consumed by its first D phase)
-  // zero_grad() without a launch of its own: D's gradient arena (+ CGAN's permuted Linear gradient) is cleared by the set-step
-  // launch of the step's first D phase, G's by D's Adam launch; the step whose arena is clean (consumed by the phase that would memset)
-  int dg_clean_step = -1, gg_clean_step = -1;
   bool capturing = false;
   bool gp_bwd = false;                  // DCGAN created with JCK_ENGINE_GP_BACKWARD: PHASE_D_GP back-propagates the penalty as CGAN's does
   float* g1_ws = nullptr; size_t g1_ws_bytes = 0;
   float* wg_ws; size_t wg_ws_bytes;
-  long long gz_step = -1;               // the step whose set-step launch wrote its own z into g_z (G.conv1's operand) as well
   // family 1 (CGAN): Linear head, label path, second-order penalty buffers
   void *l1_w, *l1_wT;                 // packed linear1: [256][8448] and transposed [8448][256]
   void *cbuf, *cbuf2;                 // [B][8448] concat(flatten(a4), e) ; [u4 | 0]
@@ -537,6 +548,7 @@ extern "C" int jck_engine_repack(jck_engine* e, int net, void* stream) {
 // building blocks
 // ---------------------------------------------------------------------------------------------------------
 static const float BN_MOM = 0.1f, BN_EPS = 1e-5f, LRELU = 0.2f;
+static const double ADAM_B1 = 0.5, ADAM_B2 = 0.999, ADAM_EPS = 1e-8;      // both optimisers (train/dcgan_trainer.py:61-62)
 
 
 // `ws` work enqueued after this starts behind everything on `st` so far: on `side` when there is one (the hand-over goes through
@@ -633,9 +645,9 @@ static int d_head_backward(jck_engine* e, DActs& D, const float* ds, int B, bool
   if (e->family == 0)       // mid_done: the input gradient is in place (d_head with g_out)
     return jck_head_bwd_conv(e->prec, ds, e->d_head_wp, D.a[TT.NS - 1], B, TT.G_C1, mid_done ? nullptr : ga4_out,
                              want_wgrad ? e->P(e->LD, e->dg, CWN[TT.NS]) : nullptr, e->head_ws, st);
-  // linear2 + sigmoid: g_hd = ds * w2, dW2 += sum ds * h_drop, db2 += sum ds.  Head buffers from row e->head_row0 on (the
+  // linear2 + sigmoid: g_hd = ds * w2, dW2 += sum ds * h_drop, db2 += sum ds.  Head buffers from row e->ss.head_row0 on (the
   // penalty group of a batched head sits at rows [2B, 3B))
-  const size_t r0 = (size_t)e->head_row0, w0 = (size_t)e->head_wrow0;
+  const size_t r0 = (size_t)e->ss.head_row0, w0 = (size_t)e->ss.head_wrow0;
   auto hb = [&](void* p, size_t row, size_t per_row) { return (void*)((unsigned char*)p + row * per_row * e->esz); };
   void *h_drop = hb(e->h_drop, r0, L1_OUT), *cbuf = hb(e->cbuf, r0, L1_KPAD);
   void *g_hd = hb(e->g_hd, w0, L1_OUT), *g_h = hb(e->g_h, w0, L1_OUT), *gc = hb(e->gc, w0, L1_KPAD);
@@ -758,7 +770,7 @@ static int d_convs_backward(jck_engine* e, const DActs& S, const void* x_in, int
     if (o.part == 1) {
       // evTail: the tail of D's gradient arena is final behind it (jck_engine_order_after_tail); lazy_join: st does not wait
       HIPCHK(hipEventRecord(e->evTail, side ? side : st));
-      e->tail_on_side = side != nullptr;
+      e->ss.tail_on_side = side != nullptr;
       if (side && !o.lazy_join) HIPCHK(hipStreamWaitEvent(st, e->evTail, 0));
       return JCK_OK;
     }
@@ -774,7 +786,7 @@ static int d_convs_backward(jck_engine* e, const DActs& S, const void* x_in, int
   if (o.gp_norm) JCK_TRY(jck_gp_norm(e->prec, S.gx, B, TT.HW, e->acc, 6, e->acc_ld, S.norms, st));
   if (side && o.join) {
     HIPCHK(hipEventRecord(e->evWdone, side));
-    if (o.lazy_join) { e->join_pending = true; e->mid_recorded = false; }
+    if (o.lazy_join) { e->ss.join_pending = true; e->ss.mid_recorded = false; }
     else HIPCHK(hipStreamWaitEvent(st, e->evWdone, 0));
   }
   return JCK_OK;
@@ -786,19 +798,17 @@ static int d_backward(jck_engine* e, DActs& D, const void* x_in, int B, const fl
   return d_convs_backward(e, D, x_in, B, st, o);
 }
 
-// DCGAN's D forward (unless forward_done: d_convs_forward has filled every group), heads and backward on the G batches stored
-// back to back from `x_in` (real_noisy | fake | xhat are consecutive): ONE launch per layer and direction instead of G.  Groups
+// DCGAN's heads and backward on the G batches stored back to back from `x_in` (real_noisy | fake | xhat are consecutive; the
+// forward has filled every group: d_batched_forward): ONE launch per layer instead of G.  Groups
 // [0, G-1) are loss passes (targets / accumulator slots given per group) and contribute weight gradients; the LAST group is the
-// penalty pass (head mode 1, gradient w.r.t. its input image -> dset[0].gx, norms -> dset[0].norms).  Group g writes BatchNorm
-// record pass0 + g.  Weight gradients run on `side`.
-static int d_batched_pass(jck_engine* e, const void* x_in, int B, int G, int pass0, const float* targets, const int* slot_loss,
-                          const int* slot_p, hipStream_t st, hipStream_t side, bool forward_done = false, int part = 0, bool lazy_tail = false) {
+// penalty pass (head mode 1, gradient w.r.t. its input image -> dset[0].gx, norms -> dset[0].norms).  Weight gradients run on `side`.
+static int d_batched_pass(jck_engine* e, const void* x_in, int B, int G, const float* targets, const int* slot_loss, const int* slot_p,
+                          hipStream_t st, hipStream_t side, int part = 0, bool lazy_tail = false) {
   const DActs S = e->bset.group(e, 0, G);
   const int gw = G - 1;
   DBackward bw;
   bw.gw = gw; bw.side = side; bw.xgrad = bw.gp_norm = true; bw.part = part; bw.lazy_join = part == 1 && lazy_tail;
   if (part == 2) return d_convs_backward(e, S, x_in, B, st, bw);
-  if (!forward_done) JCK_TRY(d_convs_forward(e, S, x_in, B, pass0, st));
   {
     float tg[4] = {0.f, 0.f, 0.f, 0.f};
     int md[4] = {0, 0, 0, 0}, sl[4] = {-1, -1, -1, -1}, sp[4] = {-1, -1, -1, -1};
@@ -853,8 +863,8 @@ static int gp_double_backward(jck_engine* e, const DActs& P, const void* xhat, i
   const float* prob1 = e->prob_gp;
   if (cg) {
     if (side) (void)hipStreamWaitEvent(st, e->evHead, 0);
-    if (e->head_row0 > 0) {
-      gh1 = (const unsigned char*)e->g_h + (size_t)e->head_row0 * L1_OUT * esz;
+    if (e->ss.head_row0 > 0) {
+      gh1 = (const unsigned char*)e->g_h + (size_t)e->ss.head_row0 * L1_OUT * esz;
       prob1 = P.prob;
     } else {
       HIPCHK(hipMemcpyAsync(e->gh_b1, e->g_h, (size_t)B * L1_OUT * esz, hipMemcpyDeviceToDevice, st));
@@ -900,7 +910,7 @@ static int gp_double_backward(jck_engine* e, const DActs& P, const void* xhat, i
     hipStream_t hs = e->head_side && e->ext_events ? side : nullptr;
     if (fuse) {
       // g_hd / g_h rows [head_wrow0, + B): not the rows the v-chain's Linear weight gradient reads (the penalty group's, or the copy)
-      const size_t w0 = (size_t)e->head_wrow0 * L1_OUT * esz;
+      const size_t w0 = (size_t)e->ss.head_wrow0 * L1_OUT * esz;
       JCK_TRY(gp_head_mid_ev(e->prec, e->l1_slab, L1_KSPLIT, drop_mask, 1.0f / 0.75f, e->ughd, e->P(e->LD, e->dp, "linear2.weight"), prob1, B, e->rs,
                              e->P(e->LD, e->dg, "linear2.weight"), e->gp2_ws, (unsigned char*)e->g_hd + w0, (unsigned char*)e->g_h + w0, st, hs,
                              hs ? e->evHead : nullptr));
@@ -923,11 +933,11 @@ static int gp_double_backward(jck_engine* e, const DActs& P, const void* xhat, i
     JCK_TRY(jck_conv_wgrad(e->prec, e->d_v[i], big, e->wg_ws, e->wg_ws_bytes, e->P(e->LD, e->dg, CWN[i]), 1, B, hb, hb, cb, cs, ws));
     // everything but the bottom conv weight's gradient is final on the side stream here (lazy join: the optimiser phase starts
     // behind this point and takes that one tensor last)
-    if (side && lazy_join && i == 1) { (void)hipEventRecord(e->evWmid, side); e->mid_recorded = true; }
+    if (side && lazy_join && i == 1) { (void)hipEventRecord(e->evWmid, side); e->ss.mid_recorded = true; }
     if (i > 0)
       JCK_TRY(jck_conv_up(e->prec, e->d_v[i], e->d_up[i], e->d_v[i - 1], nullptr, nullptr, 0, B, hb / 2, hb / 2, cs, cb, st));
   }
-  if (side && lazy_join) { (void)hipEventRecord(e->evWdone, side); e->join_pending = true; }
+  if (side && lazy_join) { (void)hipEventRecord(e->evWdone, side); e->ss.join_pending = true; }
   else join();
   return JCK_OK;
 }
@@ -944,7 +954,7 @@ static int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B
     if (!labels) JCK_FAIL(JCK_E_ARG, "CGAN generator needs labels");
     JCK_TRY(jck_cgan_z(e->prec, z, labels, B, 100, N_CLASS, zp, e->g_z, st));            // model/CGAN.py:154-155
   } else if (!z_in_place) {                 // (z_in_place: the step's set-step launch drew this z and wrote the operand rows itself)
-    e->gz_step = -1;                        // the operand rows now hold somebody else's z
+    e->ss.gz_step = -1;                        // the operand rows now hold somebody else's z
     if (e->prec == JCK_PREC_BF16) launch_pad_rows<bf16_t>(z, B, 100, zp, e->g_z, st); else launch_pad_rows<float>(z, B, 100, zp, e->g_z, st);
     HIPCHK(hipGetLastError());
   }
@@ -1014,98 +1024,381 @@ static int prep_real(jck_engine* e, const jck_step_inputs* in, int B, hipStream_
   return jck_img_prep(e->prec, in->real_nchw, in->noise_real, 0.9f, 0.1f, e->real_noisy, B, TT.HW, st);
 }
 
-// the step's accumulator rows (losses, probabilities, penalty norms): cleared by the launch that wrote the step's scalars
-// (jck_engine_set_step) when that has just run for this step, else - captured steps, a phase called twice - by a memset
 // An optimiser phase called with another learning rate than the step's loss phases (separate G and D rates): only the Adam
 // scalars of the step's slot are rewritten - NOT the accumulator rows (the step's losses are in them, the tail of G_STEP reads
 // them) and not the step's random inputs (jck_engine_set_step here logged loss_d = loss_g = gp = 0).
 static int refresh_adam_scalars(jck_engine* e, int step, float lr, hipStream_t st) {
   const int q = step & 1;
-  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, 0.5, 0.999, step, e->noise_seed, e->ema_w(step), st));
+  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, ADAM_B1, ADAM_B2, step, e->noise_seed, e->ema_w(step), st));
   e->hp_step[q] = step;
   e->hp_lr[q] = lr;
   return JCK_OK;
 }
 static int set_step_impl(jck_engine* e, int step, float lr, void* stream, bool zero_d);
-// D.zero_grad() (:155): cleared by the step's set-step launch when that has just run for this step (zero_d), else by a memset
-static int zero_d_grads(jck_engine* e, int step, hipStream_t st) {
-  const bool clean = e->dg_clean_step == step && !e->capturing;
-  e->dg_clean_step = -1;
-  if (clean) return JCK_OK;
-  HIPCHK(hipMemsetAsync(e->dg, 0, e->LD.n_params * sizeof(float), st));
-  if (e->family == 1) HIPCHK(hipMemsetAsync(e->gw1p, 0, (size_t)L1_OUT * L1_KPAD * sizeof(float), st));
+// Adam (:180, :189) on elements [first, first + count) of a network's arenas (net 0: G, 1: D) with the step's scalars `hp`.
+// zero_other: the other network's gradient arena, cleared by the same launch; ema: G's moving average, advanced by it
+static int adam_net(jck_engine* e, int net, long long first, long long count, float grad_scale, const float* hp, hipStream_t st,
+                    float* zero_other = nullptr, float* ema = nullptr) {
+  float *p = net ? e->dp : e->gp, *g = net ? e->dg : e->gg, *m = net ? e->dm : e->gm, *v = net ? e->dv : e->gv;
+  return jck_adam_hp(p + first, g + first, m + first, v + first, count, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale, hp, st, zero_other,
+                     zero_other ? (net ? e->LG : e->LD).n_params : 0, jck_grid_sync_error_word(e->gsync), ema);
+}
+// `p` (and `p2`) cleared by a neighbour launch for this step - `clean_step`, a promise that is consumed here - else by a memset
+// (captured steps, a phase called twice)
+static int clear_or_memset(jck_engine* e, int& clean_step, int step, hipStream_t st, void* p, size_t bytes, void* p2 = nullptr, size_t bytes2 = 0) {
+  const bool clean = clean_step == step && !e->capturing;
+  clean_step = -1;
+  if (!clean) HIPCHK(hipMemsetAsync(p, 0, bytes, st));
+  if (!clean && p2) HIPCHK(hipMemsetAsync(p2, 0, bytes2, st));
   return JCK_OK;
 }
+// D.zero_grad() (:155): cleared by the step's set-step launch when that has just run for this step (zero_d), else by a memset
+static int zero_d_grads(jck_engine* e, int step, hipStream_t st) {
+  return clear_or_memset(e, e->ss.dg_clean_step, step, st, e->dg, e->LD.n_params * sizeof(float), e->family == 1 ? e->gw1p : nullptr,
+                         (size_t)L1_OUT * L1_KPAD * sizeof(float));
+}
+// the step's accumulator rows (losses, probabilities, penalty norms): cleared by the launch that wrote the step's scalars
+// (jck_engine_set_step) when that has just run for this step, else - captured steps, a phase called twice - by a memset
 static int clear_acc(jck_engine* e, int step, hipStream_t st) {
-  if (e->acc_clean_step == step && !e->capturing) { e->acc_clean_step = -1; return JCK_OK; }
-  HIPCHK(hipMemsetAsync(e->acc, 0, (size_t)8 * e->acc_ld * sizeof(float), st));
-  return JCK_OK;
+  return clear_or_memset(e, e->ss.acc_clean_step, step, st, e->acc, (size_t)8 * e->acc_ld * sizeof(float));
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // phases
 // ---------------------------------------------------------------------------------------------------------
-static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void* stream);
-extern "C" int jck_engine_phase(jck_engine* e, int phase, const jck_step_inputs* in_, void* stream) {
-  // JCK_PHASE_NO_RESIDENT: no grid-barrier launch in this call (a collective may be holding CUs: include/jckgan.h)
-  const bool keep_res = e ? e->bn_res : false;
-  if (e && (phase & JCK_PHASE_NO_RESIDENT)) e->bn_res = false;
-  const int rc = phase_impl(e, phase & ~JCK_PHASE_NO_RESIDENT, in_, stream);
-  if (e) e->bn_res = keep_res;
-  if (rc != JCK_OK && e) {
-    // a phase that failed half way leaves no promise behind: the next D phase clears its arenas itself and joins the
-    // weight-gradient stream before anything else (state armed before a failing call must not outlive it)
-    e->acc_clean_step = e->dg_clean_step = e->gg_clean_step = -1;
-    if (e->join_pending && e->sA && stream && !e->capturing) (void)hipStreamWaitEvent((hipStream_t)stream, e->evWdone, 0);
-    e->join_pending = e->mid_recorded = false;
-  }
-  return rc;
+// What every phase of one jck_engine_phase call works with: made once by phase_impl, read-only from there on
+struct PhaseCtx {
+  hipStream_t st, sA;                   // the caller's stream; the weight-gradient stream, or null
+  const jck_step_inputs* in;            // the caller's inputs with the engine's own draws in place of z / alpha / masks left NULL ...
+  const jck_step_inputs* given;         // ... and as the caller handed them over
+  int B, HW;
+  bool cg, lazy, lazy_tail;             // CGAN; JCK_PHASE_LAZY_JOIN as CGAN's phases / DCGAN's PHASE_D_LOSS_A take it
+  bool par, ov_g, ov_gp;                // side streams in use; per-pass schedule: G forward beside D(real), penalty pass beside D(fake)
+  DActs &DR, &D0, &D1;
+};
+
+static int penalty_pass(jck_engine* e, const PhaseCtx& c, DActs& D, hipStream_t s) {                 // :110-127, 178
+  JCK_TRY(jck_interp(e->prec, e->real_noisy, e->fake, c.in->alpha, e->xhat, c.B, c.HW, s));
+  JCK_TRY(d_forward(e, D, e->xhat, c.B, 2, c.in->drop_mask[2], s));
+  JCK_TRY(d_head(e, D, c.B, 0.f, 1, -1, -1, s));
+  // DCGAN's per-pass schedule runs this pass on its own stream beside D(fake): three-launch BatchNorm backward (DBackward),
+  // whatever the stream layout of this call (a captured one-stream step stays launch for launch the eager one)
+  DBackward bw;
+  bw.gw = 0; bw.resident = c.cg; bw.xgrad = bw.gp_norm = true;
+  return d_backward(e, D, e->xhat, c.B, c.in->drop_mask[2], s, bw);
 }
-static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void* stream) {
-  if (!e || !e->bound || !in_) JCK_FAIL(JCK_E_ARG, "engine not bound / null inputs");
-  // z, alpha and (CGAN) the Dropout keep masks left NULL: the engine's own draws for this step (jck_engine_set_step)
-  jck_step_inputs loc = *in_;
-  {
-    const int q = loc.step & 1;
-    if (!loc.z) loc.z = e->rz[q];
-    if (!loc.alpha) loc.alpha = e->ralpha[q];
-    if (e->family == 1 && !loc.drop_mask[0] && !loc.drop_mask[1] && !loc.drop_mask[2] && !loc.drop_mask[3])
-      for (int i = 0; i < 4; ++i) loc.drop_mask[i] = e->rmask[q] + (size_t)i * e->B * L1_OUT;
+static int g_forward_step(jck_engine* e, const PhaseCtx& c, hipStream_t s) {                         // :168-169
+  return g_forward(e, c.in->z, c.in->labels, c.B, s, c.in->z == e->rz[c.in->step & 1] && e->ss.gz_step == (long long)c.in->step);
+}
+
+// The forward half of a batched D pass, both families: real batch, G's forward, the fake batch and the penalty's interpolate, D's
+// conv stack on all three.
+// pre: D(real)'s forward of this step has run already (PHASE_D_REAL_FWD)
+// split: D(real)'s conv stack by itself and [fake | penalty] as one 2B forward behind G's; else one 3B forward behind G's
+// direct (CGAN): the last layer writes the head's concat buffer (d_convs_forward: to_cbuf)
+static int d_batched_forward(jck_engine* e, const PhaseCtx& c, bool pre, bool split, bool direct) {
+  const DActs& S = e->bset;
+  // D(real)'s forward needs nothing of G, and G's forward is a chain of small launches that leaves most of the chip idle: the
+  // real batch's input transform and conv stack run on the weight-gradient stream (idle at the start of a step) beside it,
+  // [fake | penalty] follow as one 2B forward - the split PHASE_D_REAL_FWD makes across steps; the arithmetic of the 3B forward
+  // (a batch's BatchNorm statistics may be split into partial sums differently: summation order only)
+  // (1.632 -> 1.609 ms; JCK_REAL_SIDE=0: one 3B forward behind G's)
+  // (the split does not depend on the stream layout: a captured, one-stream step is the same arithmetic launch for launch)
+  const bool beside = !pre && e->real_side && c.sA;
+  const bool pre_side = pre && e->ss.pre_on_side;    // PHASE_D_REAL_FWD ran on the weight-gradient stream: joined behind G's forward
+  e->ss.pre_on_side = false;
+  hipStream_t sr = beside ? c.sA : c.st;
+  if (beside) { HIPCHK(hipEventRecord(e->ev0, c.st)); HIPCHK(hipStreamWaitEvent(c.sA, e->ev0, 0)); }
+  if (!pre) JCK_TRY(prep_real(e, c.in, c.B, sr));                                               // :160
+  if (!pre && split) JCK_TRY(d_convs_forward(e, S.group(e, 0, 1), e->real_noisy, c.B, 0, sr, direct));      // :162
+  if (beside) HIPCHK(hipEventRecord(e->evReal, c.sA));
+  JCK_TRY(g_forward_step(e, c, c.st));
+  if (beside || pre_side) HIPCHK(hipStreamWaitEvent(c.st, e->evReal, 0));
+  JCK_TRY(e->mix_fake_noise_interp(c.in, c.B, c.st));                                             // :171, :111-113
+  if (split) return d_convs_forward(e, S.group(e, 1, 2), e->fake, c.B, 0, c.st, direct);          // :173, 118 as one 2B forward
+  return d_convs_forward(e, S, e->real_noisy, c.B, 0, c.st, direct);
+}
+
+// CGAN: the real, fake and penalty passes (:181-203) share D's weights -> their conv stacks run as ONE 3B pass with
+// grouped BatchNorm.  The label / Linear / Dropout head runs per batch, forward and backward back to back, so the
+// head buffers serve all three; the penalty group goes last and leaves them as its double backward (PHASE_D_GP)
+// expects them.
+// This is the pass from the conv stack's output on: the heads of the three groups, then the backward of the 3B set.
+// head3: the head runs once over 3B rows (direct: its concat buffer is filled already)
+static int cg_batched_heads_backward(jck_engine* e, const PhaseCtx& c, bool head3, bool direct) {
+  const DActs& S = e->bset;
+  const float tg[2] = {0.9f, 0.1f};
+  const float *w2 = e->P(e->LD, e->dp, "linear2.weight"), *b2 = e->P(e->LD, e->dp, "linear2.bias");
+  e->ss.head_row0 = 0;
+  if (head3) {
+    const bool fuse = e->head_fuse;
+    const float tg3[3] = {tg[0], tg[1], 0.f};
+    const int md3[3] = {0, 0, 1}, sl3[3] = {0, 1, -1}, sp3[3] = {3, 4, -1};
+    JCK_TRY(cg_head_forward(e, direct ? nullptr : S.a[TT.NS - 1], 3 * c.B, c.in->drop_mask[0], c.st, c.B, !fuse));
+    if (fuse) JCK_TRY(cg_head_middle(e, c.B, 3, tg3, md3, sl3, sp3, S.prob, S.ds, c.in->drop_mask[0], c.st));
+    else JCK_TRY(jck_head_fwd_grouped(e->prec, e->h_drop, w2, b2, c.B, L1_OUT, 3, tg3, md3, S.prob, S.ds, e->acc, sl3, sp3, e->acc_ld, c.st));
+    JCK_TRY(cg_head_backward_batched(e, S.ds, c.B, c.in->drop_mask[0], S.g[TT.NS - 1], c.st, e->head_side ? c.sA : nullptr, fuse));
+    e->ss.head_row0 = 2 * c.B;                        // where PHASE_D_GP finds the penalty group's head state
+    e->ss.head_wrow0 = 0;
+  } else
+    for (int g = 0; g < 3; ++g) {
+      const bool pen = g == 2;
+      const DActs Sg = S.group(e, g, 1);
+      JCK_TRY(cg_head_forward(e, Sg.a[TT.NS - 1], c.B, c.in->drop_mask[g], c.st));
+      JCK_TRY(jck_head_fwd(e->prec, e->h_drop, w2, b2, c.B, L1_OUT, pen ? 0.f : tg[g], pen ? 1 : 0, Sg.prob, Sg.ds, e->acc, pen ? -1 : g,
+                           pen ? -1 : 3 + g, e->acc_ld, c.st));
+      JCK_TRY(d_head_backward(e, e->dset[0], Sg.ds, c.B, !pen, c.in->drop_mask[g], Sg.g[TT.NS - 1], c.st));
+    }
+  DBackward bw;
+  bw.gw = 2; bw.side = c.sA; bw.xgrad = bw.gp_norm = true; bw.lazy_join = c.lazy;
+  JCK_TRY(d_convs_backward(e, S, e->real_noisy, c.B, c.st, bw));
+  e->ss.gp_done = true;
+  return JCK_OK;
+}
+
+// PHASE_D_LOSS of the batched schedule, both families; PHASE_D_LOSS_A / _B, its two halves (DCGAN)
+static int phase_d_loss_batched(jck_engine* e, const PhaseCtx& c, int phase) {
+  if (phase != JCK_PHASE_D_LOSS && (c.cg || e->batched != 3 || e->capturing || e->gp_bwd))
+    JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS_A / _B: only with the batched DCGAN schedule, outside a capture, without JCK_ENGINE_GP_BACKWARD "
+                        "(D's gradients are final only after PHASE_D_GP then)");
+  // DCGAN: [real | fake | penalty] as one 3B pass after G's forward
+  const float tg[2] = {0.9f, 0.1f};
+  const int sl[2] = {0, 1}, sp[2] = {3, 4};
+  if (phase == JCK_PHASE_D_LOSS_B) {            // second half of a split pass (after the early all-reduce has started)
+    JCK_TRY(d_batched_pass(e, e->real_noisy, c.B, 3, tg, sl, sp, c.st, c.sA, 2));
+    e->ss.gp_done = true;
+    return JCK_OK;
   }
-  const jck_step_inputs* in = &loc;
-  hipStream_t st = (hipStream_t)stream;
-  const int B = e->B, HW = TT.HW;
+  if ((!c.in->real_nchw && !c.in->real_u8) || !c.in->z || !c.in->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS needs real_nchw (or real_u8), z and alpha");
+  // D(real)'s forward of this step may already have run under the previous step's G all-reduce (PHASE_D_REAL_FWD)
+  const bool pre = !c.cg && e->ss.real_fwd_step == (long long)c.in->step;
+  if (!c.cg) e->ss.real_fwd_step = -1;
+  JCK_TRY(clear_acc(e, c.in->step, c.st));
+  JCK_TRY(zero_d_grads(e, c.in->step, c.st));                                                   // D.zero_grad()  :155
+  // the three dropout masks back to back (hipgan/engine.py hands them over that way): the head runs once over 3B rows
+  const bool head3 = c.cg && c.in->drop_mask[0] && c.in->drop_mask[1] == c.in->drop_mask[0] + (size_t)c.B * L1_OUT &&
+                     c.in->drop_mask[2] == c.in->drop_mask[0] + (size_t)2 * c.B * L1_OUT;
+  const bool direct = head3 && e->cbuf_direct;
+  // D(real)'s conv stack beside G's forward, [fake | penalty] as a 2B forward behind it (d_batched_forward)
+  JCK_TRY(d_batched_forward(e, c, pre, pre || e->real_side, direct));
+  if (c.cg) return cg_batched_heads_backward(e, c, head3, direct);
+  const int part = phase == JCK_PHASE_D_LOSS_A ? 1 : 0;
+  JCK_TRY(d_batched_pass(e, e->real_noisy, c.B, 3, tg, sl, sp, c.st, c.sA, part, c.lazy_tail));      // :162-176, 178
+  if (part == 0) e->ss.gp_done = true;
+  return JCK_OK;
+}
+
+// the per-pass schedule: PHASE_D_LOSS, or its two halves PHASE_D_REAL and PHASE_D_FAKE
+static int phase_d_per_pass(jck_engine* e, const PhaseCtx& c, int phase) {
+  if (phase != JCK_PHASE_D_FAKE) {              // ---- D on the real batch (:155-165); independent of G
+    if (!c.in->real_nchw && !c.in->real_u8) JCK_FAIL(JCK_E_ARG, "PHASE_D_REAL needs real_nchw (or real_u8)");
+    JCK_TRY(clear_acc(e, c.in->step, c.st));
+    JCK_TRY(zero_d_grads(e, c.in->step, c.st));                                                 // D.zero_grad()  :155
+  }
+  hipStream_t sG = c.st;
+  if (phase == JCK_PHASE_D_LOSS || phase == JCK_PHASE_D_FAKE) {   // G forward: beside D(real) when both are in this call
+    if (!c.in->z) JCK_FAIL(JCK_E_ARG, "G forward needs z");
+    if (c.ov_gp && !c.in->alpha) JCK_FAIL(JCK_E_ARG, "alpha is needed here (the penalty pass starts inside this phase)");
+    if (c.ov_g) { HIPCHK(hipEventRecord(e->ev0, c.st)); HIPCHK(hipStreamWaitEvent(e->sB, e->ev0, 0)); sG = e->sB; }
+    JCK_TRY(g_forward_step(e, c, sG));
+    JCK_TRY(e->mix_fake_noise(c.in, c.B, sG));   // :171
+    if (c.ov_g) HIPCHK(hipEventRecord(e->evF, sG));
+  }
+  if (phase != JCK_PHASE_D_FAKE) {
+    JCK_TRY(prep_real(e, c.in, c.B, c.st));   // :160
+    if (c.ov_gp && phase == JCK_PHASE_D_LOSS) HIPCHK(hipEventRecord(e->evReal, c.st));           // penalty pass needs only this
+    JCK_TRY(d_forward(e, c.DR, e->real_noisy, c.B, 0, c.in->drop_mask[0], c.st));                      // :162
+    JCK_TRY(d_head(e, c.DR, c.B, 0.9f, 0, 0, 3, c.st));                                             // :163,165
+    // D(real)'s weight gradients stay in flight on sA while D(fake) starts (own activation set); D(fake)'s backward
+    // queues behind them on sA and joins.  PHASE_D_REAL alone (pipeline mode) and CGAN (shared set) join here.
+    DBackward bw;
+    bw.side = c.sA; bw.join = phase == JCK_PHASE_D_REAL || c.cg || !e->defer_join;
+    JCK_TRY(d_backward(e, c.DR, e->real_noisy, c.B, c.in->drop_mask[0], c.st, bw));                   // :164 (cgan :203)
+    if (phase == JCK_PHASE_D_REAL) return JCK_OK;
+  }
+  // ---- D on the fake batch (:170-176) with the penalty pass (:178) beside it
+  if (c.ov_g) HIPCHK(hipStreamWaitEvent(c.st, e->evF, 0));
+  if (c.ov_gp) {                                   // penalty pass on its own stream and activation set
+    if (phase == JCK_PHASE_D_FAKE) HIPCHK(hipEventRecord(e->evReal, c.st));    // real_noisy came from an earlier call on st
+    HIPCHK(hipStreamWaitEvent(e->sC, e->evF, 0));
+    HIPCHK(hipStreamWaitEvent(e->sC, e->evReal, 0));
+    JCK_TRY(penalty_pass(e, c, c.D1, e->sC));
+    HIPCHK(hipEventRecord(e->evGP, e->sC));
+    e->ss.gp_inflight = true;
+  }
+  JCK_TRY(d_forward(e, c.D0, e->fake, c.B, 1, c.in->drop_mask[1], c.st));                             // :173
+  JCK_TRY(d_head(e, c.D0, c.B, 0.1f, 0, 1, 4, c.st));                                               // :174,176
+  DBackward bw;
+  bw.side = c.sA;
+  return d_backward(e, c.D0, e->fake, c.B, c.in->drop_mask[1], c.st, bw);                             // :175
+}
+
+// forward half of D(real) of step in->step, ahead of its PHASE_D_LOSS: touches only real_noisy and group 0 of the batched
+// set (activations, statistic slots, scale/shift table) and the BatchNorm record of (parity of in->step, pass 0) - nothing
+// the G phase of the step before it reads or writes
+static int phase_d_real_fwd(jck_engine* e, const PhaseCtx& c) {
+  if (c.cg || e->batched != 3 || e->capturing) JCK_FAIL(JCK_E_ARG, "PHASE_D_REAL_FWD: only with the batched DCGAN schedule, outside a capture");
+  if (!c.in->real_nchw && !c.in->real_u8) JCK_FAIL(JCK_E_ARG, "PHASE_D_REAL_FWD needs real_nchw (or real_u8)");
+  // on the weight-gradient stream when there is one (idle here: G's backward has joined it): the caller's stream then only
+  // carries the wait for G's all-reduce and Adam(G), and the rest of this forward runs beside the next step's G forward
+  hipStream_t sr = (e->real_side && c.sA) ? c.sA : c.st;
+  if (sr != c.st) { HIPCHK(hipEventRecord(e->ev0, c.st)); HIPCHK(hipStreamWaitEvent(sr, e->ev0, 0)); }
+  JCK_TRY(prep_real(e, c.in, c.B, sr));                                                         // :160
+  JCK_TRY(d_convs_forward(e, e->bset.group(e, 0, 1), e->real_noisy, c.B, 0, sr));             // :162
+  if (sr != c.st) HIPCHK(hipEventRecord(e->evReal, sr));
+  e->ss.pre_on_side = sr != c.st;
+  e->ss.real_fwd_step = c.in->step;
+  return JCK_OK;
+}
+
+// The stand-alone gradient penalty of the module path (train/dcgan_trainer.py:110-127, train/cgan_trainer.py:114-131 called
+// outside this engine's step): real_nchw = real_data, noise_real = fake_data - both [B,3,S,S] fp32, taken as they are -, alpha
+// (CGAN: labels, drop_mask[2]).  Leaves the per-image gradient norms in "norms" (the caller forms mean((n - 1)^2)) and, CGAN
+// and DCGAN with JCK_ENGINE_GP_BACKWARD, d(penalty)/d(theta_D) with lambda = 1 in D's gradient arena, which is cleared first: the
+// double backward in closed form.
+static int phase_gp_only(jck_engine* e, const PhaseCtx& c) {
+  if (!c.in->real_nchw || !c.in->noise_real || !c.given->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY needs real_nchw (real), noise_real (fake) and alpha");
+  if (e->capturing) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY: not inside a capture");
+  if (c.cg && !c.given->drop_mask[2]) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY (CGAN) needs drop_mask[2]");
+  HIPCHK(hipMemsetAsync(e->acc, 0, (size_t)8 * e->acc_ld * sizeof(float), c.st));
+  HIPCHK(hipMemsetAsync(e->dg, 0, e->LD.n_params * sizeof(float), c.st));
+  if (c.cg) HIPCHK(hipMemsetAsync(e->gw1p, 0, (size_t)L1_OUT * L1_KPAD * sizeof(float), c.st));
+  e->ss.begin_gp_only();
+  JCK_TRY(jck_img_prep(e->prec, c.in->real_nchw, nullptr, 1.0f, 0.0f, e->real_noisy, c.B, c.HW, c.st));
+  JCK_TRY(jck_img_prep(e->prec, c.in->noise_real, nullptr, 1.0f, 0.0f, e->fake, c.B, c.HW, c.st));
+  JCK_TRY(penalty_pass(e, c, c.D0, c.st));
+  if (c.cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, c.D0, e->xhat, c.B, 1.0f, c.in->drop_mask[2], c.st, nullptr));
+  return JCK_OK;
+}
+
+static int phase_d_gp(jck_engine* e, const PhaseCtx& c) {
+  if (!c.in->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP needs alpha");
+  if (e->ss.gp_done && (c.cg || e->gp_bwd)) {          // forward and first backward ran as group 2 of the batched pass
+    e->ss.gp_done = false;
+    JCK_TRY(gp_double_backward(e, e->bset.group(e, 2, 1), e->xhat, c.B, 10.0f, c.in->drop_mask[2], c.st, c.sA, c.lazy));
+    if (!(c.lazy && c.sA)) e->ss.join_pending = e->ss.mid_recorded = false;      // it joined the stream itself
+    e->ss.head_row0 = 0;
+    return JCK_OK;
+  }
+  if (e->ss.gp_done) { e->ss.gp_done = false; return JCK_OK; }    // computed inside the batched pass of PHASE_D_LOSS
+  if (e->ss.gp_inflight) {                           // started in PHASE_D_LOSS: join (JCK_ENGINE_GP_BACKWARD: and back-propagate it)
+    HIPCHK(hipStreamWaitEvent(c.st, e->evGP, 0));
+    e->ss.gp_inflight = false;
+    if (e->gp_bwd) JCK_TRY(gp_double_backward(e, c.D1, e->xhat, c.B, 10.0f, nullptr, c.st, c.sA));
+    return JCK_OK;
+  }
+  JCK_TRY(penalty_pass(e, c, c.D0, c.st));
+  // CGAN back-propagates the penalty (train/cgan_trainer.py:200-203); DCGAN when created with JCK_ENGINE_GP_BACKWARD
+  if (c.cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, c.D0, e->xhat, c.B, 10.0f, c.in->drop_mask[2], c.st, c.sA));
+  return JCK_OK;
+}
+
+static int phase_d_step(jck_engine* e, const PhaseCtx& c) {                                       // :180
+  if (e->ss.gp_inflight || (e->gp_bwd && e->ss.gp_done)) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP must be called before PHASE_D_STEP");
+  if (!e->hp_holds(c.in->step, c.in->lr) && !e->capturing) JCK_TRY(refresh_adam_scalars(e, c.in->step, c.in->lr, c.st));   // (eager callers)
+  const float* hp = e->hp2 + 8 * e->parity;
+  // G.zero_grad() (:182) rides on D's Adam launch: G's gradient arena is dead between G's optimiser step and PHASE_G_LOSS
+  float* zg = (e->fold_zero && !e->capturing && e->LG.n_params % 4 == 0) ? e->gg : nullptr;
+  if (zg) e->ss.gg_clean_step = c.in->step;
+  if (e->ss.join_pending) {
+    // the weight-gradient stream is still on its last products: Adam and the Linear repack for everything behind the bottom
+    // conv weight in the arena now, [label embedding | conv1.weight] and the conv repack once that stream is through
+    const TensorInfo* c1 = find(e->LD, CWN[0]);
+    const long long cut = c1->offset + c1->numel;
+    HIPCHK(hipStreamWaitEvent(c.st, e->ss.mid_recorded ? e->evWmid : e->evWdone, 0));
+    JCK_TRY(adam_net(e, 1, cut, e->LD.n_params - cut, c.in->grad_scale, hp, c.st, zg));
+    JCK_TRY(repack_linear(e, c.st));
+    if (e->ss.mid_recorded) HIPCHK(hipStreamWaitEvent(c.st, e->evWdone, 0));
+    e->ss.join_pending = e->ss.mid_recorded = false;
+    JCK_TRY(adam_net(e, 1, 0, cut, c.in->grad_scale, hp, c.st));
+    return repack_convs(e, 1, c.st);
+  }
+  JCK_TRY(adam_net(e, 1, 0, e->LD.n_params, c.in->grad_scale, hp, c.st, zg));
+  return jck_engine_repack(e, 1, c.st);
+}
+
+static int phase_g_loss(jck_engine* e, const PhaseCtx& c) {                                       // :182-188
+  JCK_TRY(clear_or_memset(e, e->ss.gg_clean_step, c.in->step, c.st, e->gg, e->LG.n_params * sizeof(float)));
+  const bool fuse = e->head_fuse;                 // CGAN: the middle of the head as one launch (cg_head_middle); DCGAN: conv5's forward
+                                                  // writes its input gradient too
+  JCK_TRY(d_forward(e, c.D0, e->fake, c.B, 3, c.in->drop_mask[3], c.st, !fuse));
+  if (fuse && !c.cg) JCK_TRY(d_head(e, c.D0, c.B, 0.9f, 0, 2, 5, c.st, c.D0.g[TT.NS - 1]));
+  else if (fuse) {
+    const float tg1 = 0.9f;
+    const int md1 = 0, sl1 = 2, sp1 = 5;
+    JCK_TRY(cg_head_middle(e, c.B, 1, &tg1, &md1, &sl1, &sp1, c.D0.prob, c.D0.ds, c.in->drop_mask[3], c.st));
+  } else JCK_TRY(d_head(e, c.D0, c.B, 0.9f, 0, 2, 5, c.st));
+  // D's own weight gradients from this pass are dead (zeroed at :155 before they are read): skipped
+  XgradEpi xe = {e->fake_raw, 0.9f, e->g_raw, (c.sA && e->ext_events) ? e->evW[TT.NS - 1] : nullptr, false};
+  DBackward bw;
+  bw.gw = 0; bw.xgrad = true; bw.xe = e->fuse_tanh ? &xe : nullptr;
+  JCK_TRY(d_backward(e, c.D0, e->fake, c.B, c.in->drop_mask[3], c.st, bw, fuse));
+  return g_backward(e, c.D0.gx, c.B, c.st, c.sA, xe.fused);
+}
+
+static int phase_g_step(jck_engine* e, const PhaseCtx& c) {                                       // :189
+  if (!e->hp_holds(c.in->step, c.in->lr) && !e->capturing) JCK_TRY(refresh_adam_scalars(e, c.in->step, c.in->lr, c.st));
+  // ... and the moving average of G's weights, when one is bound, in the same launch (its weight is hp[2] of the step)
+  JCK_TRY(adam_net(e, 0, 0, e->LG.n_params, c.in->grad_scale, e->hp2 + 8 * e->parity, c.st, nullptr, e->gema));
+  // G's repack, the four D passes' BatchNorm records in the reference's order and the logged scalars: one launch
+  TailJobs t = {};
+  for (int i = 0; i < TT.NS; ++i) {
+    const int cs = TT.D_CS[i];
+    t.l[i].rec = e->d_rs[i] + (size_t)e->parity * 4 * 2 * cs;
+    t.l[i].rm = e->dbn + find(e->LD, RMN[i])->offset;
+    t.l[i].rv = e->dbn + find(e->LD, RVN[i])->offset;
+    t.l[i].nbt = (long long*)(e->dnbt + i);
+    t.l[i].C = cs;
+  }
+  t.nl = TT.NS; t.npass = 4; t.momentum = BN_MOM; t.acc = e->acc; t.acc_ld = e->acc_ld; t.B = c.B; t.invB = 1.0f / (float)c.B; t.lambda_gp = 10.0f; t.out = e->scal_out;
+  return repack_convs(e, 0, c.st, &t, cdiv(TT.G_C1, 256));
+}
+
+// What every phase call does first, in this order: the engine's own draws for inputs left NULL, the wait for a join left open,
+// the labels, the step's parity and its scalars
+static int phase_begin(jck_engine* e, int phase, jck_step_inputs& loc, hipStream_t st) {
   const bool cg = e->family == 1;
-  const bool lazy = (phase & JCK_PHASE_LAZY_JOIN) && cg && !e->capturing;
-  const bool lazy_tail = (phase & JCK_PHASE_LAZY_JOIN) && !cg && (phase & 0xff) == JCK_PHASE_D_LOSS_A;
-  phase &= ~JCK_PHASE_LAZY_JOIN;
+  // z, alpha and (CGAN) the Dropout keep masks left NULL: the engine's own draws for this step (jck_engine_set_step)
+  const int q = loc.step & 1;
+  if (!loc.z) loc.z = e->rz[q];
+  if (!loc.alpha) loc.alpha = e->ralpha[q];
+  if (cg && !loc.drop_mask[0] && !loc.drop_mask[1] && !loc.drop_mask[2] && !loc.drop_mask[3])
+    for (int i = 0; i < 4; ++i) loc.drop_mask[i] = e->rmask[q] + (size_t)i * e->B * L1_OUT;
   // a join left open by the phase before (JCK_PHASE_LAZY_JOIN): the penalty's double backward keeps using the weight-gradient
   // stream in order and the optimiser phase closes it tensor by tensor; anything else waits here
-  if (e->join_pending && !(phase == JCK_PHASE_D_STEP || (phase == JCK_PHASE_D_GP && cg && e->gp_done))) {
+  if (e->ss.join_pending && !(phase == JCK_PHASE_D_STEP || (phase == JCK_PHASE_D_GP && cg && e->ss.gp_done))) {
     HIPCHK(hipStreamWaitEvent(st, e->evWdone, 0));
-    e->join_pending = e->mid_recorded = false;
+    e->ss.join_pending = e->ss.mid_recorded = false;
   }
   if (cg) {
-    if (!in->labels) JCK_FAIL(JCK_E_ARG, "CGAN phases need labels");
-    e->cur_labels = in->labels;
+    if (!loc.labels) JCK_FAIL(JCK_E_ARG, "CGAN phases need labels");
+    e->cur_labels = loc.labels;
   }
-  DActs& D0 = e->dset[0];
-  DActs& D1 = e->dset[1];
-  DActs& DR = cg ? e->dset[0] : e->dset[2];          // D(real): own set so it may run beside the previous step's G phase
-  e->parity = in->step & 1;
+  e->parity = q;
   // eager callers that did not call jck_engine_set_step: the step's scalars / Philox words are written by its first phase
   // (a phase called with another learning rate than the step's earlier phases - separate G and D rates - rewrites the Adam
   // scalars only: the step's accumulator rows and random inputs are live)
   if (!e->capturing) {
-    if (e->hp_step[in->step & 1] != in->step)
-      // (PHASE_D_REAL_FWD ahead of its step: D's gradients of the step before were consumed by its PHASE_D_STEP, and nothing writes
-      // them until this step's D pass - the set-step launch clears them here as well, instead of a memset in front of that pass)
-      JCK_TRY(set_step_impl(e, in->step, in->lr, st, (phase & 0xff) == JCK_PHASE_D_LOSS || (phase & 0xff) == JCK_PHASE_D_LOSS_A || (phase & 0xff) == JCK_PHASE_D_REAL ||
-                                                    (phase & 0xff) == JCK_PHASE_D_REAL_FWD));
-    else if (e->hp_lr[in->step & 1] != in->lr) JCK_TRY(refresh_adam_scalars(e, in->step, in->lr, st));
+    // (PHASE_D_REAL_FWD ahead of its step: D's gradients of the step before were consumed by its PHASE_D_STEP, and nothing writes
+    // them until this step's D pass - the set-step launch clears them here as well, instead of a memset in front of that pass)
+    const int ph = phase & 0xff;
+    const bool zero_d = ph == JCK_PHASE_D_LOSS || ph == JCK_PHASE_D_LOSS_A || ph == JCK_PHASE_D_REAL || ph == JCK_PHASE_D_REAL_FWD;
+    if (e->hp_step[q] != loc.step) JCK_TRY(set_step_impl(e, loc.step, loc.lr, st, zero_d));
+    else if (e->hp_lr[q] != loc.lr) JCK_TRY(refresh_adam_scalars(e, loc.step, loc.lr, st));
   }
   e->acc = e->acc2 + (size_t)8 * e->acc_ld * e->parity;
   e->scal_out = e->scal2 + 8 * e->parity;
+  return JCK_OK;
+}
+static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void* stream) {
+  if (!e || !e->bound || !in_) JCK_FAIL(JCK_E_ARG, "engine not bound / null inputs");
+  hipStream_t st = (hipStream_t)stream;
+  const bool cg = e->family == 1;
+  const bool lazy = (phase & JCK_PHASE_LAZY_JOIN) && cg && !e->capturing;
+  const bool lazy_tail = (phase & JCK_PHASE_LAZY_JOIN) && !cg && (phase & 0xff) == JCK_PHASE_D_LOSS_A;
+  phase &= ~JCK_PHASE_LAZY_JOIN;
+  jck_step_inputs loc = *in_;
+  JCK_TRY(phase_begin(e, phase, loc, st));
   // stream overlap (DCGAN): A = wgrads, B = G forward beside D(real), C = penalty pass beside D(fake).  CGAN keeps the penalty
   // on the main stream (it produces gradients and shares the head buffers).
   // weight gradients beside the dgrad chain on a second stream: +8 % for DCGAN in round 1, +1.5 % now; CGAN +1.4 % (2.886 vs
@@ -1117,296 +1410,33 @@ static int phase_impl(jck_engine* e, int phase, const jck_step_inputs* in_, void
   // stream's hardware queue (hip::Graph::UpdateStreams; cause and frame in DESIGN.md section 5.6; jck_engine_capture_end refuses
   // any non-linear graph).  Same kernels, same order per stream as the eager schedule - bitwise the same results.
   const bool par = e->overlap && !e->capturing;
-  hipStream_t sA = (par && e->wgrad_side) ? e->sA : nullptr;
-  const bool ov_g = par, ov_gp = par && !cg;
-  auto penalty_pass = [&](DActs& D, hipStream_t s) -> int {                                      // :110-127, 178
-    JCK_TRY(jck_interp(e->prec, e->real_noisy, e->fake, in->alpha, e->xhat, B, HW, s));
-    JCK_TRY(d_forward(e, D, e->xhat, B, 2, in->drop_mask[2], s));
-    JCK_TRY(d_head(e, D, B, 0.f, 1, -1, -1, s));
-    // DCGAN's per-pass schedule runs this pass on its own stream beside D(fake): three-launch BatchNorm backward (DBackward),
-    // whatever the stream layout of this call (a captured one-stream step stays launch for launch the eager one)
-    DBackward bw;
-    bw.gw = 0; bw.resident = cg; bw.xgrad = bw.gp_norm = true;
-    return d_backward(e, D, e->xhat, B, in->drop_mask[2], s, bw);
-  };
+  // D(real) (DR): own set so it may run beside the previous step's G phase
+  const PhaseCtx c = {st, (par && e->wgrad_side) ? e->sA : nullptr, &loc, in_, e->B, TT.HW, cg, lazy, lazy_tail, par, par, par && !cg,
+                      cg ? e->dset[0] : e->dset[2], e->dset[0], e->dset[1]};
   switch (phase) {
-    case JCK_PHASE_D_LOSS_A:
-    case JCK_PHASE_D_LOSS_B:
-      if (cg || e->batched != 3 || e->capturing || e->gp_bwd)
-        JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS_A / _B: only with the batched DCGAN schedule, outside a capture, without JCK_ENGINE_GP_BACKWARD "
-                            "(D's gradients are final only after PHASE_D_GP then)");
-      [[fallthrough]];
-    case JCK_PHASE_D_LOSS:
-      if (cg && e->batched) {
-        // CGAN: the real, fake and penalty passes (:181-203) share D's weights -> their conv stacks run as ONE 3B pass with
-        // grouped BatchNorm.  The label / Linear / Dropout head runs per batch, forward and backward back to back, so the
-        // head buffers serve all three; the penalty group goes last and leaves them as its double backward (PHASE_D_GP)
-        // expects them.
-        if ((!in->real_nchw && !in->real_u8) || !in->z || !in->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS needs real_nchw (or real_u8), z and alpha");
-        JCK_TRY(clear_acc(e, in->step, st));
-        JCK_TRY(zero_d_grads(e, in->step, st));
-        // the three dropout masks back to back (hipgan/engine.py hands them over that way): the head runs once over 3B rows
-        const bool head3 = in->drop_mask[0] && in->drop_mask[1] == in->drop_mask[0] + (size_t)B * L1_OUT &&
-                           in->drop_mask[2] == in->drop_mask[0] + (size_t)2 * B * L1_OUT;
-        const bool direct = head3 && e->cbuf_direct;
-        // D(real)'s conv stack beside G's forward, [fake | penalty] as a 2B forward behind it (see the DCGAN branch below)
-        const bool split = e->real_side, beside = split && sA;
-        const DActs& S = e->bset;
-        hipStream_t sr = beside ? sA : st;
-        if (beside) { HIPCHK(hipEventRecord(e->ev0, st)); HIPCHK(hipStreamWaitEvent(sA, e->ev0, 0)); }
-        JCK_TRY(prep_real(e, in, B, sr));
-        if (split) JCK_TRY(d_convs_forward(e, S.group(e, 0, 1), e->real_noisy, B, 0, sr, direct));
-        if (beside) HIPCHK(hipEventRecord(e->evReal, sA));
-        JCK_TRY(g_forward(e, in->z, in->labels, B, st, in->z == e->rz[in->step & 1] && e->gz_step == (long long)in->step));
-        if (beside) HIPCHK(hipStreamWaitEvent(st, e->evReal, 0));
-        JCK_TRY(e->mix_fake_noise_interp(in, B, st));     // :171, :111-113
-        if (split) JCK_TRY(d_convs_forward(e, S.group(e, 1, 2), e->fake, B, 0, st, direct));
-        else JCK_TRY(d_convs_forward(e, S, e->real_noisy, B, 0, st, direct));
-        const float tg[2] = {0.9f, 0.1f};
-        e->head_row0 = 0;
-        const bool fuse = head3 && e->head_fuse;
-        if (head3) JCK_TRY(cg_head_forward(e, direct ? nullptr : S.a[TT.NS - 1], 3 * B, in->drop_mask[0], st, B, !fuse));
-        if (head3) {
-          const float tg3[3] = {tg[0], tg[1], 0.f};
-          const int md3[3] = {0, 0, 1}, sl3[3] = {0, 1, -1}, sp3[3] = {3, 4, -1};
-          if (fuse) JCK_TRY(cg_head_middle(e, B, 3, tg3, md3, sl3, sp3, S.prob, S.ds, in->drop_mask[0], st));
-          else
-            JCK_TRY(jck_head_fwd_grouped(e->prec, e->h_drop, e->P(e->LD, e->dp, "linear2.weight"), e->P(e->LD, e->dp, "linear2.bias"), B, L1_OUT,
-                                         3, tg3, md3, S.prob, S.ds, e->acc, sl3, sp3, e->acc_ld, st));
-        }
-        for (int g = 0; g < 3 && !head3; ++g) {
-          const bool pen = g == 2;
-          const DActs Sg = S.group(e, g, 1);
-          void *a4 = Sg.a[TT.NS - 1], *g4 = Sg.g[TT.NS - 1];
-          if (!head3) JCK_TRY(cg_head_forward(e, a4, B, in->drop_mask[g], st));
-          const void* hd = (const unsigned char*)e->h_drop + (head3 ? (size_t)g * B * L1_OUT * e->esz : 0);
-          JCK_TRY(jck_head_fwd(e->prec, hd, e->P(e->LD, e->dp, "linear2.weight"), e->P(e->LD, e->dp, "linear2.bias"), B, L1_OUT,
-                               pen ? 0.f : tg[g], pen ? 1 : 0, Sg.prob, Sg.ds, e->acc, pen ? -1 : g, pen ? -1 : 3 + g, e->acc_ld, st));
-          if (!head3) JCK_TRY(d_head_backward(e, e->dset[0], Sg.ds, B, !pen, in->drop_mask[g], g4, st));
-        }
-        if (head3) {
-          JCK_TRY(cg_head_backward_batched(e, S.ds, B, in->drop_mask[0], S.g[TT.NS - 1], st, e->head_side ? sA : nullptr, fuse));
-          e->head_row0 = 2 * B;                        // where PHASE_D_GP finds the penalty group's head state
-          e->head_wrow0 = 0;
-        }
-        DBackward bw;
-        bw.gw = 2; bw.side = sA; bw.xgrad = bw.gp_norm = true; bw.lazy_join = lazy;
-        JCK_TRY(d_convs_backward(e, S, e->real_noisy, B, st, bw));
-        e->gp_done = true;
-        return JCK_OK;
-      }
-      if (!cg && e->batched == 3) {                   // [real | fake | penalty] as one 3B pass after G's forward
-        const float tgB[2] = {0.9f, 0.1f};
-        const int slB[2] = {0, 1}, spB[2] = {3, 4};
-        if (phase == JCK_PHASE_D_LOSS_B) {            // second half of a split pass (after the early all-reduce has started)
-          JCK_TRY(d_batched_pass(e, e->real_noisy, B, 3, 0, tgB, slB, spB, st, sA, true, 2));
-          e->gp_done = true;
-          return JCK_OK;
-        }
-        const int part = phase == JCK_PHASE_D_LOSS_A ? 1 : 0;
-        if ((!in->real_nchw && !in->real_u8) || !in->z || !in->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS needs real_nchw (or real_u8), z and alpha");
-        // D(real)'s forward of this step may already have run under the previous step's G all-reduce (PHASE_D_REAL_FWD)
-        const bool pre = e->real_fwd_step == (long long)in->step;
-        e->real_fwd_step = -1;
-        JCK_TRY(clear_acc(e, in->step, st));
-        JCK_TRY(zero_d_grads(e, in->step, st));                                                   // D.zero_grad()  :155
-        // D(real)'s forward needs nothing of G, and G's forward is a chain of small launches that leaves most of the chip idle: the
-        // real batch's input transform and conv stack run on the weight-gradient stream (idle at the start of a step) beside it,
-        // [fake | penalty] follow as one 2B forward - the split PHASE_D_REAL_FWD makes across steps; the arithmetic of the 3B forward
-        // (a batch's BatchNorm statistics may be split into partial sums differently: summation order only)
-        // (1.632 -> 1.609 ms; JCK_REAL_SIDE=0: one 3B forward behind G's)
-        // (the split does not depend on the stream layout: a captured, one-stream step is the same arithmetic launch for launch)
-        const bool split = pre || e->real_side;
-        const bool beside = !pre && e->real_side && sA;
-        const bool pre_side = pre && e->pre_on_side;    // PHASE_D_REAL_FWD ran on the weight-gradient stream: joined behind G's forward
-        e->pre_on_side = false;
-        hipStream_t sr = beside ? sA : st;
-        if (beside) { HIPCHK(hipEventRecord(e->ev0, st)); HIPCHK(hipStreamWaitEvent(sA, e->ev0, 0)); }
-        if (!pre) JCK_TRY(prep_real(e, in, B, sr));                                               // :160
-        if (!pre && split) JCK_TRY(d_convs_forward(e, e->bset.group(e, 0, 1), e->real_noisy, B, 0, sr));      // :162
-        if (beside) HIPCHK(hipEventRecord(e->evReal, sA));
-        JCK_TRY(g_forward(e, in->z, in->labels, B, st, in->z == e->rz[in->step & 1] && e->gz_step == (long long)in->step));                                          // :168-169
-        if (beside || pre_side) HIPCHK(hipStreamWaitEvent(st, e->evReal, 0));
-        JCK_TRY(e->mix_fake_noise_interp(in, B, st));                                             // :171, :111-113
-        const float tg[2] = {0.9f, 0.1f};
-        const int sl[2] = {0, 1}, sp[2] = {3, 4};
-        if (split) JCK_TRY(d_convs_forward(e, e->bset.group(e, 1, 2), e->fake, B, 0, st));          // :173, 118 as one 2B forward
-        JCK_TRY(d_batched_pass(e, e->real_noisy, B, 3, 0, tg, sl, sp, st, sA, split, part, lazy_tail));      // :162-176, 178
-        if (part == 0) e->gp_done = true;
-        return JCK_OK;
-      }
-      if (phase != JCK_PHASE_D_LOSS) JCK_FAIL(JCK_E_ARG, "PHASE_D_LOSS_A / _B: only with the batched DCGAN schedule");
-      [[fallthrough]];
-    case JCK_PHASE_D_REAL:
-    case JCK_PHASE_D_FAKE: {
-      if (phase != JCK_PHASE_D_FAKE) {              // ---- D on the real batch (:155-165); independent of G
-        if (!in->real_nchw && !in->real_u8) JCK_FAIL(JCK_E_ARG, "PHASE_D_REAL needs real_nchw (or real_u8)");
-        JCK_TRY(clear_acc(e, in->step, st));
-        JCK_TRY(zero_d_grads(e, in->step, st));                                                 // D.zero_grad()  :155
-      }
-      hipStream_t sG = st;
-      if (phase == JCK_PHASE_D_LOSS || phase == JCK_PHASE_D_FAKE) {   // G forward: beside D(real) when both are in this call
-        if (!in->z) JCK_FAIL(JCK_E_ARG, "G forward needs z");
-        if (ov_gp && !in->alpha) JCK_FAIL(JCK_E_ARG, "alpha is needed here (the penalty pass starts inside this phase)");
-        if (ov_g) { HIPCHK(hipEventRecord(e->ev0, st)); HIPCHK(hipStreamWaitEvent(e->sB, e->ev0, 0)); sG = e->sB; }
-        JCK_TRY(g_forward(e, in->z, in->labels, B, sG, in->z == e->rz[in->step & 1] && e->gz_step == (long long)in->step));                                          // :168-169
-        JCK_TRY(e->mix_fake_noise(in, B, sG));   // :171
-        if (ov_g) HIPCHK(hipEventRecord(e->evF, sG));
-      }
-      if (phase != JCK_PHASE_D_FAKE) {
-        JCK_TRY(prep_real(e, in, B, st));   // :160
-        if (ov_gp && phase == JCK_PHASE_D_LOSS) HIPCHK(hipEventRecord(e->evReal, st));           // penalty pass needs only this
-        JCK_TRY(d_forward(e, DR, e->real_noisy, B, 0, in->drop_mask[0], st));                      // :162
-        JCK_TRY(d_head(e, DR, B, 0.9f, 0, 0, 3, st));                                             // :163,165
-        // D(real)'s weight gradients stay in flight on sA while D(fake) starts (own activation set); D(fake)'s backward
-        // queues behind them on sA and joins.  PHASE_D_REAL alone (pipeline mode) and CGAN (shared set) join here.
-        DBackward bw;
-        bw.side = sA; bw.join = phase == JCK_PHASE_D_REAL || cg || !e->defer_join;
-        JCK_TRY(d_backward(e, DR, e->real_noisy, B, in->drop_mask[0], st, bw));                   // :164 (cgan :203)
-        if (phase == JCK_PHASE_D_REAL) return JCK_OK;
-      }
-      // ---- D on the fake batch (:170-176) with the penalty pass (:178) beside it
-      if (ov_g) HIPCHK(hipStreamWaitEvent(st, e->evF, 0));
-      if (ov_gp) {                                   // penalty pass on its own stream and activation set
-        if (phase == JCK_PHASE_D_FAKE) HIPCHK(hipEventRecord(e->evReal, st));    // real_noisy came from an earlier call on st
-        HIPCHK(hipStreamWaitEvent(e->sC, e->evF, 0));
-        HIPCHK(hipStreamWaitEvent(e->sC, e->evReal, 0));
-        JCK_TRY(penalty_pass(D1, e->sC));
-        HIPCHK(hipEventRecord(e->evGP, e->sC));
-        e->gp_inflight = true;
-      }
-      JCK_TRY(d_forward(e, D0, e->fake, B, 1, in->drop_mask[1], st));                             // :173
-      JCK_TRY(d_head(e, D0, B, 0.1f, 0, 1, 4, st));                                               // :174,176
-      DBackward bw;
-      bw.side = sA;
-      return d_backward(e, D0, e->fake, B, in->drop_mask[1], st, bw);                             // :175
-    }
-    case JCK_PHASE_D_REAL_FWD: {
-      // forward half of D(real) of step in->step, ahead of its PHASE_D_LOSS: touches only real_noisy and group 0 of the batched
-      // set (activations, statistic slots, scale/shift table) and the BatchNorm record of (parity of in->step, pass 0) - nothing
-      // the G phase of the step before it reads or writes
-      if (cg || e->batched != 3 || e->capturing) JCK_FAIL(JCK_E_ARG, "PHASE_D_REAL_FWD: only with the batched DCGAN schedule, outside a capture");
-      if (!in->real_nchw && !in->real_u8) JCK_FAIL(JCK_E_ARG, "PHASE_D_REAL_FWD needs real_nchw (or real_u8)");
-      // on the weight-gradient stream when there is one (idle here: G's backward has joined it): the caller's stream then only
-      // carries the wait for G's all-reduce and Adam(G), and the rest of this forward runs beside the next step's G forward
-      hipStream_t sr = (e->real_side && sA) ? sA : st;
-      if (sr != st) { HIPCHK(hipEventRecord(e->ev0, st)); HIPCHK(hipStreamWaitEvent(sr, e->ev0, 0)); }
-      JCK_TRY(prep_real(e, in, B, sr));                                                           // :160
-      JCK_TRY(d_convs_forward(e, e->bset.group(e, 0, 1), e->real_noisy, B, 0, sr));             // :162
-      if (sr != st) HIPCHK(hipEventRecord(e->evReal, sr));
-      e->pre_on_side = sr != st;
-      e->real_fwd_step = in->step;
-      return JCK_OK;
-    }
-    case JCK_PHASE_GP_ONLY: {
-      // The stand-alone gradient penalty of the module path (train/dcgan_trainer.py:110-127, train/cgan_trainer.py:114-131 called
-      // outside this engine's step): real_nchw = real_data, noise_real = fake_data - both [B,3,S,S] fp32, taken as they are -, alpha
-      // (CGAN: labels, drop_mask[2]).  Leaves the per-image gradient norms in "norms" (the caller forms mean((n - 1)^2)) and, CGAN
-      // and DCGAN with JCK_ENGINE_GP_BACKWARD, d(penalty)/d(theta_D) with lambda = 1 in D's gradient arena, which is cleared first: the
-      // double backward in closed form.
-      if (!in->real_nchw || !in->noise_real || !in_->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY needs real_nchw (real), noise_real (fake) and alpha");
-      if (e->capturing) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY: not inside a capture");
-      if (cg && !in_->drop_mask[2]) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY (CGAN) needs drop_mask[2]");
-      HIPCHK(hipMemsetAsync(e->acc, 0, (size_t)8 * e->acc_ld * sizeof(float), st));
-      HIPCHK(hipMemsetAsync(e->dg, 0, e->LD.n_params * sizeof(float), st));
-      if (cg) HIPCHK(hipMemsetAsync(e->gw1p, 0, (size_t)L1_OUT * L1_KPAD * sizeof(float), st));
-      e->acc_clean_step = e->dg_clean_step = -1;
-      e->gp_done = e->gp_inflight = false;
-      e->head_row0 = e->head_wrow0 = 0;
-      JCK_TRY(jck_img_prep(e->prec, in->real_nchw, nullptr, 1.0f, 0.0f, e->real_noisy, B, HW, st));
-      JCK_TRY(jck_img_prep(e->prec, in->noise_real, nullptr, 1.0f, 0.0f, e->fake, B, HW, st));
-      JCK_TRY(penalty_pass(D0, st));
-      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, D0, e->xhat, B, 1.0f, in->drop_mask[2], st, nullptr));
-      return JCK_OK;
-    }
-    case JCK_PHASE_D_GP: {
-      if (!in->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP needs alpha");
-      if (e->gp_done && (cg || e->gp_bwd)) {          // forward and first backward ran as group 2 of the batched pass
-        e->gp_done = false;
-        JCK_TRY(gp_double_backward(e, e->bset.group(e, 2, 1), e->xhat, B, 10.0f, in->drop_mask[2], st, sA, lazy));
-        if (!(lazy && sA)) e->join_pending = e->mid_recorded = false;      // it joined the stream itself
-        e->head_row0 = 0;
-        return JCK_OK;
-      }
-      if (e->gp_done) { e->gp_done = false; return JCK_OK; }    // computed inside the batched pass of PHASE_D_LOSS
-      if (e->gp_inflight) {                           // started in PHASE_D_LOSS: join (JCK_ENGINE_GP_BACKWARD: and back-propagate it)
-        HIPCHK(hipStreamWaitEvent(st, e->evGP, 0));
-        e->gp_inflight = false;
-        if (e->gp_bwd) JCK_TRY(gp_double_backward(e, D1, e->xhat, B, 10.0f, nullptr, st, sA));
-        return JCK_OK;
-      }
-      JCK_TRY(penalty_pass(D0, st));
-      // CGAN back-propagates the penalty (train/cgan_trainer.py:200-203); DCGAN when created with JCK_ENGINE_GP_BACKWARD
-      if (cg || e->gp_bwd) JCK_TRY(gp_double_backward(e, D0, e->xhat, B, 10.0f, in->drop_mask[2], st, sA));
-      return JCK_OK;
-    }
-    case JCK_PHASE_D_STEP: {                                                                      // :180
-      if (e->gp_inflight || (e->gp_bwd && e->gp_done)) JCK_FAIL(JCK_E_ARG, "PHASE_D_GP must be called before PHASE_D_STEP");
-      if (!e->hp_holds(in->step, in->lr) && !e->capturing) JCK_TRY(refresh_adam_scalars(e, in->step, in->lr, st));   // (eager callers)
-      const float* hp = e->hp2 + 8 * e->parity;
-      // G.zero_grad() (:182) rides on D's Adam launch: G's gradient arena is dead between G's optimiser step and PHASE_G_LOSS
-      float* zg = (e->fold_zero && !e->capturing && e->LG.n_params % 4 == 0) ? e->gg : nullptr;
-      if (zg) e->gg_clean_step = in->step;
-      if (e->join_pending) {
-        // the weight-gradient stream is still on its last products: Adam and the Linear repack for everything behind the bottom
-        // conv weight in the arena now, [label embedding | conv1.weight] and the conv repack once that stream is through
-        const TensorInfo* c1 = find(e->LD, CWN[0]);
-        const long long cut = c1->offset + c1->numel;
-        HIPCHK(hipStreamWaitEvent(st, e->mid_recorded ? e->evWmid : e->evWdone, 0));
-        JCK_TRY(jck_adam_hp(e->dp + cut, e->dg + cut, e->dm + cut, e->dv + cut, e->LD.n_params - cut, 0.5, 0.999, 1e-8, in->grad_scale, hp, st,
-                            zg, e->LG.n_params, jck_grid_sync_error_word(e->gsync)));
-        JCK_TRY(repack_linear(e, st));
-        if (e->mid_recorded) HIPCHK(hipStreamWaitEvent(st, e->evWdone, 0));
-        e->join_pending = e->mid_recorded = false;
-        JCK_TRY(jck_adam_hp(e->dp, e->dg, e->dm, e->dv, cut, 0.5, 0.999, 1e-8, in->grad_scale, hp, st, nullptr, 0, jck_grid_sync_error_word(e->gsync)));
-        return repack_convs(e, 1, st);
-      }
-      JCK_TRY(jck_adam_hp(e->dp, e->dg, e->dm, e->dv, e->LD.n_params, 0.5, 0.999, 1e-8, in->grad_scale, hp, st, zg, e->LG.n_params,
-                          jck_grid_sync_error_word(e->gsync)));
-      return jck_engine_repack(e, 1, st);
-    }
-    case JCK_PHASE_G_LOSS: {                                                                      // :182-188
-      if (!(e->gg_clean_step == in->step && !e->capturing)) HIPCHK(hipMemsetAsync(e->gg, 0, e->LG.n_params * sizeof(float), st));
-      e->gg_clean_step = -1;
-      const bool fuse = e->head_fuse;                 // CGAN: the middle of the head as one launch (cg_head_middle); DCGAN: conv5's forward
-                                                      // writes its input gradient too
-      JCK_TRY(d_forward(e, D0, e->fake, B, 3, in->drop_mask[3], st, !fuse));
-      if (fuse && !cg) JCK_TRY(d_head(e, D0, B, 0.9f, 0, 2, 5, st, D0.g[TT.NS - 1]));
-      else if (fuse) {
-        const float tg1 = 0.9f;
-        const int md1 = 0, sl1 = 2, sp1 = 5;
-        JCK_TRY(cg_head_middle(e, B, 1, &tg1, &md1, &sl1, &sp1, D0.prob, D0.ds, in->drop_mask[3], st));
-      } else JCK_TRY(d_head(e, D0, B, 0.9f, 0, 2, 5, st));
-      // D's own weight gradients from this pass are dead (zeroed at :155 before they are read): skipped
-      XgradEpi xe = {e->fake_raw, 0.9f, e->g_raw, (sA && e->ext_events) ? e->evW[TT.NS - 1] : nullptr, false};
-      DBackward bw;
-      bw.gw = 0; bw.xgrad = true; bw.xe = e->fuse_tanh ? &xe : nullptr;
-      JCK_TRY(d_backward(e, D0, e->fake, B, in->drop_mask[3], st, bw, fuse));
-      JCK_TRY(g_backward(e, D0.gx, B, st, sA, xe.fused));
-      return JCK_OK;
-    }
-    case JCK_PHASE_G_STEP: {                                                                      // :189
-      if (!e->hp_holds(in->step, in->lr) && !e->capturing) JCK_TRY(refresh_adam_scalars(e, in->step, in->lr, st));
-      // ... and the moving average of G's weights, when one is bound, in the same launch (its weight is hp[2] of the step)
-      JCK_TRY(jck_adam_hp(e->gp, e->gg, e->gm, e->gv, e->LG.n_params, 0.5, 0.999, 1e-8, in->grad_scale, e->hp2 + 8 * e->parity, st, nullptr, 0,
-                          jck_grid_sync_error_word(e->gsync), e->gema));
-      {   // G's repack, the four D passes' BatchNorm records in the reference's order and the logged scalars: one launch
-        TailJobs t = {};
-        for (int i = 0; i < TT.NS; ++i) {
-          const int cs = TT.D_CS[i];
-          t.l[i].rec = e->d_rs[i] + (size_t)e->parity * 4 * 2 * cs;
-          t.l[i].rm = e->dbn + find(e->LD, RMN[i])->offset;
-          t.l[i].rv = e->dbn + find(e->LD, RVN[i])->offset;
-          t.l[i].nbt = (long long*)(e->dnbt + i);
-          t.l[i].C = cs;
-        }
-        t.nl = TT.NS; t.npass = 4; t.momentum = BN_MOM; t.acc = e->acc; t.acc_ld = e->acc_ld; t.B = B; t.invB = 1.0f / (float)B; t.lambda_gp = 10.0f; t.out = e->scal_out;
-        JCK_TRY(repack_convs(e, 0, st, &t, cdiv(TT.G_C1, 256)));
-      }
-      return JCK_OK;
-    }
+    case JCK_PHASE_D_LOSS_A: case JCK_PHASE_D_LOSS_B: return phase_d_loss_batched(e, c, phase);
+    case JCK_PHASE_D_LOSS: return e->batched ? phase_d_loss_batched(e, c, phase) : phase_d_per_pass(e, c, phase);
+    case JCK_PHASE_D_REAL: case JCK_PHASE_D_FAKE: return phase_d_per_pass(e, c, phase);
+    case JCK_PHASE_D_REAL_FWD: return phase_d_real_fwd(e, c);
+    case JCK_PHASE_GP_ONLY: return phase_gp_only(e, c);
+    case JCK_PHASE_D_GP: return phase_d_gp(e, c);
+    case JCK_PHASE_D_STEP: return phase_d_step(e, c);
+    case JCK_PHASE_G_LOSS: return phase_g_loss(e, c);
+    case JCK_PHASE_G_STEP: return phase_g_step(e, c);
   }
   JCK_FAIL(JCK_E_ARG, "unknown phase");
+}
+extern "C" int jck_engine_phase(jck_engine* e, int phase, const jck_step_inputs* in_, void* stream) {
+  // JCK_PHASE_NO_RESIDENT: no grid-barrier launch in this call (a collective may be holding CUs: include/jckgan.h)
+  const bool keep_res = e ? e->bn_res : false;
+  if (e && (phase & JCK_PHASE_NO_RESIDENT)) e->bn_res = false;
+  const int rc = phase_impl(e, phase & ~JCK_PHASE_NO_RESIDENT, in_, stream);
+  if (e) e->bn_res = keep_res;
+  if (rc != JCK_OK && e) {
+    if (e->ss.join_pending && e->sA && stream && !e->capturing) (void)hipStreamWaitEvent((hipStream_t)stream, e->evWdone, 0);
+    e->ss.drop_promises();
+  }
+  return rc;
 }
 
 // Per-step optimiser scalars (Adam bias corrections of step `step` at learning rate `lr`, computed on the host in double as
@@ -1419,16 +1449,16 @@ static int set_step_impl(jck_engine* e, int step, float lr, void* stream, bool z
   if (e->capturing) JCK_FAIL(JCK_E_ARG, "set_step inside a graph capture would bake one step's scalars into the graph");
   const int q = step & 1;
   zero_d = zero_d && e->fold_zero && e->LD.n_params % 4 == 0;
-  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, 0.5, 0.999, step, e->noise_seed, e->ema_w(step), (hipStream_t)stream, e->rz[q], (long long)e->B * 100,
+  JCK_TRY(jck_adam_set_step(e->hp2 + 8 * q, (double)lr, ADAM_B1, ADAM_B2, step, e->noise_seed, e->ema_w(step), (hipStream_t)stream, e->rz[q], (long long)e->B * 100,
                             e->ralpha[q], e->B, e->rmask[q], e->rmask[q] ? (long long)4 * e->B * L1_OUT : 0, 0.75f,
                             e->acc2 + (size_t)8 * e->acc_ld * q, (long long)8 * e->acc_ld,
                             zero_d ? e->dg : nullptr, e->LD.n_params, zero_d && e->family == 1 ? e->gw1p : nullptr, (long long)L1_OUT * L1_KPAD,
                             // DCGAN: the drawn z goes straight into G.conv1's operand rows too (no pad_rows launch in front of G's forward
                             // when the step uses the engine's own z)
                             e->family == 0 && e->fold_zero ? e->g_z : nullptr, 100, z_pad(e->family), prec_f32_storage(e->prec) ? 1 : 0));
-  e->gz_step = (e->family == 0 && e->fold_zero) ? step : -1;
-  if (zero_d) e->dg_clean_step = step;
-  e->acc_clean_step = step;
+  e->ss.gz_step = (e->family == 0 && e->fold_zero) ? step : -1;
+  if (zero_d) e->ss.dg_clean_step = step;
+  e->ss.acc_clean_step = step;
   e->hp_step[step & 1] = step;
   e->hp_lr[step & 1] = lr;
   return JCK_OK;
@@ -1529,8 +1559,8 @@ extern "C" int jck_engine_capture_abort(jck_engine* e, void* stream) {
   if (e && e->overlap) {
     destroy_side_streams(e, false);
     JCK_TRY(create_side_streams(e));
-    e->gp_inflight = false;
-    e->join_pending = e->mid_recorded = false;
+    e->ss.gp_inflight = false;
+    e->ss.join_pending = e->ss.mid_recorded = false;
     (void)hipGetLastError();
   }
   return JCK_OK;
@@ -1553,7 +1583,7 @@ extern "C" void jck_graph_destroy(void* graph_exec) {
 extern "C" int jck_engine_order_after_tail(jck_engine* e, void* stream) {
   if (!e || !e->bound || !stream) JCK_FAIL(JCK_E_ARG, "engine not bound / null stream");
   if (!e->evTail) return JCK_OK;                    // no second stream: the tail is final in the phase's stream order
-  if (e->tail_on_side) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->evW[e->T.NS - 1], 0));
+  if (e->ss.tail_on_side) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->evW[e->T.NS - 1], 0));
   HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->evTail, 0));
   return JCK_OK;
 }
@@ -1562,9 +1592,9 @@ extern "C" int jck_engine_order_after_tail(jck_engine* e, void* stream) {
 // and the next D phase computes D(real) itself.
 extern "C" int jck_engine_drop_prefetch(jck_engine* e, void* stream) {
   if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "engine not bound");
-  if (e->real_fwd_step >= 0 && e->pre_on_side && e->evReal && stream) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->evReal, 0));
-  e->real_fwd_step = -1;
-  e->pre_on_side = false;
+  if (e->ss.real_fwd_step >= 0 && e->ss.pre_on_side && e->evReal && stream) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->evReal, 0));
+  e->ss.real_fwd_step = -1;
+  e->ss.pre_on_side = false;
   return JCK_OK;
 }
 extern "C" long long jck_engine_grad_tail(const jck_engine* e, int net) {
