@@ -82,6 +82,16 @@ int jck_conv_wgrad(int prec, const void* small_side, const void* big_side, float
 /* out[B][16*Co] = z[B][CiPad] x W   (NHWC [B,4,4,Co]); stats over Co channels   model/DCGAN.py:42,62 */
 int jck_g1_fwd(int prec, const void* z, const void* w, void* out, float* stats, int* stats_slots, int B, int CiPad,
                int Co, void* stream);
+/* Inference forms of the two products above (model/DCGAN.py:42-66 under model.eval()): the BatchNorm that follows runs on its
+ * running statistics, so it is a per-channel affine, and it and the ReLU are applied to the fp32 accumulators in the product's
+ * epilogue: out = relu(scale[c] * y + shift[c]), ONE rounding to the storage type, no statistics, no pre-activation tensor.
+ * NaN passes as through torch.relu.  scale / shift: device float[Cb] (float[Co]; the channel of GEMM column (position, co) is co),
+ * 16-byte aligned - the first two quarters of an aux table (jck_bn_eval_aux).  Cb a power of two >= 8, Cs >= 16; Co >= 4.
+ * In bf16 the result is not bitwise jck_conv_up + jck_bn_act_fwd, which round y to bf16 between the two launches. */
+int jck_conv_up_affine(int prec, const void* small_in, const void* w, const float* scale, const float* shift, void* big_out,
+                       int N, int Hs, int Ws, int Cs, int Cb, void* stream);
+int jck_g1_fwd_affine(int prec, const void* z, const void* w, const float* scale, const float* shift, void* out, int B,
+                      int CiPad, int Co, void* stream);
 size_t jck_g1_wgrad_ws_bytes(int B, int CiPad, int Co);
 int jck_g1_wgrad(int prec, const void* z, const void* dy, float* ws, size_t ws_bytes, float* grad, int accumulate, int B,
                  int Ci, int CiPad, int Co, void* stream);
@@ -92,6 +102,12 @@ int jck_bn_finalize(const float* stats, int slots, float count, const float* gam
                     float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
                     float* aux, int C, void* stream);
 int jck_bn_act_fwd(int prec, const void* y, const float* aux, float slope, void* a, long long rows, int C, void* stream);
+/* Eval-mode BatchNorm (model/DCGAN.py:43-56 under model.eval(); aten::native_batch_norm, training = false): the same aux table from
+ * the RUNNING statistics, invstd = 1 / sqrtf(var + eps), scale = gamma * invstd, shift = beta - mean * scale in fp32, each operation
+ * rounded once.  One launch for the nlayers <= 8 BatchNorm layers of a network: host arrays of nlayers device pointers / channel
+ * counts; aux[k] receives 4 * C[k] floats.  Nothing else is written. */
+int jck_bn_eval_aux(int nlayers, const float* const* gamma, const float* const* beta, const float* const* running_mean,
+                    const float* const* running_var, float* const* aux, const int* C, float eps, void* stream);
 /* sums: scratch of jck_bn_bwd_ws_floats(C) floats (first 2*C = final sum g_z, sum g_z*xhat; no zeroing needed);
  * g_y may alias g_a; dgamma/dbeta (optional) are accumulated into */
 size_t jck_bn_bwd_ws_floats(int C);
@@ -153,6 +169,10 @@ int jck_img_prep_u8(int prec, const unsigned char* data, const int64_t* idx, con
 int jck_resize_norm(const float* in, float* out, int N, int C, int H, int W, int OH, int OW, float pre_scale, float pre_shift,
                     const float* mean, const float* stdv, void* stream);
 int jck_nhwc4_to_nchw(int prec, const void* in, float* out_nchw, int N, int HW, void* stream);
+/* NHWC4 image in [-1, 1] (the tanh of model/DCGAN.py:66) -> packed uint8 [N][HW][3]:
+ * u8 = (unsigned char)(fminf(fmaxf(x * 127.5f + 127.5f, 0.f), 255.f) + 0.5f), product and sum rounded separately.  NaN gives 0: that
+ * is what fmaxf returns for it.  HW % 4 == 0; `in` 16-byte, the output 4-byte aligned. */
+int jck_img_to_u8(int prec, const void* in, unsigned char* out_u8_nhwc, int N, int HW, void* stream);
 /* out = keep*x + mix*noise for an NHWC4 x                                      train/dcgan_trainer.py:171 */
 int jck_axpy_noise(int prec, const void* x, const float* noise_nchw, float keep, float mix, void* out, int N, int HW,
                    void* stream);
@@ -383,6 +403,14 @@ const float* jck_engine_scalars(const jck_engine*);
 const float* jck_engine_scalars_at(const jck_engine*, int step);   /* buffer of the given (1-based) step's parity */
 /* G forward only (train/dcgan_trainer.py:199-200, train-mode BN: running stats move); out NCHW fp32 [n,3,64,64] */
 int jck_engine_sample(jck_engine*, const float* z, const int64_t* labels /* family 1 */, int n, float* out_nchw, void* stream);
+/* The same with options, and an optional second output.  flags == 0: exactly the launches of the call above.  JCK_SAMPLE_EVAL: the
+ * generator as under model.eval() (model/DCGAN.py:42-66 with BatchNorm on its running statistics): one launch folds the layers' aux
+ * tables, every ConvTranspose + BatchNorm + ReLU is one launch, each image depends on its own z alone, any 1 <= n <= batch, and
+ * neither the running statistics nor num_batches_tracked are written.  out_nchw: fp32 [n,3,S,S] or NULL; out_u8_nhwc: uint8
+ * [n,S,S,3] as from the image-to-uint8 kernel above, or NULL. */
+#define JCK_SAMPLE_EVAL 1u   /* BatchNorm with the running statistics; no buffer moves */
+int jck_engine_sample_ex(jck_engine*, const float* z, const int64_t* labels, int n, unsigned flags, float* out_nchw /* or NULL */,
+                         unsigned char* out_u8_nhwc /* or NULL */, void* stream);
 /* debug / parity access to internal NHWC tensors: name in {"fake","real_noisy",...}; returns device ptr or NULL */
 const void* jck_engine_tensor(const jck_engine*, const char* name, long long* numel);
 

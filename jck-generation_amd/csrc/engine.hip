@@ -948,7 +948,11 @@ static void launch_pad_rows(const float* z, int B, int zd, int zp, void* out, hi
   hipLaunchKernelGGL(pad_rows_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, B, zd, zp, (T*)out);
 }
 
-static int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B, hipStream_t st, bool z_in_place = false) {
+// eval: BatchNorm with the RUNNING statistics (model.eval()): one launch folds every layer's gamma, beta and running statistics into
+// scale / shift (the stage's aux table, which every train-mode forward rewrites before its backward reads it), and each product
+// applies them and the ReLU in its epilogue - one launch and one activation store per stage, images independent of each other,
+// no statistics, running statistics and num_batches_tracked untouched.
+static int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B, hipStream_t st, bool z_in_place = false, bool eval = false) {
   const int zp = z_pad(e->family);
   if (e->family == 1) {
     if (!labels) JCK_FAIL(JCK_E_ARG, "CGAN generator needs labels");
@@ -957,6 +961,26 @@ static int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B
     e->ss.gz_step = -1;                        // the operand rows now hold somebody else's z
     if (e->prec == JCK_PREC_BF16) launch_pad_rows<bf16_t>(z, B, 100, zp, e->g_z, st); else launch_pad_rows<float>(z, B, 100, zp, e->g_z, st);
     HIPCHK(hipGetLastError());
+  }
+  if (eval) {
+    const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
+    float* aux[JCK_MAX_STAGES];
+    int Cs[JCK_MAX_STAGES];
+    for (int i = 0; i < TT.NS; ++i) {
+      gamma[i] = e->P(e->LG, e->gp, NWN[i]); beta[i] = e->P(e->LG, e->gp, NBN[i]);
+      rm[i] = e->gbn + find(e->LG, RMN[i])->offset; rv[i] = e->gbn + find(e->LG, RVN[i])->offset;
+      aux[i] = e->g_bn[i].aux; Cs[i] = TT.G_C1 >> i;
+    }
+    JCK_TRY(jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st));
+    JCK_TRY(jck_g1_fwd_affine(e->prec, e->g_z, e->g1_w, aux[0], aux[0] + Cs[0], e->g_a[0], B, zp, TT.G_C1, st));
+    for (int i = 0; i < TT.NS; ++i) {
+      const int h = 4 << i;
+      if (i < TT.NS - 1)
+        JCK_TRY(jck_conv_up_affine(e->prec, e->g_a[i], e->g_up[i], aux[i + 1], aux[i + 1] + Cs[i + 1], e->g_a[i + 1], B, h, h, TT.G_CS[i], TT.G_CB[i], st));
+      else
+        JCK_TRY(jck_conv_up(e->prec, e->g_a[i], e->g_up[i], e->fake_raw, nullptr, nullptr, 1, B, h, h, TT.G_CS[i], TT.G_CB[i], st));
+    }
+    return JCK_OK;
   }
   JCK_TRY(jck_g1_fwd(e->prec, e->g_z, e->g1_w, e->g_y[0], e->g_bn[0].stats, &e->g_bn[0].slots, B, zp, TT.G_C1, st));
   for (int i = 0; i < TT.NS; ++i) {
@@ -1621,6 +1645,18 @@ extern "C" int jck_engine_sample(jck_engine* e, const float* z, const int64_t* l
   hipStream_t st = (hipStream_t)stream;
   JCK_TRY(g_forward(e, z, labels, n, st));
   return jck_nhwc4_to_nchw(e->prec, e->fake_raw, out_nchw, n, TT.HW, st);
+}
+
+extern "C" int jck_engine_sample_ex(jck_engine* e, const float* z, const int64_t* labels, int n, unsigned flags, float* out_nchw,
+                                    unsigned char* out_u8_nhwc, void* stream) {
+  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "engine not bound");
+  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "sample: n must be in [1, batch]");
+  if (flags & ~JCK_SAMPLE_EVAL) JCK_FAIL(JCK_E_ARG, "sample: unknown flag");
+  hipStream_t st = (hipStream_t)stream;
+  JCK_TRY(g_forward(e, z, labels, n, st, false, (flags & JCK_SAMPLE_EVAL) != 0));
+  if (out_nchw) JCK_TRY(jck_nhwc4_to_nchw(e->prec, e->fake_raw, out_nchw, n, TT.HW, st));
+  if (out_u8_nhwc) JCK_TRY(jck_img_to_u8(e->prec, e->fake_raw, out_u8_nhwc, n, TT.HW, st));
+  return JCK_OK;
 }
 
 extern "C" const void* jck_engine_tensor(const jck_engine* e, const char* name, long long* numel) {

@@ -154,6 +154,33 @@ __global__ void nhwc4_to_nchw_kernel(const T* __restrict__ in, float* __restrict
   }
 }
 
+// NHWC4 T in [-1, 1] (the tanh image) -> packed uint8 [N][HW][3]: u8 = (unsigned char)(min(max(x * 127.5 + 127.5, 0), 255) + 0.5),
+// product and sum rounded separately in fp32.  NaN -> 0 (fmaxf returns its other operand).  Four pixels per thread: 16-byte loads,
+// one 12-byte store.
+template <typename T>
+__global__ void img_to_u8_kernel(const T* __restrict__ in, unsigned char* __restrict__ out, long long total4) {
+#pragma clang fp contract(off)
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
+    float v[16];
+    if constexpr (sizeof(T) == 2) {
+      ld8(in + i * 16, reinterpret_cast<float(&)[8]>(v[0]));
+      ld8(in + i * 16 + 8, reinterpret_cast<float(&)[8]>(v[8]));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ld4(in + i * 16 + k * 4, reinterpret_cast<float(&)[4]>(v[k * 4]));
+    }
+    unsigned w[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      const float x = v[(k / 3) * 4 + k % 3];
+      const unsigned b = (unsigned)(unsigned char)(fminf(fmaxf(x * 127.5f + 127.5f, 0.f), 255.f) + 0.5f);
+      w[k >> 2] |= b << (8 * (k & 3));
+    }
+    struct alignas(4) U3 { unsigned a, b, c; };
+    *reinterpret_cast<U3*>(out + i * 12) = U3{w[0], w[1], w[2]};
+  }
+}
+
 // out = keep * x(NHWC4 T) + mix * noise(NCHW f32)
 template <typename T>
 __global__ void axpy_noise_kernel(const T* __restrict__ x, const float* __restrict__ noise, float keep, float mix,
@@ -321,6 +348,29 @@ static __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __
     running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
     running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
   }
+}
+
+// Eval-mode BatchNorm folded into the aux table above from the RUNNING statistics (aten::native_batch_norm, training = false:
+// invstd = 1 / sqrt(var + eps), scale = gamma * invstd, shift = beta - mean * scale, each product and sum rounded once:
+// contraction is off in the kernel).  Every BatchNorm layer of a network in one launch: a job per layer, a thread
+// per channel, block b belongs to the job with first_block[j] <= b < first_block[j + 1].  Nothing but aux is written.
+#define BN_EVAL_MAX_JOBS 8
+struct BnEvalJob { const float *gamma, *beta, *mean, *var; float* aux; int C; };
+struct BnEvalJobs { BnEvalJob j[BN_EVAL_MAX_JOBS]; int first_block[BN_EVAL_MAX_JOBS + 1]; int n; float eps; };
+static __global__ __launch_bounds__(256) void bn_eval_aux_kernel(const BnEvalJobs jobs) {
+#pragma clang fp contract(off)
+  int k = 0;
+  while (k + 1 < jobs.n && (int)blockIdx.x >= jobs.first_block[k + 1]) ++k;
+  const BnEvalJob& q = jobs.j[k];
+  const int c = ((int)blockIdx.x - jobs.first_block[k]) * 256 + (int)threadIdx.x;
+  if (c >= q.C) return;
+  const float mean = q.mean[c];
+  const float invstd = 1.0f / sqrtf(q.var[c] + jobs.eps);
+  const float sc = q.gamma[c] * invstd;
+  q.aux[c] = sc;
+  q.aux[q.C + c] = q.beta[c] - mean * sc;
+  q.aux[2 * q.C + c] = mean;
+  q.aux[3 * q.C + c] = invstd;
 }
 
 // a = act(scale[c]*y + shift[c]), act = x>0 ? x : slope*x

@@ -60,6 +60,10 @@ struct IgemmParams {
   // instead of one row per (tile, wave); set by the launcher for the *_grouped entry points
   int stat_accum;
   double flops;           // algorithmic FLOPs of this launch (profiling only)
+  // AFFINE instantiations only (inference: BatchNorm with the running statistics folded into the product's epilogue):
+  // v = relu(aff_scale[c] * acc + aff_shift[c]), c = channel & (cstat - 1); 16-byte aligned, cstat floats each
+  const float* aff_scale;
+  const float* aff_shift;
 };
 
 #define IG_BK 64
@@ -96,14 +100,16 @@ __device__ __forceinline__ void igemm_pixel_offsets(const IgemmParams& p, int la
 }
 
 // Shared epilogue: optional BatchNorm partial statistics, bias, tanh, NHWC store of 4 consecutive channels per lane.
-template <class P, int BCH, int BPIX, int FM, int FN, int WPIXN>
+// AFFINE (compile time, the inference entry points alone): the per-channel affine of an eval-mode BatchNorm and the ReLU are applied
+// to the fp32 accumulators before the one rounding of the store - no statistics, no pre-activation tensor.  NaN passes (torch.relu).
+template <class P, int BCH, int BPIX, int FM, int FN, int WPIXN, bool AFFINE = false>
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc)[FM][FN], int lane, int wch, int wpix, int z, int zraw,
                                                int bidx, int bidy, int m0, int ch0) {
   typedef typename P::T T;
   // ---- epilogue --------------------------------------------------------------------------------------
   long long poff[FN];                                               // output offset of this lane's pixel in tile column j (-1: past M)
   igemm_pixel_offsets<FN>(p, lane, wpix, m0, poff);
-  if (p.stats) {
+  if (!AFFINE && p.stats) {
     // slot = one (pixel tile, phase, channel-set replica, pixel-wave); every (slot, channel) is written exactly once
     const int yrep = bidy / p.ytiles_per_cset, nyrep = p.gy / p.ytiles_per_cset;
     // pixel tile slowest, so that the slots of consecutive pixel ranges (BatchNorm groups) are consecutive too
@@ -147,13 +153,23 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]);
       }
+      if constexpr (AFFINE) {
+        const int cc = ch & (p.cstat - 1);
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(p.aff_scale + cc), sh = *reinterpret_cast<const f32x4*>(p.aff_shift + cc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float t = fmaf(sc[r], v[r], sh[r]);
+          v[r] = t < 0.f ? 0.f : t;
+        }
+      }
       if (p.out_f32) st4(reinterpret_cast<float*>(p.out) + off + ch, v);
       else st4(outp + off + ch, v);
     }
   }
 }
 
-template <class P, int BCH, int BPIX, int NSUB, int NST = 2>
+// NSUB: 1 - >= 64 gathered channels, 2 - exactly 4, 0 - 8..32 (AFFINE launches only: small generators at inference)
+template <class P, int BCH, int BPIX, int NSUB, int NST = 2, bool AFFINE = false>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   typedef typename P::T T;        // activation storage type
   typedef typename P::W W;        // packed-weight element type (bf16_t or float)
@@ -237,6 +253,14 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
       for (int ps = 0; ps < C::APASS; ++ps) {
         const bool ok = (unsigned)(riy[ps] + dyv) < (unsigned)p.H && (unsigned)(rix[ps] + dxv) < (unsigned)p.W;
         buf_ld8(rs_act, ok ? rowoff[ps] + (unsigned)toffb : JCK_OOB, sg.a[ps]);
+      }
+    } else if constexpr (NSUB == 0) {   // 8 <= C < 64: the k-step spans 64 / C taps, this thread's 8-element unit lies inside one of them
+      const int k = kbase + unit * 8, t = k >> p.logC;
+      const int d = tdyx[t], o = (toff[t] + (k & (Cc - 1))) * (int)ESZ;
+#pragma unroll
+      for (int ps = 0; ps < C::APASS; ++ps) {
+        const bool ok = (unsigned)(riy[ps] + (d >> 16)) < (unsigned)p.H && (unsigned)(rix[ps] + (int)(short)(d & 0xffff)) < (unsigned)p.W;
+        buf_ld8(rs_act, ok ? rowoff[ps] + (unsigned)o : JCK_OOB, sg.a[ps]);
       }
     } else {   // C == 4: the 8-element unit spans two taps (pixels), per-thread taps from the LDS tables
       const int t0 = (kbase + unit * 8) >> 2, t1 = t0 + 1;
@@ -378,7 +402,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     }
   }
 
-  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -395,7 +419,7 @@ static __device__ __attribute__((aligned(16))) unsigned int g_jck_zero_page[64];
 // about one workgroup per CU, where a 4-wave workgroup would serialise DMA issue and MFMA in every wave.
 // NCW = 8 (768 threads) with a 128 x 256 tile: the weight tile is filled once for twice the pixels - 85 instead of 64 FLOP
 // per filled byte (the kernels are bound by the LDS fill rate).
-template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4>
+template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false>
 __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(const IgemmParams p) {
   static_assert(!WS || NSTG == 3, "wave specialisation uses 3 LDS stages");
   static_assert(NCW == 4 || (WS && NCW == 8), "8 consumer waves exist in the wave-specialised form only");
@@ -523,7 +547,7 @@ __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(co
       compute(slot);
       slot = slot == 2 ? 0 : slot + 1;
     }
-    igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+    igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
     return;
   }
   // prologue: NSTG-1 stages in flight
@@ -546,7 +570,7 @@ __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(co
     st_i = (st_i + 1 == NSTG) ? 0 : st_i + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // drain the dead tail loads before the epilogue reuses nothing of LDS
-  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
 }
 
 // Epilogue of the persistent kernel: 16-byte stores.  The loader fills LDS weight row r of every 32-row block with output

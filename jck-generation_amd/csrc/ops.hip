@@ -176,7 +176,9 @@ extern "C" int jck_prof_collect(int cap, const char** name_out, int* count_out, 
 // ---------------------------------------------------------------------------------------------------------
 // gather-GEMM dispatch
 // ---------------------------------------------------------------------------------------------------------
-template <class P, int BCH, int BPIX, int NSUB>
+// (AFFINE instantiations report the name of their tile: the name says which kernel form and tile ran, not which of the epilogue's
+// options - statistics, bias, tanh, the inference affine - it applied)
+template <class P, int BCH, int BPIX, int NSUB, bool AFFINE = false>
 static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   typedef IgemmCfg<P, BCH, BPIX> C;
   constexpr int tile = BCH == 128 ? (BPIX == 128 ? 0 : 1) : (BCH == 64 ? (NSUB == 2 ? 2 : 3) : 4);
@@ -184,7 +186,7 @@ static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStre
   ProfScope prof(variant, p.flops, st);
   static_assert(P::IS_F32 || !(BCH == 64 && NSUB == 1), "bf16 has no register-staged 64 x 128 tile (and no name for one)");
   note_launch(LN_IGEMM + LN_IGEMM_TILES * (P::SPLIT ? 2 : P::IS_F32 ? 1 : 0) + tile);
-  auto kern = igemm_kernel<P, BCH, BPIX, NSUB, 2>;
+  auto kern = igemm_kernel<P, BCH, BPIX, NSUB, 2, AFFINE>;
   static bool attr_done = false;
   if (!attr_done) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
@@ -203,13 +205,13 @@ static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStre
   return JCK_OK;
 }
 
-template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4>
+template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false>
 static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   constexpr int LDSB = NSTG * (BCH + BPIX) * IG_BK * 2;
   constexpr int variant = BPIX == 256 ? 20 : BCH == 64 ? 3 : (BPIX == 128 ? 0 : 1);
   ProfScope prof(variant, p.flops, st);
   note_launch(LN_DMA + (BPIX == 256 ? 0 : BCH == 64 ? 3 : BPIX == 128 ? 1 : 2));
-  auto kern = igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW>;
+  auto kern = igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW, AFFINE>;
   static bool attr_done = false;
   if (!attr_done) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
@@ -327,6 +329,35 @@ static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsu
   JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
 }
 
+// Inference launches (p.aff_scale set): the kernels that end in the shared epilogue, in its AFFINE instantiation - never the persistent
+// ones.  Tile choice as launch_igemm_p's non-persistent branches; 8..32 gathered channels (nsub 0) take 16-row tiles whatever the row count.
+template <class P>
+static int launch_igemm_affine_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st) {
+  if (nsub == 0) {
+    if (nch_pad % 16) JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
+    return launch_igemm_t<P, 16, 256, 0, true>(p, nch_pad, phases, st, nullptr);
+  }
+  if (nsub != 1) JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue is built for >= 8 gathered channels");
+  if (nch_pad % 128 == 0) {
+    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
+    if constexpr (!P::IS_F32) {
+      const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128) * phases;
+      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, true>(p, nch_pad, phases, st, nullptr);
+      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, true>(p, nch_pad, phases, st, nullptr);
+      return launch_igemm_dma<128, 64, 3, true, 4, true>(p, nch_pad, phases, st, nullptr);
+    } else {
+      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, true>(p, nch_pad, phases, st, nullptr);
+      return launch_igemm_t<P, 128, 64, 1, true>(p, nch_pad, phases, st, nullptr);
+    }
+  }
+  if (nch_pad == 64) {
+    if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, true>(p, nch_pad, phases, st, nullptr);
+    else return launch_igemm_t<P, 64, 128, 1, true>(p, nch_pad, phases, st, nullptr);
+  }
+  if (nch_pad == 16) return launch_igemm_t<P, 16, 256, 1, true>(p, nch_pad, phases, st, nullptr);
+  JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
+}
+
 static int launch_wgrad_reduce(const float* ws, int Z, int CsRows, int ncols, int Cs, int Cb, int logCbPad, float* grad,
                                int accumulate, hipStream_t st);
 int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int nsub, hipStream_t st, int* slots) {
@@ -334,6 +365,7 @@ int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int n
   for (int zz = 0; zz < 4; ++zz)
     for (int t = 0; t < 16; ++t) p.tap[zz][t] = ((int)p.dy[zz][t] << 16) | ((int)p.dx[zz][t] & 0xffff);
   const long long esz = prec_f32_storage(prec) ? 4 : 2;
+  if (nsub == 0 && (p.logC < 3 || p.logC > 5 || !p.aff_scale)) JCK_FAIL(JCK_E_ARG, "igemm: 8..32 gathered channels are built for the affine epilogue alone");
   if (nsub == 1 && p.logC < 6 && !p.act_row_elems) JCK_FAIL(JCK_E_ARG, "igemm: the gathered tensor needs >= 64 channels (or exactly 4)");
   {
     // extent of the gathered tensor: rows (n, oy, ox) span N = M / (OH*OW) images of H x W x C
@@ -346,6 +378,15 @@ int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int n
   if (p.K % IG_BK != 0) JCK_FAIL(JCK_E_ARG, "igemm: K must be a multiple of 64, got " + std::to_string(p.K));
   if (p.M <= 0) JCK_FAIL(JCK_E_ARG, "igemm: empty problem");
   if (p.stats && !slots) JCK_FAIL(JCK_E_ARG, "igemm: stats requested without a slot-count output");
+  if (p.aff_scale) {
+    if (!p.aff_shift || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || !is_pow2(p.cstat) || p.cstat % 4 ||
+        ((uintptr_t)p.aff_scale | (uintptr_t)p.aff_shift) % 16)
+      JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue takes 16-byte aligned scale and shift, a power-of-two channel count and no other option");
+    if (prec == JCK_PREC_BF16) return launch_igemm_affine_p<PrecBf16>(p, nch_pad, phases, nsub, st);
+    if (prec == JCK_PREC_F32) return launch_igemm_affine_p<PrecF32>(p, nch_pad, phases, nsub, st);
+    if (prec == JCK_PREC_BF16X3) return launch_igemm_affine_p<PrecBf16x3>(p, nch_pad, phases, nsub, st);
+    JCK_FAIL(JCK_E_ARG, "bad prec");
+  }
   if (prec == JCK_PREC_BF16) return launch_igemm_p<PrecBf16>(p, nch_pad, phases, nsub, st, slots);
   if (prec == JCK_PREC_F32) return launch_igemm_p<PrecF32>(p, nch_pad, phases, nsub, st, slots);
   if (prec == JCK_PREC_BF16X3) return launch_igemm_p<PrecBf16x3>(p, nch_pad, phases, nsub, st, slots);
@@ -427,8 +468,11 @@ extern "C" int jck_conv_down_grouped(int prec, const void* big, const void* w, v
   return conv_down_impl(prec, big, w, small_out, stats, stats_slots, N, Hb, Wb, Cb, Cs, stream, group_images);
 }
 static int conv_up_impl(int prec, const void* small_in, const void* w, void* big_out, float* stats, int* stats_slots,
-                        int epi_tanh, int N, int Hs, int Ws, int Cs, int Cb, void* stream, int fwd_group_images = 0) {
+                        int epi_tanh, int N, int Hs, int Ws, int Cs, int Cb, void* stream, int fwd_group_images = 0,
+                        const float* aff_scale = nullptr, const float* aff_shift = nullptr) {
   const int cbp = jck_pad_chan(Cb);
+  // (<= 4 output channels run as rows-are-phases tiles or on the image-side kernel below, neither of which has the affine)
+  if (aff_scale && (Cb < 8 || !is_pow2(Cb))) JCK_FAIL(JCK_E_ARG, "conv_up_affine: Cb must be a power of two >= 8");
   if (!is_pow2(Cs) || Cs < 16 || !is_pow2(Hs) || !is_pow2(Ws) || cbp % 4 != 0)
     JCK_FAIL(JCK_E_ARG, "conv_up: shapes must be powers of two (Hs,Ws,Cs>=16)");
   if ((long long)N * Hs * Ws * 4 * cbp >= (1ll << 31)) JCK_FAIL(JCK_E_ARG, "conv_up: tensor exceeds 2^31 elements");
@@ -467,7 +511,8 @@ static int conv_up_impl(int prec, const void* small_in, const void* w, void* big
   if (p.K % 64 != 0) JCK_FAIL(JCK_E_ARG, "conv_up: 4*Cs must be a multiple of 64");
   p.flops = 2.0 * p.M * 4.0 * Cb * 4.0 * Cs;
   if (stats && fwd_group_images > 0) { p.bn_group_rows = fwd_group_images * Hs * Ws; p.stat_accum = 1; }
-  return launch_igemm(prec, p, rows, 4, 1, (hipStream_t)stream, stats_slots);
+  p.aff_scale = aff_scale; p.aff_shift = aff_shift;
+  return launch_igemm(prec, p, rows, 4, aff_scale && Cs < 64 ? 0 : 1, (hipStream_t)stream, stats_slots);
 }
 // D.conv1's input gradient with the tanh + instance-noise-mix backward of G's output in its epilogue (thin.hpp: ImgUpParams::mul_t):
 // out = scale * bf16(convT(small_in)) * (1 - tanh_y^2), bit for bit jck_conv_up followed by tanh_bwd_ev.  *fused = false (and
@@ -489,7 +534,7 @@ extern "C" int jck_conv_up_grouped(int prec, const void* small_in, const void* w
   return conv_up_impl(prec, small_in, w, big_out, stats, stats_slots, 0, N, Hs, Ws, Cs, Cb, stream, group_images);
 }
 static int g1_fwd_impl(int prec, const void* z, const void* w, void* out, float* stats, int* stats_slots, int B,
-                       int CiPad, int Co, void* stream) {
+                       int CiPad, int Co, void* stream, const float* aff_scale = nullptr, const float* aff_shift = nullptr) {
   if (!is_pow2(CiPad) || CiPad < 64 || !is_pow2(Co) || (16 * Co) % 128 != 0)
     JCK_FAIL(JCK_E_ARG, "g1_fwd: CiPad must be a power of two >= 64, Co a power of two");
   IgemmParams p = {};
@@ -499,13 +544,26 @@ static int g1_fwd_impl(int prec, const void* z, const void* w, void* out, float*
   p.dy[0][0] = 0; p.dx[0][0] = 0;
   p.osN = (long long)16 * Co; p.osY = 0; p.osX = 0; p.obase[0] = 0;
   p.cstat = Co; p.ytiles_per_cset = 1; p.epi = 0; p.w_phase_stride = 0;
-  if (Co < 128) JCK_FAIL(JCK_E_ARG, "g1_fwd: Co must be >= 128");
+  if (Co < 128 && !aff_scale) JCK_FAIL(JCK_E_ARG, "g1_fwd: Co must be >= 128");      // (statistics: a channel set must fill a tile)
   p.flops = 2.0 * B * 16.0 * Co * CiPad;
+  p.aff_scale = aff_scale; p.aff_shift = aff_shift;
   return launch_igemm(prec, p, 16 * Co, 1, 1, (hipStream_t)stream, stats_slots);
 }
 extern "C" int jck_g1_fwd(int prec, const void* z, const void* w, void* out, float* stats, int* stats_slots, int B,
                           int CiPad, int Co, void* stream) {
   return g1_fwd_impl(prec, z, w, out, stats, stats_slots, B, CiPad, Co, stream);
+}
+// inference: the product with relu(scale[c] * y + shift[c]) - an eval-mode BatchNorm folded by jck_bn_eval_aux - in its epilogue
+extern "C" int jck_conv_up_affine(int prec, const void* small_in, const void* w, const float* scale, const float* shift, void* big_out,
+                                  int N, int Hs, int Ws, int Cs, int Cb, void* stream) {
+  if (!scale || !shift) JCK_FAIL(JCK_E_ARG, "conv_up_affine: scale and shift are required");
+  return conv_up_impl(prec, small_in, w, big_out, nullptr, nullptr, 0, N, Hs, Ws, Cs, Cb, stream, 0, scale, shift);
+}
+extern "C" int jck_g1_fwd_affine(int prec, const void* z, const void* w, const float* scale, const float* shift, void* out, int B,
+                                 int CiPad, int Co, void* stream) {
+  if (!scale || !shift) JCK_FAIL(JCK_E_ARG, "g1_fwd_affine: scale and shift are required");
+  if (Co < 4) JCK_FAIL(JCK_E_ARG, "g1_fwd_affine: Co must be >= 4");
+  return g1_fwd_impl(prec, z, w, out, nullptr, nullptr, B, CiPad, Co, stream, scale, shift);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -722,6 +780,25 @@ extern "C" int jck_bn_finalize(const float* stats, int slots, float count, const
   return JCK_OK;
 }
 
+
+extern "C" int jck_bn_eval_aux(int nlayers, const float* const* gamma, const float* const* beta, const float* const* running_mean,
+                               const float* const* running_var, float* const* aux, const int* C, float eps, void* stream) {
+  if (nlayers < 1 || nlayers > BN_EVAL_MAX_JOBS) JCK_FAIL(JCK_E_ARG, "bn_eval_aux: 1 to " + std::to_string(BN_EVAL_MAX_JOBS) + " layers per launch");
+  if (!gamma || !beta || !running_mean || !running_var || !aux || !C) JCK_FAIL(JCK_E_ARG, "bn_eval_aux: null table");
+  BnEvalJobs jobs = {};
+  jobs.n = nlayers; jobs.eps = eps;
+  int blocks = 0;
+  for (int k = 0; k < nlayers; ++k) {
+    if (C[k] < 1 || !gamma[k] || !beta[k] || !running_mean[k] || !running_var[k] || !aux[k]) JCK_FAIL(JCK_E_ARG, "bn_eval_aux: bad layer " + std::to_string(k));
+    jobs.j[k] = BnEvalJob{gamma[k], beta[k], running_mean[k], running_var[k], aux[k], C[k]};
+    jobs.first_block[k] = blocks;
+    blocks += cdiv(C[k], 256);
+  }
+  jobs.first_block[nlayers] = blocks;
+  hipLaunchKernelGGL(bn_eval_aux_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, jobs);
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
 
 extern "C" int jck_bn_act_fwd(int prec, const void* y, const float* aux, float slope, void* a, long long rows, int C,
                               void* stream) {
@@ -993,6 +1070,15 @@ extern "C" int jck_img_prep(int prec, const float* img, const float* noise, floa
 extern "C" int jck_nhwc4_to_nchw(int prec, const void* in, float* out, int N, int HW, void* stream) {
   DISPATCH_T(prec, hipLaunchKernelGGL(nhwc4_to_nchw_kernel<T>, dim3(ew_grid((long long)N * HW)), dim3(256), 0,
                                       (hipStream_t)stream, (const T*)in, out, N, HW));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+extern "C" int jck_img_to_u8(int prec, const void* in, unsigned char* out_u8_nhwc, int N, int HW, void* stream) {
+  if (N < 1 || HW < 4 || HW % 4) JCK_FAIL(JCK_E_ARG, "img_to_u8: N >= 1 and HW a multiple of 4");
+  if ((uintptr_t)in % 16 || (uintptr_t)out_u8_nhwc % 4) JCK_FAIL(JCK_E_ARG, "img_to_u8: the image must be 16-byte, the output 4-byte aligned");
+  const long long total4 = (long long)N * HW / 4;
+  DISPATCH_T(prec, hipLaunchKernelGGL(img_to_u8_kernel<T>, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, (const T*)in,
+                                      out_u8_nhwc, total4));
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }

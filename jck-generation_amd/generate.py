@@ -1,0 +1,122 @@
+"""Images from a trained generator, outside the trainer.  Run from this directory:
+
+    python generate.py -m DCGAN --checkpoint ../model/DCGAN/fid/best.pt --num 64 --out samples
+    python generate.py -m CGAN --checkpoint best.pt --num 8 --classes 3,17,42 --truncation 0.7 --out samples
+    python generate.py -m DCGAN --checkpoint best.pt --interpolate 4:8 --which ema --calibrate 20 --out samples
+
+Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
+BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
+bounded by the batch.  --bn batch is the trainers' evaluation sampling: each chunk of -b images is one train-mode BatchNorm batch.
+An averaged generator (--which ema, or auto when the file has one) wants --calibrate K first: K train-mode batches that fit the
+running statistics to the averaged weights (in this process only; the file is not touched)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+
+def get_arg_parse(argv=None):
+    p = argparse.ArgumentParser(description="sample a trained DCGAN / CGAN generator")
+    p.add_argument("-m", "--model", choices=["DCGAN", "CGAN"], default="DCGAN")
+    p.add_argument("--checkpoint", required=True, help="a checkpoint written by the trainers (or the reference's)")
+    p.add_argument("--num", type=int, default=None, help="images, per class with --classes (default 64; not with --interpolate)")
+    p.add_argument("-b", "--batch_size", type=int, default=64, help="images per launch sequence")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--truncation", type=float, default=None, help="draw z from a normal truncated to [-T, T]")
+    p.add_argument("--bn", choices=["running", "batch"], default="running")
+    p.add_argument("--which", choices=["auto", "live", "ema"], default="auto")
+    p.add_argument("--calibrate", type=int, default=0, metavar="K", help="train-mode sampling batches before sampling")
+    p.add_argument("--classes", type=parse_classes, default=None, metavar="3,17,...", help="CGAN: one grid row of --num images per class")
+    p.add_argument("--interpolate", type=parse_interpolate, default=None, metavar="PAIRS:STEPS",
+                   help="PAIRS spherical interpolations of STEPS points each between random z (one grid row per pair)")
+    p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
+    p.add_argument("--out", required=True, help="output directory")
+    a = p.parse_args(argv)
+    if a.interpolate and a.num is not None:
+        p.error("--interpolate PAIRS:STEPS sets the number of images; --num does not go with it")
+    if a.num is None:
+        a.num = 64
+    if a.num < 1 or a.batch_size < 1 or a.calibrate < 0:
+        p.error("--num and -b must be >= 1, --calibrate >= 0")
+    if a.truncation is not None and not a.truncation > 0:
+        p.error("--truncation must be > 0")
+    if a.classes is not None and a.model != "CGAN":
+        p.error("--classes needs -m CGAN")
+    return a
+
+
+def parse_classes(s):
+    try:
+        ids = [int(t) for t in s.split(",") if t.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"class ids must be integers: {s!r}")
+    if not ids or min(ids) < 0 or max(ids) >= 100:
+        raise argparse.ArgumentTypeError("class ids must lie in [0, 100)")
+    return ids
+
+
+def parse_interpolate(s):
+    try:
+        pairs, steps = (int(t) for t in s.split(":"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected PAIRS:STEPS, got {s!r}")
+    if pairs < 1 or steps < 2:
+        raise argparse.ArgumentTypeError("PAIRS >= 1 and STEPS >= 2")
+    return pairs, steps
+
+
+def plan(args):
+    """(z [N,100] on the host, class ids [N] or None, images per grid row) of a run."""
+    from hipgan.sampler import latents, slerp
+    if args.interpolate:
+        pairs, steps = args.interpolate
+        ends = latents(2 * pairs, args.seed, args.truncation)
+        z = torch.cat([slerp(ends[2 * k], ends[2 * k + 1], steps) for k in range(pairs)])
+        rows, per_row = pairs, steps
+    elif args.classes:
+        rows, per_row = len(args.classes), args.num
+        z = latents(rows * per_row, args.seed, args.truncation)
+    else:
+        rows, per_row = None, 8
+        z = latents(args.num, args.seed, args.truncation)
+    cls = None
+    if args.model == "CGAN":
+        if args.classes:              # a class per grid row (interpolation rows cycle through the classes given)
+            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(rows)]).repeat_interleave(per_row)
+        else:
+            cls = torch.randint(0, 100, (z.shape[0],), generator=torch.Generator().manual_seed(args.seed + 1))
+    return z.float(), cls, per_row
+
+
+def grid_u8(images_u8, per_row, padding=2):
+    """uint8 [N,H,W,3] -> one uint8 [H',W',3] sheet, `per_row` images a row on black."""
+    from train.gan_trainer import _make_grid
+    x = torch.as_tensor(images_u8).permute(0, 3, 1, 2).float()
+    g = _make_grid(x, nrow=per_row, padding=padding, normalize=False)
+    return g.permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).numpy()
+
+
+def main(argv=None):
+    args = get_arg_parse(argv)
+    from hipgan.sampler import Sampler
+    from train.gan_trainer import _encode_png
+    s = Sampler.from_checkpoint(args.checkpoint, args.model, which=args.which, prec=args.prec, batch=args.batch_size)
+    if args.calibrate:
+        s.calibrate(args.calibrate, seed=args.seed + 2)
+    z, cls, per_row = plan(args)
+    u8 = s.from_latents(z, cls, bn=args.bn, out="uint8").cpu().numpy()
+    os.makedirs(args.out, exist_ok=True)
+    arrays = {"images": u8, "z": z.numpy()}
+    if cls is not None:
+        arrays["labels"] = cls.numpy().astype(np.int64)
+    np.savez(os.path.join(args.out, "images.npz"), **arrays)
+    with open(os.path.join(args.out, "grid.png"), "wb") as f:
+        f.write(_encode_png(grid_u8(u8, per_row)))
+    print(f"{u8.shape[0]} images ({s.which} generator, bn={args.bn}) -> {args.out}/images.npz, grid.png")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

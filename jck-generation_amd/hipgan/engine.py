@@ -795,27 +795,48 @@ class DcganEngine:
         self.step_async(real, noise, lr, **kw)
         return self.scalars()
 
-    def sample(self, z, labels=None):
-        """G(z) with train-mode BatchNorm (train/dcgan_trainer.py:199-200) -> NCHW fp32 on the device.  The whole z is ONE
-        BatchNorm batch (statistics and running-stat update over all n samples, as in the reference), so n <= batch."""
+    def sample(self, z, labels=None, bn="batch", out="float"):
+        """G(z) -> NCHW fp32 [n,3,S,S] on the device (out="float") or NHWC uint8 [n,S,S,3] (out="uint8").
+
+        bn="batch" (the default, train/dcgan_trainer.py:199-200): train-mode BatchNorm.  The whole z is ONE BatchNorm batch
+        (statistics and running-stat update over all n samples, as in the reference), so n <= batch and every image depends on
+        every z of the call.
+        bn="running": the generator as under model.eval() - BatchNorm on its running statistics, folded into the products'
+        epilogues.  Every image depends on its own z alone, the buffers do not move, and any n works: z is cut into chunks of
+        at most `batch` rows, whose images equal those of separate calls bit for bit."""
+        if bn not in ("batch", "running"):
+            raise JckError(f"sample: bn must be 'batch' or 'running', got {bn!r}")
+        if out not in ("float", "uint8"):
+            raise JckError(f"sample: out must be 'float' or 'uint8', got {out!r}")
         n = z.shape[0]
-        if n > self.batch:
+        if n < 1:
+            raise JckError("sample: z is empty")
+        if bn == "batch" and n > self.batch:
             raise JckError(f"sample: {n} latent vectors exceed this engine's batch {self.batch}; bind an engine with batch >= n "
-                           f"(DcganEngine(batch=n, share=engine))")
+                           f"(DcganEngine(batch=n, share=engine)), or sample with bn='running', which takes any n")
 
         self.join()
         if self._packed_version != self._shared["version"]:
             self.repack()
-        out = torch.empty(n, 3, self.size, self.size, dtype=torch.float32, device=self.device)
         zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
         lab = None
         if self.family == 1:
             if labels is None or labels.shape != (n, 100):
                 raise JckError("CGAN sample needs one-hot int64 labels [n,100]")
             lab = labels.to(self.device, torch.int64).contiguous()
-        lib.jck_engine_sample(self._h, zc, lab, n, out, cur_stream())
+        if out == "uint8":
+            res = torch.empty(n, self.size, self.size, 3, dtype=torch.uint8, device=self.device)
+        else:
+            res = torch.empty(n, 3, self.size, self.size, dtype=torch.float32, device=self.device)
+        if bn == "batch" and out == "float":
+            lib.jck_engine_sample(self._h, zc, lab, n, res, cur_stream())
+        else:
+            flags = SAMPLE_EVAL if bn == "running" else 0
+            for lo, hi in chunk_plan(n, self.batch):
+                lib.jck_engine_sample_ex(self._h, zc[lo:hi], None if lab is None else lab[lo:hi], hi - lo, flags,
+                                         res[lo:hi] if out == "float" else None, res[lo:hi] if out == "uint8" else None, cur_stream())
         self._keep_z = (zc, lab)
-        return out
+        return res
 
     def tensor(self, name):
         """Debug/parity view of an internal NHWC tensor as a torch tensor (copy)."""
@@ -827,6 +848,16 @@ class DcganEngine:
         f32 = name in ("prob", "ds", "norms", "acc", "rs", "prob_gp")
         dt = torch.bfloat16 if (self.prec == PREC_BF16 and not f32) else torch.float32
         return self._ws_view(p, n.value, dt).clone()
+
+
+SAMPLE_EVAL = 1            # include/jckgan.h: JCK_SAMPLE_EVAL
+
+
+def chunk_plan(n, batch):
+    """[(lo, hi)] covering range(n) in pieces of at most `batch` rows, all but the last full."""
+    if n < 0 or batch < 1:
+        raise JckError(f"chunk_plan: n >= 0 and batch >= 1, got {n}, {batch}")
+    return [(lo, min(lo + batch, n)) for lo in range(0, n, batch)]
 
 
 class CganEngine(DcganEngine):

@@ -3,7 +3,9 @@ evaluation's best-score ladder, checkpoints.  train/dcgan_trainer.py and train/c
 families (the drop-in signatures, the draws of a step, the evaluation's device part, the pictures)."""
 import operator
 import os
+import struct
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -68,6 +70,21 @@ def _make_grid(images, nrow=8, padding=2, normalize=True):
         grid[:, padding + r * (h + padding):padding + r * (h + padding) + h,
              padding + q * (w + padding):padding + q * (w + padding) + w] = x[i]
     return grid
+
+
+def _encode_png(hwc_u8):
+    """uint8 [H,W,3] (or [H,W]: grey) -> the bytes of an 8-bit PNG, with zlib and struct alone (no matplotlib, no Pillow): one
+    IDAT, filter type 0 on every row.  For the generate CLI; the trainers keep _save_png."""
+    a = np.ascontiguousarray(np.asarray(hwc_u8))
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or a.size == 0:
+        raise ValueError(f"_encode_png wants uint8 [H,W,3] or [H,W], got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), a.reshape(h, -1)], axis=1)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 2 if a.ndim == 3 else 0, 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b"")
 
 
 def _save_png(path, chw, title=None):

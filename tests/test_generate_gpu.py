@@ -1,0 +1,120 @@
+"""generate.py end to end on the device: a checkpoint written from a fresh engine, the CLI as a child process."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "jck-generation_amd")
+
+
+@pytest.fixture(scope="module")
+def ckpts(tmp_path_factory):
+    """(path without an average, path with one whose weights differ from the live ones)"""
+    from hipgan.engine import DcganEngine
+    from oracle.gan_oracle import GanOracle
+    d = tmp_path_factory.mktemp("ckpt")
+    orc = GanOracle("dcgan", lr=2e-4, seed=12345)
+    eng = DcganEngine(batch=8, prec="bf16")
+    eng.load_state(orc.g, orc.d)
+    gen = torch.Generator().manual_seed(9)
+    for _ in range(30):          # running statistics that belong to the weights (the initial (0, 1) give a flat grey image in eval mode)
+        eng.sample(torch.randn(8, 100, generator=gen))
+    g, dd = eng.state_dicts()
+    plain, both = str(d / "plain.pt"), str(d / "ema.pt")
+    torch.save({"model_g": g, "model_d": dd}, plain)
+    from hipgan.engine import CganEngine
+    co = GanOracle("cgan", lr=2e-4, seed=12345)
+    ce = CganEngine(batch=8, prec="bf16")
+    ce.load_state(co.g, co.d)
+    for _ in range(30):
+        ce.sample(torch.randn(8, 100, generator=gen), torch.nn.functional.one_hot(torch.randint(0, 100, (8,), generator=gen), 100))
+    cg, cd = ce.state_dicts()
+    torch.save({"model_g": cg, "model_d": cd}, str(d / "cgan.pt"))
+    ema = {k: (v * 0.5 if k.endswith("conv3.weight") else v.clone()) for k, v in g.items()}
+    torch.save({"model_g": g, "model_d": dd, "model_g_ema": ema}, both)
+    return plain, both
+
+
+def _generate(out, *args):
+    r = subprocess.run([sys.executable, "generate.py", "--out", str(out), *args], cwd=PKG, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    f = np.load(os.path.join(str(out), "images.npz"))
+    return {k: f[k] for k in f.files}
+
+
+BASE = ("-m", "DCGAN", "--num", "20", "-b", "8", "--seed", "3")
+
+
+@pytest.fixture(scope="module")
+def runs(ckpts, tmp_path_factory):
+    """the four child processes of this module, each run once"""
+    plain, both = ckpts
+    d = tmp_path_factory.mktemp("out")
+    before = open(both, "rb").read()
+    r = {"dir": d,
+         "plain": _generate(d / "plain", "--checkpoint", plain, *BASE),
+         "live": _generate(d / "live", "--checkpoint", both, "--which", "live", *BASE),
+         "ema": _generate(d / "ema", "--checkpoint", both, "--which", "ema", *BASE),
+         "batch": _generate(d / "batch", "--checkpoint", plain, "--bn", "batch", *BASE),
+         "cgan": _generate(d / "cgan", "--checkpoint", os.path.join(os.path.dirname(plain), "cgan.pt"), "-m", "CGAN", "--num", "5", "-b", "8",
+                           "--classes", "3,17"),
+         "ema_cal": _generate(d / "ema_cal", "--checkpoint", both, "--calibrate", "2", *BASE)}       # auto: the file has an average
+    assert open(both, "rb").read() == before, "generate.py wrote to the checkpoint"
+    return r
+
+
+def test_generate_cli(runs):
+    a = runs["plain"]
+    assert a["images"].shape == (20, 64, 64, 3) and a["images"].dtype == np.uint8
+    assert a["z"].shape == (20, 100) and a["z"].dtype == np.float32 and "labels" not in a
+    assert a["images"].std() > 1.0
+    png = open(runs["dir"] / "plain" / "grid.png", "rb").read()
+    assert png[:8] == b"\x89PNG\r\n\x1a\n" and len(png) > 1000
+    # the same seed and the same generator in another process: the same bytes (20 images = three chunks of 8)
+    b = runs["live"]
+    assert a["images"].tobytes() == b["images"].tobytes() and a["z"].tobytes() == b["z"].tobytes()
+    assert png == open(runs["dir"] / "live" / "grid.png", "rb").read()
+    # the average differs from the live generator (conv3's weights are halved in it)
+    assert runs["ema"]["images"].tobytes() != b["images"].tobytes() and runs["ema"]["z"].tobytes() == b["z"].tobytes()
+    # --calibrate moved the running statistics the images are made with
+    assert runs["ema_cal"]["images"].tobytes() != runs["ema"]["images"].tobytes()
+
+
+def test_generate_cli_train_mode_and_cgan(runs, ckpts):
+    """--bn batch cuts --num into chunks of -b images, each one train-mode BatchNorm batch: 20 images from a batch-8 engine, equal to
+    the Sampler's own chunks; -m CGAN with --classes gives --num images per class"""
+    from hipgan.sampler import Sampler, latents
+    b = runs["batch"]
+    assert b["images"].shape == (20, 64, 64, 3) and b["images"].tobytes() != runs["plain"]["images"].tobytes()
+    s = Sampler.from_checkpoint(ckpts[0], "DCGAN", batch=8)
+    z = latents(20, 3)
+    assert np.array_equal(z.numpy(), b["z"])
+    parts = [s.engine.sample(z[lo:hi], out="uint8") for lo, hi in ((0, 8), (8, 16), (16, 20))]
+    assert np.array_equal(torch.cat(parts).cpu().numpy(), b["images"])
+    c = runs["cgan"]
+    assert c["images"].shape == (10, 64, 64, 3) and c["labels"].tolist() == [3] * 5 + [17] * 5 and c["labels"].dtype == np.int64
+    assert not np.array_equal(c["images"][0], c["images"][5])
+
+
+def test_calibrate_moves_the_samplers_statistics_only(ckpts):
+    plain, both = ckpts
+    from hipgan.sampler import Sampler
+    before = open(both, "rb").read()
+    s = Sampler.from_checkpoint(both, "DCGAN", which="ema", batch=8)
+    assert s.which == "ema"
+    u0 = s.images(5, seed=1)
+    bn0, nbt0 = s.engine.arenas["g_bn"].clone(), s.engine.arenas["g_nbt"].clone()
+    s.calibrate(2, seed=0)
+    torch.cuda.synchronize()
+    assert not torch.equal(bn0, s.engine.arenas["g_bn"]) and int((s.engine.arenas["g_nbt"] - nbt0).max()) == 2
+    assert not torch.equal(u0, s.images(5, seed=1))                 # the running statistics are what bn="running" samples with
+    assert open(both, "rb").read() == before
+    saved = torch.load(both, map_location="cpu", weights_only=False)["model_g_ema"]
+    assert int(saved["norm1.num_batches_tracked"]) == int(nbt0[0])  # the file's statistics are the ones the sampler started from
+    p = s.interpolate(torch.randn(100), torch.randn(100), 4, out="float")
+    assert p.shape == (4, 3, 64, 64)
