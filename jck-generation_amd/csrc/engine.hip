@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ops_internal.hpp"
+#include "ew_optim.hpp"      // the kernels this file launches itself: pack_multi_kernel, pack_tail_kernel, pad_rows_kernel
 #define JCK_BATCHED_DEFAULT 3
 struct jck_engine;
 #define TT (e->T)        /* the engine's channel plan; `e` is the engine in every function below (this inside its members) */
@@ -489,8 +490,8 @@ extern "C" int jck_engine_bind(jck_engine* e, void* workspace, size_t ws_bytes, 
   return JCK_OK;
 }
 
-// all conv operands of one network in one launch (ew.hpp: pack_multi_kernel); the two Linear operands of CGAN's D follow
-// tail (optional): the end-of-step job rides in the same launch (ew.hpp: pack_tail_kernel)
+// all conv operands of one network in one launch (ew_optim.hpp: pack_multi_kernel); the two Linear operands of CGAN's D follow
+// tail (optional): the end-of-step job rides in the same launch (ew_optim.hpp: pack_tail_kernel)
 static int repack_convs(jck_engine* e, int net, void* stream, const TailJobs* tail = nullptr, int tail_x = 0) {
   PackJobs jobs = {};
   int n = 0, chunk = 0;
@@ -501,7 +502,7 @@ static int repack_convs(jck_engine* e, int net, void* stream, const TailJobs* ta
     chunk += (int)((total + PACK_CHUNK - 1) / PACK_CHUNK);
     ++n;
   };
-  // totals are (output channel, input channel) pairs: one thread each (ew.hpp: pack_multi_kernel)
+  // totals are (output channel, input channel) pairs: one thread each (ew_optim.hpp: pack_multi_kernel)
   auto add_down = [&](const float* w, int Cs, int Cb, void* wp) { add(0, w, wp, (long long)Cs * Cb, Cs, Cb, ilog2(jck_pad_chan(Cb))); };
   auto add_up = [&](const float* w, int Cs, int Cb, void* wp) {
     if (Cb <= 4) add(2, w, wp, (long long)Cs * Cb, Cs, Cb, 0);

@@ -1,20 +1,23 @@
-// Internal glue shared by ops.hip and engine.hip.
+// Host glue shared by the launcher units (ops.hip, ops_gemm.hip) and engine.hip: error and launch macros, the kernel registry, the knobs and the
+// prototypes of the functions that cross a unit.  No kernels: each unit includes the kernel headers it launches from.
 #pragma once
+#include <hip/hip_ext.h>
+
 #include <algorithm>
 #include <cmath>
 #include <string>
 
 #include "../../include/jckgan.h"
 #include "common.hpp"
-#include "ew.hpp"
-#include "igemm.hpp"
-#include "wgrad.hpp"
 
 void jck_set_error(const std::string& s);
 
 // fp32 storage (HBM tensors, packed weights) and the f32 path's kernel choices: JCK_PREC_F32 and JCK_PREC_BF16X3, which differ
 // only in the MFMA core of the register-staged GEMM kernels
 static inline bool prec_f32_storage(int prec) { return prec == JCK_PREC_F32 || prec == JCK_PREC_BF16X3; }
+static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// workgroups of a grid-stride elementwise launch
+static inline unsigned ew_grid(long long n, int per_block = 256) { return (unsigned)std::max<long long>(1, std::min<long long>((n + per_block - 1) / per_block, 8192)); }
 
 #define JCK_FAIL(code, msg)                                   \
   do {                                                        \
@@ -37,7 +40,79 @@ static inline bool prec_f32_storage(int prec) { return prec == JCK_PREC_F32 || p
     if (rc_ != JCK_OK) return rc_; \
   } while (0)
 
-int launch_igemm(int prec, const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st, int* slots);
+// launch whose completion hands a tensor to another stream: `ev` (may be null) is completed by the dispatch packet itself
+// (hipExtLaunchKernel's stop event) - what a hipEventRecord behind the launch would do with a marker packet of its own, which
+// costs the launch stream ~6-7 us of idle time per record on this runtime.  Every kernel argument must be passed explicitly
+// (the extended launch checks the count).
+#define LAUNCH_EV(kernel, grid, block, shmem, stream, ev, ...)                                                      \
+  do {                                                                                                              \
+    if (ev) hipExtLaunchKernelGGL(kernel, grid, block, shmem, stream, (hipEvent_t) nullptr, (hipEvent_t)(ev), 0u, __VA_ARGS__); \
+    else hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                                       \
+  } while (0)
+#define DISPATCH_T(prec, CALL)                                  \
+  do {                                                          \
+    if ((prec) == JCK_PREC_BF16) { typedef bf16_t T; CALL; }    \
+    else if (prec_f32_storage(prec)) { typedef float T; CALL; } \
+    else JCK_FAIL(JCK_E_ARG, "bad prec");                       \
+  } while (0)
+
+// ---------------------------------------------------------------------------------------------------------
+// kernel registry: one id per kernel the library reports on.  KERNELS[id] (ops.hip) holds the id's launch name - what
+// jck_last_launch says after a call and jck_launch_name enumerates, one name per kernel; tests assert that a case still lands on the
+// kernel it was written for - and its profiler label - what jck_prof_collect hands to bench.py, which merges the persistent and the
+// non-persistent forms of a tile.  A read-only report: it selects nothing.  Launch sites name an id or compute one from their
+// template parameters with the kid_* functions below; a new kernel is one entry of the table and one launch site.
+// ---------------------------------------------------------------------------------------------------------
+enum KernelId : int {
+  K_PRECS = 3,                                    // bf16, f32, bf16x3
+  K_IGEMM_TILES = 5,                              // 128x128, 128x64, 64x128 img, 64x128, 16x256
+  K_DMA_TILES = 4,                                // 128x256, 128x128, 128x64, 64x128
+  K_WGRAD_TILES = 4,                              // 128x128, 128x64, 64x64 img, 64x64
+  K_IGEMM = 0,                                    // + K_IGEMM_TILES * precision + tile     (kid_igemm)
+  K_IGEMM_PERSIST = K_IGEMM + K_PRECS * K_IGEMM_TILES,      // + tile                       (kid_igemm_dma)
+  K_IGEMM_DMA = K_IGEMM_PERSIST + K_DMA_TILES,              // + tile                       (kid_igemm_dma)
+  K_IMG_DOWN = K_IGEMM_DMA + K_DMA_TILES, K_IMG_UP,
+  K_WGRAD_DMA_WS, K_WGRAD_DMA,
+  K_WGRAD,                                        // + K_WGRAD_TILES * precision + tile     (kid_wgrad)
+  K_BN_ACT_FWD = K_WGRAD + K_PRECS * K_WGRAD_TILES, K_BN_BWD_RES, K_BN_BWD_3L,      // profiler labels without a launch name
+  K_COUNT
+};
+template <class P> constexpr int kid_prec() { return P::SPLIT ? 2 : P::IS_F32 ? 1 : 0; }
+// register-staged gather-GEMM (AFFINE instantiations report the id of their tile: it says which kernel form and tile ran, not which
+// of the epilogue's options - statistics, bias, tanh, the inference affine - it applied)
+template <class P, int BCH, int BPIX, int NSUB> constexpr KernelId kid_igemm() {
+  static_assert(P::IS_F32 || !(BCH == 64 && NSUB == 1), "bf16 has no register-staged 64 x 128 tile (and no name for one)");
+  return KernelId(K_IGEMM + K_IGEMM_TILES * kid_prec<P>() + (BCH == 128 ? (BPIX == 128 ? 0 : 1) : BCH == 64 ? (NSUB == 2 ? 2 : 3) : 4));
+}
+// LDS-DMA gather-GEMM: family = K_IGEMM_PERSIST or K_IGEMM_DMA
+constexpr KernelId kid_igemm_dma(KernelId family, int BCH, int BPIX) { return KernelId(family + (BPIX == 256 ? 0 : BCH == 64 ? 3 : BPIX == 128 ? 1 : 2)); }
+template <class P, int BG, int BS, int NSUB> constexpr KernelId kid_wgrad() {
+  return KernelId(K_WGRAD + K_WGRAD_TILES * kid_prec<P>() + (BG == 128 ? (BS == 128 ? 0 : 1) : NSUB == 2 ? 2 : 3));
+}
+// records the id's launch name as the calling thread's last launch
+void note_launch(KernelId k);
+
+// optional per-launch timing with HIP events on the launch stream (bench.py's roofline leg; jck_prof_enable).  Off by default:
+// zero cost in the timed region.  A launch is priced in algorithmic FLOPs (MFMA kernels) or algorithmic bytes (the streaming
+// BatchNorm kernels: bytes > 0).
+extern bool g_prof_on;
+struct ProfRec { KernelId kernel; double flops, bytes; hipStream_t st; hipEvent_t e0, e1; };
+struct ProfScope {
+  ProfScope(KernelId k, double flops, hipStream_t st, double bytes = 0.0) : on(g_prof_on) { if (on) begin(k, flops, st, bytes); }
+  ~ProfScope() { if (on) end(); }
+ private:
+  void begin(KernelId k, double flops, hipStream_t st, double bytes);
+  void end();
+  bool on; ProfRec r;
+};
+bool jck_prof_is_on();
+
+// kernel-selection knobs (ops.hip: defaults, JCK_<KEY> presets, jck_tune)
+extern int g_igemm_dma_ksplit, g_bn_bwd_fuse, g_bn_res, g_wgrad_wgs, g_wgrad_ws, g_wgrad_dma;
+
+// ---------------------------------------------------------------------------------------------------------
+// functions that cross a unit
+// ---------------------------------------------------------------------------------------------------------
 // Adam with {step_size, bc2_sqrt} in device memory (ops.hip): the engine's step has no per-step kernel argument
 // ema_w: the generator EMA's weight of this step, written to hp[2] (0: no EMA configured)
 int jck_adam_set_step(float* hp, double lr, double beta1, double beta2, int step, unsigned long long seed, float ema_w, hipStream_t st,
@@ -50,7 +125,6 @@ int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, doubl
                 const unsigned* skip_if = nullptr,       // skip_if: device word; non-zero = leave p, m, v untouched (a grid barrier of the step timed out)
                 float* ema = nullptr);                   // ema: moving average of p, advanced in the same launch with the weight in hp[2]
 const unsigned* jck_grid_sync_error_word(const void* sync_ws);
-bool jck_prof_is_on();
 // BatchNorm finalize + apply as one launch where the statistics rows are few (ops.hip); *fused = false: nothing was launched
 int bn_fwd_fused(int prec, const void* y, const float* stats, int slots_per_group, float count, const float* gamma, const float* beta,
                  float eps, float slope, void* a, float* aux, float* stat_out, float* running_mean, float* running_var, int64_t* nbt,

@@ -1,4 +1,4 @@
-"""Exponential moving average of the generator's weights: fused into Adam(G)'s launch (csrc/ew.hpp adam_kernel<true>), sampled
+"""Exponential moving average of the generator's weights: fused into Adam(G)'s launch (csrc/ew_optim.hpp adam_kernel<true>), sampled
 through an engine bound to the average, checkpointed by the trainers.  The reference has no average and neither has the
 oracle, so every numeric case carries the recurrence itself, in float64:
 
