@@ -92,6 +92,24 @@ int jck_conv_up_affine(int prec, const void* small_in, const void* w, const floa
                        int N, int Hs, int Ws, int Cs, int Cb, void* stream);
 int jck_g1_fwd_affine(int prec, const void* z, const void* w, const float* scale, const float* shift, void* out, int B,
                       int CiPad, int Co, void* stream);
+/* Latent projection, per op.  jck_conv_down_mask: jck_conv_down (a ConvTranspose's input gradient) through a folded eval-mode stage
+ * a = relu(scale[c] * y + shift[c]) in front of it: out = a_small[m, c] > 0 ? scale[c] * acc : +0 on the fp32 accumulators, ONE rounding
+ * to the storage type; a NaN activation masks (torch.relu's backward).  a_small has small_out's layout [N, Hb/2, Wb/2, Cs]; scale:
+ * device float[Cs], 16-byte aligned; Cs a power of two; Cb 3 / 4, 8..32 (with Cs = 64) or >= 64.  Never the persistent kernels or the
+ * image-side streaming kernel: every launch ends in the gather-GEMM's shared epilogue. */
+int jck_conv_down_mask(int prec, const void* big, const void* w, const void* a_small, const float* scale, void* small_out,
+                       int N, int Hb, int Wb, int Cb, int Cs, void* stream);
+/* loss_out[b] = mean over the 3 * HW real elements of (x_b - t_b)^2 with x the stored tanh output (NHWC4, element type of prec) and t
+ * the caller's NCHW fp32 target, read in place; g_raw_out (NHWC4, same type) = 2 (x - t) / (3 HW) * (1 - x^2), padding channel +0.
+ * One launch, one workgroup per image, a fixed-order reduction: equal bits on every run and for every N. */
+int jck_latent_loss(int prec, const void* x_nhwc4, const float* target_nchw_f32, void* g_raw_out, float* loss_out, int N, int HW,
+                    void* stream);
+/* g = slab[0] + slab[1] + ... (Z fp32 split-K slabs [Z][N][ld] of the dz product, summed in order) + 2 * prior * z / 100, then update
+ * number t >= 1 of torch.optim.Adam(lr, betas = (0.9, 0.999), eps = 1e-8) on z, m, v (fp32 [N][100]); z is also written, in the element
+ * type of prec, to the first 100 columns of the operand rows z_operand [N][CiPad] (the columns behind them are left alone).
+ * t = 0: sum only - z receives the summed slabs; m, v and z_operand are not touched and may be NULL. */
+int jck_latent_adam(int prec, const float* slab, int Z, int ld, float* z, float* m, float* v, float lr, float prior, int t,
+                    void* z_operand, int CiPad, int N, void* stream);
 size_t jck_g1_wgrad_ws_bytes(int B, int CiPad, int Co);
 int jck_g1_wgrad(int prec, const void* z, const void* dy, float* ws, size_t ws_bytes, float* grad, int accumulate, int B,
                  int Ci, int CiPad, int Co, void* stream);
@@ -411,6 +429,20 @@ int jck_engine_sample(jck_engine*, const float* z, const int64_t* labels /* fami
 #define JCK_SAMPLE_EVAL 1u   /* BatchNorm with the running statistics; no buffer moves */
 int jck_engine_sample_ex(jck_engine*, const float* z, const int64_t* labels, int n, unsigned flags, float* out_nchw /* or NULL */,
                          unsigned char* out_u8_nhwc /* or NULL */, void* stream);
+/* Latent projection through the frozen generator under model.eval(): for image b, L_b = mean((G(z_b) - t_b)^2) over the 3 S^2
+ * real elements, target_nchw fp32 [n,3,S,S] in [-1, 1] on the device (read in place, never rounded), labels fixed (family 1).
+ * latent_grad: loss [n] and dz = dL/dz [n,100].  project: `steps` updates of torch.optim.Adam(lr, (0.9, 0.999), 1e-8) on z [n,100]
+ * (in, out) minimising L_b + prior * mean_k(z_bk^2), all on the stream without a host synchronisation; m, v [n,100] are the
+ * caller's Adam state (zeros and t0 = 0 to begin, the returned state and the updates done so far to continue), loss_hist[s][n]
+ * (or NULL) is L before update s.  1 <= n <= batch; row b of every output is bit for bit what a call with that row alone returns.
+ * Neither the running statistics nor num_batches_tracked nor any parameter is written.  On a training engine both may be called
+ * between two steps: they use buffers that every step rewrites before it reads them, and memory of their own that the first call
+ * allocates (so: not inside a graph capture) and jck_engine_destroy frees. */
+int jck_engine_latent_grad(jck_engine*, const float* z, const int64_t* labels, const float* target_nchw, int n,
+                           float* loss /* [n] */, float* dz /* [n,100] */, void* stream);
+int jck_engine_project(jck_engine*, float* z /* in, out */, const int64_t* labels, const float* target_nchw, int n,
+                       int steps, float lr, float prior, float* m, float* v /* [n,100], caller-owned */, int t0,
+                       float* loss_hist /* [steps][n] or NULL */, void* stream);
 /* debug / parity access to internal NHWC tensors: name in {"fake","real_noisy",...}; returns device ptr or NULL */
 const void* jck_engine_tensor(const jck_engine*, const char* name, long long* numel);
 

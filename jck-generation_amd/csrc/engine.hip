@@ -237,6 +237,9 @@ struct jck_engine {
   void *d_v[JCK_MAX_STAGES], *d_xdir[JCK_MAX_STAGES], *d_u0;
   float* bn2_ws[JCK_MAX_STAGES]; float* bn2_ws_rev;
   const int64_t* cur_labels = nullptr;
+  // latent projection (jck_engine_latent_grad / jck_engine_project): memory of its own, allocated by the first such call and freed
+  // with the engine - G.conv1's weight as the dz product's operand [128][16 * G_C1], that product's split-K slabs, a loss row (one allocation)
+  void* lat_w = nullptr; float *lat_slab = nullptr, *lat_loss = nullptr;
 
   void carve(unsigned char* base) {
     jck_engine* e = this;
@@ -437,6 +440,7 @@ extern "C" int jck_engine_create_ex(jck_engine** out, int family, int prec, int 
 extern "C" void jck_engine_destroy(jck_engine* e) {
   if (!e) return;
   if (e->overlap) destroy_side_streams(e, true);
+  if (e->lat_w) (void)hipFree(e->lat_w);
   delete e;
 }
 extern "C" int jck_engine_num_tensors(int family, int net) { return (int)make_layout(family, net).t.size(); }
@@ -949,6 +953,35 @@ static void launch_pad_rows(const float* z, int B, int zd, int zp, void* out, hi
   hipLaunchKernelGGL(pad_rows_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, B, zd, zp, (T*)out);
 }
 
+// The eval-mode generator in two pieces (g_forward(eval) runs both; a latent projection folds once and runs the products per iteration).
+// Fold: one launch writes every layer's scale / shift (gamma, beta and the running statistics) into the stage's aux table ...
+static int g_eval_fold(jck_engine* e, hipStream_t st) {
+  const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
+  float* aux[JCK_MAX_STAGES];
+  int Cs[JCK_MAX_STAGES];
+  for (int i = 0; i < TT.NS; ++i) {
+    gamma[i] = e->P(e->LG, e->gp, NWN[i]); beta[i] = e->P(e->LG, e->gp, NBN[i]);
+    rm[i] = e->gbn + find(e->LG, RMN[i])->offset; rv[i] = e->gbn + find(e->LG, RVN[i])->offset;
+    aux[i] = e->g_bn[i].aux; Cs[i] = TT.G_C1 >> i;
+  }
+  return jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st);
+}
+// ... and the products apply them and the ReLU in their epilogues: g_z -> g_a[0..NS-1] -> fake_raw
+static int g_eval_products(jck_engine* e, int B, hipStream_t st) {
+  const int zp = z_pad(e->family);
+  auto scale = [&](int i) { return e->g_bn[i].aux; };
+  auto shift = [&](int i) { return e->g_bn[i].aux + (TT.G_C1 >> i); };
+  JCK_TRY(jck_g1_fwd_affine(e->prec, e->g_z, e->g1_w, scale(0), shift(0), e->g_a[0], B, zp, TT.G_C1, st));
+  for (int i = 0; i < TT.NS; ++i) {
+    const int h = 4 << i;
+    if (i < TT.NS - 1)
+      JCK_TRY(jck_conv_up_affine(e->prec, e->g_a[i], e->g_up[i], scale(i + 1), shift(i + 1), e->g_a[i + 1], B, h, h, TT.G_CS[i], TT.G_CB[i], st));
+    else
+      JCK_TRY(jck_conv_up(e->prec, e->g_a[i], e->g_up[i], e->fake_raw, nullptr, nullptr, 1, B, h, h, TT.G_CS[i], TT.G_CB[i], st));
+  }
+  return JCK_OK;
+}
+
 // eval: BatchNorm with the RUNNING statistics (model.eval()): one launch folds every layer's gamma, beta and running statistics into
 // scale / shift (the stage's aux table, which every train-mode forward rewrites before its backward reads it), and each product
 // applies them and the ReLU in its epilogue - one launch and one activation store per stage, images independent of each other,
@@ -964,24 +997,8 @@ static int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B
     HIPCHK(hipGetLastError());
   }
   if (eval) {
-    const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
-    float* aux[JCK_MAX_STAGES];
-    int Cs[JCK_MAX_STAGES];
-    for (int i = 0; i < TT.NS; ++i) {
-      gamma[i] = e->P(e->LG, e->gp, NWN[i]); beta[i] = e->P(e->LG, e->gp, NBN[i]);
-      rm[i] = e->gbn + find(e->LG, RMN[i])->offset; rv[i] = e->gbn + find(e->LG, RVN[i])->offset;
-      aux[i] = e->g_bn[i].aux; Cs[i] = TT.G_C1 >> i;
-    }
-    JCK_TRY(jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st));
-    JCK_TRY(jck_g1_fwd_affine(e->prec, e->g_z, e->g1_w, aux[0], aux[0] + Cs[0], e->g_a[0], B, zp, TT.G_C1, st));
-    for (int i = 0; i < TT.NS; ++i) {
-      const int h = 4 << i;
-      if (i < TT.NS - 1)
-        JCK_TRY(jck_conv_up_affine(e->prec, e->g_a[i], e->g_up[i], aux[i + 1], aux[i + 1] + Cs[i + 1], e->g_a[i + 1], B, h, h, TT.G_CS[i], TT.G_CB[i], st));
-      else
-        JCK_TRY(jck_conv_up(e->prec, e->g_a[i], e->g_up[i], e->fake_raw, nullptr, nullptr, 1, B, h, h, TT.G_CS[i], TT.G_CB[i], st));
-    }
-    return JCK_OK;
+    JCK_TRY(g_eval_fold(e, st));
+    return g_eval_products(e, B, st);
   }
   JCK_TRY(jck_g1_fwd(e->prec, e->g_z, e->g1_w, e->g_y[0], e->g_bn[0].stats, &e->g_bn[0].slots, B, zp, TT.G_C1, st));
   for (int i = 0; i < TT.NS; ++i) {
@@ -1657,6 +1674,77 @@ extern "C" int jck_engine_sample_ex(jck_engine* e, const float* z, const int64_t
   JCK_TRY(g_forward(e, z, labels, n, st, false, (flags & JCK_SAMPLE_EVAL) != 0));
   if (out_nchw) JCK_TRY(jck_nhwc4_to_nchw(e->prec, e->fake_raw, out_nchw, n, TT.HW, st));
   if (out_u8_nhwc) JCK_TRY(jck_img_to_u8(e->prec, e->fake_raw, out_u8_nhwc, n, TT.HW, st));
+  return JCK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// latent projection: dL/dz through the frozen generator under model.eval(), L_b = mean((G(z_b) - t_b)^2), and Adam on z.
+// Beside the step: it uses only buffers that every step rewrites before reading (g_z, g_a, g_gr, g_raw, fake_raw, the stages' aux) -
+// never real_noisy or D's activations, which a prefetched D(real) forward may own - and memory of its own.  Image b's numbers do not
+// depend on n: no statistic, a per-image loss reduction, a split-K factor that is a constant.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int LAT_KSPLIT = 16, LAT_LD = 128;          // 16 * G_C1 / 64 = 128 (64 x 64) or 256 (128 x 128) k-steps: 8 or 16 per slab
+static int latent_check(jck_engine* e, const float* z, const int64_t* labels, const float* target, int n, const char* who) {
+  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, std::string(who) + ": engine not bound");
+  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, std::string(who) + ": n must be in [1, batch]");
+  if (!z || !target) JCK_FAIL(JCK_E_ARG, std::string(who) + ": null z / target");
+  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, std::string(who) + ": CGAN generator needs labels");
+  if (e->capturing) JCK_FAIL(JCK_E_ARG, std::string(who) + ": not inside a graph capture");
+  return JCK_OK;
+}
+// operand rows from z (and the labels), the BatchNorm fold and the pack of G.conv1's weight for the dz product: once per call
+static int latent_begin(jck_engine* e, const float* z, const int64_t* labels, int n, hipStream_t st) {
+  const int K = 16 * TT.G_C1, zp = z_pad(e->family);
+  if (!e->lat_w) {
+    const size_t wb = (size_t)LAT_LD * K * e->esz, sb = (size_t)LAT_KSPLIT * e->B * LAT_LD * sizeof(float);      // both multiples of 256
+    HIPCHK(hipMalloc(&e->lat_w, wb + sb + (size_t)e->B * sizeof(float)));
+    e->lat_slab = reinterpret_cast<float*>((unsigned char*)e->lat_w + wb);
+    e->lat_loss = reinterpret_cast<float*>((unsigned char*)e->lat_w + wb + sb);
+  }
+  if (e->family == 1) JCK_TRY(jck_cgan_z(e->prec, z, labels, n, 100, N_CLASS, zp, e->g_z, st));
+  else {
+    e->ss.gz_step = -1;                        // the operand rows now hold somebody else's z
+    if (e->prec == JCK_PREC_BF16) launch_pad_rows<bf16_t>(z, n, 100, zp, e->g_z, st); else launch_pad_rows<float>(z, n, 100, zp, e->g_z, st);
+    HIPCHK(hipGetLastError());
+  }
+  JCK_TRY(g_eval_fold(e, st));
+  // conv1.weight [z_dim][G_C1][4][4]: its first 100 rows as a Linear weight [100][G_C1 * 16] whose columns go from (c, pos) to (pos, c)
+  return jck_pack_linear(e->prec, e->P(e->LG, e->gp, CWN[0]), 100, K, LAT_LD, K, 0, TT.G_C1, 16, e->lat_w, st);
+}
+// one evaluation: the eval forward's products, the loss and its gradient, the masked dgrads, the dz product's slabs
+static int latent_eval(jck_engine* e, const float* target, int n, float* loss, hipStream_t st) {
+  JCK_TRY(g_eval_products(e, n, st));
+  JCK_TRY(jck_latent_loss(e->prec, e->fake_raw, target, e->g_raw, loss, n, TT.HW, st));
+  const void* gbig = e->g_raw;
+  for (int i = TT.NS - 1; i >= 0; --i) {       // through conv(i+2) and the folded stage in front of it
+    const int hs = TT.G_HS[i];
+    JCK_TRY(jck_conv_down_mask(e->prec, gbig, e->g_down[i], e->g_a[i], e->g_bn[i].aux, e->g_gr[i], n, 2 * hs, 2 * hs, TT.G_CB[i], TT.G_CS[i], st));
+    gbig = e->g_gr[i];
+  }
+  return jck_linear_fwd(e->prec, e->g_gr[0], e->lat_w, nullptr, e->lat_slab, n, 16 * TT.G_C1, 100, LAT_LD, LAT_KSPLIT, st);
+}
+extern "C" int jck_engine_latent_grad(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, int n, float* loss,
+                                      float* dz, void* stream) {
+  JCK_TRY(latent_check(e, z, labels, target_nchw, n, "latent_grad"));
+  if (!loss || !dz) JCK_FAIL(JCK_E_ARG, "latent_grad: null loss / dz");
+  hipStream_t st = (hipStream_t)stream;
+  JCK_TRY(latent_begin(e, z, labels, n, st));
+  JCK_TRY(latent_eval(e, target_nchw, n, loss, st));
+  return jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, dz, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, n, st);
+}
+// `steps` Adam updates of z [n][100] (in, out) towards target_nchw on the stream, no host synchronisation: m, v [n][100] are the
+// caller's (zero them for a fresh run), t0 the number of updates they have seen; loss_hist[s][n] (or null) is the loss BEFORE update s.
+extern "C" int jck_engine_project(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
+                                  float prior, float* m, float* v, int t0, float* loss_hist, void* stream) {
+  JCK_TRY(latent_check(e, z, labels, target_nchw, n, "project"));
+  if (steps < 1 || t0 < 0 || !m || !v) JCK_FAIL(JCK_E_ARG, "project: steps >= 1, t0 >= 0 and the Adam state m, v are required");
+  if (!(lr > 0.f) || !(prior >= 0.f)) JCK_FAIL(JCK_E_ARG, "project: lr > 0 and prior >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  JCK_TRY(latent_begin(e, z, labels, n, st));
+  for (int s = 0; s < steps; ++s) {
+    JCK_TRY(latent_eval(e, target_nchw, n, loss_hist ? loss_hist + (size_t)s * n : e->lat_loss, st));
+    JCK_TRY(jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, z, m, v, lr, prior, t0 + s + 1, e->g_z, z_pad(e->family), n, st));
+  }
   return JCK_OK;
 }
 

@@ -5,6 +5,7 @@
 #include "ew.hpp"
 #include "ew_optim.hpp"
 #include "bnres.hpp"
+#include "latent.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -40,7 +41,8 @@ static constexpr KernelInfo KERNELS[] = {
     SAME("wgrad<bf16,128,128>"),   SAME("wgrad<bf16,128,64>"),   SAME("wgrad<bf16,64,64,img>"),   SAME("wgrad<bf16,64,64>"),
     SAME("wgrad<f32,128,128>"),    SAME("wgrad<f32,128,64>"),    SAME("wgrad<f32,64,64,img>"),    SAME("wgrad<f32,64,64>"),
     SAME("wgrad<bf16x3,128,128>"), SAME("wgrad<bf16x3,128,64>"), SAME("wgrad<bf16x3,64,64,img>"), SAME("wgrad<bf16x3,64,64>"),
-    {nullptr, "bn_act_fwd"}, {nullptr, "bn_bwd_resident"}, {nullptr, "bn_bwd_3launch"}};
+    {nullptr, "bn_act_fwd"}, {nullptr, "bn_bwd_resident"}, {nullptr, "bn_bwd_3launch"},
+    {nullptr, "latent_loss"}, {nullptr, "latent_adam"}};
 #undef SAME
 static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "KERNELS and the KernelId offsets disagree");
 // the id arithmetic against the table, row by row: what every launch site's id resolves to (the affine 16 x 256 form with 8..32 gathered
@@ -56,11 +58,12 @@ static_assert(row(kid_igemm<PrecBf16, 128, 128, 1>(), "igemm<bf16,128,128>", "ig
               row(kid_wgrad<PrecBf16, 128, 128, 1>(), "wgrad<bf16,128,128>", "wgrad<bf16,128,128>") && row(kid_wgrad<PrecBf16, 128, 64, 1>(), "wgrad<bf16,128,64>", "wgrad<bf16,128,64>") && row(kid_wgrad<PrecBf16, 64, 64, 2>(), "wgrad<bf16,64,64,img>", "wgrad<bf16,64,64,img>") && row(kid_wgrad<PrecBf16, 64, 64, 1>(), "wgrad<bf16,64,64>", "wgrad<bf16,64,64>") &&
               row(kid_wgrad<PrecF32, 128, 128, 1>(), "wgrad<f32,128,128>", "wgrad<f32,128,128>") && row(kid_wgrad<PrecF32, 128, 64, 1>(), "wgrad<f32,128,64>", "wgrad<f32,128,64>") && row(kid_wgrad<PrecF32, 64, 64, 2>(), "wgrad<f32,64,64,img>", "wgrad<f32,64,64,img>") && row(kid_wgrad<PrecF32, 64, 64, 1>(), "wgrad<f32,64,64>", "wgrad<f32,64,64>") &&
               row(kid_wgrad<PrecBf16x3, 128, 128, 1>(), "wgrad<bf16x3,128,128>", "wgrad<bf16x3,128,128>") && row(kid_wgrad<PrecBf16x3, 128, 64, 1>(), "wgrad<bf16x3,128,64>", "wgrad<bf16x3,128,64>") && row(kid_wgrad<PrecBf16x3, 64, 64, 2>(), "wgrad<bf16x3,64,64,img>", "wgrad<bf16x3,64,64,img>") && row(kid_wgrad<PrecBf16x3, 64, 64, 1>(), "wgrad<bf16x3,64,64>", "wgrad<bf16x3,64,64>") &&
+              same_str(KERNELS[K_LATENT_LOSS].label, "latent_loss") && same_str(KERNELS[K_LATENT_ADAM].label, "latent_adam") &&
               same_str(KERNELS[K_BN_ACT_FWD].label, "bn_act_fwd") && same_str(KERNELS[K_BN_BWD_RES].label, "bn_bwd_resident") && same_str(KERNELS[K_BN_BWD_3L].label, "bn_bwd_3launch") &&
               kid_igemm<PrecBf16, 16, 256, 0>() == kid_igemm<PrecBf16, 16, 256, 1>() && !KERNELS[K_IGEMM + 3].launch,
               "KERNELS and the kid_* functions disagree");
 static thread_local const char* g_last_launch = "";
-void note_launch(KernelId k) { g_last_launch = KERNELS[k].launch; }
+void note_launch(KernelId k) { g_last_launch = KERNELS[k].launch ? KERNELS[k].launch : ""; }      // (a tile without a name: bf16's register-staged 64 x 128)
 extern "C" const char* jck_last_launch(void) { return g_last_launch; }
 extern "C" const char* jck_launch_name(int i) {       // the i-th launch name, in the order of the ids
   for (int k = 0; k < K_COUNT; ++k)
@@ -721,6 +724,40 @@ int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, doubl
   else
     hipLaunchKernelGGL(adam_kernel<false>, dim3(ew_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, st, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps, 0.f, 1.f, grad_scale, hp, vec, zero, zero ? nzero / 4 : 0, skip_if);
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// latent projection (latent.hpp)
+// ---------------------------------------------------------------------------------------------------------
+// loss_out[b] = mean((x_b - t_b)^2) over the 3 * HW real elements; g_raw_out = its gradient at the pre-tanh product (NHWC4, element
+// type of prec, padding channel 0).  The target is the caller's NCHW fp32 tensor, read in place.
+extern "C" int jck_latent_loss(int prec, const void* x_nhwc4, const float* target_nchw_f32, void* g_raw_out, float* loss_out, int N,
+                               int HW, void* stream) {
+  if (!x_nhwc4 || !target_nchw_f32 || !g_raw_out || !loss_out || N < 1 || HW < 1) JCK_FAIL(JCK_E_ARG, "latent_loss: bad arguments");
+  if ((((uintptr_t)x_nhwc4 | (uintptr_t)g_raw_out) & 15) != 0) JCK_FAIL(JCK_E_ARG, "latent_loss: the image tensors must be 16-byte aligned");
+  ProfScope prof(K_LATENT_LOSS, 0.0, (hipStream_t)stream, (double)N * HW * (12.0 + 8.0 * (prec_f32_storage(prec) ? 4 : 2)));
+  DISPATCH_T(prec, hipLaunchKernelGGL(latent_loss_kernel<T>, dim3(N), dim3(256), 0, (hipStream_t)stream, (const T*)x_nhwc4, target_nchw_f32,
+                                      (T*)g_raw_out, loss_out, HW));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// Sums the Z split-K slabs [Z][N][ld] of the dz product in order, adds the prior's gradient 2 * prior * z / 100 and applies
+// torch.optim.Adam(betas = (0.9, 0.999), eps = 1e-8) update number t >= 1 to z, m, v [N][100]; z also goes, in the element type, to
+// the first 100 columns of the operand rows z_operand [N][CiPad].  t = 0: sum only - z receives the summed gradient, m, v and
+// z_operand are not touched (and may be null).
+extern "C" int jck_latent_adam(int prec, const float* slab, int Z, int ld, float* z, float* m, float* v, float lr, float prior, int t,
+                               void* z_operand, int CiPad, int N, void* stream) {
+  const int zd = 100;
+  if (!slab || !z || Z < 1 || ld < zd || N < 1 || t < 0) JCK_FAIL(JCK_E_ARG, "latent_adam: bad arguments");
+  if (t > 0 && (!m || !v || !z_operand || CiPad < zd)) JCK_FAIL(JCK_E_ARG, "latent_adam: an update needs m, v and the operand rows");
+  const double bc1 = 1.0 - std::pow(0.9, (double)t), bc2 = 1.0 - std::pow(0.999, (double)t);
+  const double step_size = t > 0 ? (double)lr / bc1 : 0.0, bc2_sqrt = t > 0 ? std::sqrt(bc2) : 1.0;
+  ProfScope prof(K_LATENT_ADAM, 0.0, (hipStream_t)stream, (double)N * zd * 4.0 * (Z + 6));
+  DISPATCH_T(prec, hipLaunchKernelGGL(latent_adam_kernel<T>, dim3((unsigned)((N * zd + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slab, Z,
+                                      (long long)N * ld, ld, z, m, v, step_size, bc2_sqrt, 2.0 * (double)prior / zd, (T*)z_operand, CiPad, zd,
+                                      N, t == 0 ? 1 : 0));
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }

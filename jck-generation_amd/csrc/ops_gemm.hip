@@ -43,7 +43,7 @@ static void igemm_tile_stats(IgemmParams& q, const dim3& grid, int BCH, int rows
   if (slots) *slots = (int)(grid.x * grid.z * (grid.y / q.ytiles_per_cset) * rows_per_tile);
 }
 
-template <class P, int BCH, int BPIX, int NSUB, bool AFFINE = false>
+template <class P, int BCH, int BPIX, int NSUB, bool AFFINE = false, bool MASK = false>
 static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   typedef IgemmCfg<P, BCH, BPIX> C;
   constexpr KernelId id = kid_igemm<P, BCH, BPIX, NSUB>();
@@ -55,10 +55,10 @@ static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStre
     if (q.cstat % BCH != 0 && BCH % q.cstat != 0) JCK_FAIL(JCK_E_ARG, "igemm: stats channel count incompatible with the tile");
     igemm_tile_stats(q, grid, BCH, C::WPIX, slots);
   }
-  return launch_lds<igemm_kernel<P, BCH, BPIX, NSUB, 2, AFFINE>>(dim3(grid.x * grid.y * grid.z), dim3(256), C::LDS_BYTES, st, q);
+  return launch_lds<igemm_kernel<P, BCH, BPIX, NSUB, 2, AFFINE, MASK>>(dim3(grid.x * grid.y * grid.z), dim3(256), C::LDS_BYTES, st, q);
 }
 
-template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false>
+template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false, bool MASK = false>
 static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   constexpr int LDSB = NSTG * (BCH + BPIX) * IG_BK * 2;
   ProfScope prof(kid_igemm_dma(K_IGEMM_DMA, BCH, BPIX), p.flops, st);
@@ -66,7 +66,7 @@ static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipSt
   IgemmParams q;
   const dim3 grid = igemm_grid(p, nch_pad, phases, BCH, BPIX, q);
   if (q.stats) igemm_tile_stats(q, grid, BCH, IgemmCfg<PrecBf16, BCH, BPIX, NCW>::WPIX, slots);
-  return launch_lds<igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW, AFFINE>>(dim3(grid.x * grid.y * grid.z), dim3(WS ? (NCW + 4) * 64 : 256), LDSB, st, q);
+  return launch_lds<igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW, AFFINE, MASK>>(dim3(grid.x * grid.y * grid.z), dim3(WS ? (NCW + 4) * 64 : 256), LDSB, st, q);
 }
 
 // persistent wave-specialised form: at most `cap` workgroups (what the chip holds at this tile's LDS footprint) walk the tiles
@@ -185,6 +185,37 @@ static int launch_igemm_affine_p(const IgemmParams& p, int nch_pad, int phases, 
   JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
 }
 
+// Masked dgrad launches (p.mask_act set: jck_conv_down_mask): the same kernels in the epilogue's MASK instantiation, tile choice as
+// launch_igemm_affine_p's.  nsub 2: the image-side layer (4 gathered channels) on the register-staged 64 x 128 tile in every precision.
+template <class P>
+static int launch_igemm_mask_p(const IgemmParams& p, int nch_pad, int nsub, hipStream_t st) {
+  if (nsub == 2) {
+    if (nch_pad != 64) JCK_FAIL(JCK_E_ARG, "igemm: a 4-channel gather is built for 64 output rows");
+    return launch_igemm_t<P, 64, 128, 2, false, true>(p, nch_pad, 1, st, nullptr);
+  }
+  if (nsub == 0) {                                                     // 8..32 gathered channels: small generators
+    if (nch_pad == 64) return launch_igemm_t<P, 64, 128, 0, false, true>(p, nch_pad, 1, st, nullptr);
+    JCK_FAIL(JCK_E_ARG, "igemm: 8..32 gathered channels are built for 64 output rows");
+  }
+  if (nch_pad % 128 == 0) {
+    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128);
+    if constexpr (!P::IS_F32) {
+      const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128);
+      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, false, true>(p, nch_pad, 1, st, nullptr);
+      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, false, true>(p, nch_pad, 1, st, nullptr);
+      return launch_igemm_dma<128, 64, 3, true, 4, false, true>(p, nch_pad, 1, st, nullptr);
+    } else {
+      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, false, true>(p, nch_pad, 1, st, nullptr);
+      return launch_igemm_t<P, 128, 64, 1, false, true>(p, nch_pad, 1, st, nullptr);
+    }
+  }
+  if (nch_pad == 64) {
+    if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, false, true>(p, nch_pad, 1, st, nullptr);
+    else return launch_igemm_t<P, 64, 128, 1, false, true>(p, nch_pad, 1, st, nullptr);
+  }
+  JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
+}
+
 static int launch_wgrad_reduce(const float* ws, int Z, int CsRows, int ncols, int Cs, int Cb, int logCbPad, float* grad,
                                int accumulate, hipStream_t st);
 static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int nsub, hipStream_t st, int* slots) {
@@ -192,7 +223,7 @@ static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases
   for (int zz = 0; zz < 4; ++zz)
     for (int t = 0; t < 16; ++t) p.tap[zz][t] = ((int)p.dy[zz][t] << 16) | ((int)p.dx[zz][t] & 0xffff);
   const long long esz = prec_f32_storage(prec) ? 4 : 2;
-  if (nsub == 0 && (p.logC < 3 || p.logC > 5 || !p.aff_scale)) JCK_FAIL(JCK_E_ARG, "igemm: 8..32 gathered channels are built for the affine epilogue alone");
+  if (nsub == 0 && (p.logC < 3 || p.logC > 5 || !(p.aff_scale || p.mask_act))) JCK_FAIL(JCK_E_ARG, "igemm: 8..32 gathered channels are built for the affine and mask epilogues alone");
   if (nsub == 1 && p.logC < 6 && !p.act_row_elems) JCK_FAIL(JCK_E_ARG, "igemm: the gathered tensor needs >= 64 channels (or exactly 4)");
   {
     // extent of the gathered tensor: rows (n, oy, ox) span N = M / (OH*OW) images of H x W x C
@@ -210,6 +241,12 @@ static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases
         ((uintptr_t)p.aff_scale | (uintptr_t)p.aff_shift) % 16)
       JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue takes 16-byte aligned scale and shift, a power-of-two channel count and no other option");
     DISPATCH_P(prec, launch_igemm_affine_p<P>(p, nch_pad, phases, nsub, st));
+  }
+  if (p.mask_act) {
+    if (!p.mask_scale || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || phases != 1 || !is_pow2(p.cstat) || p.cstat % 4 ||
+        (uintptr_t)p.mask_scale % 16 || (uintptr_t)p.mask_act % 16)
+      JCK_FAIL(JCK_E_ARG, "igemm: the mask epilogue takes a 16-byte aligned scale and activation, a power-of-two channel count and no other option");
+    DISPATCH_P(prec, launch_igemm_mask_p<P>(p, nch_pad, nsub, st));
   }
   DISPATCH_P(prec, launch_igemm_p<P>(p, nch_pad, phases, nsub, st, slots));
 }
@@ -249,7 +286,8 @@ static int launch_img_up(const void* a, const void* w, void* out, int epi_tanh, 
 }
 
 static int conv_down_impl(int prec, const void* big, const void* w, void* small_out, float* stats, int* stats_slots,
-                          int N, int Hb, int Wb, int Cb, int Cs, void* stream, int fwd_group_images = 0) {
+                          int N, int Hb, int Wb, int Cb, int Cs, void* stream, int fwd_group_images = 0,
+                          const void* mask_act = nullptr, const float* mask_scale = nullptr) {
   const int cbp = jck_pad_chan(Cb);
   if (!is_pow2(cbp) || !is_pow2(Hb) || !is_pow2(Wb) || Hb < 2 || Wb < 2 || Cs % 4 != 0)
     JCK_FAIL(JCK_E_ARG, "conv_down: shapes must be powers of two (Hb,Wb,Cb) and Cs % 4 == 0");
@@ -265,9 +303,19 @@ static int conv_down_impl(int prec, const void* big, const void* w, void* small_
   if (stats && !is_pow2(Cs)) JCK_FAIL(JCK_E_ARG, "conv_down: BN statistics need a power-of-two channel count");
   p.flops = 2.0 * p.M * Cs * 16.0 * Cb;
   if (stats && fwd_group_images > 0) { p.bn_group_rows = fwd_group_images * OH * OW; p.stat_accum = 1; }
-  if (prec == JCK_PREC_BF16 && cbp == 4 && Cs == 64 && OW % 16 == 0 && is_pow2(OH))
+  p.mask_act = mask_act; p.mask_scale = mask_scale;
+  if (!mask_act && prec == JCK_PREC_BF16 && cbp == 4 && Cs == 64 && OW % 16 == 0 && is_pow2(OH))
     return launch_img_down(big, w, small_out, stats, stats_slots, N, Hb, Wb, p.flops, (hipStream_t)stream);
-  return launch_igemm(prec, p, jck_pad_rows(Cs), 1, cbp == 4 ? 2 : 1, (hipStream_t)stream, stats_slots);
+  return launch_igemm(prec, p, jck_pad_rows(Cs), 1, cbp == 4 ? 2 : (mask_act && cbp < 64 ? 0 : 1), (hipStream_t)stream, stats_slots);
+}
+// Input gradient of a ConvTranspose2d whose INPUT is a folded eval-mode stage a = relu(scale[c] * y + shift[c]) (latent projection):
+// jck_conv_down with v = a_small[m, c] > 0 ? scale[c] * acc : +0 applied to the fp32 accumulators before the one rounding of the store.
+// Never the persistent kernels or the image-side streaming kernel: Cb = 4 runs on the register-staged 64 x 128 tile in every precision.
+extern "C" int jck_conv_down_mask(int prec, const void* big, const void* w, const void* a_small, const float* scale, void* small_out,
+                                  int N, int Hb, int Wb, int Cb, int Cs, void* stream) {
+  if (!a_small || !scale) JCK_FAIL(JCK_E_ARG, "conv_down_mask: the activation and the scale are required");
+  if (!is_pow2(Cs)) JCK_FAIL(JCK_E_ARG, "conv_down_mask: Cs must be a power of two");
+  return conv_down_impl(prec, big, w, small_out, nullptr, nullptr, N, Hb, Wb, Cb, Cs, stream, 0, a_small, scale);
 }
 extern "C" int jck_conv_down(int prec, const void* big, const void* w, void* small_out, float* stats, int* stats_slots,
                              int N, int Hb, int Wb, int Cb, int Cs, void* stream) {

@@ -75,6 +75,7 @@ enum KernelId : int {
   K_WGRAD_DMA_WS, K_WGRAD_DMA,
   K_WGRAD,                                        // + K_WGRAD_TILES * precision + tile     (kid_wgrad)
   K_BN_ACT_FWD = K_WGRAD + K_PRECS * K_WGRAD_TILES, K_BN_BWD_RES, K_BN_BWD_3L,      // profiler labels without a launch name
+  K_LATENT_LOSS, K_LATENT_ADAM,                   // latent projection (latent.hpp): labels without a launch name as well
   K_COUNT
 };
 template <class P> constexpr int kid_prec() { return P::SPLIT ? 2 : P::IS_F32 ? 1 : 0; }

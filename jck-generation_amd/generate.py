@@ -3,12 +3,17 @@
     python generate.py -m DCGAN --checkpoint ../model/DCGAN/fid/best.pt --num 64 --out samples
     python generate.py -m CGAN --checkpoint best.pt --num 8 --classes 3,17,42 --truncation 0.7 --out samples
     python generate.py -m DCGAN --checkpoint best.pt --interpolate 4:8 --which ema --calibrate 20 --out samples
+    python generate.py -m DCGAN --checkpoint best.pt --project samples/images.npz --project_steps 300 --out projected
 
 Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
 BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
 bounded by the batch.  --bn batch is the trainers' evaluation sampling: each chunk of -b images is one train-mode BatchNorm batch.
 An averaged generator (--which ema, or auto when the file has one) wants --calibrate K first: K train-mode batches that fit the
-running statistics to the averaged weights (in this process only; the file is not touched)."""
+running statistics to the averaged weights (in this process only; the file is not touched).
+--project FILE.npz fits a latent to every picture of the file's `images` array (uint8 [n,S,S,3]: an images.npz of this tool, or any
+such array; a CGAN takes the file's `labels` or cycles through --classes) by Adam through the frozen eval-mode generator and writes
+<out>/projected.npz (z: fp32 [n,100]; loss: the mean squared error of each reconstruction in [-1, 1] units; images: the
+reconstructions, uint8) and <out>/projected.png, each row of targets above the row of their reconstructions."""
 import argparse
 import os
 import sys
@@ -31,11 +36,19 @@ def get_arg_parse(argv=None):
     p.add_argument("--classes", type=parse_classes, default=None, metavar="3,17,...", help="CGAN: one grid row of --num images per class")
     p.add_argument("--interpolate", type=parse_interpolate, default=None, metavar="PAIRS:STEPS",
                    help="PAIRS spherical interpolations of STEPS points each between random z (one grid row per pair)")
+    p.add_argument("--project", default=None, metavar="FILE.npz", help="fit z to the uint8 [n,S,S,3] `images` array of this file")
+    p.add_argument("--project_steps", type=int, default=200, help="Adam updates per image")
+    p.add_argument("--project_lr", type=float, default=0.05)
+    p.add_argument("--project_prior", type=float, default=0.0, help="weight of mean(z^2) beside the image loss")
     p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     p.add_argument("--out", required=True, help="output directory")
     a = p.parse_args(argv)
     if a.interpolate and a.num is not None:
         p.error("--interpolate PAIRS:STEPS sets the number of images; --num does not go with it")
+    if a.project and (a.interpolate or a.num is not None or a.truncation is not None):
+        p.error("--project takes its images from the file; --num, --interpolate and --truncation do not go with it")
+    if a.project_steps < 1 or not a.project_lr > 0 or a.project_prior < 0:
+        p.error("--project_steps must be >= 1, --project_lr > 0, --project_prior >= 0")
     if a.num is None:
         a.num = 64
     if a.num < 1 or a.batch_size < 1 or a.calibrate < 0:
@@ -70,6 +83,8 @@ def parse_interpolate(s):
 def plan(args):
     """(z [N,100] on the host, class ids [N] or None, images per grid row) of a run."""
     from hipgan.sampler import latents, slerp
+    if args.project:
+        return plan_project(args)[1:]
     if args.interpolate:
         pairs, steps = args.interpolate
         ends = latents(2 * pairs, args.seed, args.truncation)
@@ -90,6 +105,35 @@ def plan(args):
     return z.float(), cls, per_row
 
 
+def plan_project(args):
+    """(target images uint8 [n,S,S,3], start z0 [n,100], class ids [n] or None, images per grid row) of a --project run."""
+    from hipgan._lib import JckError
+    from hipgan.sampler import latents, load_projection_targets
+    u8, labels = load_projection_targets(args.project)
+    n = u8.shape[0]
+    cls = None
+    if args.model == "CGAN":
+        if args.classes:
+            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(n)])
+        elif labels is not None:
+            cls = labels.to(torch.int64).view(-1)
+        else:
+            raise JckError(f"{args.project} has no 'labels' array: a CGAN projection needs it, or --classes")
+    return u8, latents(n, args.seed), cls, min(n, 8)
+
+
+def pair_rows(targets_u8, recon_u8, per_row):
+    """[targets of row 0 | reconstructions of row 0 | targets of row 1 | ...], each row padded to per_row with black images: the
+    order in which grid_u8 puts every target above its reconstruction."""
+    t, r = np.asarray(targets_u8), np.asarray(recon_u8)
+    out = []
+    for lo in range(0, t.shape[0], per_row):
+        for part in (t[lo:lo + per_row], r[lo:lo + per_row]):
+            pad = np.zeros((per_row - part.shape[0],) + part.shape[1:], np.uint8)
+            out += [part, pad]
+    return np.concatenate(out)
+
+
 def grid_u8(images_u8, per_row, padding=2):
     """uint8 [N,H,W,3] -> one uint8 [H',W',3] sheet, `per_row` images a row on black."""
     from train.gan_trainer import _make_grid
@@ -105,6 +149,8 @@ def main(argv=None):
     s = Sampler.from_checkpoint(args.checkpoint, args.model, which=args.which, prec=args.prec, batch=args.batch_size)
     if args.calibrate:
         s.calibrate(args.calibrate, seed=args.seed + 2)
+    if args.project:
+        return project_main(args, s)
     z, cls, per_row = plan(args)
     u8 = s.from_latents(z, cls, bn=args.bn, out="uint8").cpu().numpy()
     os.makedirs(args.out, exist_ok=True)
@@ -115,6 +161,23 @@ def main(argv=None):
     with open(os.path.join(args.out, "grid.png"), "wb") as f:
         f.write(_encode_png(grid_u8(u8, per_row)))
     print(f"{u8.shape[0]} images ({s.which} generator, bn={args.bn}) -> {args.out}/images.npz, grid.png")
+    return 0
+
+
+def project_main(args, s):
+    from train.gan_trainer import _encode_png
+    targets, z0, cls, per_row = plan_project(args)
+    z, loss = s.project(targets, cls, steps=args.project_steps, lr=args.project_lr, prior=args.project_prior, z0=z0)
+    recon = s.from_latents(z, cls, bn="running", out="uint8").cpu().numpy()
+    os.makedirs(args.out, exist_ok=True)
+    arrays = {"z": z.cpu().numpy(), "loss": loss.cpu().numpy(), "images": recon}
+    if cls is not None:
+        arrays["labels"] = cls.numpy().astype(np.int64)
+    np.savez(os.path.join(args.out, "projected.npz"), **arrays)
+    with open(os.path.join(args.out, "projected.png"), "wb") as f:
+        f.write(_encode_png(grid_u8(pair_rows(targets.numpy(), recon, per_row), per_row)))
+    print(f"{recon.shape[0]} images projected ({s.which} generator, {args.project_steps} steps, mean loss {float(loss.mean()):.5f}) "
+          f"-> {args.out}/projected.npz, projected.png")
     return 0
 
 

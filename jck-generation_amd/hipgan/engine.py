@@ -838,6 +838,72 @@ class DcganEngine:
         self._keep_z = (zc, lab)
         return res
 
+    def _latent_args(self, what, n, target, labels):
+        """Validated device tensors (target fp32 NCHW, one-hot labels or None) of a latent_grad / project call."""
+        if n < 1:
+            raise JckError(f"{what}: no images")
+        if target.dim() != 4 or tuple(target.shape) != (n, 3, self.size, self.size):
+            raise JckError(f"{what}: target must be [{n},3,{self.size},{self.size}] (NCHW, values in [-1, 1]), got {tuple(target.shape)}")
+        lab = None
+        if self.family == 1:
+            if labels is None or tuple(labels.shape) != (n, 100):
+                raise JckError(f"CGAN {what} needs one-hot int64 labels [n,100]")
+            lab = labels.to(self.device, torch.int64).contiguous()
+        self.join()
+        if self._packed_version != self._shared["version"]:
+            self.repack()
+        return target.to(self.device, torch.float32).contiguous(), lab
+
+    def latent_grad(self, z, target, labels=None):
+        """(loss [n], dz [n,100]): L_b = mean((G(z_b) - target_b)^2) and dL_b/dz_b through the generator as under model.eval()
+        (BatchNorm on the running statistics; nothing is written to them).  target: fp32 NCHW [n,3,S,S] in [-1, 1].  Any n: rows
+        go through in chunks of at most `batch`, each row's numbers those of a call with that row alone."""
+        n = z.shape[0]
+        t, lab = self._latent_args("latent_grad", n, target, labels)
+        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
+        if zc.shape[0] != n:
+            raise JckError("latent_grad: z must be [n,100]")
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        dz = torch.empty(n, 100, dtype=torch.float32, device=self.device)
+        for lo, hi in chunk_plan(n, self.batch):
+            lib.jck_engine_latent_grad(self._h, zc[lo:hi], None if lab is None else lab[lo:hi], t[lo:hi], hi - lo, loss[lo:hi], dz[lo:hi],
+                                       cur_stream())
+        self._keep_z = (zc, lab, t)
+        return loss, dz
+
+    def project(self, target, labels=None, steps=200, lr=0.05, prior=0.0, z0=None, seed=0, state=None):
+        """Fits z to `target` (fp32 NCHW [n,3,S,S] in [-1, 1]) through the frozen eval-mode generator: `steps` Adam updates
+        (lr, betas (0.9, 0.999)) of z minimising mean((G(z) - target)^2) + prior * mean(z^2) per image, all on the device.
+        -> (z [n,100], loss_hist [steps,n]: the loss before each update).  z0: the start (default: randn from `seed` on the host);
+        state: {"m", "v", "t"} of an earlier call to continue it - the state reached is left in `self.project_state`.
+        Any n (chunks of at most `batch` rows; a row's result does not depend on the rows beside it)."""
+        n = target.shape[0]
+        if int(steps) < 1:
+            raise JckError(f"project: steps must be >= 1, got {steps}")
+        if not float(lr) > 0.0 or float(prior) < 0.0:
+            raise JckError(f"project: lr > 0 and prior >= 0, got {lr}, {prior}")
+        t, lab = self._latent_args("project", n, target, labels)
+        if z0 is None:
+            z0 = torch.randn(n, 100, generator=torch.Generator().manual_seed(int(seed)))
+        if tuple(z0.shape) != (n, 100):
+            raise JckError(f"project: z0 must be [{n},100], got {tuple(z0.shape)}")
+        z = z0.to(self.device, torch.float32).clone().contiguous()
+        if state is None:
+            m, v, t0 = torch.zeros_like(z), torch.zeros_like(z), 0
+        else:
+            m, v, t0 = state["m"].to(self.device, torch.float32).clone(), state["v"].to(self.device, torch.float32).clone(), int(state["t"])
+            if tuple(m.shape) != (n, 100) or tuple(v.shape) != (n, 100) or t0 < 0:
+                raise JckError("project: state must hold m, v [n,100] and t >= 0")
+        hist = torch.empty(int(steps), n, dtype=torch.float32, device=self.device)
+        for lo, hi in chunk_plan(n, self.batch):
+            h = torch.empty(int(steps), hi - lo, dtype=torch.float32, device=self.device)
+            lib.jck_engine_project(self._h, z[lo:hi], None if lab is None else lab[lo:hi], t[lo:hi], hi - lo, int(steps), float(lr),
+                                   float(prior), m[lo:hi], v[lo:hi], t0, h, cur_stream())
+            hist[:, lo:hi] = h
+        self._keep_z = (z, lab, t)
+        self.project_state = {"m": m, "v": v, "t": t0 + int(steps)}
+        return z, hist
+
     def tensor(self, name):
         """Debug/parity view of an internal NHWC tensor as a torch tensor (copy)."""
         self.join()

@@ -77,6 +77,44 @@ def one_hot(classes):
     return torch.nn.functional.one_hot(c, N_CLASS).to(torch.int64)
 
 
+def images_to_target(images):
+    """What a projection fits: uint8 NHWC [n,S,S,3] (as Sampler.images returns and generate.py stores) -> u8 / 127.5 - 1, or fp32
+    NCHW [n,3,S,S] in [-1, 1] as it is -> fp32 NCHW [n,3,S,S], S in (64, 128)."""
+    x = torch.as_tensor(images)
+    if x.dim() != 4:
+        raise JckError(f"images must be uint8 [n,S,S,3] or float [n,3,S,S], got shape {tuple(x.shape)}")
+    if x.dtype == torch.uint8:
+        if x.shape[3] != 3 or x.shape[1] != x.shape[2]:
+            raise JckError(f"uint8 images must be NHWC [n,S,S,3], got {tuple(x.shape)}")
+        x = (x.to(torch.float32) / 127.5 - 1.0).permute(0, 3, 1, 2).contiguous()
+    elif x.is_floating_point():
+        if x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise JckError(f"float images must be NCHW [n,3,S,S], got {tuple(x.shape)}")
+        x = x.to(torch.float32)
+    else:
+        raise JckError(f"images must be uint8 or floating point, got {x.dtype}")
+    if x.shape[0] < 1 or x.shape[2] not in (64, 128):
+        raise JckError(f"images must be a non-empty batch of 64x64 or 128x128 pictures, got {tuple(x.shape)}")
+    return x
+
+
+def load_projection_targets(path):
+    """The `images` array of an .npz (generate.py's images.npz, or any uint8 [n,S,S,3]) -> (uint8 tensor, labels or None)."""
+    import numpy as np
+    with np.load(path) as f:
+        if "images" not in f.files:
+            raise JckError(f"{path}: no 'images' array (found {sorted(f.files)})")
+        im = f["images"]
+        labels = f["labels"] if "labels" in f.files else None
+    if im.dtype != np.uint8 or im.ndim != 4 or im.shape[3] != 3 or im.shape[1] != im.shape[2] or im.shape[0] < 1:
+        raise JckError(f"{path}: 'images' must be uint8 [n,S,S,3], got {im.dtype} {tuple(im.shape)}")
+    if im.shape[1] not in (64, 128):
+        raise JckError(f"{path}: images are {im.shape[1]}x{im.shape[2]}; 64x64 or 128x128 expected")
+    if labels is not None and labels.shape[0] != im.shape[0]:
+        raise JckError(f"{path}: {labels.shape[0]} labels for {im.shape[0]} images")
+    return torch.from_numpy(im.copy()), None if labels is None else torch.from_numpy(labels.copy())
+
+
 class Sampler:
     def __init__(self, engine, which):
         self.engine, self.which = engine, which
@@ -126,6 +164,33 @@ class Sampler:
 
     def interpolate(self, z0, z1, steps, labels=None, bn="running", out="uint8"):
         return self.from_latents(slerp(z0.reshape(NZ), z1.reshape(NZ), steps).float(), labels, bn, out)
+
+    def project(self, images, labels=None, steps=200, lr=0.05, prior=0.0, seed=0, restarts=1, z0=None):
+        """The latent z whose image is closest to each of `images` (uint8 NHWC [n,S,S,3] or fp32 NCHW in [-1, 1]): `steps` Adam
+        updates through the frozen eval-mode generator (DcganEngine.project) -> (z [n,100], final loss [n]: mean squared error of
+        G(z) at the returned z).  restarts=R starts every image from R seeds (seed, seed + 1, ...; run as extra rows) and keeps
+        the start that ends lowest."""
+        t = images_to_target(images)
+        n, R = t.shape[0], int(restarts)
+        if t.shape[2] != self.engine.size:
+            raise JckError(f"images are {t.shape[2]}x{t.shape[2]}, the generator makes {self.engine.size}x{self.engine.size}")
+        if R < 1:
+            raise JckError(f"restarts must be >= 1, got {restarts}")
+        if z0 is not None and R != 1:
+            raise JckError("z0 fixes the start: restarts must be 1")
+        lab = self._labels(labels, n)
+        t = t.to(self.engine.device)
+        tt = t.repeat(R, 1, 1, 1) if R > 1 else t                     # row r * n + i: image i from seed + r
+        ll = None if lab is None else lab.repeat(R, 1)
+        if z0 is None:
+            z0 = torch.cat([latents(n, int(seed) + r) for r in range(R)])
+        z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, prior=prior, z0=z0.reshape(-1, NZ))
+        loss, _ = self.engine.latent_grad(z, tt, ll)
+        if R > 1:
+            best = loss.view(R, n).argmin(0)                            # ties: the lowest seed
+            pick = best * n + torch.arange(n, device=best.device)
+            z, loss = z[pick], loss[pick]
+        return z, loss
 
     def calibrate(self, batches, seed=0):
         """`batches` train-mode sampling batches (full engine batches of fresh z, uniform random classes for a CGAN) through the
