@@ -99,6 +99,16 @@ int jck_g1_fwd_affine(int prec, const void* z, const void* w, const float* scale
  * image-side streaming kernel: every launch ends in the gather-GEMM's shared epilogue. */
 int jck_conv_down_mask(int prec, const void* big, const void* w, const void* a_small, const float* scale, void* small_out,
                        int N, int Hb, int Wb, int Cb, int Cs, void* stream);
+/* Discriminator inference, per op.  jck_conv_down_affine: jck_conv_down (Conv2d k4 s2 p1, NHWC) with the eval-mode BatchNorm that
+ * follows it (model/DCGAN.py:40-43 under model.eval(); scale / shift folded by jck_bn_eval_aux) and the LeakyReLU applied to the fp32
+ * accumulators in the product's epilogue: t = fmaf(scale[c], acc, shift[c]), out = t > 0 ? t : t * slope (ATen's form: NaN passes,
+ * -0 stays -0), ONE rounding to the storage type, no statistics, no pre-activation tensor.  scale / shift: device float[Cs], 16-byte
+ * aligned - the first two quarters of an aux table.  Cb 3 or 4 with Cs = 64, or Cb a power of two >= 64; Cs a power of two >= 64;
+ * anything else is JCK_E_ARG.  Never the persistent kernels or the image-side streaming kernel: every launch ends in the gather-GEMM's
+ * shared epilogue (Cb = 4: the register-staged 64 x 128 tile in every precision), and jck_last_launch reports that tile's name.
+ * In bf16 the result is not bitwise jck_conv_down + jck_bn_act_fwd, which round y to bf16 between the two launches. */
+int jck_conv_down_affine(int prec, const void* big, const void* w, const float* scale, const float* shift, float slope,
+                         void* small_out, int N, int Hb, int Wb, int Cb, int Cs, void* stream);
 /* loss_out[b] = mean over the 3 * HW real elements of (x_b - t_b)^2 with x the stored tanh output (NHWC4, element type of prec) and t
  * the caller's NCHW fp32 target, read in place; g_raw_out (NHWC4, same type) = 2 (x - t) / (3 HW) * (1 - x^2), padding channel +0.
  * One launch, one workgroup per image, a fixed-order reduction: equal bits on every run and for every N. */
@@ -211,6 +221,11 @@ int jck_tanh_bwd(int prec, const void* g, const void* y, float scale, void* out,
  * stores, summed in a fixed order by the step tail (no float atomics anywhere on the path). */
 int jck_head_fwd(int prec, const void* a4, const float* wp, const float* bias /* device scalar or NULL */, int B, int K,
                  float target, int mode, float* prob, float* ds, float* scal, int slot_loss, int slot_p, int scal_ld, void* stream);
+/* The head at inference: logit[n] = <x[n,:], w> (+ bias[0]), prob[n] = 1 / (1 + expf(-logit)) (prob may be NULL); x [B][K] of the
+ * element type, w fp32 [K], both 16-byte aligned, K % 8 == 0.  One workgroup per row, a fixed-order reduction (the dot product of
+ * jck_head_fwd), no loss, no gradient, no scalar slots: a row's numbers do not depend on B. */
+int jck_score_head(int prec, const void* x, const float* w, const float* bias /* device scalar or NULL */, int B, int K,
+                   float* logit, float* prob /* or NULL */, void* stream);
 /* G (<= 4) batches of B rows stacked in a4 / prob / ds (the real | fake | penalty groups of a batched D pass), each with its own
  * target, mode and scalar slots, in one launch; the scalar table is indexed by the row inside its group */
 int jck_head_fwd_grouped(int prec, const void* a4, const float* wp, const float* bias, int B, int K, int G, const float* targets,
@@ -443,6 +458,21 @@ int jck_engine_latent_grad(jck_engine*, const float* z, const int64_t* labels, c
 int jck_engine_project(jck_engine*, float* z /* in, out */, const int64_t* labels, const float* target_nchw, int n,
                        int steps, float lr, float prior, float* m, float* v /* [n,100], caller-owned */, int t0,
                        float* loss_hist /* [steps][n] or NULL */, void* stream);
+/* The discriminator as under model.eval() (model/DCGAN.py:28-50, model/CGAN.py:18-42 with BatchNorm on its running statistics and
+ * Dropout the identity): logit[b] = D's pre-sigmoid output for image b, prob[b] (or NULL) its sigmoid.  images_nchw: fp32 [n,3,S,S]
+ * in [-1, 1] on the device, or NULL to score the generator's current output where it lies (jck_engine_sample_ex just before: the images
+ * never leave the device); noise_nchw (with images only, or NULL): the trainers' instance noise, D sees 0.9 * image + 0.1 * noise
+ * (train/dcgan_trainer.py:160); labels: one-hot int64 [n,100], family 1.  One launch folds D's BatchNorm layers; every Conv2d +
+ * BatchNorm + LeakyReLU stage is one launch (jck_conv_down_affine) in f32 / bf16x3 and jck_conv_down + jck_bn_act_fwd on the folded
+ * table in bf16, where that form measured faster; the head computes no loss; no host synchronisation.
+ * 1 <= n <= batch; row b of both outputs is bit for bit what a call with that row alone returns.  Nothing of the training state
+ * is written: parameters, gradients, Adam moments, running statistics, num_batches_tracked, the step's scalars.  On a training engine
+ * it may be called between two steps, also with the next batch's D(real) forward in flight: every buffer it writes is memory of its
+ * own that the first call allocates, clears and waits for (so: the first call not inside a graph capture, and the only one that
+ * synchronises with the host; later calls may use any stream) and jck_engine_destroy frees.  D's operands must
+ * have been packed (jck_engine_repack(net 1) after loading its state, or a training step): JCK_E_ARG otherwise. */
+int jck_engine_score(jck_engine*, const float* images_nchw /* fp32 [n,3,S,S] or NULL */, const float* noise_nchw /* or NULL */,
+                     const int64_t* labels /* family 1 */, int n, float* logit /* [n] */, float* prob /* [n] or NULL */, void* stream);
 /* debug / parity access to internal NHWC tensors: name in {"fake","real_noisy",...}; returns device ptr or NULL */
 const void* jck_engine_tensor(const jck_engine*, const char* name, long long* numel);
 

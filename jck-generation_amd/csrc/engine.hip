@@ -240,6 +240,15 @@ struct jck_engine {
   // latent projection (jck_engine_latent_grad / jck_engine_project): memory of its own, allocated by the first such call and freed
   // with the engine - G.conv1's weight as the dz product's operand [128][16 * G_C1], that product's split-K slabs, a loss row (one allocation)
   void* lat_w = nullptr; float *lat_slab = nullptr, *lat_loss = nullptr;
+  // discriminator inference (jck_engine_score): memory of its own as well, one allocation made by the first scoring call - the
+  // transformed input, a stage's activations and folded aux table each, one pre-activation tensor that the stages share (bf16: see
+  // jck_engine_score), and CGAN's head rows (concat buffer, split-K slabs, hidden row)
+  struct ScoreBufs {
+    void* base = nullptr;
+    void *x = nullptr, *y = nullptr, *a[JCK_MAX_STAGES] = {}, *cbuf = nullptr, *h = nullptr;
+    float *aux[JCK_MAX_STAGES] = {}, *slab = nullptr;
+  } sc;
+  bool d_packed = false;                // D's operands were derived from its parameters at least once (jck_engine_repack, a D step)
 
   void carve(unsigned char* base) {
     jck_engine* e = this;
@@ -441,6 +450,7 @@ extern "C" void jck_engine_destroy(jck_engine* e) {
   if (!e) return;
   if (e->overlap) destroy_side_streams(e, true);
   if (e->lat_w) (void)hipFree(e->lat_w);
+  if (e->sc.base) (void)hipFree(e->sc.base);
   delete e;
 }
 extern "C" int jck_engine_num_tensors(int family, int net) { return (int)make_layout(family, net).t.size(); }
@@ -529,6 +539,7 @@ static int repack_convs(jck_engine* e, int net, void* stream, const TailJobs* ta
   }
   jobs.first_chunk[n] = chunk;
   jobs.n = n;
+  if (net == 1) e->d_packed = true;
   if (tail) {
     const int nblk = chunk + tail_x * (tail->nl + 1);
     if (e->prec == JCK_PREC_BF16) hipLaunchKernelGGL(pack_tail_kernel<bf16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, jobs, chunk, *tail, tail_x);
@@ -1746,6 +1757,100 @@ extern "C" int jck_engine_project(jck_engine* e, float* z, const int64_t* labels
     JCK_TRY(jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, z, m, v, lr, prior, t0 + s + 1, e->g_z, z_pad(e->family), n, st));
   }
   return JCK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// discriminator inference: D as under model.eval() - every Conv2d + BatchNorm (running statistics) + LeakyReLU stage one launch
+// (jck_conv_down_affine) in fp32 storage, two (the product, then the folded BatchNorm + LeakyReLU) in bf16 - score_stage_fused says
+// why -, the head without loss, gradient or scalar slots.  Beside the step like the projection above, and stricter:
+// D's training activations, real_noisy and the head's concat buffer may belong to a prefetched D(real) forward, so every buffer this
+// writes is memory of its own; it reads fake_raw when no image is given.  Row b's numbers do not depend on n: no statistic, a
+// per-row head reduction in a fixed order, a split-K factor that is a constant.
+// ---------------------------------------------------------------------------------------------------------
+// Which form a stage takes.  fp32 storage (f32, bf16x3): fused - jck_conv_down_affine runs the tile jck_conv_down would and saves the
+// BatchNorm launch and its pass over the output.  bf16: jck_conv_down + jck_bn_act_fwd on the same folded aux table - there jck_conv_down
+// has the image-side streaming kernel and the persistent gather-GEMMs with their 16-byte-store epilogue, which the fused form (shared
+// epilogue only) gives up, and the whole call measured 4 % faster that way at batch 64 and 256 (tools/score_rate.py).
+static bool score_stage_fused(int prec) { return prec_f32_storage(prec); }
+static int score_alloc(jck_engine* e, hipStream_t st) {
+  if (e->sc.base) return JCK_OK;
+  if (e->capturing) JCK_FAIL(JCK_E_ARG, "score: the first scoring call allocates and cannot run inside a graph capture");
+  Carver c;
+  auto carve = [&](jck_engine::ScoreBufs& b) {
+    c.off = 0;
+    b.x = c.take<unsigned char>((size_t)e->B * TT.HW * 4 * e->esz);
+    if (!score_stage_fused(e->prec)) b.y = c.take<unsigned char>((size_t)e->B * (TT.S / 2) * (TT.S / 2) * TT.D_CS[0] * e->esz);   // the largest stage's
+    for (int i = 0; i < TT.NS; ++i) {
+      b.a[i] = c.take<unsigned char>((size_t)e->B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i] * e->esz);
+      b.aux[i] = c.take<float>(4 * TT.D_CS[i]);
+    }
+    if (e->family == 1) {
+      b.cbuf = c.take<unsigned char>((size_t)e->B * L1_KPAD * e->esz);
+      b.slab = c.take<float>((size_t)L1_KSPLIT * e->B * L1_OUT);
+      b.h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
+    }
+  };
+  jck_engine::ScoreBufs b;
+  carve(b);                                                          // sizes
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, c.off));
+  // the concat buffer's padding columns are a GEMM operand: they read as zero from the start - for a later call on ANY stream, so this
+  // one call, which allocates anyway, waits for the clear
+  if (hipMemsetAsync(base, 0, c.off, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    (void)hipFree(base);
+    JCK_FAIL(JCK_E_HIP, "score: clearing the buffers failed");
+  }
+  c.base = reinterpret_cast<unsigned char*>(base);
+  carve(b);
+  b.base = base;
+  e->sc = b;
+  return JCK_OK;
+}
+extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const float* noise_nchw, const int64_t* labels, int n, float* logit,
+                                float* prob, void* stream) {
+  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "score: engine not bound");
+  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "score: n must be in [1, batch]");
+  if (!logit) JCK_FAIL(JCK_E_ARG, "score: null logit");
+  if (noise_nchw && !images_nchw) JCK_FAIL(JCK_E_ARG, "score: instance noise goes with images");
+  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, "score: CGAN discriminator needs labels");
+  if (!e->d_packed) JCK_FAIL(JCK_E_ARG, "score: the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
+  hipStream_t st = (hipStream_t)stream;
+  JCK_TRY(score_alloc(e, st));
+  const jck_engine::ScoreBufs& S = e->sc;
+  const void* in = e->fake_raw;                                       // NULL images: the generator's last output, where it lies
+  if (images_nchw) {
+    JCK_TRY(jck_img_prep(e->prec, images_nchw, noise_nchw, noise_nchw ? 0.9f : 1.0f, noise_nchw ? 0.1f : 0.0f, S.x, n, TT.HW, st));
+    in = S.x;
+  }
+  {
+    const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
+    float* aux[JCK_MAX_STAGES];
+    int Cs[JCK_MAX_STAGES];
+    for (int i = 0; i < TT.NS; ++i) {
+      gamma[i] = e->P(e->LD, e->dp, NWN[i]); beta[i] = e->P(e->LD, e->dp, NBN[i]);
+      rm[i] = e->dbn + find(e->LD, RMN[i])->offset; rv[i] = e->dbn + find(e->LD, RVN[i])->offset;
+      aux[i] = S.aux[i]; Cs[i] = TT.D_CS[i];
+    }
+    JCK_TRY(jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st));
+  }
+  for (int i = 0; i < TT.NS; ++i) {
+    const int hb = TT.D_HB[i], cs = TT.D_CS[i];
+    if (score_stage_fused(e->prec)) {
+      JCK_TRY(jck_conv_down_affine(e->prec, in, e->d_down[i], S.aux[i], S.aux[i] + cs, LRELU, S.a[i], n, hb, hb, TT.D_CB[i], cs, st));
+    } else {
+      JCK_TRY(jck_conv_down(e->prec, in, e->d_down[i], S.y, nullptr, nullptr, n, hb, hb, TT.D_CB[i], cs, st));
+      JCK_TRY(jck_bn_act_fwd(e->prec, S.y, S.aux[i], LRELU, S.a[i], (long long)n * (hb / 2) * (hb / 2), cs, st));
+    }
+    in = S.a[i];
+  }
+  if (e->family == 0) return jck_score_head(e->prec, in, e->d_head_wp, nullptr, n, TT.FEAT, logit, prob, st);
+  JCK_TRY(jck_concat_rows(e->prec, in, TT.FEAT, S.cbuf, L1_KPAD, n, st));
+  JCK_TRY(jck_label_embed_fwd(e->prec, labels, e->P(e->LD, e->dp, "label_embedding.weight"), e->P(e->LD, e->dp, "label_embedding.bias"), LRELU, n,
+                              N_CLASS, EMB, S.cbuf, L1_KPAD, TT.FEAT, nullptr, st));
+  JCK_TRY(jck_linear_fwd(e->prec, S.cbuf, e->l1_w, nullptr, S.slab, n, L1_KPAD, L1_OUT, L1_OUT, L1_KSPLIT, st));
+  // Dropout is the identity under model.eval(): no mask
+  JCK_TRY(jck_linear_finish(e->prec, S.slab, L1_KSPLIT, e->P(e->LD, e->dp, "linear1.bias"), nullptr, 1.0f, S.h, nullptr, n, L1_OUT, st));
+  return jck_score_head(e->prec, S.h, e->P(e->LD, e->dp, "linear2.weight"), e->P(e->LD, e->dp, "linear2.bias"), n, L1_OUT, logit, prob, st);
 }
 
 extern "C" const void* jck_engine_tensor(const jck_engine* e, const char* name, long long* numel) {

@@ -795,6 +795,30 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a4,
   }
 }
 
+// D head at inference (jck_engine_score): logit[n] = <x[n,:], w> (+ bias), prob[n] = sigmoid(logit) - head_fwd_kernel's dot product and
+// sigmoid without loss, gradient or scalar slots.  One workgroup per row, a fixed-order reduction, no atomics: a row's numbers do not
+// depend on the rows beside it.
+template <typename T>
+__global__ __launch_bounds__(256) void score_head_kernel(const T* __restrict__ x, const float* __restrict__ w, int K, const float* __restrict__ bias,
+                                                         float* __restrict__ logit, float* __restrict__ prob) {
+  __shared__ float sm[4];
+  const T* xr = x + (long long)blockIdx.x * K;
+  float s = 0.f;
+  for (int i = threadIdx.x * 8; i < K; i += 256 * 8) {
+    float v[8];
+    ld8(xr + i, v);
+    const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + i), w1 = *reinterpret_cast<const f32x4*>(w + i + 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += v[k] * w0[k] + v[4 + k] * w1[k];
+  }
+  s = block_sum256(s, sm);
+  if (threadIdx.x == 0) {
+    if (bias) s += bias[0];
+    logit[blockIdx.x] = s;
+    if (prob) prob[blockIdx.x] = 1.f / (1.f + expf(-s));
+  }
+}
+
 // g_a4[n][k] = ds[n] * w[k]
 template <typename T>
 __global__ void head_dgrad_kernel(const float* __restrict__ ds, const float* __restrict__ w, int K, T* __restrict__ g,

@@ -68,6 +68,9 @@ struct IgemmParams {
   // v = mask_act[pixel][c] > 0 ? mask_scale[c] * acc : +0, c = channel & (cstat - 1); mask_act has the output's layout and type
   const void* mask_act;
   const float* mask_scale;
+  // LEAKY form of the AFFINE instantiations (discriminator inference, jck_conv_down_affine): t = aff_scale[c] * acc + aff_shift[c],
+  // v = t > 0 ? t : t * aff_slope
+  float aff_slope;
 };
 
 #define IG_BK 64
@@ -108,7 +111,9 @@ __device__ __forceinline__ void igemm_pixel_offsets(const IgemmParams& p, int la
 // to the fp32 accumulators before the one rounding of the store - no statistics, no pre-activation tensor.  NaN passes (torch.relu).
 // MASK (compile time, jck_conv_down_mask alone): the gradient through a folded stage a = relu(scale[c] * y + shift[c]) - scale[c]
 // where the stored activation is > 0, else +0 (a NaN activation masks: torch.relu's backward) - on the fp32 accumulators.
-template <class P, int BCH, int BPIX, int FM, int FN, int WPIXN, bool AFFINE = false, bool MASK = false>
+// LEAKY (compile time, with AFFINE; jck_conv_down_affine alone): LeakyReLU in the ReLU's place, t > 0 ? t : t * aff_slope - ATen's
+// form: NaN passes, -0 stays -0.
+template <class P, int BCH, int BPIX, int FM, int FN, int WPIXN, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc)[FM][FN], int lane, int wch, int wpix, int z, int zraw,
                                                int bidx, int bidy, int m0, int ch0) {
   typedef typename P::T T;
@@ -165,7 +170,8 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float t = fmaf(sc[r], v[r], sh[r]);
-          v[r] = t < 0.f ? 0.f : t;
+          if constexpr (LEAKY) v[r] = t > 0.f ? t : t * p.aff_slope;
+          else v[r] = t < 0.f ? 0.f : t;
         }
       }
       if constexpr (MASK) {
@@ -181,8 +187,8 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
   }
 }
 
-// NSUB: 1 - >= 64 gathered channels, 2 - exactly 4, 0 - 8..32 (AFFINE and MASK launches only: small generators at inference / projection)
-template <class P, int BCH, int BPIX, int NSUB, int NST = 2, bool AFFINE = false, bool MASK = false>
+// NSUB: 1 - >= 64 gathered channels, 2 - exactly 4, 0 - 8..32 (ReLU AFFINE and MASK launches only: small generators at inference / projection)
+template <class P, int BCH, int BPIX, int NSUB, int NST = 2, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   typedef typename P::T T;        // activation storage type
   typedef typename P::W W;        // packed-weight element type (bf16_t or float)
@@ -415,7 +421,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     }
   }
 
-  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK, LEAKY>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -432,7 +438,7 @@ static __device__ __attribute__((aligned(16))) unsigned int g_jck_zero_page[64];
 // about one workgroup per CU, where a 4-wave workgroup would serialise DMA issue and MFMA in every wave.
 // NCW = 8 (768 threads) with a 128 x 256 tile: the weight tile is filled once for twice the pixels - 85 instead of 64 FLOP
 // per filled byte (the kernels are bound by the LDS fill rate).
-template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false, bool MASK = false>
+template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
 __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(const IgemmParams p) {
   static_assert(!WS || NSTG == 3, "wave specialisation uses 3 LDS stages");
   static_assert(NCW == 4 || (WS && NCW == 8), "8 consumer waves exist in the wave-specialised form only");
@@ -560,7 +566,7 @@ __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(co
       compute(slot);
       slot = slot == 2 ? 0 : slot + 1;
     }
-    igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+    igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK, LEAKY>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
     return;
   }
   // prologue: NSTG-1 stages in flight
@@ -583,7 +589,7 @@ __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(co
     st_i = (st_i + 1 == NSTG) ? 0 : st_i + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // drain the dead tail loads before the epilogue reuses nothing of LDS
-  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK, LEAKY>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
 }
 
 // Epilogue of the persistent kernel: 16-byte stores.  The loader fills LDS weight row r of every 32-row block with output

@@ -582,6 +582,15 @@ extern "C" int jck_head_fwd(int prec, const void* a4, const float* wp, const flo
                             float* prob, float* ds, float* scal, int slot_loss, int slot_p, int scal_ld, void* stream) {
   return jck_head_fwd_grouped(prec, a4, wp, bias, B, K, 1, &target, &mode, prob, ds, scal, &slot_loss, &slot_p, scal_ld, stream);
 }
+// the head at inference: logit and sigmoid alone (ew.hpp: score_head_kernel)
+extern "C" int jck_score_head(int prec, const void* x, const float* w, const float* bias, int B, int K, float* logit, float* prob, void* stream) {
+  if (!x || !w || !logit) JCK_FAIL(JCK_E_ARG, "score_head: null x / w / logit");
+  if (B < 1 || K < 8 || K % 8) JCK_FAIL(JCK_E_ARG, "score_head: B >= 1 and K a multiple of 8");
+  if ((uintptr_t)x % 16 || (uintptr_t)w % 16) JCK_FAIL(JCK_E_ARG, "score_head: x and w must be 16-byte aligned");
+  DISPATCH_T(prec, hipLaunchKernelGGL(score_head_kernel<T>, dim3(B), dim3(256), 0, (hipStream_t)stream, (const T*)x, w, K, bias, logit, prob));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
 // jck_linear_finish + jck_head_fwd_grouped + the input-gradient half of jck_head_bwd + jck_dropout of CGAN's head in one launch
 // (ew.hpp: cg_head_mid_kernel); N = 256 columns; rows = G * B; mask required
 int cg_head_mid(int prec, const float* slab, int ksplit, const float* bias1, const float* mask, float scale, void* h, void* hd, const float* w2,

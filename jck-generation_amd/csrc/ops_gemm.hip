@@ -43,7 +43,7 @@ static void igemm_tile_stats(IgemmParams& q, const dim3& grid, int BCH, int rows
   if (slots) *slots = (int)(grid.x * grid.z * (grid.y / q.ytiles_per_cset) * rows_per_tile);
 }
 
-template <class P, int BCH, int BPIX, int NSUB, bool AFFINE = false, bool MASK = false>
+template <class P, int BCH, int BPIX, int NSUB, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
 static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   typedef IgemmCfg<P, BCH, BPIX> C;
   constexpr KernelId id = kid_igemm<P, BCH, BPIX, NSUB>();
@@ -55,10 +55,10 @@ static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStre
     if (q.cstat % BCH != 0 && BCH % q.cstat != 0) JCK_FAIL(JCK_E_ARG, "igemm: stats channel count incompatible with the tile");
     igemm_tile_stats(q, grid, BCH, C::WPIX, slots);
   }
-  return launch_lds<igemm_kernel<P, BCH, BPIX, NSUB, 2, AFFINE, MASK>>(dim3(grid.x * grid.y * grid.z), dim3(256), C::LDS_BYTES, st, q);
+  return launch_lds<igemm_kernel<P, BCH, BPIX, NSUB, 2, AFFINE, MASK, LEAKY>>(dim3(grid.x * grid.y * grid.z), dim3(256), C::LDS_BYTES, st, q);
 }
 
-template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false, bool MASK = false>
+template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
 static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   constexpr int LDSB = NSTG * (BCH + BPIX) * IG_BK * 2;
   ProfScope prof(kid_igemm_dma(K_IGEMM_DMA, BCH, BPIX), p.flops, st);
@@ -66,7 +66,7 @@ static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipSt
   IgemmParams q;
   const dim3 grid = igemm_grid(p, nch_pad, phases, BCH, BPIX, q);
   if (q.stats) igemm_tile_stats(q, grid, BCH, IgemmCfg<PrecBf16, BCH, BPIX, NCW>::WPIX, slots);
-  return launch_lds<igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW, AFFINE, MASK>>(dim3(grid.x * grid.y * grid.z), dim3(WS ? (NCW + 4) * 64 : 256), LDSB, st, q);
+  return launch_lds<igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW, AFFINE, MASK, LEAKY>>(dim3(grid.x * grid.y * grid.z), dim3(WS ? (NCW + 4) * 64 : 256), LDSB, st, q);
 }
 
 // persistent wave-specialised form: at most `cap` workgroups (what the chip holds at this tile's LDS footprint) walk the tiles
@@ -158,30 +158,42 @@ static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsu
 
 // Inference launches (p.aff_scale set): the kernels that end in the shared epilogue, in its AFFINE instantiation - never the persistent
 // ones.  Tile choice as launch_igemm_p's non-persistent branches; 8..32 gathered channels (nsub 0) take 16-row tiles whatever the row count.
-template <class P>
+// LEAKY (jck_conv_down_affine: D's stages): the same tiles in the epilogue's leaky form for >= 64 output rows; nsub 2 - the image-side
+// layer, 4 gathered channels - on the register-staged 64 x 128 tile in every precision, as launch_igemm_mask_p does.
+template <class P, bool LEAKY = false>
 static int launch_igemm_affine_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st) {
-  if (nsub == 0) {
-    if (nch_pad % 16) JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
-    return launch_igemm_t<P, 16, 256, 0, true>(p, nch_pad, phases, st, nullptr);
+  if constexpr (LEAKY) {
+    if (nsub == 2) {
+      if (nch_pad != 64) JCK_FAIL(JCK_E_ARG, "igemm: a 4-channel gather is built for 64 output rows");
+      return launch_igemm_t<P, 64, 128, 2, true, false, true>(p, nch_pad, phases, st, nullptr);
+    }
+    if (nsub != 1 || (nch_pad != 64 && nch_pad % 128)) JCK_FAIL(JCK_E_ARG, "igemm: the leaky affine epilogue is built for 4 or >= 64 gathered channels and >= 64 output rows");
+  } else {
+    if (nsub == 0) {
+      if (nch_pad % 16) JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
+      return launch_igemm_t<P, 16, 256, 0, true>(p, nch_pad, phases, st, nullptr);
+    }
+    if (nsub != 1) JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue is built for >= 8 gathered channels");
   }
-  if (nsub != 1) JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue is built for >= 8 gathered channels");
   if (nch_pad % 128 == 0) {
     const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
     if constexpr (!P::IS_F32) {
       const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128) * phases;
-      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, true>(p, nch_pad, phases, st, nullptr);
-      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, true>(p, nch_pad, phases, st, nullptr);
-      return launch_igemm_dma<128, 64, 3, true, 4, true>(p, nch_pad, phases, st, nullptr);
+      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
+      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
+      return launch_igemm_dma<128, 64, 3, true, 4, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
     } else {
-      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, true>(p, nch_pad, phases, st, nullptr);
-      return launch_igemm_t<P, 128, 64, 1, true>(p, nch_pad, phases, st, nullptr);
+      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
+      return launch_igemm_t<P, 128, 64, 1, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
     }
   }
   if (nch_pad == 64) {
-    if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, true>(p, nch_pad, phases, st, nullptr);
-    else return launch_igemm_t<P, 64, 128, 1, true>(p, nch_pad, phases, st, nullptr);
+    if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
+    else return launch_igemm_t<P, 64, 128, 1, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
   }
-  if (nch_pad == 16) return launch_igemm_t<P, 16, 256, 1, true>(p, nch_pad, phases, st, nullptr);
+  if constexpr (!LEAKY) {
+    if (nch_pad == 16) return launch_igemm_t<P, 16, 256, 1, true>(p, nch_pad, phases, st, nullptr);
+  }
   JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
 }
 
@@ -218,7 +230,8 @@ static int launch_igemm_mask_p(const IgemmParams& p, int nch_pad, int nsub, hipS
 
 static int launch_wgrad_reduce(const float* ws, int Z, int CsRows, int ncols, int Cs, int Cb, int logCbPad, float* grad,
                                int accumulate, hipStream_t st);
-static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int nsub, hipStream_t st, int* slots) {
+// leaky: with p0.aff_scale, the LeakyReLU form of the affine epilogue (slope p0.aff_slope)
+static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int nsub, hipStream_t st, int* slots, bool leaky = false) {
   IgemmParams p = p0;
   for (int zz = 0; zz < 4; ++zz)
     for (int t = 0; t < 16; ++t) p.tap[zz][t] = ((int)p.dy[zz][t] << 16) | ((int)p.dx[zz][t] & 0xffff);
@@ -240,6 +253,7 @@ static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases
     if (!p.aff_shift || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || !is_pow2(p.cstat) || p.cstat % 4 ||
         ((uintptr_t)p.aff_scale | (uintptr_t)p.aff_shift) % 16)
       JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue takes 16-byte aligned scale and shift, a power-of-two channel count and no other option");
+    if (leaky) DISPATCH_P(prec, (launch_igemm_affine_p<P, true>(p, nch_pad, phases, nsub, st)));
     DISPATCH_P(prec, launch_igemm_affine_p<P>(p, nch_pad, phases, nsub, st));
   }
   if (p.mask_act) {
@@ -287,7 +301,8 @@ static int launch_img_up(const void* a, const void* w, void* out, int epi_tanh, 
 
 static int conv_down_impl(int prec, const void* big, const void* w, void* small_out, float* stats, int* stats_slots,
                           int N, int Hb, int Wb, int Cb, int Cs, void* stream, int fwd_group_images = 0,
-                          const void* mask_act = nullptr, const float* mask_scale = nullptr) {
+                          const void* mask_act = nullptr, const float* mask_scale = nullptr, const float* aff_scale = nullptr,
+                          const float* aff_shift = nullptr, float aff_slope = 0.f) {
   const int cbp = jck_pad_chan(Cb);
   if (!is_pow2(cbp) || !is_pow2(Hb) || !is_pow2(Wb) || Hb < 2 || Wb < 2 || Cs % 4 != 0)
     JCK_FAIL(JCK_E_ARG, "conv_down: shapes must be powers of two (Hb,Wb,Cb) and Cs % 4 == 0");
@@ -304,6 +319,8 @@ static int conv_down_impl(int prec, const void* big, const void* w, void* small_
   p.flops = 2.0 * p.M * Cs * 16.0 * Cb;
   if (stats && fwd_group_images > 0) { p.bn_group_rows = fwd_group_images * OH * OW; p.stat_accum = 1; }
   p.mask_act = mask_act; p.mask_scale = mask_scale;
+  p.aff_scale = aff_scale; p.aff_shift = aff_shift; p.aff_slope = aff_slope;
+  if (aff_scale) return launch_igemm(prec, p, jck_pad_rows(Cs), 1, cbp == 4 ? 2 : 1, (hipStream_t)stream, nullptr, true);
   if (!mask_act && prec == JCK_PREC_BF16 && cbp == 4 && Cs == 64 && OW % 16 == 0 && is_pow2(OH))
     return launch_img_down(big, w, small_out, stats, stats_slots, N, Hb, Wb, p.flops, (hipStream_t)stream);
   return launch_igemm(prec, p, jck_pad_rows(Cs), 1, cbp == 4 ? 2 : (mask_act && cbp < 64 ? 0 : 1), (hipStream_t)stream, stats_slots);
@@ -316,6 +333,21 @@ extern "C" int jck_conv_down_mask(int prec, const void* big, const void* w, cons
   if (!a_small || !scale) JCK_FAIL(JCK_E_ARG, "conv_down_mask: the activation and the scale are required");
   if (!is_pow2(Cs)) JCK_FAIL(JCK_E_ARG, "conv_down_mask: Cs must be a power of two");
   return conv_down_impl(prec, big, w, small_out, nullptr, nullptr, N, Hb, Wb, Cb, Cs, stream, 0, a_small, scale);
+}
+// D's stage at inference: jck_conv_down with an eval-mode BatchNorm (folded by jck_bn_eval_aux) and the LeakyReLU applied to the fp32
+// accumulators, t = fmaf(scale[c], acc, shift[c]), out = t > 0 ? t : t * slope, before the one rounding of the store.  Never the persistent
+// kernels or the image-side streaming kernel: Cb = 4 runs on the register-staged 64 x 128 tile in every precision.
+extern "C" int jck_conv_down_affine(int prec, const void* big, const void* w, const float* scale, const float* shift, float slope,
+                                    void* small_out, int N, int Hb, int Wb, int Cb, int Cs, void* stream) {
+  if (!big || !w || !small_out || !scale || !shift) JCK_FAIL(JCK_E_ARG, "conv_down_affine: null tensor, scale or shift");
+  if (N < 1) JCK_FAIL(JCK_E_ARG, "conv_down_affine: N must be >= 1");
+  if (!is_pow2(Cs) || Cs < 64) JCK_FAIL(JCK_E_ARG, "conv_down_affine: Cs must be a power of two >= 64");
+  if (Cb == 3 || Cb == 4) {
+    if (Cs != 64) JCK_FAIL(JCK_E_ARG, "conv_down_affine: a 3 / 4-channel input is built for Cs = 64");
+  } else if (Cb < 64 || !is_pow2(Cb)) {
+    JCK_FAIL(JCK_E_ARG, "conv_down_affine: Cb must be 3, 4 or a power of two >= 64");
+  }
+  return conv_down_impl(prec, big, w, small_out, nullptr, nullptr, N, Hb, Wb, Cb, Cs, stream, 0, nullptr, nullptr, scale, shift, slope);
 }
 extern "C" int jck_conv_down(int prec, const void* big, const void* w, void* small_out, float* stats, int* stats_slots,
                              int N, int Hb, int Wb, int Cb, int Cs, void* stream) {

@@ -4,6 +4,8 @@
     python generate.py -m CGAN --checkpoint best.pt --num 8 --classes 3,17,42 --truncation 0.7 --out samples
     python generate.py -m DCGAN --checkpoint best.pt --interpolate 4:8 --which ema --calibrate 20 --out samples
     python generate.py -m DCGAN --checkpoint best.pt --project samples/images.npz --project_steps 300 --out projected
+    python generate.py -m DCGAN --checkpoint best.pt --num 64 --select top --oversample 8 --score --out best_of
+    python generate.py -m DCGAN --checkpoint best.pt --score_images samples/images.npz --out scored
 
 Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
 BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
@@ -13,7 +15,11 @@ running statistics to the averaged weights (in this process only; the file is no
 --project FILE.npz fits a latent to every picture of the file's `images` array (uint8 [n,S,S,3]: an images.npz of this tool, or any
 such array; a CGAN takes the file's `labels` or cycles through --classes) by Adam through the frozen eval-mode generator and writes
 <out>/projected.npz (z: fp32 [n,100]; loss: the mean squared error of each reconstruction in [-1, 1] units; images: the
-reconstructions, uint8) and <out>/projected.png, each row of targets above the row of their reconstructions."""
+reconstructions, uint8) and <out>/projected.png, each row of targets above the row of their reconstructions.
+The checkpoint's discriminator (`model_d`), as under Discriminator.eval(): --score adds `logit` and `prob` fp32 [N] to images.npz;
+--select top|drs with --oversample M keeps the --num best of M * --num draws, or runs discriminator rejection sampling with rounds
+of that size (Sampler.images; a CGAN ranks within one class: --classes ID, else one drawn from the seed); --score_images FILE.npz scores an existing uint8 `images` array into <out>/scores.npz (logit, prob).
+Whether the discriminator's running statistics make it a good ranker is a property of the run that trained it."""
 import argparse
 import os
 import sys
@@ -40,6 +46,10 @@ def get_arg_parse(argv=None):
     p.add_argument("--project_steps", type=int, default=200, help="Adam updates per image")
     p.add_argument("--project_lr", type=float, default=0.05)
     p.add_argument("--project_prior", type=float, default=0.0, help="weight of mean(z^2) beside the image loss")
+    p.add_argument("--score", action="store_true", help="add the discriminator's logit and prob of every image to images.npz")
+    p.add_argument("--select", choices=["top", "drs"], default=None, help="keep the best / rejection-sample by the discriminator's score")
+    p.add_argument("--oversample", type=int, default=None, metavar="M", help="with --select: draws per image kept (top), per round (drs)")
+    p.add_argument("--score_images", default=None, metavar="FILE.npz", help="score the uint8 [n,S,S,3] `images` array of this file")
     p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     p.add_argument("--out", required=True, help="output directory")
     a = p.parse_args(argv)
@@ -49,6 +59,18 @@ def get_arg_parse(argv=None):
         p.error("--project takes its images from the file; --num, --interpolate and --truncation do not go with it")
     if a.project_steps < 1 or not a.project_lr > 0 or a.project_prior < 0:
         p.error("--project_steps must be >= 1, --project_lr > 0, --project_prior >= 0")
+    if a.select and (a.oversample is None or a.oversample < 1):
+        p.error("--select needs --oversample M with M >= 1")
+    if a.oversample is not None and not a.select:
+        p.error("--oversample goes with --select")
+    if a.select and (a.interpolate or a.project or a.bn != "running"):
+        p.error("--select draws its own latents under --bn running; --interpolate, --project and --bn batch do not go with it")
+    if a.select and a.classes and len(a.classes) != 1:
+        p.error("--select ranks within ONE class: give --classes a single id (scores of different classes do not compare)")
+    if a.score_images and (a.interpolate or a.project or a.select or a.score or a.num is not None or a.truncation is not None):
+        p.error("--score_images takes its images from the file; the sampling options do not go with it")
+    if a.score and (a.project or a.bn != "running"):
+        p.error("--score scores the eval-mode generator's images: not with --project or --bn batch")
     if a.num is None:
         a.num = 64
     if a.num < 1 or a.batch_size < 1 or a.calibrate < 0:
@@ -78,6 +100,17 @@ def parse_interpolate(s):
     if pairs < 1 or steps < 2:
         raise argparse.ArgumentTypeError("PAIRS >= 1 and STEPS >= 2")
     return pairs, steps
+
+
+def needs_discriminator(args):
+    return bool(args.score or args.select or args.score_images)
+
+
+def check_checkpoint(args, ckpt):
+    """Refuses, before any engine exists, a run whose flags need a discriminator the checkpoint does not have."""
+    from hipgan.sampler import pick_discriminator_state
+    if needs_discriminator(args):
+        pick_discriminator_state(ckpt)
 
 
 def plan(args):
@@ -146,21 +179,65 @@ def main(argv=None):
     args = get_arg_parse(argv)
     from hipgan.sampler import Sampler
     from train.gan_trainer import _encode_png
-    s = Sampler.from_checkpoint(args.checkpoint, args.model, which=args.which, prec=args.prec, batch=args.batch_size)
+    with_d = needs_discriminator(args)
+    ckpt = args.checkpoint
+    if with_d:
+        ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
+        check_checkpoint(args, ckpt)
+    s = Sampler.from_checkpoint(ckpt, args.model, which=args.which, prec=args.prec, batch=args.batch_size, **({"with_d": True} if with_d else {}))
     if args.calibrate:
         s.calibrate(args.calibrate, seed=args.seed + 2)
     if args.project:
         return project_main(args, s)
-    z, cls, per_row = plan(args)
-    u8 = s.from_latents(z, cls, bn=args.bn, out="uint8").cpu().numpy()
+    if args.score_images:
+        return score_main(args, s)
+    if args.select:
+        cls = None
+        if args.model == "CGAN":          # one class for the whole run (--classes ID, else drawn from the seed): scores of different classes do not compare
+            cls = torch.tensor(args.classes) if args.classes else torch.randint(0, 100, (1,), generator=torch.Generator().manual_seed(args.seed + 1))
+        img, info = s.images(args.num, seed=args.seed, truncation=args.truncation, labels=cls, select=args.select,
+                             oversample=args.oversample, return_info=True)
+        u8, z, per_row, scores = img.cpu().numpy(), info["z"], 8, (info["logit"], info["prob"])
+        cls = None if cls is None else cls.repeat(args.num)
+    else:
+        z, cls, per_row = plan(args)
+        if args.score:                    # the scores of exactly these pictures, from the generator pass that made them
+            img, *scores = s.from_latents_scored(z, cls, out="uint8")
+            u8 = img.cpu().numpy()
+        else:
+            u8 = s.from_latents(z, cls, bn=args.bn, out="uint8").cpu().numpy()
     os.makedirs(args.out, exist_ok=True)
     arrays = {"images": u8, "z": z.numpy()}
     if cls is not None:
         arrays["labels"] = cls.numpy().astype(np.int64)
+    if args.score:
+        arrays["logit"], arrays["prob"] = scores[0].cpu().numpy(), scores[1].cpu().numpy()
     np.savez(os.path.join(args.out, "images.npz"), **arrays)
     with open(os.path.join(args.out, "grid.png"), "wb") as f:
         f.write(_encode_png(grid_u8(u8, per_row)))
     print(f"{u8.shape[0]} images ({s.which} generator, bn={args.bn}) -> {args.out}/images.npz, grid.png")
+    return 0
+
+
+def score_main(args, s):
+    from hipgan._lib import JckError
+    from hipgan.sampler import load_projection_targets
+    u8, labels = load_projection_targets(args.score_images)
+    cls = None
+    if args.model == "CGAN":
+        if args.classes:
+            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(u8.shape[0])])
+        elif labels is not None:
+            cls = labels.to(torch.int64).view(-1)
+        else:
+            raise JckError(f"{args.score_images} has no 'labels' array: a CGAN discriminator needs it, or --classes")
+    logit, prob = s.score(u8, cls)
+    os.makedirs(args.out, exist_ok=True)
+    arrays = {"logit": logit.cpu().numpy(), "prob": prob.cpu().numpy()}
+    if cls is not None:
+        arrays["labels"] = cls.numpy().astype(np.int64)
+    np.savez(os.path.join(args.out, "scores.npz"), **arrays)
+    print(f"{u8.shape[0]} images scored (mean prob {float(prob.mean()):.4f}) -> {args.out}/scores.npz")
     return 0
 
 

@@ -39,6 +39,8 @@ PROTOS = {
     "jck_conv_up_affine": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "jck_g1_fwd_affine": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "jck_conv_down_mask": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "jck_conv_down_affine": (i32, [i32, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp]),
+    "jck_score_head": (i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "jck_latent_loss": (i32, [i32, vp, vp, vp, vp, i32, i32, vp]),
     "jck_latent_adam": (i32, [i32, vp, i32, i32, vp, vp, vp, f32, f32, i32, vp, i32, i32, vp]),
     "jck_bn_eval_aux": (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), f32, vp]),
@@ -126,6 +128,7 @@ PROTOS = {
     "jck_engine_sample_ex": (i32, [vp, vp, vp, i32, C.c_uint, vp, vp, vp]),
     "jck_engine_latent_grad": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "jck_engine_project": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, i32, vp, vp]),
+    "jck_engine_score": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "jck_engine_tensor": (vp, [vp, C.c_char_p, C.POINTER(i64)]),
     "jck_debug_tr_read": (i32, [vp, i32, vp, vp]),
     "jck_tune": (i32, [C.c_char_p, i32]),

@@ -121,7 +121,7 @@ class DcganEngine:
         self.batch = batch
         self.size = image_size if share is None else share.size
         self.gp_backward = (bool(gp_backward) if share is None else share.gp_backward) or self.family == 1
-        self._shared = share._shared if share is not None else {"t": 0, "version": 0, "last_step": 0}
+        self._shared = share._shared if share is not None else {"t": 0, "version": 0, "last_step": 0, "d_loaded": False}
         if share is not None:
             self.ema_decay, self.ema_start = share.ema_decay, share.ema_start
         else:
@@ -273,6 +273,8 @@ class DcganEngine:
                 if k not in views:
                     raise JckError(f"unexpected key {k}")
                 views[k].copy_(v.detach().to(self.device).view(views[k].shape))
+        if d_state:
+            self._shared["d_loaded"] = True
         if "g_ema" in self.arenas:
             self.reset_ema()
         self.mark_weights_changed()
@@ -327,6 +329,7 @@ class DcganEngine:
                     for part in path:
                         owner = getattr(owner, part)
                     owner._buffers[leaf] = views[name]
+        self._shared["d_loaded"] = True
         if "g_ema" in self.arenas:
             self.reset_ema()
         self.mark_weights_changed()
@@ -605,6 +608,7 @@ class DcganEngine:
         runs under ~0.13 ms of compute that needs no G weights, instead of being waited for at once; the next step_async call
         must be given that same batch.  Results are bitwise those of the plain order (PHASE_D_REAL_FWD, include/jckgan.h)."""
         self._training_only("step_async")
+        self._shared["d_loaded"] = True             # a trained discriminator is a discriminator to score with
         if self._packed_version != self._shared["version"]:
             self.join()
             self.repack()
@@ -903,6 +907,104 @@ class DcganEngine:
         self._keep_z = (z, lab, t)
         self.project_state = {"m": m, "v": v, "t": t0 + int(steps)}
         return z, hist
+
+    def _score_ready(self, what):
+        if not self._shared.get("d_loaded"):
+            raise JckError(f"{what}: this engine's discriminator was never loaded or trained (load_state with a model_d state, "
+                           f"Sampler.from_checkpoint(..., with_d=True)); it would score with all-zero weights")
+        self.join()
+        if self._packed_version != self._shared["version"]:
+            self.repack()
+
+    def _score_labels(self, what, labels, n):
+        if self.family != 1:
+            return None
+        if labels is None or tuple(labels.shape) != (n, 100):
+            raise JckError(f"CGAN {what} needs one-hot int64 labels [n,100]")
+        return labels.to(self.device, torch.int64).contiguous()
+
+    def score(self, images, labels=None, noise=None):
+        """(logit [n], prob [n]) fp32 on the device: the discriminator as under model.eval() - BatchNorm on its running statistics,
+        Dropout the identity - so every image is scored on its own and nothing of the training state is written.
+        images: fp32 NCHW [n,3,S,S] in [-1, 1], or uint8 NHWC [n,S,S,3] (taken as u8 / 127.5 - 1, hipgan.sampler.images_to_target);
+        noise: None, or a tensor shaped like the fp32 images - D then sees 0.9 * image + 0.1 * noise, the trainers' instance noise.
+        Any n: rows go through in chunks of at most `batch`, each row's numbers those of a call with that row alone."""
+        from .sampler import images_to_target
+        x = images_to_target(images)
+        n = x.shape[0]
+        if x.shape[2] != self.size:
+            raise JckError(f"score: images are {x.shape[2]}x{x.shape[2]}, this discriminator takes {self.size}x{self.size}")
+        lab = self._score_labels("score", labels, n)
+        nz = None
+        if noise is not None:
+            if tuple(noise.shape) != tuple(x.shape):
+                raise JckError(f"score: noise must be shaped like the images {tuple(x.shape)}, got {tuple(noise.shape)}")
+            nz = noise.to(self.device, torch.float32).contiguous()
+        self._score_ready("score")
+        x = x.to(self.device, torch.float32).contiguous()
+        logit = torch.empty(n, dtype=torch.float32, device=self.device)
+        prob = torch.empty(n, dtype=torch.float32, device=self.device)
+        for lo, hi in chunk_plan(n, self.batch):
+            lib.jck_engine_score(self._h, x[lo:hi], None if nz is None else nz[lo:hi], None if lab is None else lab[lo:hi], hi - lo,
+                                 logit[lo:hi], prob[lo:hi], cur_stream())
+        self._keep_score = (x, nz, lab)
+        return logit, prob
+
+    def score_latents(self, z, labels=None):
+        """(logit [n], prob [n]) of D(G(z)), both networks as under model.eval(): per chunk of at most `batch` rows the eval-mode
+        generator (sample(bn="running")) leaves its images on the device and the discriminator scores them where they lie."""
+        n = z.shape[0]
+        if n < 1:
+            raise JckError("score_latents: z is empty")
+        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
+        if zc.shape[0] != n:
+            raise JckError("score_latents: z must be [n,100]")
+        lab = self._score_labels("score_latents", labels, n)
+        self._score_ready("score_latents")
+        logit = torch.empty(n, dtype=torch.float32, device=self.device)
+        prob = torch.empty(n, dtype=torch.float32, device=self.device)
+        for lo, hi in chunk_plan(n, self.batch):
+            lc = None if lab is None else lab[lo:hi]
+            lib.jck_engine_sample_ex(self._h, zc[lo:hi], lc, hi - lo, SAMPLE_EVAL, None, None, cur_stream())
+            lib.jck_engine_score(self._h, None, None, lc, hi - lo, logit[lo:hi], prob[lo:hi], cur_stream())
+        self._keep_score = (zc, lab)
+        return logit, prob
+
+    def sample_scored(self, z, labels=None, out="float"):
+        """(images, logit [n], prob [n]): sample(z, bn="running", out=out) and score_latents(z) from ONE generator pass per chunk."""
+        if out not in ("float", "uint8"):
+            raise JckError(f"sample_scored: out must be 'float' or 'uint8', got {out!r}")
+        n = z.shape[0]
+        if n < 1:
+            raise JckError("sample_scored: z is empty")
+        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
+        if zc.shape[0] != n:
+            raise JckError("sample_scored: z must be [n,100]")
+        lab = self._score_labels("sample_scored", labels, n)
+        self._score_ready("sample_scored")
+        shape, dt = ((n, self.size, self.size, 3), torch.uint8) if out == "uint8" else ((n, 3, self.size, self.size), torch.float32)
+        res = torch.empty(shape, dtype=dt, device=self.device)
+        logit = torch.empty(n, dtype=torch.float32, device=self.device)
+        prob = torch.empty(n, dtype=torch.float32, device=self.device)
+        for lo, hi in chunk_plan(n, self.batch):
+            lc = None if lab is None else lab[lo:hi]
+            lib.jck_engine_sample_ex(self._h, zc[lo:hi], lc, hi - lo, SAMPLE_EVAL, res[lo:hi] if out == "float" else None,
+                                     res[lo:hi] if out == "uint8" else None, cur_stream())
+            lib.jck_engine_score(self._h, None, None, lc, hi - lo, logit[lo:hi], prob[lo:hi], cur_stream())
+        self._keep_score = (zc, lab)
+        return res, logit, prob
+
+    def score_current(self, n, labels=None):
+        """(logit [n], prob [n]) of the n images the generator produced last (sample(...) just before), scored where they lie."""
+        if not 1 <= n <= self.batch:
+            raise JckError(f"score_current: n must be in [1, {self.batch}]")
+        lab = self._score_labels("score_current", labels, n)
+        self._score_ready("score_current")
+        logit = torch.empty(n, dtype=torch.float32, device=self.device)
+        prob = torch.empty(n, dtype=torch.float32, device=self.device)
+        lib.jck_engine_score(self._h, None, None, lab, n, logit, prob, cur_stream())
+        self._keep_score = (lab,)
+        return logit, prob
 
     def tensor(self, name):
         """Debug/parity view of an internal NHWC tensor as a torch tensor (copy)."""

@@ -30,6 +30,55 @@ def pick_generator_state(ckpt, which="auto"):
     return ckpt["model_g"], "live"
 
 
+def pick_discriminator_state(ckpt):
+    """The discriminator state dict of a checkpoint dict ('model_d')."""
+    if not isinstance(ckpt, dict) or "model_d" not in ckpt:
+        raise JckError("checkpoint has no 'model_d' entry: scoring and score-guided sampling need the trained discriminator")
+    d = ckpt["model_d"]
+    if not isinstance(d, dict) or not d:
+        raise JckError("checkpoint's 'model_d' is empty: scoring and score-guided sampling need the trained discriminator")
+    return d
+
+
+def _f64(x):
+    """a flat fp64 host copy (Python numbers are taken as fp64, not rounded to the default fp32)"""
+    t = x.detach().double() if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=torch.float64)
+    return t.reshape(-1).cpu()
+
+
+def select_top(logits, keep):
+    """Indices (int64 [keep], best first) of the `keep` largest logits; ties go to the lower index, NaN is never selected."""
+    l = _f64(logits)
+    keep = int(keep)
+    if keep < 0:
+        raise JckError(f"select_top: keep must be >= 0, got {keep}")
+    ok = ~torch.isnan(l)
+    finite = int(ok.sum())
+    if finite < keep:
+        raise JckError(f"select_top: {keep} wanted, only {finite} of {l.numel()} logits are numbers")
+    key = torch.where(ok, l, torch.full_like(l, -math.inf))
+    order = torch.sort(key, descending=True, stable=True).indices      # stable: equal logits keep their index order
+    order = order[ok[order]]                                            # (a -inf logit is a number; a NaN sorted beside it is not)
+    return order[:keep]
+
+
+def drs_f(logits, max_logit, gamma, eps=1e-8):
+    """F of discriminator rejection sampling (Azadi et al. 2019, eq. 8) in fp64:
+    F = (l - M) - log(1 - exp(l - M - eps)) - gamma, l clamped to M; NaN stays NaN."""
+    l = _f64(logits)
+    d = torch.clamp(l - float(max_logit), max=0.0)                      # (clamp passes NaN)
+    return d - torch.log(1.0 - torch.exp(d - float(eps))) - float(gamma)
+
+
+def drs_accept(logits, max_logit, gamma, u, eps=1e-8):
+    """bool [n]: sample i is accepted where u[i] < sigmoid(F_i) (drs_f); a NaN logit is rejected."""
+    f = drs_f(logits, max_logit, gamma, eps)
+    uu = _f64(u)
+    if uu.shape != f.shape:
+        raise JckError(f"drs_accept: {uu.numel()} uniforms for {f.numel()} logits")
+    return (uu < torch.sigmoid(f)) & ~torch.isnan(f)
+
+
 def image_size_of(g_state):
     """64 for the reference's five-layer generator, 128 for the six-layer plan."""
     n = sum(1 for k in g_state if k.startswith("conv") and k.endswith(".weight"))
@@ -38,10 +87,10 @@ def image_size_of(g_state):
     return 64 if n == 5 else 128
 
 
-def latents(n, seed, truncation=None):
+def latents(n, seed, truncation=None, generator=None):
     """z [n,100] fp32 on the host from a seeded torch.Generator; truncation t: a standard normal truncated to [-t, t]
-    (torch.nn.init.trunc_normal_)."""
-    g = torch.Generator().manual_seed(int(seed))
+    (torch.nn.init.trunc_normal_).  generator: continue this stream instead of starting one from `seed`."""
+    g = torch.Generator().manual_seed(int(seed)) if generator is None else generator
     if truncation is None:
         return torch.randn(n, NZ, generator=g)
     t = float(truncation)
@@ -121,8 +170,9 @@ class Sampler:
         self.conditional = engine.family == 1
 
     @classmethod
-    def from_checkpoint(cls, path, model="DCGAN", which="auto", prec="bf16", batch=64, device="cuda:0"):
-        """path: a file written by the trainers' save_model (or the reference's), or the dict itself."""
+    def from_checkpoint(cls, path, model="DCGAN", which="auto", prec="bf16", batch=64, device="cuda:0", with_d=False):
+        """path: a file written by the trainers' save_model (or the reference's), or the dict itself.
+        with_d: load the checkpoint's discriminator too ('model_d'), for score() and images(select=...)."""
         if model not in ("DCGAN", "CGAN"):
             raise JckError(f"model must be 'DCGAN' or 'CGAN', got {model!r}")
         if not torch.cuda.is_available():
@@ -133,7 +183,12 @@ class Sampler:
         size = image_size_of(g_state)
         kw = {"image_size": size} if size != 64 else {}
         eng = (CganEngine if model == "CGAN" else DcganEngine)(batch=batch, prec=prec, device=device, **kw)
-        eng.load_state(g_state, {})            # the chosen generator is this engine's generator; its D stays unset and unused
+        d_state = pick_discriminator_state(ckpt) if with_d else {}
+        if with_d:
+            kind = "CGAN" if "linear1.weight" in d_state else "DCGAN"
+            if kind != model:
+                raise JckError(f"checkpoint's 'model_d' is a {kind} discriminator, the sampler was asked for {model}")
+        eng.load_state(g_state, d_state)       # the chosen generator is this engine's generator; without with_d its D stays unset
         return cls(eng, picked)
 
     def _labels(self, labels, n):
@@ -158,9 +213,92 @@ class Sampler:
         return torch.cat([self.engine.sample(z[lo:hi], None if lab is None else lab[lo:hi], bn=bn, out=out)
                           for lo, hi in chunk_plan(z.shape[0], self.engine.batch)])
 
-    def images(self, n, seed=0, truncation=None, labels=None, bn="running", out="uint8"):
-        """n images from z = latents(n, seed, truncation): uint8 [n,S,S,3] or fp32 [n,3,S,S] on the device."""
-        return self.from_latents(latents(n, seed, truncation), labels, bn, out)
+    def images(self, n, seed=0, truncation=None, labels=None, bn="running", out="uint8", select=None, oversample=4,
+               gamma_percentile=80.0, return_info=False):
+        """n images from z = latents(n, seed, truncation): uint8 [n,S,S,3] or fp32 [n,3,S,S] on the device.
+
+        select (needs the discriminator: from_checkpoint(..., with_d=True); eval-mode BatchNorm; labels: None or ONE class id / one-hot
+        row for all draws of a CGAN): "top" draws oversample * n latents from the seeded stream and keeps the n the discriminator
+        scores highest (best first); "drs" is discriminator rejection sampling (Azadi et al. 2019): one burn-in draw of oversample * n
+        fixes M (its largest logit) and gamma (the gamma_percentile-th percentile of F at gamma = 0), then rounds of oversample * n
+        latents and uniforms from the same seeded generator are accepted where u < sigmoid(F) until n are kept - at most 50 * n
+        draws after the burn-in, JckError beyond.  Deterministic for a seed.
+        return_info: (images, {"z": [n,100], "logit": [n], "prob": [n], "drawn": latents drawn, "max_logit", "gamma"})."""
+        if select is None:
+            z = latents(n, seed, truncation)
+            img = self.from_latents(z, labels, bn, out)
+            return (img, {"z": z, "logit": None, "prob": None, "drawn": n}) if return_info else img
+        if select not in ("top", "drs"):
+            raise JckError(f"select must be None, 'top' or 'drs', got {select!r}")
+        if bn != "running":
+            raise JckError("score-guided sampling scores the eval-mode generator: bn must be 'running'")
+        n, m = int(n), int(oversample)
+        if n < 1 or m < 1:
+            raise JckError(f"select={select!r}: n >= 1 and oversample >= 1, got {n}, {oversample}")
+        if not 0.0 <= float(gamma_percentile) <= 100.0:
+            raise JckError(f"gamma_percentile must lie in [0, 100], got {gamma_percentile}")
+        if select == "drs" and m > 50:
+            raise JckError(f"select='drs': oversample {m} exceeds the cap of 50 * n draws in its first round; use oversample <= 50")
+        g = torch.Generator().manual_seed(int(seed))
+        draw = lambda k: latents(k, seed, truncation, generator=g)          # successive pieces of ONE seeded stream
+
+        def lab_for(k):
+            if not self.conditional:
+                return None
+            if labels is None:
+                raise JckError("a CGAN sampler needs labels (one class id or one one-hot row for score-guided sampling)")
+            lab = torch.as_tensor(labels)
+            lab = one_hot(lab.view(-1)) if lab.dim() <= 1 else lab.to(torch.int64)
+            if lab.shape != (1, N_CLASS):
+                raise JckError("score-guided sampling of a CGAN takes ONE class (an id or a [1,100] one-hot row)")
+            return lab.expand(k, N_CLASS).contiguous()
+
+        info = {}
+        if select == "top":
+            z = draw(m * n)
+            logit, prob = (t.cpu() for t in self.engine.score_latents(z, lab_for(m * n)))
+            idx = select_top(logit, n)
+            zk, lk, pk, drawn = z[idx], logit[idx], prob[idx], m * n
+        else:
+            burn = self.engine.score_latents(draw(m * n), lab_for(m * n))[0].cpu()
+            finite = burn[~torch.isnan(burn)].double()
+            if finite.numel() == 0:
+                raise JckError("select='drs': every burn-in logit is NaN")
+            M = float(finite.max())
+            gamma = float(torch.quantile(drs_f(finite, M, 0.0), float(gamma_percentile) / 100.0))
+            zs, ls, ps, drawn, kept = [], [], [], 0, 0
+            while kept < n:
+                if drawn + m * n > 50 * n:
+                    raise JckError(f"select='drs': {kept} of {n} accepted after {drawn} draws (cap 50 * n); lower gamma_percentile")
+                z = draw(m * n)
+                u = torch.rand(m * n, generator=g, dtype=torch.float64)
+                logit, prob = (t.cpu() for t in self.engine.score_latents(z, lab_for(m * n)))
+                acc = drs_accept(logit, M, gamma, u)
+                zs.append(z[acc]); ls.append(logit[acc]); ps.append(prob[acc])
+                drawn += m * n
+                kept += int(acc.sum())
+            zk, lk, pk = torch.cat(zs)[:n], torch.cat(ls)[:n], torch.cat(ps)[:n]
+            info.update(max_logit=M, gamma=gamma, burn_in=m * n)
+        img = self.from_latents(zk, None if not self.conditional else lab_for(n), "running", out)
+        info.update(z=zk, logit=lk, prob=pk, drawn=drawn)
+        return (img, info) if return_info else img
+
+    def from_latents_scored(self, z, labels=None, out="uint8"):
+        """(images, logit [n], prob [n]): the eval-mode generator's images of z and the discriminator's scores of exactly those
+        images, each chunk scored where the generator left it - G runs once."""
+        z = z.reshape(-1, NZ)
+        return self.engine.sample_scored(z, self._labels(labels, z.shape[0]), out=out)
+
+    def score(self, images, labels=None):
+        """(logit [n], prob [n]) on the device: the checkpoint's discriminator under model.eval() on uint8 NHWC or fp32 NCHW images
+        (DcganEngine.score).  Needs from_checkpoint(..., with_d=True)."""
+        n = torch.as_tensor(images).shape[0]
+        return self.engine.score(images, self._labels(labels, n))
+
+    def score_latents(self, z, labels=None):
+        """(logit [n], prob [n]) of D(G(z)), both networks in eval mode, the images never leaving the device."""
+        z = z.reshape(-1, NZ)
+        return self.engine.score_latents(z, self._labels(labels, z.shape[0]))
 
     def interpolate(self, z0, z1, steps, labels=None, bn="running", out="uint8"):
         return self.from_latents(slerp(z0.reshape(NZ), z1.reshape(NZ), steps).float(), labels, bn, out)
