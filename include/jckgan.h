@@ -299,6 +299,13 @@ int jck_gp_head2(int prec, const void* ughd, const float* w2, const float* prob,
 size_t jck_gp_head2_conv_ws_floats(int B);
 int jck_gp_head2_conv(int prec, const void* v4, const void* a4, const float* wp, const float* prob, int B, int C, float* rs,
                       void* g_a4, float* grad, float* ws, void* stream);
+/* Second-order BatchNorm steps of the back-propagated penalty at one layer (closed form: tests/bn_ref.py, held to fp64 autograd in
+ * tests/test_bn2_math.py; aux, y as in the first backward, gy and s1 = {sum g_z, sum g_z*xhat} what jck_bn_act_bwd left).
+ * jck_bn2_vchain: u (may alias v) and xdir from the adjoint v of gy; ws[0..3C) = {sum v, sum v*xhat, sum v*gy} on return (keep it
+ * for jck_bn2_reverse); dgamma (optional) += sum v*gy / gamma.  g_z is reconstructed as gy / (gamma / sigma): gamma ≠ 0.
+ * jck_bn2_reverse: uy from the adjoint ua of the activation, xdir and vsums = the v-chain's ws; ws[0..4C) = {sum uz, sum uz*xhat,
+ * sum xdir, sum xdir*xhat}; dgamma += sum uz*xhat and dbeta += sum uz when BOTH are given (neither is written otherwise).
+ * ws: jck_bn2_ws_floats(C) floats each, no zeroing needed; C a power of two in [8, 2048]. */
 size_t jck_bn2_ws_floats(int C);
 int jck_bn2_vchain(int prec, const void* v, const void* y, const void* gy, const float* aux, const float* s1, const float* gamma,
                    float slope, float* ws, void* u, void* xdir, float* dgamma, long long rows, int C, void* stream);
