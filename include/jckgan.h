@@ -516,6 +516,25 @@ int jck_knn_radius2_f32(const float* x, int N, int D, int k, float* r2, void* st
  * A reference row whose radius is NaN never hits. */
 int jck_manifold_hit_u8(const float* q, int M, const float* ref, const float* r2, int N, int D, unsigned char* hit, void* stream);
 
+/* Nearest reference rows WITH their indices (memorisation checks: a sample beside its nearest training images).  For every
+ * query row q_i the k (1..8) rows of ref[N][D] with the smallest squared Euclidean distance, ascending by (d2, index): equal
+ * distances go to the lower index.  idx[i][t] = ref_base + j (or -1), d2[i][t] its distance.  Two stages on the device: the 8
+ * smallest Gram distances max(0, (|a|^2 + |b|^2) - 2 G) per query pick the candidates (the tile core above; the walk over the
+ * references is split over the grid, partial lists go to ws and merge in a fixed order - no atomics, two runs give the same
+ * bits); each candidate's distance is then recomputed from differences, sum_c (q_c - ref_c)^2 in fp32 in a fixed order, so that
+ * |d2 - exact| <= (D + 4) 2^-24 exact even for a near copy, where the Gram form has no correct digit left.
+ *   exclude_self != 0   leaves out the pair with q_base + i == ref_base + j (by index: a duplicate row elsewhere stays a
+ *                       neighbour at distance 0)
+ *   merge != 0          idx / d2 come in holding earlier results (real distances, tail-padded as below) and are merged by
+ *                       (d2, idx): a reference set fed in chunks with the right ref_base gives the one-call result
+ *   fewer than k eligible references: the tail is idx -1 / d2 +inf.  A query row with a non-finite norm: idx -1 / d2 NaN in
+ *   all k places.  A reference row with a non-finite norm is never a neighbour.
+ * jck_knn_index_ws_bytes: bytes of ws for M queries against N references in one call (host only; 0 for sizes the entry point
+ * refuses). */
+size_t jck_knn_index_ws_bytes(int M, int N);
+int jck_knn_index_f32(const float* q, int M, const float* ref, int N, int D, int k, long long q_base, long long ref_base,
+                      int exclude_self, int merge, long long* idx, float* d2, void* ws, void* stream);
+
 /* Per-step optimiser scalars into device memory (so that a captured graph of the step has no per-step kernel argument), and
  * hipGraph capture of a sequence of jck_engine_phase calls: begin -> phases on `stream` (not the default stream) -> end
  * returns an executable graph; launch replays it.  The jck_step_inputs pointers are baked: keep the buffers in place,

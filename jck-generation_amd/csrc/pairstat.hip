@@ -7,6 +7,8 @@
 //   jck_manifold_hit_u8   hit[i] = 1 when q_i lies inside the k-NN ball of some reference row
 //   jck_pairstat_ws_bytes workspace of the first (host only)
 //
+// (The nearest rows WITH their indices, jck_knn_index_f32, live in knnindex.hip over the same tile geometry, pairtile.hpp.)
+//
 // One Gram-tile core serves the three: G[i][j] = sum_c a[i][c] * b[j][c] on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32,
 // bitwise an fmaf chain - the convolutions of infer.hip use it for the same reason), 64 x 64 per 256-thread workgroup, each
 // wave a 32 x 32 quarter as 2 x 2 accumulator fragments, c in steps of 16 through LDS rows of 20 floats ((20 m + k) % 64 is
@@ -21,11 +23,11 @@
 // a fixed order, one partial per workgroup into the caller's workspace, and a second one-workgroup launch adds the partials
 // in a fixed order.  Non-finite values: the sums carry them; a row with a non-finite norm gets radius NaN / hit 255, and a
 // NaN distance or radius compares false, so such a reference row is never a neighbour and never hit.
-#include "ops_internal.hpp"
+#include "pairtile.hpp"
 
 namespace {
 
-constexpr int PT = 64, PK = 16, PLD = 20, PSTRIP = 8, PKMAX = 8;
+constexpr int PSTRIP = 8;
 enum { EPI_POLY3 = 0, EPI_KNN = 1, EPI_HIT = 2 };
 
 struct PairP {
@@ -34,25 +36,6 @@ struct PairP {
   double gamma, coef0;
   double* ws; float* r2out; const float* r2in; unsigned char* hit;
 };
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// rows r0 .. r0+63, columns k0 .. k0+15 of p[R][D] into S[row][k]; zero outside the matrix
-__device__ __forceinline__ void stage_tile(float (*S)[PLD], const float* __restrict__ p, int R, int D, int r0, int k0, int vec, int tid) {
-  if (vec) {
-    const int row = tid >> 2, kq = (tid & 3) * 4, gr = r0 + row, c = k0 + kq;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (gr < R && c < D) v = *reinterpret_cast<const f32x4*>(p + (long long)gr * D + c);      // D % 4 == 0: c + 3 < D
-    *reinterpret_cast<f32x4*>(&S[row][kq]) = v;
-  } else {
-    const int k = tid & 15, c = k0 + k;
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      const int row = (tid >> 4) + 16 * ps, gr = r0 + row;
-      S[row][k] = (gr < R && c < D) ? p[(long long)gr * D + c] : 0.f;
-    }
-  }
-}
 
 // keeps the PKMAX smallest values seen, ascending (v is not NaN)
 __device__ __forceinline__ void keep_smallest(float (&L)[PKMAX], float v) {
@@ -211,12 +194,9 @@ __global__ __launch_bounds__(256) void sum_partials_f64_kernel(const double* __r
   if (threadIdx.x == 0) out[0] = sm[0];
 }
 
-constexpr int P_MAX_ROWS = 1 << 30;
-long long tiles_of(int n) { return ((long long)n + PT - 1) / PT; }
 // walked tiles per workgroup of the polynomial sum: PSTRIP, more only where the grid's y extent would overflow
 int strip_of(int M) { return (int)std::max<long long>(PSTRIP, (tiles_of(M) + 32767) / 32768); }
 long long strips_of(int M) { const int s = strip_of(M); return (tiles_of(M) + s - 1) / s; }
-int vec_ok(const float* a, const float* b, int D) { return D % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
 }  // namespace
 

@@ -6,6 +6,7 @@
     python generate.py -m DCGAN --checkpoint best.pt --project samples/images.npz --project_steps 300 --out projected
     python generate.py -m DCGAN --checkpoint best.pt --num 64 --select top --oversample 8 --score --out best_of
     python generate.py -m DCGAN --checkpoint best.pt --score_images samples/images.npz --out scored
+    python generate.py -m DCGAN --checkpoint best.pt --num 64 --neighbours train.npz --k 4 --out samples
 
 Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
 BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
@@ -19,7 +20,11 @@ reconstructions, uint8) and <out>/projected.png, each row of targets above the r
 The checkpoint's discriminator (`model_d`), as under Discriminator.eval(): --score adds `logit` and `prob` fp32 [N] to images.npz;
 --select top|drs with --oversample M keeps the --num best of M * --num draws, or runs discriminator rejection sampling with rounds
 of that size (Sampler.images; a CGAN ranks within one class: --classes ID, else one drawn from the seed); --score_images FILE.npz scores an existing uint8 `images` array into <out>/scores.npz (logit, prob).
-Whether the discriminator's running statistics make it a good ranker is a property of the run that trained it."""
+Whether the discriminator's running statistics make it a good ranker is a property of the run that trained it.
+--neighbours REF.npz (with a sampling run, or with --score_images, whose images it then takes) looks up the --k nearest images of
+REF's uint8 `images` array (the samples' size, or 32x32 training data, upscaled as the trainers do) for every sample, in pixel space:
+<out>/neighbours.npz (idx int64 [n,k]; d2 squared distance in [-1, 1] units; rmse = sqrt(d2 / D); ref_nn_d2: the nearest other
+reference image's d2 from the image idx[:,0]; copy = d2[:,0] < ref_nn_d2) and <out>/neighbours.png, each sample followed by its neighbours."""
 import argparse
 import os
 import sys
@@ -50,6 +55,8 @@ def get_arg_parse(argv=None):
     p.add_argument("--select", choices=["top", "drs"], default=None, help="keep the best / rejection-sample by the discriminator's score")
     p.add_argument("--oversample", type=int, default=None, metavar="M", help="with --select: draws per image kept (top), per round (drs)")
     p.add_argument("--score_images", default=None, metavar="FILE.npz", help="score the uint8 [n,S,S,3] `images` array of this file")
+    p.add_argument("--neighbours", default=None, metavar="REF.npz", help="nearest images of this file's uint8 `images` array for every sample")
+    p.add_argument("--k", type=int, default=4, help="with --neighbours: neighbours per sample (1..8)")
     p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     p.add_argument("--out", required=True, help="output directory")
     a = p.parse_args(argv)
@@ -71,6 +78,10 @@ def get_arg_parse(argv=None):
         p.error("--score_images takes its images from the file; the sampling options do not go with it")
     if a.score and (a.project or a.bn != "running"):
         p.error("--score scores the eval-mode generator's images: not with --project or --bn batch")
+    if a.neighbours and a.project:
+        p.error("--neighbours looks up sampled or given images: not with --project")
+    if not 1 <= a.k <= 8:
+        p.error("--k must lie in 1..8")
     if a.num is None:
         a.num = 64
     if a.num < 1 or a.batch_size < 1 or a.calibrate < 0:
@@ -180,6 +191,10 @@ def main(argv=None):
     from hipgan.sampler import Sampler
     from train.gan_trainer import _encode_png
     with_d = needs_discriminator(args)
+    ref = None
+    if args.neighbours:                   # a bad reference file ends the run before an engine exists
+        from hipgan.neighbours import load_reference_images
+        ref = load_reference_images(args.neighbours)
     ckpt = args.checkpoint
     if with_d:
         ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
@@ -190,7 +205,10 @@ def main(argv=None):
     if args.project:
         return project_main(args, s)
     if args.score_images:
-        return score_main(args, s)
+        return score_main(args, s, ref)
+    if ref is not None:                   # ... and one of the wrong size before anything is sampled
+        from hipgan.neighbours import upscale_steps
+        upscale_steps(ref.shape[1], s.engine.size, what=args.neighbours)
     if args.select:
         cls = None
         if args.model == "CGAN":          # one class for the whole run (--classes ID, else drawn from the seed): scores of different classes do not compare
@@ -216,13 +234,33 @@ def main(argv=None):
     with open(os.path.join(args.out, "grid.png"), "wb") as f:
         f.write(_encode_png(grid_u8(u8, per_row)))
     print(f"{u8.shape[0]} images ({s.which} generator, bn={args.bn}) -> {args.out}/images.npz, grid.png")
+    if ref is not None:
+        neighbours_main(args, s, u8, ref)
     return 0
 
 
-def score_main(args, s):
+def neighbours_main(args, s, u8, ref):
+    """--neighbours: the samples' nearest reference images -> <out>/neighbours.npz, neighbours.png and one line"""
+    from hipgan.neighbours import neighbour_rows, upscale_steps
+    from train.gan_trainer import _encode_png
+    steps = upscale_steps(ref.shape[1], u8.shape[1], what=args.neighbours)
+    r = s.neighbours(u8, ref, k=args.k)
+    os.makedirs(args.out, exist_ok=True)
+    np.savez(os.path.join(args.out, "neighbours.npz"), **{k_: r[k_] for k_ in ("idx", "d2", "rmse", "ref_nn_d2", "copy")})
+    with open(os.path.join(args.out, "neighbours.png"), "wb") as f:
+        f.write(_encode_png(grid_u8(neighbour_rows(u8, ref, r["idx"], steps), 1 + args.k)))
+    near = r["rmse"][:, 0]
+    print(f"neighbours: {int(r['copy'].sum())} of {u8.shape[0]} samples flagged as copies, nearest rmse min {float(np.nanmin(near)):.5f} "
+          f"median {float(np.nanmedian(near)):.5f} -> {args.out}/neighbours.npz, neighbours.png")
+
+
+def score_main(args, s, ref=None):
     from hipgan._lib import JckError
     from hipgan.sampler import load_projection_targets
     u8, labels = load_projection_targets(args.score_images)
+    if ref is not None:
+        from hipgan.neighbours import upscale_steps
+        upscale_steps(ref.shape[1], u8.shape[1], what=args.neighbours)
     cls = None
     if args.model == "CGAN":
         if args.classes:
@@ -238,6 +276,8 @@ def score_main(args, s):
         arrays["labels"] = cls.numpy().astype(np.int64)
     np.savez(os.path.join(args.out, "scores.npz"), **arrays)
     print(f"{u8.shape[0]} images scored (mean prob {float(prob.mean()):.4f}) -> {args.out}/scores.npz")
+    if ref is not None:
+        neighbours_main(args, s, u8.numpy(), ref)
     return 0
 
 

@@ -141,6 +141,8 @@ PROTOS = {
     "jck_poly3_sum_f64": (i32, [vp, i32, vp, i32, i32, f64, f64, i32, vp, vp, vp]),
     "jck_knn_radius2_f32": (i32, [vp, i32, i32, i32, vp, vp]),
     "jck_manifold_hit_u8": (i32, [vp, i32, vp, vp, i32, i32, vp, vp]),
+    "jck_knn_index_ws_bytes": (sz, [i32, i32]),
+    "jck_knn_index_f32": (i32, [vp, i32, vp, i32, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
     "jck_engine_set_step": (i32, [vp, i32, f32, vp]),
     "jck_engine_bind_ema": (i32, [vp, vp]),
     "jck_engine_set_ema": (i32, [vp, f64, i32]),

@@ -2,6 +2,7 @@
 
     s = Sampler.from_checkpoint("best.pt", "DCGAN")          # the averaged generator when the file has one
     u8 = s.images(1000, seed=0, truncation=0.7)                # uint8 [1000,S,S,3] on the device
+    r = s.neighbours(u8, train_u8, k=4)                        # nearest training images: r["idx"], r["rmse"], r["copy"]
 
 Sampling runs with bn="running" by default (DcganEngine.sample): BatchNorm on the running statistics, every image a function of
 its own z, any n.  The running statistics of an AVERAGED generator were never fitted to its weights - they are the live ones at
@@ -329,6 +330,12 @@ class Sampler:
             pick = best * n + torch.arange(n, device=best.device)
             z, loss = z[pick], loss[pick]
         return z, loss
+
+    def neighbours(self, images, ref, k=4, **kw):
+        """The k nearest reference (training) images of `images` in pixel space, both uint8 NHWC, and the `copy` flags
+        (hipgan.neighbours.nearest_images; on this sampler's device)."""
+        from .neighbours import nearest_images
+        return nearest_images(images, ref, k=k, device=self.engine.device, **kw)
 
     def calibrate(self, batches, seed=0):
         """`batches` train-mode sampling batches (full engine batches of fresh z, uniform random classes for a CGAN) through the

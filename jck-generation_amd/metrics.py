@@ -8,7 +8,8 @@ reference's network (inception_v3 with a Linear(2048,100) head, weights from ./s
 missing, construction raises MetricsUnavailable and the trainer carries on without scores.  Feature means and covariances are
 formed in fp64 on the device (jck_mean_cov_f64) when the features live there; the matrix square root stays on the host
 (scipy), as in the reference.  Beyond the reference (opt-in in the trainers): KID, intra-KID and improved precision / recall
-from pairwise kernels over the feature matrices (csrc/pairstat.hip; numpy fp64 for host arrays).  Fixes the reference's `.targets` defect for DCGAN (its loader has none): targets are optional."""
+from pairwise kernels over the feature matrices (csrc/pairstat.hip; numpy fp64 for host arrays), and the nearest real rows of
+given rows with their indices (csrc/knnindex.hip).  Fixes the reference's `.targets` defect for DCGAN (its loader has none): targets are optional."""
 import os
 import pickle
 
@@ -192,6 +193,67 @@ def manifold_hit(q, ref, r2):
                 hit[i:i + _HOST_BLOCK] |= (d2 <= r2[None, j:j + _HOST_BLOCK]).any(axis=1).astype(np.uint8)
     hit[~np.isfinite(nq)] = 255
     return hit
+
+
+def nearest(q, ref, k, exclude_self=False, chunk=None):
+    """(idx int64 [M,k], d2 [M,k]): the k rows of ref nearest to every row of q, ascending by (d2, index) - equal distances go to the
+    lower index.  exclude_self leaves out the pair i == j (by index: a duplicate row elsewhere stays a neighbour at distance 0).
+    Fewer than k eligible rows: the tail is idx -1 / d2 +inf; a non-finite query row: idx -1 / d2 NaN; a non-finite reference row is
+    never a neighbour.  CUDA (any argument a CUDA tensor): device tensors from jck_knn_index_f32 (1 <= k <= 8; fp32 distances from
+    differences, within (D + 4) 2^-24 relative), the reference walked `chunk` rows at a time and merged on the device; else float64 numpy."""
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError(f"nearest: k = {k} needs 1 <= k <= 8")
+    if q.ndim != 2 or ref.ndim != 2 or q.shape[1] != ref.shape[1] or q.shape[0] < 1 or ref.shape[0] < 1:
+        raise ValueError(f"nearest: q and ref must be non-empty [rows, D] matrices of one D, got {tuple(q.shape)} and {tuple(ref.shape)}")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError(f"nearest: chunk = {chunk} must be >= 1")
+    dev = _pair_device(q, ref)
+    m, n = q.shape[0], ref.shape[0]
+    step = n if chunk is None else min(n, int(chunk))
+    if dev is not None:
+        q = _dev32(q, dev)
+        idx = torch.empty(m, k, dtype=torch.int64, device=dev)
+        d2 = torch.empty(m, k, dtype=torch.float32, device=dev)
+        for lo in range(0, n, step):
+            nearest_chunk(q, _dev32(ref[lo:lo + step], dev), k, idx, d2, ref_base=lo, exclude_self=exclude_self, merge=lo > 0)
+        return idx, d2
+    q, ref = _np64(q), _np64(ref)
+    idx, d2 = np.full((m, k), -1, np.int64), np.full((m, k), np.inf)
+    with np.errstate(all="ignore"):
+        nq, nr = (q * q).sum(axis=1), (ref * ref).sum(axis=1)
+        rows = max(1, min(_HOST_BLOCK, (_HOST_BLOCK * _HOST_BLOCK) // n, (_HOST_BLOCK * _HOST_BLOCK) // (16 * q.shape[1])))
+        for i in range(0, m, rows):
+            g = np.maximum((nq[i:i + rows, None] + nr[None, :]) - 2.0 * (q[i:i + rows] @ ref.T), 0.0)
+            g[:, ~np.isfinite(nr)] = np.inf
+            g[np.isnan(g)] = np.inf
+            if exclude_self:
+                r = np.arange(i, min(i + g.shape[0], n))
+                g[r - i, r] = np.inf
+            cand = np.argsort(g, axis=1, kind="stable")[:, :min(n, 2 * 8)]              # ties: the lower index first
+            # the Gram form picks, differences rank: (q - ref)^2 summed keeps its relative accuracy for a near copy
+            e = ((q[i:i + rows, None, :] - ref[cand]) ** 2).sum(axis=2)
+            e[np.take_along_axis(g, cand, axis=1) == np.inf] = np.inf
+            order = np.lexsort((cand, e), axis=1)[:, :k]
+            ci, ce = np.take_along_axis(cand, order, axis=1), np.take_along_axis(e, order, axis=1)
+            kk = ci.shape[1]
+            idx[i:i + rows, :kk] = np.where(ce < np.inf, ci, -1)
+            d2[i:i + rows, :kk] = ce
+    bad = ~np.isfinite(nq)
+    idx[bad], d2[bad] = -1, np.nan
+    return idx, d2
+
+
+def nearest_chunk(q, ref, k, idx, d2, q_base=0, ref_base=0, exclude_self=False, merge=False):
+    """One jck_knn_index_f32 call on contiguous fp32 device matrices: the k nearest rows of this `ref` chunk (global indices
+    ref_base + j) into idx int64 [M,k] / d2 fp32 [M,k], merged with what they hold when `merge`."""
+    from hipgan._lib import JckError, cur_stream, lib, load_library
+    (m, d), n = q.shape, ref.shape[0]
+    nbytes = load_library().jck_knn_index_ws_bytes(m, n)
+    if nbytes == 0:
+        raise JckError(f"nearest: {m} x {n} rows are outside what jck_knn_index_f32 takes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+    lib.jck_knn_index_f32(q, m, ref, n, d, k, int(q_base), int(ref_base), int(bool(exclude_self)), int(bool(merge)), idx, d2, ws, cur_stream())
 
 
 def _scalar(v):
@@ -448,6 +510,13 @@ class Metrics:
         comparable with."""
         return float(np.mean([self.kid(torch.utils.data.DataLoader(generated_images[self.fake_superclass_idx[s]], 128, shuffle=False),
                                        intra_kid=True, label=s) for s in range(20)]))
+
+    def nearest_real(self, generated_images, k=3):
+        """(idx int64 [n,k], d2 [n,k]): the k real images nearest to each generated image in the metric network's feature space,
+        against the cached real features (metrics.nearest; on the device when the features are there)."""
+        gen = self._extract(generated_images, keep_on_device=True)
+        on_dev = torch.is_tensor(gen) and gen.is_cuda and self._real_on_device() is not None
+        return nearest(gen, self._real_on_device() if on_dev else np.asarray(self.real_features), k)
 
     def precision_recall(self, generated_images, k=3):
         """(precision, recall) of the generated images against real's k-NN manifold and of the real features against theirs;
