@@ -120,6 +120,28 @@ int jck_latent_loss(int prec, const void* x_nhwc4, const float* target_nchw_f32,
  * t = 0: sum only - z receives the summed slabs; m, v and z_operand are not touched and may be NULL. */
 int jck_latent_adam(int prec, const float* slab, int Z, int ld, float* z, float* m, float* v, float lr, float prior, int t,
                     void* z_operand, int CiPad, int N, void* stream);
+/* The critic's latent gradient, per op (D(G(z)) differentiated with respect to z under model.eval(): jck_engine_latent_grad_ex).
+ * jck_conv_up_mask: jck_conv_up (a Conv2d's input gradient, 4 output parities) through the folded eval-mode stage
+ * a = leaky(scale[c] * y + shift[c]) in front of it: t = scale[c] * acc, out = a_big[m, c] > 0 ? t : t * slope on the fp32 accumulators,
+ * ONE rounding to the storage type - ATen's leaky_relu_backward on the stored result: a = +-0 and a NaN activation take the slope.
+ * a_big has big_out's layout [N, 2Hs, 2Ws, Cb]; scale: device float[Cb], 16-byte aligned; Cs and Cb powers of two >= 64, anything
+ * else is JCK_E_ARG.  Never the persistent kernels; jck_last_launch reports the tile's name. */
+int jck_conv_up_mask(int prec, const void* small_in, const void* w, const void* a_big, const float* scale, float slope, void* big_out,
+                     int N, int Hs, int Ws, int Cs, int Cb, void* stream);
+/* The same backward without a product (the deepest stage, whose gradient comes from the head): g_y[r, c] = a[r, c] > 0 ? scale[c] *
+ * g[r, c] : scale[c] * g[r, c] * slope, 16 bytes per access along C (a power of two >= 8); g_y may be g. */
+int jck_leaky_affine_bwd(int prec, const void* g, const void* a, const float* scale, float slope, void* g_y, long long rows, int C,
+                         void* stream);
+/* ds[b] = weight * c'(logit[b]), term[b] = weight * c(logit[b]).  mode 1 (nsgan): c = softplus(-logit) = -log D, the generator's
+ * training loss, c' = -sigmoid(-logit), overflow-free at any logit; mode 2 (logit): c = -logit, c' = -1.  A non-finite logit gives
+ * NaN in both. */
+int jck_critic_ds(const float* logit, int mode, float weight, int B, float* ds, float* term, void* stream);
+/* jck_latent_loss with a per-pixel weight (fp32 [N][HW], or NULL: 1) and an additive image gradient g_x (NHWC4, element type, or NULL):
+ * loss_out[b] = sum_p w_p sum_c (x - t)^2 / (3 sum_p w_p), g_raw_out = (k w_p (x - t) + g_x) (1 - x^2), k = 2 / (3 sum_p w_p); two
+ * fixed-order passes per image (sum w, then the loss); sum w = 0: loss 0 and no reconstruction gradient.  target NULL (g_x required):
+ * loss 0, g_raw_out = g_x (1 - x^2).  weight NULL or all ones and g_x NULL: jck_latent_loss' bits. */
+int jck_latent_loss_ex(int prec, const void* x_nhwc4, const float* target_nchw_f32, const float* weight, const void* g_x, void* g_raw_out,
+                       float* loss_out, int N, int HW, void* stream);
 size_t jck_g1_wgrad_ws_bytes(int B, int CiPad, int Co);
 int jck_g1_wgrad(int prec, const void* z, const void* dy, float* ws, size_t ws_bytes, float* grad, int accumulate, int B,
                  int Ci, int CiPad, int Co, void* stream);
@@ -465,6 +487,25 @@ int jck_engine_latent_grad(jck_engine*, const float* z, const int64_t* labels, c
 int jck_engine_project(jck_engine*, float* z /* in, out */, const int64_t* labels, const float* target_nchw, int n,
                        int steps, float lr, float prior, float* m, float* v /* [n,100], caller-owned */, int t0,
                        float* loss_hist /* [steps][n] or NULL */, void* stream);
+/* The same with a per-pixel weight and the eval-mode discriminator as a critic: per image J_b = L_b + term_b + prior * mean_k(z_bk^2),
+ * L_b = sum_p w_p sum_c (G(z_b) - t_b)^2 / (3 sum_p w_p) (weight: fp32 [n,S,S] on the device, or NULL for 1; target NULL: L_b = 0,
+ * critic only) and term_b = critic_weight * c(D(G(z_b))), c = softplus(-logit) (critic_mode 1, nsgan) or -logit (2, logit); mode 0:
+ * no critic.  latent_grad_ex: loss = L [n], term [n] (or NULL), logit [n] (or NULL) and dz = d(L + term)/dz.  project_ex:
+ * jck_engine_project on that objective; term_hist[s][n] (or NULL) is term before update s.  With weight NULL and critic_mode 0 both
+ * issue the launches of the entry points above and return their bits.  With a critic one evaluation is: the eval generator's products,
+ * jck_engine_score's stages and head on its output, jck_critic_ds, the head's input gradient, jck_leaky_affine_bwd at the deepest stage,
+ * jck_conv_up_mask per stage down to stage 1, jck_conv_up into an image gradient, jck_latent_loss_ex, then the projection's backward.
+ * D's gradients, the image gradient and the critic's rows are ONE allocation that the first call with a critic makes (so: not inside
+ * a graph capture) and jck_engine_destroy frees; D's training activations, real_noisy and the head's concat buffer are never used, and
+ * nothing of the training state is written.  critic_mode != 0 needs D's packed operands (as jck_engine_score) and, family 1, labels;
+ * critic_weight >= 0; target NULL requires a critic: JCK_E_ARG otherwise, nothing launched.  Rows are independent bit for bit. */
+int jck_engine_latent_grad_ex(jck_engine*, const float* z, const int64_t* labels, const float* target_nchw /* or NULL */,
+                              const float* weight /* or NULL */, int critic_mode, float critic_weight, int n, float* loss /* [n] */,
+                              float* term /* [n] or NULL */, float* logit /* [n] or NULL */, float* dz /* [n,100] */, void* stream);
+int jck_engine_project_ex(jck_engine*, float* z /* in, out */, const int64_t* labels, const float* target_nchw /* or NULL */, int n,
+                          int steps, float lr, float prior, const float* weight /* or NULL */, int critic_mode, float critic_weight,
+                          float* m, float* v, int t0, float* loss_hist /* [steps][n] or NULL */, float* term_hist /* [steps][n] or NULL */,
+                          void* stream);
 /* The discriminator as under model.eval() (model/DCGAN.py:28-50, model/CGAN.py:18-42 with BatchNorm on its running statistics and
  * Dropout the identity): logit[b] = D's pre-sigmoid output for image b, prob[b] (or NULL) its sigmoid.  images_nchw: fp32 [n,3,S,S]
  * in [-1, 1] on the device, or NULL to score the generator's current output where it lies (jck_engine_sample_ex just before: the images

@@ -248,6 +248,14 @@ struct jck_engine {
     void *x = nullptr, *y = nullptr, *a[JCK_MAX_STAGES] = {}, *cbuf = nullptr, *h = nullptr;
     float *aux[JCK_MAX_STAGES] = {}, *slab = nullptr;
   } sc;
+  // the critic's latent gradient (jck_engine_latent_grad_ex / jck_engine_project_ex with critic_mode != 0): memory of its own too, one
+  // allocation made by the first such call - the gradient at every stage's pre-activation, the image gradient (NHWC4), the rows
+  // ds / term / logit, and CGAN's gradient rows at the Linear(8392,256) output and at the concat buffer
+  struct CriticBufs {
+    void* base = nullptr;
+    void *g[JCK_MAX_STAGES] = {}, *gx = nullptr, *g_h = nullptr, *gc = nullptr;
+    float *ds = nullptr, *term = nullptr, *logit = nullptr;
+  } cr;
   bool d_packed = false;                // D's operands were derived from its parameters at least once (jck_engine_repack, a D step)
 
   void carve(unsigned char* base) {
@@ -451,6 +459,7 @@ extern "C" void jck_engine_destroy(jck_engine* e) {
   if (e->overlap) destroy_side_streams(e, true);
   if (e->lat_w) (void)hipFree(e->lat_w);
   if (e->sc.base) (void)hipFree(e->sc.base);
+  if (e->cr.base) (void)hipFree(e->cr.base);
   delete e;
 }
 extern "C" int jck_engine_num_tensors(int family, int net) { return (int)make_layout(family, net).t.size(); }
@@ -1722,10 +1731,15 @@ static int latent_begin(jck_engine* e, const float* z, const int64_t* labels, in
   // conv1.weight [z_dim][G_C1][4][4]: its first 100 rows as a Linear weight [100][G_C1 * 16] whose columns go from (c, pos) to (pos, c)
   return jck_pack_linear(e->prec, e->P(e->LG, e->gp, CWN[0]), 100, K, LAT_LD, K, 0, TT.G_C1, 16, e->lat_w, st);
 }
+static int latent_backward(jck_engine* e, int n, hipStream_t st);
 // one evaluation: the eval forward's products, the loss and its gradient, the masked dgrads, the dz product's slabs
 static int latent_eval(jck_engine* e, const float* target, int n, float* loss, hipStream_t st) {
   JCK_TRY(g_eval_products(e, n, st));
   JCK_TRY(jck_latent_loss(e->prec, e->fake_raw, target, e->g_raw, loss, n, TT.HW, st));
+  return latent_backward(e, n, st);
+}
+// from g_raw, the gradient at the pre-tanh product: the masked dgrads and the dz product's slabs
+static int latent_backward(jck_engine* e, int n, hipStream_t st) {
   const void* gbig = e->g_raw;
   for (int i = TT.NS - 1; i >= 0; --i) {       // through conv(i+2) and the folded stage in front of it
     const int hs = TT.G_HS[i];
@@ -1806,33 +1820,23 @@ static int score_alloc(jck_engine* e, hipStream_t st) {
   e->sc = b;
   return JCK_OK;
 }
-extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const float* noise_nchw, const int64_t* labels, int n, float* logit,
-                                float* prob, void* stream) {
-  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "score: engine not bound");
-  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "score: n must be in [1, batch]");
-  if (!logit) JCK_FAIL(JCK_E_ARG, "score: null logit");
-  if (noise_nchw && !images_nchw) JCK_FAIL(JCK_E_ARG, "score: instance noise goes with images");
-  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, "score: CGAN discriminator needs labels");
-  if (!e->d_packed) JCK_FAIL(JCK_E_ARG, "score: the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
-  hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(score_alloc(e, st));
+// the fold of D's BatchNorm layers (gamma, beta and the running statistics) into the stages' aux tables: one launch ...
+static int score_fold(jck_engine* e, hipStream_t st) {
   const jck_engine::ScoreBufs& S = e->sc;
-  const void* in = e->fake_raw;                                       // NULL images: the generator's last output, where it lies
-  if (images_nchw) {
-    JCK_TRY(jck_img_prep(e->prec, images_nchw, noise_nchw, noise_nchw ? 0.9f : 1.0f, noise_nchw ? 0.1f : 0.0f, S.x, n, TT.HW, st));
-    in = S.x;
+  const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
+  float* aux[JCK_MAX_STAGES];
+  int Cs[JCK_MAX_STAGES];
+  for (int i = 0; i < TT.NS; ++i) {
+    gamma[i] = e->P(e->LD, e->dp, NWN[i]); beta[i] = e->P(e->LD, e->dp, NBN[i]);
+    rm[i] = e->dbn + find(e->LD, RMN[i])->offset; rv[i] = e->dbn + find(e->LD, RVN[i])->offset;
+    aux[i] = S.aux[i]; Cs[i] = TT.D_CS[i];
   }
-  {
-    const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
-    float* aux[JCK_MAX_STAGES];
-    int Cs[JCK_MAX_STAGES];
-    for (int i = 0; i < TT.NS; ++i) {
-      gamma[i] = e->P(e->LD, e->dp, NWN[i]); beta[i] = e->P(e->LD, e->dp, NBN[i]);
-      rm[i] = e->dbn + find(e->LD, RMN[i])->offset; rv[i] = e->dbn + find(e->LD, RVN[i])->offset;
-      aux[i] = S.aux[i]; Cs[i] = TT.D_CS[i];
-    }
-    JCK_TRY(jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st));
-  }
+  return jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st);
+}
+// ... and the stages and the head on the NHWC4 images `in`: jck_engine_score, and the forward half of the critic's latent gradient,
+// which reads the stages' activations S.a[i] and aux tables afterwards
+static int score_stages_head(jck_engine* e, const void* in, const int64_t* labels, int n, float* logit, float* prob, hipStream_t st) {
+  const jck_engine::ScoreBufs& S = e->sc;
   for (int i = 0; i < TT.NS; ++i) {
     const int hb = TT.D_HB[i], cs = TT.D_CS[i];
     if (score_stage_fused(e->prec)) {
@@ -1851,6 +1855,137 @@ extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const f
   // Dropout is the identity under model.eval(): no mask
   JCK_TRY(jck_linear_finish(e->prec, S.slab, L1_KSPLIT, e->P(e->LD, e->dp, "linear1.bias"), nullptr, 1.0f, S.h, nullptr, n, L1_OUT, st));
   return jck_score_head(e->prec, S.h, e->P(e->LD, e->dp, "linear2.weight"), e->P(e->LD, e->dp, "linear2.bias"), n, L1_OUT, logit, prob, st);
+}
+extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const float* noise_nchw, const int64_t* labels, int n, float* logit,
+                                float* prob, void* stream) {
+  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "score: engine not bound");
+  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "score: n must be in [1, batch]");
+  if (!logit) JCK_FAIL(JCK_E_ARG, "score: null logit");
+  if (noise_nchw && !images_nchw) JCK_FAIL(JCK_E_ARG, "score: instance noise goes with images");
+  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, "score: CGAN discriminator needs labels");
+  if (!e->d_packed) JCK_FAIL(JCK_E_ARG, "score: the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
+  hipStream_t st = (hipStream_t)stream;
+  JCK_TRY(score_alloc(e, st));
+  const void* in = e->fake_raw;                                       // NULL images: the generator's last output, where it lies
+  if (images_nchw) {
+    JCK_TRY(jck_img_prep(e->prec, images_nchw, noise_nchw, noise_nchw ? 0.9f : 1.0f, noise_nchw ? 0.1f : 0.0f, e->sc.x, n, TT.HW, st));
+    in = e->sc.x;
+  }
+  JCK_TRY(score_fold(e, st));
+  return score_stages_head(e, in, labels, n, logit, prob, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the critic's latent gradient: the projection above with a per-pixel weight on the image loss and c(D(G(z))) as a second term -
+// masked projection (semantic inpainting) and refinement of a latent along the discriminator's gradient.  D runs as jck_engine_score
+// runs it, and its input gradient comes from the activations and folded aux tables that pass keeps in memory of its own: the head's
+// input gradient, the leaky backward of the deepest stage, one masked ConvTranspose-direction product per stage (jck_conv_up_mask)
+// and the plain one of stage 0 into an image gradient that jck_latent_loss_ex adds in front of the tanh.  Nothing of D's training
+// buffers (DActs, real_noisy, the head's cbuf, any gradient arena) is read or written.
+// ---------------------------------------------------------------------------------------------------------
+static int critic_alloc(jck_engine* e) {
+  if (e->cr.base) return JCK_OK;
+  Carver c;
+  auto carve = [&](jck_engine::CriticBufs& b) {
+    c.off = 0;
+    for (int i = 0; i < TT.NS; ++i) b.g[i] = c.take<unsigned char>((size_t)e->B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i] * e->esz);
+    b.gx = c.take<unsigned char>((size_t)e->B * TT.HW * 4 * e->esz);
+    b.ds = c.take<float>(e->B); b.term = c.take<float>(e->B); b.logit = c.take<float>(e->B);
+    if (e->family == 1) {
+      b.g_h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
+      b.gc = c.take<unsigned char>((size_t)e->B * L1_KPAD * e->esz);
+    }
+  };
+  jck_engine::CriticBufs b;
+  carve(b);                                                          // sizes
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, c.off));
+  c.base = reinterpret_cast<unsigned char*>(base);
+  carve(b);
+  b.base = base;
+  e->cr = b;
+  return JCK_OK;
+}
+static int latent_ex_check(jck_engine* e, const float* z, const int64_t* labels, const float* target, int critic_mode, float critic_weight,
+                           int n, const char* who) {
+  const std::string w(who);
+  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, w + ": engine not bound");
+  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, w + ": n must be in [1, batch]");
+  if (!z) JCK_FAIL(JCK_E_ARG, w + ": null z");
+  if (critic_mode < 0 || critic_mode > 2) JCK_FAIL(JCK_E_ARG, w + ": critic_mode must be 0 (none), 1 (nsgan) or 2 (logit)");
+  if (!target && !critic_mode) JCK_FAIL(JCK_E_ARG, w + ": without a target a critic is required");
+  if (!(critic_weight >= 0.f)) JCK_FAIL(JCK_E_ARG, w + ": critic_weight >= 0");
+  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, w + ": CGAN needs labels");
+  if (critic_mode && !e->d_packed)
+    JCK_FAIL(JCK_E_ARG, w + ": the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
+  if (e->capturing) JCK_FAIL(JCK_E_ARG, w + ": not inside a graph capture");
+  return JCK_OK;
+}
+struct LatentEx { const float* target; const float* weight; int mode; float cw; const int64_t* labels; };
+// once per call, behind latent_begin: the critic's buffers and D's BatchNorm fold
+static int latent_ex_begin(jck_engine* e, const LatentEx& o, hipStream_t st) {
+  if (!o.mode) return JCK_OK;
+  JCK_TRY(score_alloc(e, st));
+  JCK_TRY(critic_alloc(e));
+  return score_fold(e, st);
+}
+// one evaluation; plain (no weight, no critic): latent_eval's launches
+static int latent_eval_ex(jck_engine* e, const LatentEx& o, int n, float* loss, float* term, float* logit, hipStream_t st) {
+  if (!o.weight && !o.mode) return latent_eval(e, o.target, n, loss, st);
+  JCK_TRY(g_eval_products(e, n, st));
+  const jck_engine::ScoreBufs& S = e->sc;
+  const jck_engine::CriticBufs& C = e->cr;
+  if (o.mode) {
+    const int top = TT.NS - 1;
+    if (!logit) logit = C.logit;
+    JCK_TRY(score_stages_head(e, e->fake_raw, o.labels, n, logit, nullptr, st));
+    JCK_TRY(jck_critic_ds(logit, o.mode, o.cw, n, C.ds, term ? term : C.term, st));
+    if (e->family == 0) {
+      JCK_TRY(jck_head_bwd_conv(e->prec, C.ds, e->d_head_wp, S.a[top], n, TT.G_C1, C.g[top], nullptr, nullptr, st));
+    } else {
+      // Linear(8392,256) -> Dropout (the identity) -> Linear(256,1): no nonlinearity between the two products under model.eval()
+      JCK_TRY(jck_head_bwd(e->prec, C.ds, e->P(e->LD, e->dp, "linear2.weight"), nullptr, n, L1_OUT, C.g_h, nullptr, 0, nullptr, st));
+      JCK_TRY(jck_linear_fwd(e->prec, C.g_h, e->l1_wT, nullptr, C.gc, n, L1_OUT, L1_KPAD, L1_KPAD, 1, st));
+      JCK_TRY(jck_split_rows(e->prec, C.gc, L1_KPAD, TT.FEAT, C.g[top], n, st));
+    }
+    JCK_TRY(jck_leaky_affine_bwd(e->prec, C.g[top], S.a[top], S.aux[top], LRELU, C.g[top], (long long)n * (TT.D_HB[top] / 2) * (TT.D_HB[top] / 2),
+                                 TT.D_CS[top], st));
+    for (int i = top; i >= 1; --i) {            // through conv(i+1) and the folded stage in front of it
+      const int hs = TT.D_HB[i] / 2;
+      JCK_TRY(jck_conv_up_mask(e->prec, C.g[i], e->d_up[i], S.a[i - 1], S.aux[i - 1], LRELU, C.g[i - 1], n, hs, hs, TT.D_CS[i], TT.D_CB[i], st));
+    }
+    JCK_TRY(jck_conv_up(e->prec, C.g[0], e->d_up[0], C.gx, nullptr, nullptr, 0, n, TT.D_HB[0] / 2, TT.D_HB[0] / 2, TT.D_CS[0], TT.D_CB[0], st));
+  }
+  JCK_TRY(jck_latent_loss_ex(e->prec, e->fake_raw, o.target, o.weight, o.mode ? C.gx : nullptr, e->g_raw, loss, n, TT.HW, st));
+  return latent_backward(e, n, st);
+}
+extern "C" int jck_engine_latent_grad_ex(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
+                                         int critic_mode, float critic_weight, int n, float* loss, float* term, float* logit, float* dz,
+                                         void* stream) {
+  JCK_TRY(latent_ex_check(e, z, labels, target_nchw, critic_mode, critic_weight, n, "latent_grad_ex"));
+  if (!loss || !dz) JCK_FAIL(JCK_E_ARG, "latent_grad_ex: null loss / dz");
+  hipStream_t st = (hipStream_t)stream;
+  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels};
+  JCK_TRY(latent_begin(e, z, labels, n, st));
+  JCK_TRY(latent_ex_begin(e, o, st));
+  JCK_TRY(latent_eval_ex(e, o, n, loss, term, logit, st));
+  return jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, dz, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, n, st);
+}
+extern "C" int jck_engine_project_ex(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
+                                     float prior, const float* weight, int critic_mode, float critic_weight, float* m, float* v, int t0,
+                                     float* loss_hist, float* term_hist, void* stream) {
+  JCK_TRY(latent_ex_check(e, z, labels, target_nchw, critic_mode, critic_weight, n, "project_ex"));
+  if (steps < 1 || t0 < 0 || !m || !v) JCK_FAIL(JCK_E_ARG, "project_ex: steps >= 1, t0 >= 0 and the Adam state m, v are required");
+  if (!(lr > 0.f) || !(prior >= 0.f)) JCK_FAIL(JCK_E_ARG, "project_ex: lr > 0 and prior >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels};
+  JCK_TRY(latent_begin(e, z, labels, n, st));
+  JCK_TRY(latent_ex_begin(e, o, st));
+  for (int s = 0; s < steps; ++s) {
+    JCK_TRY(latent_eval_ex(e, o, n, loss_hist ? loss_hist + (size_t)s * n : e->lat_loss, term_hist ? term_hist + (size_t)s * n : nullptr, nullptr, st));
+    JCK_TRY(jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, z, m, v, lr, prior, t0 + s + 1, e->g_z, z_pad(e->family), n, st));
+  }
+  return JCK_OK;
 }
 
 extern "C" const void* jck_engine_tensor(const jck_engine* e, const char* name, long long* numel) {

@@ -69,7 +69,8 @@ struct IgemmParams {
   const void* mask_act;
   const float* mask_scale;
   // LEAKY form of the AFFINE instantiations (discriminator inference, jck_conv_down_affine): t = aff_scale[c] * acc + aff_shift[c],
-  // v = t > 0 ? t : t * aff_slope
+  // v = t > 0 ? t : t * aff_slope.  LEAKY form of the MASK instantiations (the critic's latent gradient, jck_conv_up_mask): the backward of
+  // a folded BatchNorm + LeakyReLU, t = mask_scale[c] * acc, v = mask_act[pixel][c] > 0 ? t : t * aff_slope
   float aff_slope;
 };
 
@@ -112,7 +113,8 @@ __device__ __forceinline__ void igemm_pixel_offsets(const IgemmParams& p, int la
 // MASK (compile time, jck_conv_down_mask alone): the gradient through a folded stage a = relu(scale[c] * y + shift[c]) - scale[c]
 // where the stored activation is > 0, else +0 (a NaN activation masks: torch.relu's backward) - on the fp32 accumulators.
 // LEAKY (compile time, with AFFINE; jck_conv_down_affine alone): LeakyReLU in the ReLU's place, t > 0 ? t : t * aff_slope - ATen's
-// form: NaN passes, -0 stays -0.
+// form: NaN passes, -0 stays -0.  With MASK (jck_conv_up_mask alone): the gradient through a = leaky(scale[c] * y + shift[c]) - scale[c]
+// where the stored activation is > 0, else scale[c] * aff_slope (ATen's leaky_relu_backward on the result: +-0 and NaN take the slope).
 template <class P, int BCH, int BPIX, int FM, int FN, int WPIXN, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc)[FM][FN], int lane, int wch, int wpix, int z, int zraw,
                                                int bidx, int bidy, int m0, int ch0) {
@@ -179,7 +181,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
         float a[4];
         ld4(reinterpret_cast<const T*>(p.mask_act) + off + ch, a);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = a[r] > 0.f ? sc[r] * v[r] : 0.f;
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (LEAKY) { const float t = sc[r] * v[r]; v[r] = a[r] > 0.f ? t : t * p.aff_slope; }
+          else v[r] = a[r] > 0.f ? sc[r] * v[r] : 0.f;
+        }
       }
       if (p.out_f32) st4(reinterpret_cast<float*>(p.out) + off + ch, v);
       else st4(outp + off + ch, v);

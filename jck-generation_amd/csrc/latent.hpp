@@ -58,3 +58,102 @@ __global__ void latent_adam_kernel(const float* __restrict__ slab, int Z, long l
   m[i] = (float)mn; v[i] = (float)vn; z[i] = zn;
   stf(z_operand + (long long)b * zp + k, zn);
 }
+
+// ---- the critic's latent gradient (jck_engine_latent_grad_ex / _project_ex): D(G(z)) differentiated with respect to z under model.eval() ----
+// latent_loss_kernel with a per-pixel weight w [n][HW] (fp32, or null: 1) and an additive image gradient g_x (NHWC4 of T, or null):
+// L_b = sum_p w_p sum_c (x - t)^2 / (3 sum_p w_p), g_raw = (k w_p (x - t) + g_x) (1 - x^2), k = 2 / (3 sum_p w_p).  One workgroup per
+// image, two passes in latent_loss_kernel's fixed order: sum w, then the loss.  sum w = 0: loss 0, no reconstruction gradient.
+// target null (g_x required): L_b = 0, g_raw = g_x (1 - x^2).  With w null and g_x null the arithmetic is latent_loss_kernel's,
+// expression for expression (w d = d, sum w = HW): the same bits.
+template <typename T>
+__global__ __launch_bounds__(256) void latent_loss_ex_kernel(const T* __restrict__ x, const float* __restrict__ target, const float* __restrict__ w,
+                                                             const T* __restrict__ g_x, T* __restrict__ g_raw, float* __restrict__ loss, int HW) {
+  __shared__ float sm[4];
+  const int b = blockIdx.x;
+  const T* xb = x + (long long)b * HW * 4;
+  T* gb = g_raw + (long long)b * HW * 4;
+  const T* gxb = g_x ? g_x + (long long)b * HW * 4 : nullptr;
+  if (!target) {                                       // critic only
+    for (int p = threadIdx.x; p < HW; p += 256) {
+      float v[4], c[4], g[4];
+      ld4(xb + (long long)p * 4, v);
+      ld4(gxb + (long long)p * 4, c);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g[k] = c[k] * (1.f - v[k] * v[k]);
+      g[3] = 0.f;
+      st4(gb + (long long)p * 4, g);
+    }
+    if (threadIdx.x == 0) loss[b] = 0.f;
+    return;
+  }
+  const float* tb = target + (long long)b * 3 * HW;
+  const float* wb = w ? w + (long long)b * HW : nullptr;
+  float sw = (float)HW;
+  if (wb) {
+    float a = 0.f;
+    for (int p = threadIdx.x; p < HW; p += 256) a += wb[p];
+    sw = block_sum256(a, sm);
+    __syncthreads();                                   // sm is reused by the second sum
+  }
+  const float k = sw > 0.f ? 2.0f / (3.0f * sw) : 0.f;
+  float s = 0.f;
+  for (int p = threadIdx.x; p < HW; p += 256) {
+    float v[4], g[4], c[4] = {0.f, 0.f, 0.f, 0.f};
+    ld4(xb + (long long)p * 4, v);
+    if (gxb) ld4(gxb + (long long)p * 4, c);
+    const float wp = wb ? wb[p] : 1.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float d = v[ch] - tb[(long long)ch * HW + p];
+      const float wd = wb ? wp * d : d;
+      s = fmaf(wd, d, s);
+      if (gxb) g[ch] = (k * wd + c[ch]) * (1.f - v[ch] * v[ch]);
+      else g[ch] = k * wd * (1.f - v[ch] * v[ch]);
+    }
+    g[3] = 0.f;
+    st4(gb + (long long)p * 4, g);
+  }
+  s = block_sum256(s, sm);
+  if (threadIdx.x == 0) loss[b] = sw > 0.f ? s / (3.0f * sw) : 0.f;
+}
+
+// The backward of a folded eval-mode stage a = leaky(scale[c] * y + shift[c]) on a gradient of its output, 8 channels per thread:
+// g_y[r, c] = a[r, c] > 0 ? scale[c] g[r, c] : scale[c] g[r, c] slope (ATen's leaky_relu_backward: a = +-0 and NaN take the slope).
+// g_y may be g.  C a power of two >= 8.
+template <typename T>
+__global__ void leaky_affine_bwd_kernel(const T* g, const T* __restrict__ a, const float* __restrict__ scale, float slope, T* g_y,
+                                        long long total8, int C) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)((i * 8) & (C - 1));
+    float v[8], av[8];
+    ld8(g + i * 8, v);
+    ld8(a + i * 8, av);
+    const f32x4 s0 = *reinterpret_cast<const f32x4*>(scale + c), s1 = *reinterpret_cast<const f32x4*>(scale + c + 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float t = (j < 4 ? s0[j] : s1[j - 4]) * v[j];
+      v[j] = av[j] > 0.f ? t : t * slope;
+    }
+    st8(g_y + i * 8, v);
+  }
+}
+
+// The critic's objective on a logit, one thread per row: ds[b] = lambda c'(logit), term[b] = lambda c(logit).
+// mode 1 (nsgan): c = softplus(-logit) = -log sigmoid(logit), the generator's own training loss, c' = -sigmoid(-logit), both from
+// e = exp(-|logit|) <= 1 (no overflow at any logit).  mode 2 (logit): c = -logit, c' = -1.  A non-finite logit: NaN in both.
+__global__ void critic_ds_kernel(const float* __restrict__ logit, int mode, float lambda, int B, float* __restrict__ ds, float* __restrict__ term) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float l = logit[b];
+  float c, dc;
+  if (mode == 1) {
+    const float e = expf(-fabsf(l));
+    c = fmaxf(-l, 0.f) + log1pf(e);
+    dc = l >= 0.f ? -e / (1.f + e) : -1.f / (1.f + e);
+  } else {
+    c = -l; dc = -1.f;
+  }
+  if (!(fabsf(l) <= 3.402823466e38f)) c = dc = __builtin_nanf("");
+  ds[b] = lambda * dc;
+  term[b] = lambda * c;
+}

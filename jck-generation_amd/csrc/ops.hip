@@ -42,7 +42,8 @@ static constexpr KernelInfo KERNELS[] = {
     SAME("wgrad<f32,128,128>"),    SAME("wgrad<f32,128,64>"),    SAME("wgrad<f32,64,64,img>"),    SAME("wgrad<f32,64,64>"),
     SAME("wgrad<bf16x3,128,128>"), SAME("wgrad<bf16x3,128,64>"), SAME("wgrad<bf16x3,64,64,img>"), SAME("wgrad<bf16x3,64,64>"),
     {nullptr, "bn_act_fwd"}, {nullptr, "bn_bwd_resident"}, {nullptr, "bn_bwd_3launch"},
-    {nullptr, "latent_loss"}, {nullptr, "latent_adam"}};
+    {nullptr, "latent_loss"}, {nullptr, "latent_adam"},
+    {nullptr, "conv_up_mask"}, {nullptr, "leaky_affine_bwd"}, {nullptr, "critic_ds"}, {nullptr, "latent_loss_ex"}};
 #undef SAME
 static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "KERNELS and the KernelId offsets disagree");
 // the id arithmetic against the table, row by row: what every launch site's id resolves to (the affine 16 x 256 form with 8..32 gathered
@@ -59,6 +60,8 @@ static_assert(row(kid_igemm<PrecBf16, 128, 128, 1>(), "igemm<bf16,128,128>", "ig
               row(kid_wgrad<PrecF32, 128, 128, 1>(), "wgrad<f32,128,128>", "wgrad<f32,128,128>") && row(kid_wgrad<PrecF32, 128, 64, 1>(), "wgrad<f32,128,64>", "wgrad<f32,128,64>") && row(kid_wgrad<PrecF32, 64, 64, 2>(), "wgrad<f32,64,64,img>", "wgrad<f32,64,64,img>") && row(kid_wgrad<PrecF32, 64, 64, 1>(), "wgrad<f32,64,64>", "wgrad<f32,64,64>") &&
               row(kid_wgrad<PrecBf16x3, 128, 128, 1>(), "wgrad<bf16x3,128,128>", "wgrad<bf16x3,128,128>") && row(kid_wgrad<PrecBf16x3, 128, 64, 1>(), "wgrad<bf16x3,128,64>", "wgrad<bf16x3,128,64>") && row(kid_wgrad<PrecBf16x3, 64, 64, 2>(), "wgrad<bf16x3,64,64,img>", "wgrad<bf16x3,64,64,img>") && row(kid_wgrad<PrecBf16x3, 64, 64, 1>(), "wgrad<bf16x3,64,64>", "wgrad<bf16x3,64,64>") &&
               same_str(KERNELS[K_LATENT_LOSS].label, "latent_loss") && same_str(KERNELS[K_LATENT_ADAM].label, "latent_adam") &&
+              same_str(KERNELS[K_CONV_UP_MASK].label, "conv_up_mask") && same_str(KERNELS[K_LEAKY_AFFINE_BWD].label, "leaky_affine_bwd") &&
+              same_str(KERNELS[K_CRITIC_DS].label, "critic_ds") && same_str(KERNELS[K_LATENT_LOSS_EX].label, "latent_loss_ex") &&
               same_str(KERNELS[K_BN_ACT_FWD].label, "bn_act_fwd") && same_str(KERNELS[K_BN_BWD_RES].label, "bn_bwd_resident") && same_str(KERNELS[K_BN_BWD_3L].label, "bn_bwd_3launch") &&
               kid_igemm<PrecBf16, 16, 256, 0>() == kid_igemm<PrecBf16, 16, 256, 1>() && !KERNELS[K_IGEMM + 3].launch,
               "KERNELS and the kid_* functions disagree");
@@ -767,6 +770,42 @@ extern "C" int jck_latent_adam(int prec, const float* slab, int Z, int ld, float
   DISPATCH_T(prec, hipLaunchKernelGGL(latent_adam_kernel<T>, dim3((unsigned)((N * zd + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slab, Z,
                                       (long long)N * ld, ld, z, m, v, step_size, bc2_sqrt, 2.0 * (double)prior / zd, (T*)z_operand, CiPad, zd,
                                       N, t == 0 ? 1 : 0));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// jck_latent_loss with a per-pixel weight (fp32 [N][HW], or null: 1) and an additive image gradient g_x (NHWC4, element type, or null):
+// loss_out[b] = sum_p w_p sum_c (x - t)^2 / (3 sum_p w_p), g_raw_out = (k w_p (x - t) + g_x) (1 - x^2) with k = 2 / (3 sum_p w_p).
+// target null (g_x required): loss 0, g_raw_out = g_x (1 - x^2).  weight null and g_x null: jck_latent_loss' bits.
+extern "C" int jck_latent_loss_ex(int prec, const void* x_nhwc4, const float* target_nchw_f32, const float* weight, const void* g_x,
+                                  void* g_raw_out, float* loss_out, int N, int HW, void* stream) {
+  if (!x_nhwc4 || !g_raw_out || !loss_out || N < 1 || HW < 1) JCK_FAIL(JCK_E_ARG, "latent_loss_ex: bad arguments");
+  if (!target_nchw_f32 && !g_x) JCK_FAIL(JCK_E_ARG, "latent_loss_ex: without a target the image gradient g_x is required");
+  if ((((uintptr_t)x_nhwc4 | (uintptr_t)g_raw_out | (uintptr_t)g_x) & 15) != 0) JCK_FAIL(JCK_E_ARG, "latent_loss_ex: the image tensors must be 16-byte aligned");
+  ProfScope prof(K_LATENT_LOSS_EX, 0.0, (hipStream_t)stream, (double)N * HW * (16.0 + 12.0 * (prec_f32_storage(prec) ? 4 : 2)));
+  DISPATCH_T(prec, hipLaunchKernelGGL(latent_loss_ex_kernel<T>, dim3(N), dim3(256), 0, (hipStream_t)stream, (const T*)x_nhwc4, target_nchw_f32,
+                                      weight, (const T*)g_x, (T*)g_raw_out, loss_out, HW));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// g_y[r, c] = a[r, c] > 0 ? scale[c] g[r, c] : scale[c] g[r, c] slope over `rows` rows of C channels (a power of two >= 8); g_y may be g
+extern "C" int jck_leaky_affine_bwd(int prec, const void* g, const void* a, const float* scale, float slope, void* g_y, long long rows, int C,
+                                    void* stream) {
+  if (!g || !a || !scale || !g_y || rows < 1) JCK_FAIL(JCK_E_ARG, "leaky_affine_bwd: null tensor or no rows");
+  if (!is_pow2(C) || C < 8) JCK_FAIL(JCK_E_ARG, "leaky_affine_bwd: C must be a power of two >= 8");
+  if ((((uintptr_t)g | (uintptr_t)a | (uintptr_t)g_y | (uintptr_t)scale) & 15) != 0) JCK_FAIL(JCK_E_ARG, "leaky_affine_bwd: tensors and scale must be 16-byte aligned");
+  const long long total8 = rows * C / 8;
+  ProfScope prof(K_LEAKY_AFFINE_BWD, 0.0, (hipStream_t)stream, (double)rows * C * 3.0 * (prec_f32_storage(prec) ? 4 : 2));
+  DISPATCH_T(prec, hipLaunchKernelGGL(leaky_affine_bwd_kernel<T>, dim3(ew_grid(total8)), dim3(256), 0, (hipStream_t)stream, (const T*)g, (const T*)a,
+                                      scale, slope, (T*)g_y, total8, C));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// ds[b] = weight c'(logit[b]), term[b] = weight c(logit[b]); mode 1 (nsgan): c = softplus(-logit); mode 2 (logit): c = -logit
+extern "C" int jck_critic_ds(const float* logit, int mode, float weight, int B, float* ds, float* term, void* stream) {
+  if (!logit || !ds || !term || B < 1) JCK_FAIL(JCK_E_ARG, "critic_ds: null logit / ds / term or no rows");
+  if (mode != 1 && mode != 2) JCK_FAIL(JCK_E_ARG, "critic_ds: mode must be 1 (nsgan) or 2 (logit)");
+  ProfScope prof(K_CRITIC_DS, 0.0, (hipStream_t)stream, (double)B * 12.0);
+  hipLaunchKernelGGL(critic_ds_kernel, dim3(cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logit, mode, weight, B, ds, term);
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }

@@ -228,9 +228,31 @@ static int launch_igemm_mask_p(const IgemmParams& p, int nch_pad, int nsub, hipS
   JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
 }
 
+// Leaky masked dgrad launches (jck_conv_up_mask: a Conv2d's input gradient through a folded BatchNorm + LeakyReLU stage, 4 output
+// parities as phases): the epilogue's MASK + LEAKY instantiation on launch_igemm_affine_p's tiles, `phases` counted into the tile
+// choice.  >= 64 gathered channels and >= 64 output rows alone; never the persistent kernels.
+template <class P>
+static int launch_igemm_mask_leaky_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st) {
+  if (nsub != 1 || (nch_pad != 64 && nch_pad % 128)) JCK_FAIL(JCK_E_ARG, "igemm: the leaky mask epilogue is built for >= 64 gathered channels and >= 64 output rows");
+  if (nch_pad % 128 == 0) {
+    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
+    if constexpr (!P::IS_F32) {
+      const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128) * phases;
+      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, false, true, true>(p, nch_pad, phases, st, nullptr);
+      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, false, true, true>(p, nch_pad, phases, st, nullptr);
+      return launch_igemm_dma<128, 64, 3, true, 4, false, true, true>(p, nch_pad, phases, st, nullptr);
+    } else {
+      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, false, true, true>(p, nch_pad, phases, st, nullptr);
+      return launch_igemm_t<P, 128, 64, 1, false, true, true>(p, nch_pad, phases, st, nullptr);
+    }
+  }
+  if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, false, true, true>(p, nch_pad, phases, st, nullptr);
+  else return launch_igemm_t<P, 64, 128, 1, false, true, true>(p, nch_pad, phases, st, nullptr);
+}
+
 static int launch_wgrad_reduce(const float* ws, int Z, int CsRows, int ncols, int Cs, int Cb, int logCbPad, float* grad,
                                int accumulate, hipStream_t st);
-// leaky: with p0.aff_scale, the LeakyReLU form of the affine epilogue (slope p0.aff_slope)
+// leaky: with p0.aff_scale, the LeakyReLU form of the affine epilogue (slope p0.aff_slope); with p0.mask_act, that of the mask epilogue
 static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int nsub, hipStream_t st, int* slots, bool leaky = false) {
   IgemmParams p = p0;
   for (int zz = 0; zz < 4; ++zz)
@@ -255,6 +277,12 @@ static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases
       JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue takes 16-byte aligned scale and shift, a power-of-two channel count and no other option");
     if (leaky) DISPATCH_P(prec, (launch_igemm_affine_p<P, true>(p, nch_pad, phases, nsub, st)));
     DISPATCH_P(prec, launch_igemm_affine_p<P>(p, nch_pad, phases, nsub, st));
+  }
+  if (p.mask_act && leaky) {
+    if (!p.mask_scale || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || !is_pow2(p.cstat) || p.cstat % 4 ||
+        (uintptr_t)p.mask_scale % 16 || (uintptr_t)p.mask_act % 16)
+      JCK_FAIL(JCK_E_ARG, "igemm: the mask epilogue takes a 16-byte aligned scale and activation, a power-of-two channel count and no other option");
+    DISPATCH_P(prec, launch_igemm_mask_leaky_p<P>(p, nch_pad, phases, nsub, st));
   }
   if (p.mask_act) {
     if (!p.mask_scale || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || phases != 1 || !is_pow2(p.cstat) || p.cstat % 4 ||
@@ -363,7 +391,8 @@ extern "C" int jck_conv_down_grouped(int prec, const void* big, const void* w, v
 }
 static int conv_up_impl(int prec, const void* small_in, const void* w, void* big_out, float* stats, int* stats_slots,
                         int epi_tanh, int N, int Hs, int Ws, int Cs, int Cb, void* stream, int fwd_group_images = 0,
-                        const float* aff_scale = nullptr, const float* aff_shift = nullptr) {
+                        const float* aff_scale = nullptr, const float* aff_shift = nullptr, const void* mask_act = nullptr,
+                        const float* mask_scale = nullptr, float mask_slope = 0.f) {
   const int cbp = jck_pad_chan(Cb);
   // (<= 4 output channels run as rows-are-phases tiles or on the image-side kernel below, neither of which has the affine)
   if (aff_scale && (Cb < 8 || !is_pow2(Cb))) JCK_FAIL(JCK_E_ARG, "conv_up_affine: Cb must be a power of two >= 8");
@@ -406,6 +435,8 @@ static int conv_up_impl(int prec, const void* small_in, const void* w, void* big
   p.flops = 2.0 * p.M * 4.0 * Cb * 4.0 * Cs;
   if (stats && fwd_group_images > 0) { p.bn_group_rows = fwd_group_images * Hs * Ws; p.stat_accum = 1; }
   p.aff_scale = aff_scale; p.aff_shift = aff_shift;
+  p.mask_act = mask_act; p.mask_scale = mask_scale;
+  if (mask_act) { p.aff_slope = mask_slope; return launch_igemm(prec, p, rows, 4, 1, (hipStream_t)stream, nullptr, true); }
   return launch_igemm(prec, p, rows, 4, aff_scale && Cs < 64 ? 0 : 1, (hipStream_t)stream, stats_slots);
 }
 // D.conv1's input gradient with the tanh + instance-noise-mix backward of G's output in its epilogue (thin.hpp: ImgUpParams::mul_t):
@@ -421,6 +452,18 @@ int conv_up_tanh_bwd_ev(int prec, const void* small_in, const void* w, const voi
 extern "C" int jck_conv_up(int prec, const void* small_in, const void* w, void* big_out, float* stats, int* stats_slots,
                            int epi_tanh, int N, int Hs, int Ws, int Cs, int Cb, void* stream) {
   return conv_up_impl(prec, small_in, w, big_out, stats, stats_slots, epi_tanh, N, Hs, Ws, Cs, Cb, stream);
+}
+// Input gradient of a Conv2d(k4, s2, p1) whose INPUT is a folded eval-mode stage a = leaky(scale[c] * y + shift[c]) (the critic's latent
+// gradient): jck_conv_up with t = scale[c] * acc, v = a_big[m, c] > 0 ? t : t * slope applied to the fp32 accumulators before the one
+// rounding of the store (ATen's leaky_relu_backward on the stored result: a = +-0 and a NaN activation take the slope).  Never the
+// persistent kernels; Cs and Cb powers of two >= 64.
+extern "C" int jck_conv_up_mask(int prec, const void* small_in, const void* w, const void* a_big, const float* scale, float slope,
+                                void* big_out, int N, int Hs, int Ws, int Cs, int Cb, void* stream) {
+  if (!small_in || !w || !a_big || !scale || !big_out) JCK_FAIL(JCK_E_ARG, "conv_up_mask: null tensor, activation or scale");
+  if (N < 1) JCK_FAIL(JCK_E_ARG, "conv_up_mask: N must be >= 1");
+  if (!is_pow2(Cs) || Cs < 64 || !is_pow2(Cb) || Cb < 64) JCK_FAIL(JCK_E_ARG, "conv_up_mask: Cs and Cb must be powers of two >= 64");
+  if ((uintptr_t)scale % 16 || (uintptr_t)a_big % 16) JCK_FAIL(JCK_E_ARG, "conv_up_mask: the scale and the activation must be 16-byte aligned");
+  return conv_up_impl(prec, small_in, w, big_out, nullptr, nullptr, 0, N, Hs, Ws, Cs, Cb, stream, 0, nullptr, nullptr, a_big, scale, slope);
 }
 extern "C" int jck_conv_up_grouped(int prec, const void* small_in, const void* w, void* big_out, float* stats, int* stats_slots,
                                    int N, int Hs, int Ws, int Cs, int Cb, int group_images, void* stream) {

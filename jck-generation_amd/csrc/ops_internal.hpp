@@ -76,6 +76,9 @@ enum KernelId : int {
   K_WGRAD,                                        // + K_WGRAD_TILES * precision + tile     (kid_wgrad)
   K_BN_ACT_FWD = K_WGRAD + K_PRECS * K_WGRAD_TILES, K_BN_BWD_RES, K_BN_BWD_3L,      // profiler labels without a launch name
   K_LATENT_LOSS, K_LATENT_ADAM,                   // latent projection (latent.hpp): labels without a launch name as well
+  // the critic's latent gradient: labels without a launch name.  K_CONV_UP_MASK names the leaky mask epilogue in the table only: its
+  // launches are timed and reported under the id of the tile they run on, like every other epilogue option
+  K_CONV_UP_MASK, K_LEAKY_AFFINE_BWD, K_CRITIC_DS, K_LATENT_LOSS_EX,
   K_COUNT
 };
 template <class P> constexpr int kid_prec() { return P::SPLIT ? 2 : P::IS_F32 ? 1 : 0; }

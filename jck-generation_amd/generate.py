@@ -7,6 +7,8 @@
     python generate.py -m DCGAN --checkpoint best.pt --num 64 --select top --oversample 8 --score --out best_of
     python generate.py -m DCGAN --checkpoint best.pt --score_images samples/images.npz --out scored
     python generate.py -m DCGAN --checkpoint best.pt --num 64 --neighbours train.npz --k 4 --out samples
+    python generate.py -m DCGAN --checkpoint best.pt --inpaint samples/images.npz --mask center:32 --out inpainted
+    python generate.py -m DCGAN --checkpoint best.pt --num 64 --refine 10 --out refined
 
 Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
 BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
@@ -24,7 +26,14 @@ Whether the discriminator's running statistics make it a good ranker is a proper
 --neighbours REF.npz (with a sampling run, or with --score_images, whose images it then takes) looks up the --k nearest images of
 REF's uint8 `images` array (the samples' size, or 32x32 training data, upscaled as the trainers do) for every sample, in pixel space:
 <out>/neighbours.npz (idx int64 [n,k]; d2 squared distance in [-1, 1] units; rmse = sqrt(d2 / D); ref_nn_d2: the nearest other
-reference image's d2 from the image idx[:,0]; copy = d2[:,0] < ref_nn_d2) and <out>/neighbours.png, each sample followed by its neighbours."""
+reference image's d2 from the image idx[:,0]; copy = d2[:,0] < ref_nn_d2) and <out>/neighbours.png, each sample followed by its neighbours.
+--inpaint FILE.npz --mask SPEC is semantic inpainting (Yeh et al. 2017; Sampler.inpaint): SPEC names the KNOWN pixels of the file's
+pictures ("center:K": a centred K x K hole; "half:left|right|top|bottom": that half is the hole; an .npz / .npy file holding `mask`),
+z is fitted to them alone (--project_steps, --project_lr) with --critic_weight W times -log D(G(z)) as the realism prior (0: none, no
+discriminator needed), and <out>/inpainted.npz holds z, loss, term, known, images (G(z)) and completed (the known pixels of the input,
+the holes from G); <out>/inpainted.png has one row per picture: masked input, G(z), completed.
+--refine STEPS (with a sampling run) moves every latent STEPS Adam updates (--refine_lr) along the discriminator's gradient before its
+image is made; images.npz then holds the refined z and gains logit_before / logit_after."""
 import argparse
 import os
 import sys
@@ -57,6 +66,11 @@ def get_arg_parse(argv=None):
     p.add_argument("--score_images", default=None, metavar="FILE.npz", help="score the uint8 [n,S,S,3] `images` array of this file")
     p.add_argument("--neighbours", default=None, metavar="REF.npz", help="nearest images of this file's uint8 `images` array for every sample")
     p.add_argument("--k", type=int, default=4, help="with --neighbours: neighbours per sample (1..8)")
+    p.add_argument("--inpaint", default=None, metavar="FILE.npz", help="fill the holes of the uint8 [n,S,S,3] `images` array of this file")
+    p.add_argument("--mask", default=None, metavar="SPEC", help="with --inpaint: center:K, half:left|right|top|bottom, or an .npz / .npy with `mask`")
+    p.add_argument("--critic_weight", type=float, default=None, metavar="W", help="with --inpaint: weight of -log D(G(z)) (default 0.003; 0: no critic)")
+    p.add_argument("--refine", type=int, default=None, metavar="STEPS", help="Adam updates of every latent along the discriminator's gradient")
+    p.add_argument("--refine_lr", type=float, default=None, metavar="LR", help="with --refine (default 0.02)")
     p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     p.add_argument("--out", required=True, help="output directory")
     a = p.parse_args(argv)
@@ -82,6 +96,26 @@ def get_arg_parse(argv=None):
         p.error("--neighbours looks up sampled or given images: not with --project")
     if not 1 <= a.k <= 8:
         p.error("--k must lie in 1..8")
+    if bool(a.inpaint) != bool(a.mask):
+        p.error("--inpaint FILE.npz and --mask SPEC go together")
+    if a.inpaint and (a.project or a.interpolate or a.select or a.score or a.score_images or a.neighbours or a.num is not None or
+                      a.truncation is not None or a.refine is not None):
+        p.error("--inpaint takes its images from the file; the sampling, projection and scoring options do not go with it")
+    if a.critic_weight is not None and not a.inpaint:
+        p.error("--critic_weight goes with --inpaint")
+    if a.critic_weight is not None and not a.critic_weight >= 0:
+        p.error("--critic_weight must be >= 0")
+    if a.inpaint and a.critic_weight is None:
+        a.critic_weight = 0.003
+    if a.refine_lr is not None and a.refine is None:
+        p.error("--refine_lr goes with --refine")
+    if a.refine is not None:
+        if a.refine < 1 or (a.refine_lr is not None and not a.refine_lr > 0):
+            p.error("--refine STEPS must be >= 1 and --refine_lr > 0")
+        if a.project or a.score_images or a.select or a.interpolate or a.bn != "running":
+            p.error("--refine moves the latents of a plain sampling run under --bn running: not with --project, --score_images, --select, --interpolate or --bn batch")
+        if a.refine_lr is None:
+            a.refine_lr = 0.02
     if a.num is None:
         a.num = 64
     if a.num < 1 or a.batch_size < 1 or a.calibrate < 0:
@@ -114,7 +148,7 @@ def parse_interpolate(s):
 
 
 def needs_discriminator(args):
-    return bool(args.score or args.select or args.score_images)
+    return bool(args.score or args.select or args.score_images or args.refine is not None or (args.inpaint and args.critic_weight > 0))
 
 
 def check_checkpoint(args, ckpt):
@@ -195,6 +229,9 @@ def main(argv=None):
     if args.neighbours:                   # a bad reference file ends the run before an engine exists
         from hipgan.neighbours import load_reference_images
         ref = load_reference_images(args.neighbours)
+    job = None
+    if args.inpaint:                      # ... and so does a bad picture file or mask
+        job = plan_inpaint(args)
     ckpt = args.checkpoint
     if with_d:
         ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
@@ -204,6 +241,8 @@ def main(argv=None):
         s.calibrate(args.calibrate, seed=args.seed + 2)
     if args.project:
         return project_main(args, s)
+    if args.inpaint:
+        return inpaint_main(args, s, job)
     if args.score_images:
         return score_main(args, s, ref)
     if ref is not None:                   # ... and one of the wrong size before anything is sampled
@@ -219,6 +258,10 @@ def main(argv=None):
         cls = None if cls is None else cls.repeat(args.num)
     else:
         z, cls, per_row = plan(args)
+        refined = None
+        if args.refine is not None:       # the pictures are those of the refined latents
+            zr, before, after = s.refine(z, cls, steps=args.refine, lr=args.refine_lr)
+            z, refined = zr.cpu(), (before.cpu().numpy(), after.cpu().numpy())
         if args.score:                    # the scores of exactly these pictures, from the generator pass that made them
             img, *scores = s.from_latents_scored(z, cls, out="uint8")
             u8 = img.cpu().numpy()
@@ -230,6 +273,8 @@ def main(argv=None):
         arrays["labels"] = cls.numpy().astype(np.int64)
     if args.score:
         arrays["logit"], arrays["prob"] = scores[0].cpu().numpy(), scores[1].cpu().numpy()
+    if args.refine is not None:
+        arrays["logit_before"], arrays["logit_after"] = refined
     np.savez(os.path.join(args.out, "images.npz"), **arrays)
     with open(os.path.join(args.out, "grid.png"), "wb") as f:
         f.write(_encode_png(grid_u8(u8, per_row)))
@@ -278,6 +323,48 @@ def score_main(args, s, ref=None):
     print(f"{u8.shape[0]} images scored (mean prob {float(prob.mean()):.4f}) -> {args.out}/scores.npz")
     if ref is not None:
         neighbours_main(args, s, u8.numpy(), ref)
+    return 0
+
+
+def plan_inpaint(args):
+    """(pictures uint8 [n,S,S,3], known bool [S,S] or [n,S,S], class ids [n] or None) of an --inpaint run; JckError for a bad file or mask"""
+    from hipgan._lib import JckError
+    from hipgan.inpaint import parse_mask
+    from hipgan.sampler import load_projection_targets
+    u8, labels = load_projection_targets(args.inpaint)
+    n = u8.shape[0]
+    known = parse_mask(args.mask, u8.shape[1])
+    if known.dim() == 3 and known.shape[0] != n:
+        raise JckError(f"{args.mask}: {known.shape[0]} masks for {n} images")
+    cls = None
+    if args.model == "CGAN":
+        if args.classes:
+            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(n)])
+        elif labels is not None:
+            cls = labels.to(torch.int64).view(-1)
+        else:
+            raise JckError(f"{args.inpaint} has no 'labels' array: a CGAN needs it, or --classes")
+    return u8, known, cls
+
+
+def inpaint_main(args, s, job):
+    from train.gan_trainer import _encode_png
+    u8, known, cls = job
+    r = s.inpaint(u8, known, cls, steps=args.project_steps, lr=args.project_lr, critic_weight=args.critic_weight, seed=args.seed)
+    gen, done = r["generated"].cpu().numpy(), r["completed"].cpu().numpy()
+    k3 = (known if known.dim() == 3 else known.unsqueeze(0).expand(u8.shape[0], -1, -1)).numpy()
+    masked = u8.numpy() * k3[..., None].astype(np.uint8)              # the holes black
+    os.makedirs(args.out, exist_ok=True)
+    arrays = {"z": r["z"].cpu().numpy(), "loss": r["loss"].cpu().numpy(), "term": r["term"].cpu().numpy(), "known": known.numpy(),
+              "images": gen, "completed": done}
+    if cls is not None:
+        arrays["labels"] = cls.numpy().astype(np.int64)
+    np.savez(os.path.join(args.out, "inpainted.npz"), **arrays)
+    rows = np.stack([masked, gen, done], axis=1).reshape((-1,) + gen.shape[1:])      # one row per picture: masked input, G(z), completed
+    with open(os.path.join(args.out, "inpainted.png"), "wb") as f:
+        f.write(_encode_png(grid_u8(rows, 3)))
+    print(f"{gen.shape[0]} images inpainted ({s.which} generator, {args.project_steps} steps, critic weight {args.critic_weight}, "
+          f"mean loss {float(r['loss'].mean()):.5f}) -> {args.out}/inpainted.npz, inpainted.png")
     return 0
 
 

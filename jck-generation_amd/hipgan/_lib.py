@@ -40,6 +40,10 @@ PROTOS = {
     "jck_g1_fwd_affine": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "jck_conv_down_mask": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "jck_conv_down_affine": (i32, [i32, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp]),
+    "jck_conv_up_mask": (i32, [i32, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp]),
+    "jck_leaky_affine_bwd": (i32, [i32, vp, vp, vp, f32, vp, i64, i32, vp]),
+    "jck_critic_ds": (i32, [vp, i32, f32, i32, vp, vp, vp]),
+    "jck_latent_loss_ex": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "jck_score_head": (i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "jck_latent_loss": (i32, [i32, vp, vp, vp, vp, i32, i32, vp]),
     "jck_latent_adam": (i32, [i32, vp, i32, i32, vp, vp, vp, f32, f32, i32, vp, i32, i32, vp]),
@@ -128,6 +132,8 @@ PROTOS = {
     "jck_engine_sample_ex": (i32, [vp, vp, vp, i32, C.c_uint, vp, vp, vp]),
     "jck_engine_latent_grad": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "jck_engine_project": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, i32, vp, vp]),
+    "jck_engine_latent_grad_ex": (i32, [vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp]),
+    "jck_engine_project_ex": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, i32, f32, vp, vp, i32, vp, vp, vp]),
     "jck_engine_score": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "jck_engine_tensor": (vp, [vp, C.c_char_p, C.POINTER(i64)]),
     "jck_debug_tr_read": (i32, [vp, i32, vp, vp]),

@@ -858,10 +858,39 @@ class DcganEngine:
             self.repack()
         return target.to(self.device, torch.float32).contiguous(), lab
 
-    def latent_grad(self, z, target, labels=None):
+    def _critic_args(self, what, n, weight, critic, critic_weight, has_target=True):
+        """(weight fp32 [n,S,S] on the device or None, critic mode 0 / 1 / 2, critic weight) of an _ex call, validated on the host"""
+        if critic not in CRITIC_MODES:
+            raise JckError(f"{what}: critic must be None, 'nsgan' or 'logit', got {critic!r}")
+        mode, cw = CRITIC_MODES[critic], float(critic_weight)
+        if not cw >= 0.0:
+            raise JckError(f"{what}: critic_weight must be >= 0, got {critic_weight}")
+        if not mode and not has_target:
+            raise JckError(f"{what}: without a target a critic is required")
+        w = None
+        if weight is not None:
+            w = torch.as_tensor(weight)
+            if w.dim() == 2:
+                w = w.unsqueeze(0).expand(n, -1, -1)
+            if tuple(w.shape) != (n, self.size, self.size):
+                raise JckError(f"{what}: weight must be [{self.size},{self.size}] or [{n},{self.size},{self.size}], got {tuple(w.shape)}")
+            w = w.to(torch.float32)
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise JckError(f"{what}: weights must be finite and >= 0")
+            if bool((w.reshape(n, -1).sum(1) <= 0).any()):
+                raise JckError(f"{what}: an image's weights are all zero (nothing of it is known)")
+            w = w.to(self.device).contiguous()
+        if mode:
+            self._score_ready(what)
+        return w, mode, cw
+
+    def latent_grad(self, z, target, labels=None, weight=None, critic=None, critic_weight=0.0):
         """(loss [n], dz [n,100]): L_b = mean((G(z_b) - target_b)^2) and dL_b/dz_b through the generator as under model.eval()
         (BatchNorm on the running statistics; nothing is written to them).  target: fp32 NCHW [n,3,S,S] in [-1, 1].  Any n: rows
-        go through in chunks of at most `batch`, each row's numbers those of a call with that row alone."""
+        go through in chunks of at most `batch`, each row's numbers those of a call with that row alone.
+        weight ([S,S] or [n,S,S], >= 0): L_b becomes the weighted mean sum_p w_p sum_c (.)^2 / (3 sum_p w_p).  critic ("nsgan" |
+        "logit") with critic_weight: the eval-mode discriminator's term critic_weight * c(D(G(z_b))) joins the objective, dz is the
+        gradient of the sum and the result is (loss, term [n], logit [n], dz)."""
         n = z.shape[0]
         t, lab = self._latent_args("latent_grad", n, target, labels)
         zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
@@ -869,24 +898,67 @@ class DcganEngine:
             raise JckError("latent_grad: z must be [n,100]")
         loss = torch.empty(n, dtype=torch.float32, device=self.device)
         dz = torch.empty(n, 100, dtype=torch.float32, device=self.device)
+        sub = lambda x, lo, hi: None if x is None else x[lo:hi]
+        if weight is None and critic is None:
+            for lo, hi in chunk_plan(n, self.batch):
+                lib.jck_engine_latent_grad(self._h, zc[lo:hi], sub(lab, lo, hi), t[lo:hi], hi - lo, loss[lo:hi], dz[lo:hi], cur_stream())
+            self._keep_z = (zc, lab, t)
+            return loss, dz
+        w, mode, cw = self._critic_args("latent_grad", n, weight, critic, critic_weight)
+        term, logit = torch.zeros_like(loss), torch.full_like(loss, float("nan"))
         for lo, hi in chunk_plan(n, self.batch):
-            lib.jck_engine_latent_grad(self._h, zc[lo:hi], None if lab is None else lab[lo:hi], t[lo:hi], hi - lo, loss[lo:hi], dz[lo:hi],
-                                       cur_stream())
-        self._keep_z = (zc, lab, t)
-        return loss, dz
+            lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], sub(lab, lo, hi), t[lo:hi], sub(w, lo, hi), mode, cw, hi - lo, loss[lo:hi],
+                                          term[lo:hi] if mode else None, logit[lo:hi] if mode else None, dz[lo:hi], cur_stream())
+        self._keep_z = (zc, lab, t, w)
+        return (loss, term, logit, dz) if mode else (loss, dz)
 
-    def project(self, target, labels=None, steps=200, lr=0.05, prior=0.0, z0=None, seed=0, state=None):
+    def critic_grad(self, z, labels=None, mode="nsgan"):
+        """(logit [n], term [n], dz [n,100]): D(G(z)), both networks as under model.eval(), the critic's objective c of it - "nsgan":
+        softplus(-logit) = -log D, the generator's training loss; "logit": -logit - and dz = dc/dz.  Any n, rows independent."""
+        n = z.shape[0]
+        if n < 1:
+            raise JckError("critic_grad: z is empty")
+        if mode not in ("nsgan", "logit"):
+            raise JckError(f"critic_grad: mode must be 'nsgan' or 'logit', got {mode!r}")
+        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
+        if zc.shape[0] != n:
+            raise JckError("critic_grad: z must be [n,100]")
+        lab = self._score_labels("critic_grad", labels, n)
+        self._score_ready("critic_grad")
+        f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=self.device)
+        loss, term, logit, dz = f(n), f(n), f(n), f(n, 100)
+        for lo, hi in chunk_plan(n, self.batch):
+            lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], None if lab is None else lab[lo:hi], None, None, CRITIC_MODES[mode], 1.0, hi - lo,
+                                          loss[lo:hi], term[lo:hi], logit[lo:hi], dz[lo:hi], cur_stream())
+        self._keep_z = (zc, lab)
+        return logit, term, dz
+
+    def project(self, target, labels=None, steps=200, lr=0.05, prior=0.0, z0=None, seed=0, state=None, weight=None, critic=None,
+                critic_weight=0.0):
         """Fits z to `target` (fp32 NCHW [n,3,S,S] in [-1, 1]) through the frozen eval-mode generator: `steps` Adam updates
         (lr, betas (0.9, 0.999)) of z minimising mean((G(z) - target)^2) + prior * mean(z^2) per image, all on the device.
         -> (z [n,100], loss_hist [steps,n]: the loss before each update).  z0: the start (default: randn from `seed` on the host);
         state: {"m", "v", "t"} of an earlier call to continue it - the state reached is left in `self.project_state`.
-        Any n (chunks of at most `batch` rows; a row's result does not depend on the rows beside it)."""
-        n = target.shape[0]
+        Any n (chunks of at most `batch` rows; a row's result does not depend on the rows beside it).
+        weight / critic / critic_weight: the objective of latent_grad with the same keywords (masked projection: weight 0 on the
+        unknown pixels); the critic's term before each update is left in `self.project_term` [steps,n].
+        target None (refinement): the critic's term alone."""
+        if target is None and z0 is None:
+            raise JckError("project: without a target the start z0 is required")
+        n = (z0 if target is None else target).shape[0]
         if int(steps) < 1:
             raise JckError(f"project: steps must be >= 1, got {steps}")
         if not float(lr) > 0.0 or float(prior) < 0.0:
             raise JckError(f"project: lr > 0 and prior >= 0, got {lr}, {prior}")
-        t, lab = self._latent_args("project", n, target, labels)
+        if target is None:
+            if n < 1:
+                raise JckError("project: no latents")
+            t, lab = None, self._score_labels("project", labels, n)
+        else:
+            t, lab = self._latent_args("project", n, target, labels)
+        ex = weight is not None or critic is not None or target is None
+        if ex:
+            w, mode, cw = self._critic_args("project", n, weight, critic, critic_weight, target is not None)
         if z0 is None:
             z0 = torch.randn(n, 100, generator=torch.Generator().manual_seed(int(seed)))
         if tuple(z0.shape) != (n, 100):
@@ -899,14 +971,35 @@ class DcganEngine:
             if tuple(m.shape) != (n, 100) or tuple(v.shape) != (n, 100) or t0 < 0:
                 raise JckError("project: state must hold m, v [n,100] and t >= 0")
         hist = torch.empty(int(steps), n, dtype=torch.float32, device=self.device)
+        terms = torch.zeros(int(steps), n, dtype=torch.float32, device=self.device) if ex else None
+        sub = lambda x, lo, hi: None if x is None else x[lo:hi]
         for lo, hi in chunk_plan(n, self.batch):
             h = torch.empty(int(steps), hi - lo, dtype=torch.float32, device=self.device)
-            lib.jck_engine_project(self._h, z[lo:hi], None if lab is None else lab[lo:hi], t[lo:hi], hi - lo, int(steps), float(lr),
-                                   float(prior), m[lo:hi], v[lo:hi], t0, h, cur_stream())
+            if not ex:
+                lib.jck_engine_project(self._h, z[lo:hi], sub(lab, lo, hi), t[lo:hi], hi - lo, int(steps), float(lr),
+                                       float(prior), m[lo:hi], v[lo:hi], t0, h, cur_stream())
+            else:
+                th = torch.empty_like(h) if mode else None
+                lib.jck_engine_project_ex(self._h, z[lo:hi], sub(lab, lo, hi), sub(t, lo, hi), hi - lo, int(steps), float(lr), float(prior),
+                                          sub(w, lo, hi), mode, cw, m[lo:hi], v[lo:hi], t0, h, th, cur_stream())
+                if mode:
+                    terms[:, lo:hi] = th
             hist[:, lo:hi] = h
-        self._keep_z = (z, lab, t)
+        self._keep_z = (z, lab, t) + ((w,) if ex else ())
         self.project_state = {"m": m, "v": v, "t": t0 + int(steps)}
+        self.project_term = terms
         return z, hist
+
+    def refine(self, z, labels=None, steps=10, lr=0.02, mode="logit", prior=0.0):
+        """Moves latents along the discriminator's gradient: `steps` Adam updates of z minimising the critic's objective alone
+        ("logit": -D's logit; "nsgan": -log D) + prior * mean(z^2), both networks as under model.eval().
+        -> (z' [n,100], logit_before [n], logit_after [n]); logit_after is score_latents(z')."""
+        if mode not in ("nsgan", "logit"):
+            raise JckError(f"refine: mode must be 'nsgan' or 'logit', got {mode!r}")
+        z = z.reshape(-1, 100)
+        before = self.score_latents(z, labels)[0]
+        z2, _ = self.project(None, labels, steps=steps, lr=lr, prior=prior, z0=z, critic=mode, critic_weight=1.0)
+        return z2, before, self.score_latents(z2, labels)[0]
 
     def _score_ready(self, what):
         if not self._shared.get("d_loaded"):
@@ -1019,6 +1112,7 @@ class DcganEngine:
 
 
 SAMPLE_EVAL = 1            # include/jckgan.h: JCK_SAMPLE_EVAL
+CRITIC_MODES = {None: 0, "nsgan": 1, "logit": 2}      # jck_engine_latent_grad_ex's critic_mode
 
 
 def chunk_plan(n, batch):

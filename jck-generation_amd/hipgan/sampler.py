@@ -3,6 +3,9 @@
     s = Sampler.from_checkpoint("best.pt", "DCGAN")          # the averaged generator when the file has one
     u8 = s.images(1000, seed=0, truncation=0.7)                # uint8 [1000,S,S,3] on the device
     r = s.neighbours(u8, train_u8, k=4)                        # nearest training images: r["idx"], r["rmse"], r["copy"]
+    s = Sampler.from_checkpoint("best.pt", "DCGAN", with_d=True)   # ... with the checkpoint's discriminator
+    r = s.inpaint(u8, parse_mask("center:32", 64))             # hipgan.inpaint: z fitted to the known pixels, D as realism prior
+    z2, before, after = s.refine(z, steps=10)                  # latents moved along the discriminator's gradient
 
 Sampling runs with bn="running" by default (DcganEngine.sample): BatchNorm on the running statistics, every image a function of
 its own z, any n.  The running statistics of an AVERAGED generator were never fitted to its weights - they are the live ones at
@@ -215,7 +218,7 @@ class Sampler:
                           for lo, hi in chunk_plan(z.shape[0], self.engine.batch)])
 
     def images(self, n, seed=0, truncation=None, labels=None, bn="running", out="uint8", select=None, oversample=4,
-               gamma_percentile=80.0, return_info=False):
+               gamma_percentile=80.0, return_info=False, refine_steps=10, refine_lr=0.02):
         """n images from z = latents(n, seed, truncation): uint8 [n,S,S,3] or fp32 [n,3,S,S] on the device.
 
         select (needs the discriminator: from_checkpoint(..., with_d=True); eval-mode BatchNorm; labels: None or ONE class id / one-hot
@@ -224,13 +227,25 @@ class Sampler:
         fixes M (its largest logit) and gamma (the gamma_percentile-th percentile of F at gamma = 0), then rounds of oversample * n
         latents and uniforms from the same seeded generator are accepted where u < sigmoid(F) until n are kept - at most 50 * n
         draws after the burn-in, JckError beyond.  Deterministic for a seed.
+        "refine" draws n latents and moves each along the discriminator's gradient (refine_steps Adam updates at refine_lr on -logit,
+        DcganEngine.refine): the images are those of the refined latents, info holds "logit_before" and "logit_after" too.
         return_info: (images, {"z": [n,100], "logit": [n], "prob": [n], "drawn": latents drawn, "max_logit", "gamma"})."""
+        if select == "refine":
+            if bn != "running":
+                raise JckError("refinement follows the eval-mode discriminator's gradient: bn must be 'running'")
+            z0 = latents(int(n), seed, truncation)
+            lab = self._labels(labels, int(n))
+            z, before, after = self.refine(z0, lab, steps=refine_steps, lr=refine_lr)
+            img = self.engine.sample(z, lab, bn="running", out=out)
+            info = {"z": z.cpu(), "logit": after.cpu(), "prob": torch.sigmoid(after).cpu(), "drawn": int(n), "logit_before": before.cpu(),
+                    "logit_after": after.cpu()}
+            return (img, info) if return_info else img
         if select is None:
             z = latents(n, seed, truncation)
             img = self.from_latents(z, labels, bn, out)
             return (img, {"z": z, "logit": None, "prob": None, "drawn": n}) if return_info else img
         if select not in ("top", "drs"):
-            raise JckError(f"select must be None, 'top' or 'drs', got {select!r}")
+            raise JckError(f"select must be None, 'top', 'drs' or 'refine', got {select!r}")
         if bn != "running":
             raise JckError("score-guided sampling scores the eval-mode generator: bn must be 'running'")
         n, m = int(n), int(oversample)
@@ -330,6 +345,61 @@ class Sampler:
             pick = best * n + torch.arange(n, device=best.device)
             z, loss = z[pick], loss[pick]
         return z, loss
+
+    def _needs_d(self, what):
+        if not self.engine._shared.get("d_loaded"):
+            raise JckError(f"{what}: the critic is this checkpoint's discriminator: Sampler.from_checkpoint(..., with_d=True)")
+
+    def refine(self, z, labels=None, steps=10, lr=0.02, mode="logit", prior=0.0):
+        """(z' [n,100], logit_before [n], logit_after [n]) on the device: `steps` Adam updates of each latent along the eval-mode
+        discriminator's gradient (DcganEngine.refine).  Needs from_checkpoint(..., with_d=True)."""
+        self._needs_d("refine")
+        z = z.reshape(-1, NZ)
+        return self.engine.refine(z, self._labels(labels, z.shape[0]), steps=steps, lr=lr, mode=mode, prior=prior)
+
+    def inpaint(self, images_u8, known, labels=None, steps=300, lr=0.05, critic_weight=0.003, window=7, restarts=1, seed=0):
+        """Semantic inpainting (Yeh et al. 2017): fits z to the KNOWN pixels of `images_u8` (uint8 NHWC [n,S,S,3]; known: bool [S,S]
+        or [n,S,S], hipgan.inpaint.parse_mask) with the importance weighting of `window` (hipgan.inpaint.importance_weights) and
+        critic_weight * -log D(G(z)) as the realism prior (0: none, and no discriminator is needed).
+        -> {"z" [n,100], "loss" [n] (weighted, at z), "term" [n], "generated" uint8 [n,S,S,3] = G(z), "completed" uint8: the known
+        pixels of the input, the holes from G}.  restarts=R: R seeds per image, the one ending at the lowest loss + term kept."""
+        from .inpaint import _check_known, blend, importance_weights
+        x = torch.as_tensor(images_u8)
+        if x.dtype != torch.uint8:
+            raise JckError(f"inpaint: images must be uint8 [n,S,S,3], got {x.dtype}")
+        t = images_to_target(x)
+        n, R, S = t.shape[0], int(restarts), self.engine.size
+        if t.shape[2] != S:
+            raise JckError(f"images are {t.shape[2]}x{t.shape[2]}, the generator makes {S}x{S}")
+        if R < 1:
+            raise JckError(f"restarts must be >= 1, got {restarts}")
+        k = _check_known(torch.as_tensor(known).cpu(), S, "inpaint")
+        if k.dim() == 3 and k.shape[0] != n:
+            raise JckError(f"inpaint: {k.shape[0]} masks for {n} images")
+        cw = float(critic_weight)
+        if not cw >= 0.0:
+            raise JckError(f"inpaint: critic_weight must be >= 0, got {critic_weight}")
+        critic = "nsgan" if cw > 0.0 else None
+        if critic:
+            self._needs_d("inpaint")
+        w = importance_weights(k, window)
+        w = w if w.dim() == 3 else w.unsqueeze(0).expand(n, -1, -1)
+        if bool((w.reshape(n, -1).sum(1) <= 0).any()):
+            raise JckError("inpaint: the importance weights of an image are all zero (no known pixel has a hole within the window)")
+        lab = self._labels(labels, n)
+        t = t.to(self.engine.device)
+        rep = lambda a, *ones: a if a is None or R == 1 else a.repeat(R, *ones)
+        tt, ww, ll = rep(t, 1, 1, 1), rep(w.contiguous(), 1, 1), rep(lab, 1)
+        z0 = torch.cat([latents(n, int(seed) + r) for r in range(R)])
+        z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, z0=z0, weight=ww, critic=critic, critic_weight=cw)
+        res = self.engine.latent_grad(z, tt, ll, weight=ww, critic=critic, critic_weight=cw)
+        loss, term = (res[0], res[1]) if critic else (res[0], torch.zeros_like(res[0]))
+        if R > 1:
+            best = (loss + term).view(R, n).argmin(0)
+            pick = best * n + torch.arange(n, device=best.device)
+            z, loss, term = z[pick], loss[pick], term[pick]
+        gen = self.engine.sample(z, lab, bn="running", out="uint8")
+        return {"z": z, "loss": loss, "term": term, "generated": gen, "completed": blend(x.to(gen.device), gen, k)}
 
     def neighbours(self, images, ref, k=4, **kw):
         """The k nearest reference (training) images of `images` in pixel space, both uint8 NHWC, and the `copy` flags
