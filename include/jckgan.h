@@ -111,7 +111,8 @@ int jck_conv_down_affine(int prec, const void* big, const void* w, const float* 
                          void* small_out, int N, int Hb, int Wb, int Cb, int Cs, void* stream);
 /* loss_out[b] = mean over the 3 * HW real elements of (x_b - t_b)^2 with x the stored tanh output (NHWC4, element type of prec) and t
  * the caller's NCHW fp32 target, read in place; g_raw_out (NHWC4, same type) = 2 (x - t) / (3 HW) * (1 - x^2), padding channel +0.
- * One launch, one workgroup per image, a fixed-order reduction: equal bits on every run and for every N. */
+ * One launch, one workgroup per image, a fixed-order reduction: equal bits on every run and for every N.  It is jck_latent_loss_ex
+ * below with weight = g_x = NULL: the same kernel, under a profiler label of its own. */
 int jck_latent_loss(int prec, const void* x_nhwc4, const float* target_nchw_f32, void* g_raw_out, float* loss_out, int N, int HW,
                     void* stream);
 /* g = slab[0] + slab[1] + ... (Z fp32 split-K slabs [Z][N][ld] of the dz product, summed in order) + 2 * prior * z / 100, then update
@@ -139,7 +140,8 @@ int jck_critic_ds(const float* logit, int mode, float weight, int B, float* ds, 
 /* jck_latent_loss with a per-pixel weight (fp32 [N][HW], or NULL: 1) and an additive image gradient g_x (NHWC4, element type, or NULL):
  * loss_out[b] = sum_p w_p sum_c (x - t)^2 / (3 sum_p w_p), g_raw_out = (k w_p (x - t) + g_x) (1 - x^2), k = 2 / (3 sum_p w_p); two
  * fixed-order passes per image (sum w, then the loss); sum w = 0: loss 0 and no reconstruction gradient.  target NULL (g_x required):
- * loss 0, g_raw_out = g_x (1 - x^2).  weight NULL or all ones and g_x NULL: jck_latent_loss' bits. */
+ * loss 0, g_raw_out = g_x (1 - x^2).  weight NULL and g_x NULL is jck_latent_loss: no first pass, w and g_x never read; all-one
+ * weights return the same bits. */
 int jck_latent_loss_ex(int prec, const void* x_nhwc4, const float* target_nchw_f32, const float* weight, const void* g_x, void* g_raw_out,
                        float* loss_out, int N, int HW, void* stream);
 size_t jck_g1_wgrad_ws_bytes(int B, int CiPad, int Co);
@@ -463,9 +465,10 @@ int jck_engine_drop_prefetch(jck_engine*, void* stream);
 int jck_engine_check(jck_engine*);
 const float* jck_engine_scalars(const jck_engine*);
 const float* jck_engine_scalars_at(const jck_engine*, int step);   /* buffer of the given (1-based) step's parity */
-/* G forward only (train/dcgan_trainer.py:199-200, train-mode BN: running stats move); out NCHW fp32 [n,3,64,64] */
+/* G forward only (train/dcgan_trainer.py:199-200, train-mode BN: running stats move); out NCHW fp32 [n,3,64,64].
+ * jck_engine_sample_ex(flags = 0, out_u8_nhwc = NULL). */
 int jck_engine_sample(jck_engine*, const float* z, const int64_t* labels /* family 1 */, int n, float* out_nchw, void* stream);
-/* The same with options, and an optional second output.  flags == 0: exactly the launches of the call above.  JCK_SAMPLE_EVAL: the
+/* The same with options, and an optional second output.  flags == 0: train-mode BatchNorm as above.  JCK_SAMPLE_EVAL: the
  * generator as under model.eval() (model/DCGAN.py:42-66 with BatchNorm on its running statistics): one launch folds the layers' aux
  * tables, every ConvTranspose + BatchNorm + ReLU is one launch, each image depends on its own z alone, any 1 <= n <= batch, and
  * neither the running statistics nor num_batches_tracked are written.  out_nchw: fp32 [n,3,S,S] or NULL; out_u8_nhwc: uint8
@@ -481,7 +484,8 @@ int jck_engine_sample_ex(jck_engine*, const float* z, const int64_t* labels, int
  * (or NULL) is L before update s.  1 <= n <= batch; row b of every output is bit for bit what a call with that row alone returns.
  * Neither the running statistics nor num_batches_tracked nor any parameter is written.  On a training engine both may be called
  * between two steps: they use buffers that every step rewrites before it reads them, and memory of their own that the first call
- * allocates (so: not inside a graph capture) and jck_engine_destroy frees. */
+ * allocates (so: not inside a graph capture) and jck_engine_destroy frees.  Both forward to the _ex entry points below with
+ * weight = NULL, critic_mode = 0, critic_weight = 0 and term = logit = term_hist = NULL: one implementation. */
 int jck_engine_latent_grad(jck_engine*, const float* z, const int64_t* labels, const float* target_nchw, int n,
                            float* loss /* [n] */, float* dz /* [n,100] */, void* stream);
 int jck_engine_project(jck_engine*, float* z /* in, out */, const int64_t* labels, const float* target_nchw, int n,
@@ -492,7 +496,7 @@ int jck_engine_project(jck_engine*, float* z /* in, out */, const int64_t* label
  * critic only) and term_b = critic_weight * c(D(G(z_b))), c = softplus(-logit) (critic_mode 1, nsgan) or -logit (2, logit); mode 0:
  * no critic.  latent_grad_ex: loss = L [n], term [n] (or NULL), logit [n] (or NULL) and dz = d(L + term)/dz.  project_ex:
  * jck_engine_project on that objective; term_hist[s][n] (or NULL) is term before update s.  With weight NULL and critic_mode 0 both
- * issue the launches of the entry points above and return their bits.  With a critic one evaluation is: the eval generator's products,
+ * are the entry points above (the products, jck_latent_loss_ex, the projection's backward).  With a critic one evaluation is: the eval generator's products,
  * jck_engine_score's stages and head on its output, jck_critic_ds, the head's input gradient, jck_leaky_affine_bwd at the deepest stage,
  * jck_conv_up_mask per stage down to stage 1, jck_conv_up into an image gradient, jck_latent_loss_ex, then the projection's backward.
  * D's gradients, the image gradient and the critic's rows are ONE allocation that the first call with a critic makes (so: not inside

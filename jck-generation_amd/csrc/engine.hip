@@ -2,23 +2,11 @@
 // schedule of kernel launches on a HIP stream.  The host makes one call per phase; nothing in here
 // allocates, synchronises or reads back - scalars stay on the device until the trainer logs them.
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "ops_internal.hpp"
-#include "ew_optim.hpp"      // the kernels this file launches itself: pack_multi_kernel, pack_tail_kernel, pad_rows_kernel
+#include "engine_internal.hpp"      // ew_optim.hpp with it: the kernels this file launches itself (pack_multi_kernel, pack_tail_kernel)
 #define JCK_BATCHED_DEFAULT 3
-struct jck_engine;
-#define TT (e->T)        /* the engine's channel plan; `e` is the engine in every function below (this inside its members) */
 
 namespace {
-
-struct TensorInfo { const char* name; int kind; long long offset, numel; int shape[4]; };
-
-struct NetLayout {
-  std::vector<TensorInfo> t;
-  long long n_params = 0, n_bn = 0;
-};
 
 constexpr long long ALIGN_F = 64;   // floats
 
@@ -38,17 +26,6 @@ void add_bn(NetLayout& L, const char* wn, const char* bn, const char* rm, const 
   L.n_bn += (c + ALIGN_F - 1) / ALIGN_F * ALIGN_F;
 }
 
-// Channel plan.  S = 64 is the reference's topology (model/DCGAN.py:10-26, :42-58): NS = 4 stride-2 stages, 512 channels at
-// the 4x4 end.  S = 128 (BASELINE.json configs[4]; no reference behaviour exists - SURVEY section 8d) adds ONE stage at the
-// deep end, the usual way a DCGAN is grown: D 3 -> 64 -> 128 -> 256 -> 512 -> 1024 -> 1, G 100 -> 1024 -> ... -> 64 -> 3,
-// so every layer keeps >= 64 channels on its wide side and the image-side layers stay 3 <-> 64.
-#define JCK_MAX_STAGES 5
-struct Topo {
-  int S, NS, HW;                       // image size, stride-2 stages, S*S
-  int D_CS[JCK_MAX_STAGES], D_CB[JCK_MAX_STAGES], D_HB[JCK_MAX_STAGES];
-  int G_CS[JCK_MAX_STAGES], G_CB[JCK_MAX_STAGES], G_HS[JCK_MAX_STAGES];     // G.conv2 .. G.conv(NS+1)
-  int G_C1, FEAT;                      // channels at the 4x4 end; D's flattened top features 16*G_C1
-};
 Topo make_topo(int S) {
   Topo T = {};
   T.S = S; T.NS = S == 128 ? 5 : 4; T.HW = S * S;
@@ -60,18 +37,6 @@ Topo make_topo(int S) {
   }
   return T;
 }
-const int N_CLASS = 100, EMB = 200, L1_OUT = 256, L1_FEAT = 8192, L1_K = L1_FEAT + EMB, L1_KPAD = 8448;   // model/CGAN.py:83,104
-// split-K of Linear(8392, 256): 132 k-steps of 64 over L1_KSPLIT workgroups per tile (a divisor of 132; hipgan/functional.py uses the same)
-constexpr int L1_KSPLIT = 12;
-inline int z_dim(int family) { return family == 1 ? 200 : 100; }      // model/CGAN.py:132: ConvTranspose2d(200, 512)
-inline int z_pad(int family) { return family == 1 ? 256 : 128; }
-
-static const char* const CWN[6] = {"conv1.weight", "conv2.weight", "conv3.weight", "conv4.weight", "conv5.weight", "conv6.weight"};
-static const char* const NWN[5] = {"norm1.weight", "norm2.weight", "norm3.weight", "norm4.weight", "norm5.weight"};
-static const char* const NBN[5] = {"norm1.bias", "norm2.bias", "norm3.bias", "norm4.bias", "norm5.bias"};
-static const char* const RMN[5] = {"norm1.running_mean", "norm2.running_mean", "norm3.running_mean", "norm4.running_mean", "norm5.running_mean"};
-static const char* const RVN[5] = {"norm1.running_var", "norm2.running_var", "norm3.running_var", "norm4.running_var", "norm5.running_var"};
-
 NetLayout make_layout(int family, int net, int S = 64) {
   NetLayout L;
   const Topo T = make_topo(S);
@@ -104,277 +69,11 @@ NetLayout make_layout(int family, int net, int S = 64) {
   return L;
 }
 
-const TensorInfo* find(const NetLayout& L, const char* name) {
-  for (auto& t : L.t) if (!strcmp(t.name, name)) return &t;
-  return nullptr;
-}
-
-struct Carver {
-  size_t off = 0;
-  unsigned char* base = nullptr;
-  template <typename T> T* take(size_t count) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off = (off + count * sizeof(T) + 255) / 256 * 256;
-    return p;
-  }
-};
-
-struct BnBuf { float *stats, *sums, *aux; int slots; };      // G's BatchNorm buffers of one stage
-
-// D's activations for `cap` batches of B images stored back to back (cap = 1: the set of one pass, 3: the batched schedule's
-// [real | fake | penalty]), or a view of `groups` of them from group `g0` on.  Per stage: conv output y, activation a, gradient g,
-// BatchNorm statistic slots / scale-shift table / backward sums.  Per set: probabilities and logit gradients, and - the penalty
-// pass - the gradient w.r.t. its input image and that gradient's per-image norms.
-struct DActs {
-  void *y[JCK_MAX_STAGES], *a[JCK_MAX_STAGES], *g[JCK_MAX_STAGES], *gx;
-  float *stats[JCK_MAX_STAGES], *aux[JCK_MAX_STAGES], *sums[JCK_MAX_STAGES], *prob, *ds, *norms;
-  int cap, g0, groups;
-  DActs group(const jck_engine* e, int first, int n) const;      // groups [first, first + n) of this set or view
-};
-
 }  // namespace
 
 // the engine's events order kernels of ONE device across its streams: no system-scope fence (cache write-back for the host's sake)
 // when they are recorded
 static unsigned jck_event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
-// What one phase call leaves behind for a later one - the state of the step in flight.  Everything else in jck_engine is
-// configuration, buffers, streams or the per-call selection (parity, acc, scal_out, cur_labels) that every phase call makes anew.
-struct StepState {
-  bool gp_done = false;                 // the penalty's forward and first backward ran as group 2 of the batched pass (PHASE_D_LOSS / _B; consumed by PHASE_D_GP)
-  bool gp_inflight = false;             // the penalty pass runs on sC, evGP behind it (per-pass PHASE_D_LOSS / PHASE_D_FAKE; joined by PHASE_D_GP)
-  bool join_pending = false, mid_recorded = false;    // PHASE_LAZY_JOIN: evWdone (and evWmid) recorded on sA, not yet waited for
-  long long real_fwd_step = -1;         // step whose D(real) forward already ran (PHASE_D_REAL_FWD), -1: none
-  bool tail_on_side = false, pre_on_side = false;       // PHASE_D_LOSS_A's tail marker sits on sA; PHASE_D_REAL_FWD ran on sA (evReal)
-  int head_row0 = 0;                    // CGAN: first row of the head state (h_drop, cbuf, pre_e) the pass in hand READS (2B: penalty group of a batched head)
-  int head_wrow0 = 0;                   //       first row of the head buffers it WRITES (g_hd, g_h, gc)
-  int acc_clean_step = -1;              // the step whose accumulator rows jck_engine_set_step has just cleared (consumed by its first D phase)
-  // zero_grad() without a launch of its own: D's gradient arena (+ CGAN's permuted Linear gradient) is cleared by the set-step
-  // launch of the step's first D phase, G's by D's Adam launch; the step whose arena is clean (consumed by the phase that would memset)
-  int dg_clean_step = -1, gg_clean_step = -1;
-  long long gz_step = -1;               // the step whose set-step launch wrote its own z into g_z (G.conv1's operand) as well
-  // a phase that failed half way leaves no promise behind: the next D phase clears its arenas itself and joins the
-  // weight-gradient stream before anything else (state armed before a failing call must not outlive it)
-  void drop_promises() { acc_clean_step = dg_clean_step = gg_clean_step = -1; join_pending = mid_recorded = false; }
-  // PHASE_GP_ONLY clears the accumulator rows and D's gradient arena itself and runs the penalty as a pass of its own on set 0
-  void begin_gp_only() { acc_clean_step = dg_clean_step = -1; gp_done = gp_inflight = false; head_row0 = head_wrow0 = 0; }
-};
-struct jck_engine {
-  int family, prec, B;
-  Topo T;
-  size_t esz;
-  NetLayout LG, LD;
-  size_t ws_bytes = 0;
-  bool bound = false;
-  // arenas
-  float *gp = nullptr, *gg = nullptr, *gm = nullptr, *gv = nullptr, *gbn = nullptr;
-  float *dp = nullptr, *dg = nullptr, *dm = nullptr, *dv = nullptr, *dbn = nullptr;
-  int64_t *gnbt = nullptr, *dnbt = nullptr;
-  // exponential moving average of G's parameters (jck_engine_bind_ema; null: none): advanced by Adam(G)'s launch with the weight
-  // jck_engine_set_ema configures - 1 below ema_start (the average tracks the weights), 1 - decay from there on
-  float* gema = nullptr;
-  double ema_decay = 0.0; int ema_start = 0;
-  float ema_w(int step) const { return !gema ? 0.f : (step < ema_start ? 1.f : (float)(1.0 - ema_decay)); }
-  int graph_nodes = 0;                  // nodes of the graph jck_engine_capture_end instantiated last
-  // packed weights
-  void *d_down[JCK_MAX_STAGES], *d_up[JCK_MAX_STAGES];
-  float *d_head_wp, *d_head_dwp;
-  void *g1_w, *g_up[JCK_MAX_STAGES], *g_down[JCK_MAX_STAGES];
-  // activations: three B-image D sets for the per-pass schedules (each pass that may run concurrently has its own)
-  DActs dset[3] = {};                   // 0: D(fake) and the G-phase pass, 1: penalty pass, 2: D(real) (may overlap the previous step's G phase)
-  // batched D passes: up to 3 batches that share D's weights go through ONE launch per layer, BatchNorm grouped.  The penalty
-  // group's image gradient and norms go where the per-pass schedule leaves them: bset.gx / .norms are dset[0]'s
-  DActs bset = {};
-  int batched = 0;                      // 0: one D pass per batch (batch % 8 != 0, JCK_BATCHED=0), 3: [real | fake | penalty] as ONE 3B pass
-  StepState ss;                         // what the phases of a step hand to one another
-  float* d_rs[JCK_MAX_STAGES];                       // deferred BatchNorm running-stat records of D: [step parity][pass 0..3][2*C] per layer
-  int parity = 0;                       // step & 1: selects the scalar accumulators and the BN records of the step in flight
-  // side streams: A = weight gradients beside the dgrad chain, B = G forward beside D(real), C = penalty pass beside D(fake)
-  hipStream_t sA = nullptr, sB = nullptr, sC = nullptr;
-  hipEvent_t evW[JCK_MAX_STAGES] = {}, evWdone = nullptr, evWmid = nullptr, evHead = nullptr, evTail = nullptr, ev0 = nullptr, evF = nullptr, evReal = nullptr, evGP = nullptr;
-  template <typename F> void for_each_side_stream(F f) { for (hipStream_t* p : {&sA, &sB, &sC}) f(*p); }
-  template <typename F> void for_each_event(F f) {
-    for (hipEvent_t* p : {&evWdone, &evWmid, &evHead, &evTail, &ev0, &evF, &evReal, &evGP}) f(*p);
-    for (hipEvent_t& p : evW) f(p);
-  }
-  bool overlap = true, defer_join = true;
-  bool wgrad_side = true;               // weight gradients beside the dgrad chain on sA (JCK_WGRAD_SIDE=0: on the main stream)
-  bool head_side = true;                // the head's parameter gradients on sA as well (JCK_HEAD_SIDE=0: on the main stream)
-  // cross-stream hand-overs of the backward: the producing launch completes the event itself (the `done` argument of
-  // bn_act_bwd_res_ev / tanh_bwd_ev: hipExtLaunchKernel's stop event) instead of a
-  // hipEventRecord behind it; JCK_EXT_EVENTS=0 restores the records
-  bool ext_events = true;
-  // resident one-launch BatchNorm backward (bnres.hpp): grid-barrier state (zeroed at bind); JCK_BN_RES=0 switches it off
-  unsigned* gsync = nullptr; bool bn_res = true;
-  bool cbuf_direct = true;              // CGAN: D's last BatchNorm+LeakyReLU writes straight into the head's concat buffer (JCK_CBUF_DIRECT=0: a copy)
-  bool head_fuse = true;                // CGAN: Linear finish + Linear(256,1)/sigmoid/BCE + its input gradient + Dropout backward as one launch; DCGAN: conv5's
-                                        // forward writes its input gradient too (JCK_HEAD_FUSE=0: separate launches)
-  bool real_side = true;                // batched D pass: D(real)'s forward beside G's forward on the weight-gradient stream (JCK_REAL_SIDE=0: one 3B forward)
-  bool fold_zero = true;                // zero_grad() of both networks inside neighbouring launches (JCK_FOLD_ZERO=0: memsets)
-  bool fuse_tanh = true;                // G's loss pass: tanh backward in the epilogue of D.conv1's input gradient (JCK_FUSE_TANH=0: a launch of its own)
-  void *g_z, *g_y[JCK_MAX_STAGES], *g_a[JCK_MAX_STAGES], *g_gr[JCK_MAX_STAGES], *fake_raw, *fake, *g_raw;
-  void *real_noisy, *xhat;
-  // small buffers
-  BnBuf g_bn[JCK_MAX_STAGES];
-  float *acc, *scal_out;                // current-parity views into acc2 / scal2
-  float *acc2, *scal2;                  // acc2: [2 parities][8 rows][acc_ld] per-image scalar table (summed by the step tail)
-  int acc_ld = 0;
-  float *head_ws, *gp2_ws;              // partial rows of the head weight gradients (deterministic two-stage sums)
-  float* hp2;                           // [2 parities][8]: {step_size, bc2_sqrt, EMA weight, -, noise seed lo, hi, step, 0} of the step in flight (jck_engine_set_step)
-  unsigned long long noise_seed = 0x6a636b67616e0001ull;      // in-kernel instance noise (jck_engine_set_noise_seed)
-  float *rz[2] = {nullptr, nullptr}, *ralpha[2] = {nullptr, nullptr}, *rmask[2] = {nullptr, nullptr};
-  int hp_step[2] = {0, 0};              // which step's scalars each parity holds (checked by the optimiser phases) ...
-  float hp_lr[2] = {-1.f, -1.f};        // ... and at which learning rate they were computed (a scheduler may change it between steps)
-  bool hp_holds(int step, float lr) const { return hp_step[step & 1] == step && hp_lr[step & 1] == lr; }
-  bool capturing = false;
-  bool gp_bwd = false;                  // DCGAN created with JCK_ENGINE_GP_BACKWARD: PHASE_D_GP back-propagates the penalty as CGAN's does
-  float* g1_ws = nullptr; size_t g1_ws_bytes = 0;
-  float* wg_ws; size_t wg_ws_bytes;
-  // family 1 (CGAN): Linear head, label path, second-order penalty buffers
-  void *l1_w, *l1_wT;                 // packed linear1: [256][8448] and transposed [8448][256]
-  void *cbuf, *cbuf2;                 // [B][8448] concat(flatten(a4), e) ; [u4 | 0]
-  void *h_pre, *h_drop, *g_h, *g_hd, *gh_b1, *ughd, *gc;    // [B][256] x6, [B][8448]
-  float *pre_e, *l1_slab, *gw1p, *rs, *prob_gp;
-  void *d_v[JCK_MAX_STAGES], *d_xdir[JCK_MAX_STAGES], *d_u0;
-  float* bn2_ws[JCK_MAX_STAGES]; float* bn2_ws_rev;
-  const int64_t* cur_labels = nullptr;
-  // latent projection (jck_engine_latent_grad / jck_engine_project): memory of its own, allocated by the first such call and freed
-  // with the engine - G.conv1's weight as the dz product's operand [128][16 * G_C1], that product's split-K slabs, a loss row (one allocation)
-  void* lat_w = nullptr; float *lat_slab = nullptr, *lat_loss = nullptr;
-  // discriminator inference (jck_engine_score): memory of its own as well, one allocation made by the first scoring call - the
-  // transformed input, a stage's activations and folded aux table each, one pre-activation tensor that the stages share (bf16: see
-  // jck_engine_score), and CGAN's head rows (concat buffer, split-K slabs, hidden row)
-  struct ScoreBufs {
-    void* base = nullptr;
-    void *x = nullptr, *y = nullptr, *a[JCK_MAX_STAGES] = {}, *cbuf = nullptr, *h = nullptr;
-    float *aux[JCK_MAX_STAGES] = {}, *slab = nullptr;
-  } sc;
-  // the critic's latent gradient (jck_engine_latent_grad_ex / jck_engine_project_ex with critic_mode != 0): memory of its own too, one
-  // allocation made by the first such call - the gradient at every stage's pre-activation, the image gradient (NHWC4), the rows
-  // ds / term / logit, and CGAN's gradient rows at the Linear(8392,256) output and at the concat buffer
-  struct CriticBufs {
-    void* base = nullptr;
-    void *g[JCK_MAX_STAGES] = {}, *gx = nullptr, *g_h = nullptr, *gc = nullptr;
-    float *ds = nullptr, *term = nullptr, *logit = nullptr;
-  } cr;
-  bool d_packed = false;                // D's operands were derived from its parameters at least once (jck_engine_repack, a D step)
-
-  void carve(unsigned char* base) {
-    jck_engine* e = this;
-    Carver c; c.base = base;
-    auto bytes = [&](size_t n) { return n * esz; };
-    for (int i = 0; i < TT.NS; ++i) {
-      d_down[i] = c.take<unsigned char>(bytes((size_t)jck_pad_rows(TT.D_CS[i]) * 16 * jck_pad_chan(TT.D_CB[i])));
-      d_up[i] = c.take<unsigned char>(bytes((size_t)4 * jck_pad_rows(TT.D_CB[i]) * 4 * TT.D_CS[i]));
-    }
-    d_head_wp = c.take<float>(TT.FEAT); d_head_dwp = c.take<float>(TT.FEAT);
-    g1_w = c.take<unsigned char>(bytes((size_t)16 * TT.G_C1 * z_pad(family)));
-    for (int i = 0; i < TT.NS; ++i) {
-      g_up[i] = c.take<unsigned char>(bytes((size_t)4 * jck_pad_rows(TT.G_CB[i]) * 4 * TT.G_CS[i]));
-      g_down[i] = c.take<unsigned char>(bytes((size_t)jck_pad_rows(TT.G_CS[i]) * 16 * jck_pad_chan(TT.G_CB[i])));
-    }
-    const size_t img = (size_t)B * TT.HW * 4;
-    auto take_set = [&](DActs& D, int cap, bool penalty_out) {
-      D.cap = D.groups = cap; D.g0 = 0;
-      for (int i = 0; i < TT.NS; ++i) {
-        const size_t n = (size_t)cap * B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i];
-        D.y[i] = c.take<unsigned char>(bytes(n)); D.a[i] = c.take<unsigned char>(bytes(n)); D.g[i] = c.take<unsigned char>(bytes(n));
-        D.sums[i] = c.take<float>(cap * jck_bn_bwd_ws_floats(TT.D_CS[i]));
-        D.aux[i] = c.take<float>(cap * 4 * TT.D_CS[i]);
-        D.stats[i] = c.take<float>(jck_stats_floats((long long)cap * B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2), TT.D_CS[i], 1));
-      }
-      if (penalty_out) D.gx = c.take<unsigned char>(bytes(img));
-      D.prob = c.take<float>((size_t)cap * B); D.ds = c.take<float>((size_t)cap * B);
-      if (penalty_out) D.norms = c.take<float>(B);
-    };
-    for (DActs& D : dset) take_set(D, 1, true);
-    for (int i = 0; i < TT.NS; ++i) d_rs[i] = c.take<float>(2 * 4 * 2 * TT.D_CS[i]);
-    g_z = c.take<unsigned char>(bytes((size_t)B * z_pad(family)));
-    // G layer i (0..3): output of conv(i+1) = [B, h, h, C] with (h, C) = (4,512), (8,256), (16,128), (32,64)
-    for (int i = 0; i < TT.NS; ++i) {
-      const int h = 4 << i, C = TT.G_C1 >> i;
-      const size_t n = (size_t)B * h * h * C;
-      g_y[i] = c.take<unsigned char>(bytes(n)); g_a[i] = c.take<unsigned char>(bytes(n)); g_gr[i] = c.take<unsigned char>(bytes(n));
-    }
-    fake_raw = c.take<unsigned char>(bytes(img)); g_raw = c.take<unsigned char>(bytes(img));
-    // real_noisy | fake | xhat are consecutive (img bytes % 256 == 0): the batched D pass reads them as one 3B-image tensor
-    real_noisy = c.take<unsigned char>(bytes(img)); fake = c.take<unsigned char>(bytes(img)); xhat = c.take<unsigned char>(bytes(img));
-    if (batched) {
-      take_set(bset, 3, false);
-      bset.gx = dset[0].gx; bset.norms = dset[0].norms;
-    }
-    for (int i = 0; i < TT.NS; ++i) g_bn[i].sums = c.take<float>(jck_bn_bwd_ws_floats(TT.G_C1 >> i));
-    for (int i = 0; i < TT.NS; ++i) {
-      const int C = TT.G_C1 >> i, h = 4 << i;
-      g_bn[i].aux = c.take<float>(4 * C);
-      g_bn[i].stats = c.take<float>(jck_stats_floats((long long)B * h * h, C, i == 0 ? 16 : 1));
-    }
-    acc_ld = (B + 63) / 64 * 64;
-    acc2 = c.take<float>((size_t)2 * 8 * acc_ld); scal2 = c.take<float>(16);
-    acc = acc2; scal_out = scal2;
-    hp2 = c.take<float>(16);
-    // the step's small random inputs when the caller hands over none, per step parity (jck_engine_set_step draws them)
-    for (int q = 0; q < 2; ++q) {
-      rz[q] = c.take<float>((size_t)B * 100); ralpha[q] = c.take<float>((size_t)(B + 3) / 4 * 4);
-      rmask[q] = family == 1 ? c.take<float>((size_t)4 * B * L1_OUT) : nullptr;
-    }
-    head_ws = c.take<float>(jck_head_bwd_ws_floats(TT.FEAT));
-    gp2_ws = c.take<float>((size_t)acc_ld + jck_head_bwd_ws_floats(L1_OUT));
-    gsync = c.take<unsigned>(jck_grid_sync_bytes() / sizeof(unsigned));
-    size_t w = 0;
-    for (int i = 0; i < TT.NS; ++i) {
-      w = std::max(w, jck_conv_wgrad_ws_bytes(B, TT.D_HB[i], TT.D_HB[i], TT.D_CB[i], TT.D_CS[i]));
-      w = std::max(w, jck_conv_wgrad_ws_bytes(2 * B, TT.D_HB[i], TT.D_HB[i], TT.D_CB[i], TT.D_CS[i]));
-      w = std::max(w, jck_conv_wgrad_ws_bytes(B, TT.G_HS[i] * 2, TT.G_HS[i] * 2, TT.G_CB[i], TT.G_CS[i]));
-    }
-    w = std::max(w, jck_g1_wgrad_ws_bytes(B, z_pad(family), TT.G_C1));
-    if (family == 1) w = std::max(std::max(w, jck_linear_wgrad_ws_bytes(B, L1_KPAD, L1_OUT)), jck_linear_wgrad_ws_bytes(2 * B, L1_KPAD, L1_OUT));
-    wg_ws_bytes = w;
-    wg_ws = c.take<float>(w / 4);
-    // G.conv1's weight gradient runs on the MAIN stream at the very end of G's backward (it needs the last BatchNorm backward,
-    // which is on that stream): its own split-K workspace, because the side stream may still be using wg_ws
-    g1_ws_bytes = jck_g1_wgrad_ws_bytes(B, z_pad(family), TT.G_C1);
-    g1_ws = c.take<float>(g1_ws_bytes / 4);
-    if (family == 1) {
-      l1_w = c.take<unsigned char>(bytes((size_t)L1_OUT * L1_KPAD)); l1_wT = c.take<unsigned char>(bytes((size_t)L1_KPAD * L1_OUT));
-      // head buffers: HR batches of rows - the batched schedule runs the label / Linear / Dropout head of the real | fake |
-      // penalty groups as ONE 3B-row pass (cg_head_batched)
-      const size_t HR = batched ? 3 : 1;
-      cbuf = c.take<unsigned char>(bytes(HR * B * L1_KPAD)); cbuf2 = c.take<unsigned char>(bytes((size_t)B * L1_KPAD));
-      h_pre = c.take<unsigned char>(bytes(HR * B * L1_OUT)); h_drop = c.take<unsigned char>(bytes(HR * B * L1_OUT));
-      g_h = c.take<unsigned char>(bytes(HR * B * L1_OUT)); g_hd = c.take<unsigned char>(bytes(HR * B * L1_OUT));
-      gh_b1 = c.take<unsigned char>(bytes((size_t)B * L1_OUT)); ughd = c.take<unsigned char>(bytes((size_t)B * L1_OUT));
-      gc = c.take<unsigned char>(bytes(HR * B * L1_KPAD));
-      pre_e = c.take<float>(HR * B * EMB); l1_slab = c.take<float>((size_t)L1_KSPLIT * HR * B * L1_OUT);
-      gw1p = c.take<float>((size_t)L1_OUT * L1_KPAD);
-    }
-    // second-order penalty buffers: CGAN, and DCGAN with JCK_ENGINE_GP_BACKWARD (a default DCGAN engine carves none of them)
-    if (family == 1 || gp_bwd) {
-      rs = c.take<float>(B); prob_gp = c.take<float>(B);
-      for (int i = 0; i < TT.NS; ++i) {
-        const size_t n = (size_t)B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i];
-        d_v[i] = c.take<unsigned char>(bytes(n)); d_xdir[i] = c.take<unsigned char>(bytes(n));
-        bn2_ws[i] = c.take<float>(jck_bn2_ws_floats(TT.D_CS[i]));
-      }
-      bn2_ws_rev = c.take<float>(jck_bn2_ws_floats(TT.G_C1));          // the widest D stage: 512, 1024 on the 128x128 plan
-      d_u0 = c.take<unsigned char>(bytes(img));
-    }
-    ws_bytes = c.off;
-  }
-
-  float* P(const NetLayout& L, float* arena, const char* name) const { return arena + find(L, name)->offset; }
-  const unsigned* rng() const { return reinterpret_cast<const unsigned*>(hp2 + 8 * parity + 4); }     // this step's Philox words
-  // fake = 0.9 * G(z) + 0.1 * N(0,1) (:171): uploaded noise, or drawn in the kernel when the step carries none
-  int mix_fake_noise(const jck_step_inputs* in, int B, hipStream_t st) {
-    if (!in->noise_fake) return jck_axpy_noise_rng(prec, fake_raw, rng(), 1, 0.9f, 0.1f, fake, B, T.HW, st);
-    return jck_axpy_noise(prec, fake_raw, in->noise_fake, 0.9f, 0.1f, fake, B, T.HW, st);
-  }
-  // ... and the penalty's interpolate (:111-113) in the same launch
-  int mix_fake_noise_interp(const jck_step_inputs* in, int B, hipStream_t st) {
-    return jck_mix_interp(prec, fake_raw, in->noise_fake, in->noise_fake ? nullptr : rng(), 1, 0.9f, 0.1f, fake, real_noisy, in->alpha, xhat,
-                          B, T.HW, st);
-  }
-};
-
 
 DActs DActs::group(const jck_engine* e, int first, int n) const {
   DActs v = *this;
@@ -572,7 +271,6 @@ extern "C" int jck_engine_repack(jck_engine* e, int net, void* stream) {
 // ---------------------------------------------------------------------------------------------------------
 // building blocks
 // ---------------------------------------------------------------------------------------------------------
-static const float BN_MOM = 0.1f, BN_EPS = 1e-5f, LRELU = 0.2f;
 static const double ADAM_B1 = 0.5, ADAM_B2 = 0.999, ADAM_EPS = 1e-8;      // both optimisers (train/dcgan_trainer.py:61-62)
 
 
@@ -967,15 +665,9 @@ static int gp_double_backward(jck_engine* e, const DActs& P, const void* xhat, i
   return JCK_OK;
 }
 
-template <typename T>
-static void launch_pad_rows(const float* z, int B, int zd, int zp, void* out, hipStream_t st) {
-  const long long total = (long long)B * zp;
-  hipLaunchKernelGGL(pad_rows_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, B, zd, zp, (T*)out);
-}
-
 // The eval-mode generator in two pieces (g_forward(eval) runs both; a latent projection folds once and runs the products per iteration).
 // Fold: one launch writes every layer's scale / shift (gamma, beta and the running statistics) into the stage's aux table ...
-static int g_eval_fold(jck_engine* e, hipStream_t st) {
+int g_eval_fold(jck_engine* e, hipStream_t st) {
   const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
   float* aux[JCK_MAX_STAGES];
   int Cs[JCK_MAX_STAGES];
@@ -987,7 +679,7 @@ static int g_eval_fold(jck_engine* e, hipStream_t st) {
   return jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st);
 }
 // ... and the products apply them and the ReLU in their epilogues: g_z -> g_a[0..NS-1] -> fake_raw
-static int g_eval_products(jck_engine* e, int B, hipStream_t st) {
+int g_eval_products(jck_engine* e, int B, hipStream_t st) {
   const int zp = z_pad(e->family);
   auto scale = [&](int i) { return e->g_bn[i].aux; };
   auto shift = [&](int i) { return e->g_bn[i].aux + (TT.G_C1 >> i); };
@@ -1006,7 +698,7 @@ static int g_eval_products(jck_engine* e, int B, hipStream_t st) {
 // scale / shift (the stage's aux table, which every train-mode forward rewrites before its backward reads it), and each product
 // applies them and the ReLU in its epilogue - one launch and one activation store per stage, images independent of each other,
 // no statistics, running statistics and num_batches_tracked untouched.
-static int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B, hipStream_t st, bool z_in_place = false, bool eval = false) {
+int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B, hipStream_t st, bool z_in_place, bool eval) {
   const int zp = z_pad(e->family);
   if (e->family == 1) {
     if (!labels) JCK_FAIL(JCK_E_ARG, "CGAN generator needs labels");
@@ -1676,317 +1368,6 @@ extern "C" int jck_engine_check(jck_engine* e) {
 }
 extern "C" const float* jck_engine_scalars(const jck_engine* e) { return e ? e->scal_out : nullptr; }
 extern "C" const float* jck_engine_scalars_at(const jck_engine* e, int step) { return e ? e->scal2 + 8 * (step & 1) : nullptr; }
-
-extern "C" int jck_engine_sample(jck_engine* e, const float* z, const int64_t* labels, int n, float* out_nchw, void* stream) {
-  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "engine not bound");
-  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "sample: n must be in [1, batch]");
-  hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(g_forward(e, z, labels, n, st));
-  return jck_nhwc4_to_nchw(e->prec, e->fake_raw, out_nchw, n, TT.HW, st);
-}
-
-extern "C" int jck_engine_sample_ex(jck_engine* e, const float* z, const int64_t* labels, int n, unsigned flags, float* out_nchw,
-                                    unsigned char* out_u8_nhwc, void* stream) {
-  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "engine not bound");
-  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "sample: n must be in [1, batch]");
-  if (flags & ~JCK_SAMPLE_EVAL) JCK_FAIL(JCK_E_ARG, "sample: unknown flag");
-  hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(g_forward(e, z, labels, n, st, false, (flags & JCK_SAMPLE_EVAL) != 0));
-  if (out_nchw) JCK_TRY(jck_nhwc4_to_nchw(e->prec, e->fake_raw, out_nchw, n, TT.HW, st));
-  if (out_u8_nhwc) JCK_TRY(jck_img_to_u8(e->prec, e->fake_raw, out_u8_nhwc, n, TT.HW, st));
-  return JCK_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// latent projection: dL/dz through the frozen generator under model.eval(), L_b = mean((G(z_b) - t_b)^2), and Adam on z.
-// Beside the step: it uses only buffers that every step rewrites before reading (g_z, g_a, g_gr, g_raw, fake_raw, the stages' aux) -
-// never real_noisy or D's activations, which a prefetched D(real) forward may own - and memory of its own.  Image b's numbers do not
-// depend on n: no statistic, a per-image loss reduction, a split-K factor that is a constant.
-// ---------------------------------------------------------------------------------------------------------
-constexpr int LAT_KSPLIT = 16, LAT_LD = 128;          // 16 * G_C1 / 64 = 128 (64 x 64) or 256 (128 x 128) k-steps: 8 or 16 per slab
-static int latent_check(jck_engine* e, const float* z, const int64_t* labels, const float* target, int n, const char* who) {
-  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, std::string(who) + ": engine not bound");
-  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, std::string(who) + ": n must be in [1, batch]");
-  if (!z || !target) JCK_FAIL(JCK_E_ARG, std::string(who) + ": null z / target");
-  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, std::string(who) + ": CGAN generator needs labels");
-  if (e->capturing) JCK_FAIL(JCK_E_ARG, std::string(who) + ": not inside a graph capture");
-  return JCK_OK;
-}
-// operand rows from z (and the labels), the BatchNorm fold and the pack of G.conv1's weight for the dz product: once per call
-static int latent_begin(jck_engine* e, const float* z, const int64_t* labels, int n, hipStream_t st) {
-  const int K = 16 * TT.G_C1, zp = z_pad(e->family);
-  if (!e->lat_w) {
-    const size_t wb = (size_t)LAT_LD * K * e->esz, sb = (size_t)LAT_KSPLIT * e->B * LAT_LD * sizeof(float);      // both multiples of 256
-    HIPCHK(hipMalloc(&e->lat_w, wb + sb + (size_t)e->B * sizeof(float)));
-    e->lat_slab = reinterpret_cast<float*>((unsigned char*)e->lat_w + wb);
-    e->lat_loss = reinterpret_cast<float*>((unsigned char*)e->lat_w + wb + sb);
-  }
-  if (e->family == 1) JCK_TRY(jck_cgan_z(e->prec, z, labels, n, 100, N_CLASS, zp, e->g_z, st));
-  else {
-    e->ss.gz_step = -1;                        // the operand rows now hold somebody else's z
-    if (e->prec == JCK_PREC_BF16) launch_pad_rows<bf16_t>(z, n, 100, zp, e->g_z, st); else launch_pad_rows<float>(z, n, 100, zp, e->g_z, st);
-    HIPCHK(hipGetLastError());
-  }
-  JCK_TRY(g_eval_fold(e, st));
-  // conv1.weight [z_dim][G_C1][4][4]: its first 100 rows as a Linear weight [100][G_C1 * 16] whose columns go from (c, pos) to (pos, c)
-  return jck_pack_linear(e->prec, e->P(e->LG, e->gp, CWN[0]), 100, K, LAT_LD, K, 0, TT.G_C1, 16, e->lat_w, st);
-}
-static int latent_backward(jck_engine* e, int n, hipStream_t st);
-// one evaluation: the eval forward's products, the loss and its gradient, the masked dgrads, the dz product's slabs
-static int latent_eval(jck_engine* e, const float* target, int n, float* loss, hipStream_t st) {
-  JCK_TRY(g_eval_products(e, n, st));
-  JCK_TRY(jck_latent_loss(e->prec, e->fake_raw, target, e->g_raw, loss, n, TT.HW, st));
-  return latent_backward(e, n, st);
-}
-// from g_raw, the gradient at the pre-tanh product: the masked dgrads and the dz product's slabs
-static int latent_backward(jck_engine* e, int n, hipStream_t st) {
-  const void* gbig = e->g_raw;
-  for (int i = TT.NS - 1; i >= 0; --i) {       // through conv(i+2) and the folded stage in front of it
-    const int hs = TT.G_HS[i];
-    JCK_TRY(jck_conv_down_mask(e->prec, gbig, e->g_down[i], e->g_a[i], e->g_bn[i].aux, e->g_gr[i], n, 2 * hs, 2 * hs, TT.G_CB[i], TT.G_CS[i], st));
-    gbig = e->g_gr[i];
-  }
-  return jck_linear_fwd(e->prec, e->g_gr[0], e->lat_w, nullptr, e->lat_slab, n, 16 * TT.G_C1, 100, LAT_LD, LAT_KSPLIT, st);
-}
-extern "C" int jck_engine_latent_grad(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, int n, float* loss,
-                                      float* dz, void* stream) {
-  JCK_TRY(latent_check(e, z, labels, target_nchw, n, "latent_grad"));
-  if (!loss || !dz) JCK_FAIL(JCK_E_ARG, "latent_grad: null loss / dz");
-  hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(latent_begin(e, z, labels, n, st));
-  JCK_TRY(latent_eval(e, target_nchw, n, loss, st));
-  return jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, dz, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, n, st);
-}
-// `steps` Adam updates of z [n][100] (in, out) towards target_nchw on the stream, no host synchronisation: m, v [n][100] are the
-// caller's (zero them for a fresh run), t0 the number of updates they have seen; loss_hist[s][n] (or null) is the loss BEFORE update s.
-extern "C" int jck_engine_project(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
-                                  float prior, float* m, float* v, int t0, float* loss_hist, void* stream) {
-  JCK_TRY(latent_check(e, z, labels, target_nchw, n, "project"));
-  if (steps < 1 || t0 < 0 || !m || !v) JCK_FAIL(JCK_E_ARG, "project: steps >= 1, t0 >= 0 and the Adam state m, v are required");
-  if (!(lr > 0.f) || !(prior >= 0.f)) JCK_FAIL(JCK_E_ARG, "project: lr > 0 and prior >= 0");
-  hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(latent_begin(e, z, labels, n, st));
-  for (int s = 0; s < steps; ++s) {
-    JCK_TRY(latent_eval(e, target_nchw, n, loss_hist ? loss_hist + (size_t)s * n : e->lat_loss, st));
-    JCK_TRY(jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, z, m, v, lr, prior, t0 + s + 1, e->g_z, z_pad(e->family), n, st));
-  }
-  return JCK_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// discriminator inference: D as under model.eval() - every Conv2d + BatchNorm (running statistics) + LeakyReLU stage one launch
-// (jck_conv_down_affine) in fp32 storage, two (the product, then the folded BatchNorm + LeakyReLU) in bf16 - score_stage_fused says
-// why -, the head without loss, gradient or scalar slots.  Beside the step like the projection above, and stricter:
-// D's training activations, real_noisy and the head's concat buffer may belong to a prefetched D(real) forward, so every buffer this
-// writes is memory of its own; it reads fake_raw when no image is given.  Row b's numbers do not depend on n: no statistic, a
-// per-row head reduction in a fixed order, a split-K factor that is a constant.
-// ---------------------------------------------------------------------------------------------------------
-// Which form a stage takes.  fp32 storage (f32, bf16x3): fused - jck_conv_down_affine runs the tile jck_conv_down would and saves the
-// BatchNorm launch and its pass over the output.  bf16: jck_conv_down + jck_bn_act_fwd on the same folded aux table - there jck_conv_down
-// has the image-side streaming kernel and the persistent gather-GEMMs with their 16-byte-store epilogue, which the fused form (shared
-// epilogue only) gives up, and the whole call measured 4 % faster that way at batch 64 and 256 (tools/score_rate.py).
-static bool score_stage_fused(int prec) { return prec_f32_storage(prec); }
-static int score_alloc(jck_engine* e, hipStream_t st) {
-  if (e->sc.base) return JCK_OK;
-  if (e->capturing) JCK_FAIL(JCK_E_ARG, "score: the first scoring call allocates and cannot run inside a graph capture");
-  Carver c;
-  auto carve = [&](jck_engine::ScoreBufs& b) {
-    c.off = 0;
-    b.x = c.take<unsigned char>((size_t)e->B * TT.HW * 4 * e->esz);
-    if (!score_stage_fused(e->prec)) b.y = c.take<unsigned char>((size_t)e->B * (TT.S / 2) * (TT.S / 2) * TT.D_CS[0] * e->esz);   // the largest stage's
-    for (int i = 0; i < TT.NS; ++i) {
-      b.a[i] = c.take<unsigned char>((size_t)e->B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i] * e->esz);
-      b.aux[i] = c.take<float>(4 * TT.D_CS[i]);
-    }
-    if (e->family == 1) {
-      b.cbuf = c.take<unsigned char>((size_t)e->B * L1_KPAD * e->esz);
-      b.slab = c.take<float>((size_t)L1_KSPLIT * e->B * L1_OUT);
-      b.h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
-    }
-  };
-  jck_engine::ScoreBufs b;
-  carve(b);                                                          // sizes
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, c.off));
-  // the concat buffer's padding columns are a GEMM operand: they read as zero from the start - for a later call on ANY stream, so this
-  // one call, which allocates anyway, waits for the clear
-  if (hipMemsetAsync(base, 0, c.off, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    (void)hipFree(base);
-    JCK_FAIL(JCK_E_HIP, "score: clearing the buffers failed");
-  }
-  c.base = reinterpret_cast<unsigned char*>(base);
-  carve(b);
-  b.base = base;
-  e->sc = b;
-  return JCK_OK;
-}
-// the fold of D's BatchNorm layers (gamma, beta and the running statistics) into the stages' aux tables: one launch ...
-static int score_fold(jck_engine* e, hipStream_t st) {
-  const jck_engine::ScoreBufs& S = e->sc;
-  const float *gamma[JCK_MAX_STAGES], *beta[JCK_MAX_STAGES], *rm[JCK_MAX_STAGES], *rv[JCK_MAX_STAGES];
-  float* aux[JCK_MAX_STAGES];
-  int Cs[JCK_MAX_STAGES];
-  for (int i = 0; i < TT.NS; ++i) {
-    gamma[i] = e->P(e->LD, e->dp, NWN[i]); beta[i] = e->P(e->LD, e->dp, NBN[i]);
-    rm[i] = e->dbn + find(e->LD, RMN[i])->offset; rv[i] = e->dbn + find(e->LD, RVN[i])->offset;
-    aux[i] = S.aux[i]; Cs[i] = TT.D_CS[i];
-  }
-  return jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st);
-}
-// ... and the stages and the head on the NHWC4 images `in`: jck_engine_score, and the forward half of the critic's latent gradient,
-// which reads the stages' activations S.a[i] and aux tables afterwards
-static int score_stages_head(jck_engine* e, const void* in, const int64_t* labels, int n, float* logit, float* prob, hipStream_t st) {
-  const jck_engine::ScoreBufs& S = e->sc;
-  for (int i = 0; i < TT.NS; ++i) {
-    const int hb = TT.D_HB[i], cs = TT.D_CS[i];
-    if (score_stage_fused(e->prec)) {
-      JCK_TRY(jck_conv_down_affine(e->prec, in, e->d_down[i], S.aux[i], S.aux[i] + cs, LRELU, S.a[i], n, hb, hb, TT.D_CB[i], cs, st));
-    } else {
-      JCK_TRY(jck_conv_down(e->prec, in, e->d_down[i], S.y, nullptr, nullptr, n, hb, hb, TT.D_CB[i], cs, st));
-      JCK_TRY(jck_bn_act_fwd(e->prec, S.y, S.aux[i], LRELU, S.a[i], (long long)n * (hb / 2) * (hb / 2), cs, st));
-    }
-    in = S.a[i];
-  }
-  if (e->family == 0) return jck_score_head(e->prec, in, e->d_head_wp, nullptr, n, TT.FEAT, logit, prob, st);
-  JCK_TRY(jck_concat_rows(e->prec, in, TT.FEAT, S.cbuf, L1_KPAD, n, st));
-  JCK_TRY(jck_label_embed_fwd(e->prec, labels, e->P(e->LD, e->dp, "label_embedding.weight"), e->P(e->LD, e->dp, "label_embedding.bias"), LRELU, n,
-                              N_CLASS, EMB, S.cbuf, L1_KPAD, TT.FEAT, nullptr, st));
-  JCK_TRY(jck_linear_fwd(e->prec, S.cbuf, e->l1_w, nullptr, S.slab, n, L1_KPAD, L1_OUT, L1_OUT, L1_KSPLIT, st));
-  // Dropout is the identity under model.eval(): no mask
-  JCK_TRY(jck_linear_finish(e->prec, S.slab, L1_KSPLIT, e->P(e->LD, e->dp, "linear1.bias"), nullptr, 1.0f, S.h, nullptr, n, L1_OUT, st));
-  return jck_score_head(e->prec, S.h, e->P(e->LD, e->dp, "linear2.weight"), e->P(e->LD, e->dp, "linear2.bias"), n, L1_OUT, logit, prob, st);
-}
-extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const float* noise_nchw, const int64_t* labels, int n, float* logit,
-                                float* prob, void* stream) {
-  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "score: engine not bound");
-  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "score: n must be in [1, batch]");
-  if (!logit) JCK_FAIL(JCK_E_ARG, "score: null logit");
-  if (noise_nchw && !images_nchw) JCK_FAIL(JCK_E_ARG, "score: instance noise goes with images");
-  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, "score: CGAN discriminator needs labels");
-  if (!e->d_packed) JCK_FAIL(JCK_E_ARG, "score: the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
-  hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(score_alloc(e, st));
-  const void* in = e->fake_raw;                                       // NULL images: the generator's last output, where it lies
-  if (images_nchw) {
-    JCK_TRY(jck_img_prep(e->prec, images_nchw, noise_nchw, noise_nchw ? 0.9f : 1.0f, noise_nchw ? 0.1f : 0.0f, e->sc.x, n, TT.HW, st));
-    in = e->sc.x;
-  }
-  JCK_TRY(score_fold(e, st));
-  return score_stages_head(e, in, labels, n, logit, prob, st);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// the critic's latent gradient: the projection above with a per-pixel weight on the image loss and c(D(G(z))) as a second term -
-// masked projection (semantic inpainting) and refinement of a latent along the discriminator's gradient.  D runs as jck_engine_score
-// runs it, and its input gradient comes from the activations and folded aux tables that pass keeps in memory of its own: the head's
-// input gradient, the leaky backward of the deepest stage, one masked ConvTranspose-direction product per stage (jck_conv_up_mask)
-// and the plain one of stage 0 into an image gradient that jck_latent_loss_ex adds in front of the tanh.  Nothing of D's training
-// buffers (DActs, real_noisy, the head's cbuf, any gradient arena) is read or written.
-// ---------------------------------------------------------------------------------------------------------
-static int critic_alloc(jck_engine* e) {
-  if (e->cr.base) return JCK_OK;
-  Carver c;
-  auto carve = [&](jck_engine::CriticBufs& b) {
-    c.off = 0;
-    for (int i = 0; i < TT.NS; ++i) b.g[i] = c.take<unsigned char>((size_t)e->B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i] * e->esz);
-    b.gx = c.take<unsigned char>((size_t)e->B * TT.HW * 4 * e->esz);
-    b.ds = c.take<float>(e->B); b.term = c.take<float>(e->B); b.logit = c.take<float>(e->B);
-    if (e->family == 1) {
-      b.g_h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
-      b.gc = c.take<unsigned char>((size_t)e->B * L1_KPAD * e->esz);
-    }
-  };
-  jck_engine::CriticBufs b;
-  carve(b);                                                          // sizes
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, c.off));
-  c.base = reinterpret_cast<unsigned char*>(base);
-  carve(b);
-  b.base = base;
-  e->cr = b;
-  return JCK_OK;
-}
-static int latent_ex_check(jck_engine* e, const float* z, const int64_t* labels, const float* target, int critic_mode, float critic_weight,
-                           int n, const char* who) {
-  const std::string w(who);
-  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, w + ": engine not bound");
-  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, w + ": n must be in [1, batch]");
-  if (!z) JCK_FAIL(JCK_E_ARG, w + ": null z");
-  if (critic_mode < 0 || critic_mode > 2) JCK_FAIL(JCK_E_ARG, w + ": critic_mode must be 0 (none), 1 (nsgan) or 2 (logit)");
-  if (!target && !critic_mode) JCK_FAIL(JCK_E_ARG, w + ": without a target a critic is required");
-  if (!(critic_weight >= 0.f)) JCK_FAIL(JCK_E_ARG, w + ": critic_weight >= 0");
-  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, w + ": CGAN needs labels");
-  if (critic_mode && !e->d_packed)
-    JCK_FAIL(JCK_E_ARG, w + ": the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
-  if (e->capturing) JCK_FAIL(JCK_E_ARG, w + ": not inside a graph capture");
-  return JCK_OK;
-}
-struct LatentEx { const float* target; const float* weight; int mode; float cw; const int64_t* labels; };
-// once per call, behind latent_begin: the critic's buffers and D's BatchNorm fold
-static int latent_ex_begin(jck_engine* e, const LatentEx& o, hipStream_t st) {
-  if (!o.mode) return JCK_OK;
-  JCK_TRY(score_alloc(e, st));
-  JCK_TRY(critic_alloc(e));
-  return score_fold(e, st);
-}
-// one evaluation; plain (no weight, no critic): latent_eval's launches
-static int latent_eval_ex(jck_engine* e, const LatentEx& o, int n, float* loss, float* term, float* logit, hipStream_t st) {
-  if (!o.weight && !o.mode) return latent_eval(e, o.target, n, loss, st);
-  JCK_TRY(g_eval_products(e, n, st));
-  const jck_engine::ScoreBufs& S = e->sc;
-  const jck_engine::CriticBufs& C = e->cr;
-  if (o.mode) {
-    const int top = TT.NS - 1;
-    if (!logit) logit = C.logit;
-    JCK_TRY(score_stages_head(e, e->fake_raw, o.labels, n, logit, nullptr, st));
-    JCK_TRY(jck_critic_ds(logit, o.mode, o.cw, n, C.ds, term ? term : C.term, st));
-    if (e->family == 0) {
-      JCK_TRY(jck_head_bwd_conv(e->prec, C.ds, e->d_head_wp, S.a[top], n, TT.G_C1, C.g[top], nullptr, nullptr, st));
-    } else {
-      // Linear(8392,256) -> Dropout (the identity) -> Linear(256,1): no nonlinearity between the two products under model.eval()
-      JCK_TRY(jck_head_bwd(e->prec, C.ds, e->P(e->LD, e->dp, "linear2.weight"), nullptr, n, L1_OUT, C.g_h, nullptr, 0, nullptr, st));
-      JCK_TRY(jck_linear_fwd(e->prec, C.g_h, e->l1_wT, nullptr, C.gc, n, L1_OUT, L1_KPAD, L1_KPAD, 1, st));
-      JCK_TRY(jck_split_rows(e->prec, C.gc, L1_KPAD, TT.FEAT, C.g[top], n, st));
-    }
-    JCK_TRY(jck_leaky_affine_bwd(e->prec, C.g[top], S.a[top], S.aux[top], LRELU, C.g[top], (long long)n * (TT.D_HB[top] / 2) * (TT.D_HB[top] / 2),
-                                 TT.D_CS[top], st));
-    for (int i = top; i >= 1; --i) {            // through conv(i+1) and the folded stage in front of it
-      const int hs = TT.D_HB[i] / 2;
-      JCK_TRY(jck_conv_up_mask(e->prec, C.g[i], e->d_up[i], S.a[i - 1], S.aux[i - 1], LRELU, C.g[i - 1], n, hs, hs, TT.D_CS[i], TT.D_CB[i], st));
-    }
-    JCK_TRY(jck_conv_up(e->prec, C.g[0], e->d_up[0], C.gx, nullptr, nullptr, 0, n, TT.D_HB[0] / 2, TT.D_HB[0] / 2, TT.D_CS[0], TT.D_CB[0], st));
-  }
-  JCK_TRY(jck_latent_loss_ex(e->prec, e->fake_raw, o.target, o.weight, o.mode ? C.gx : nullptr, e->g_raw, loss, n, TT.HW, st));
-  return latent_backward(e, n, st);
-}
-extern "C" int jck_engine_latent_grad_ex(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
-                                         int critic_mode, float critic_weight, int n, float* loss, float* term, float* logit, float* dz,
-                                         void* stream) {
-  JCK_TRY(latent_ex_check(e, z, labels, target_nchw, critic_mode, critic_weight, n, "latent_grad_ex"));
-  if (!loss || !dz) JCK_FAIL(JCK_E_ARG, "latent_grad_ex: null loss / dz");
-  hipStream_t st = (hipStream_t)stream;
-  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels};
-  JCK_TRY(latent_begin(e, z, labels, n, st));
-  JCK_TRY(latent_ex_begin(e, o, st));
-  JCK_TRY(latent_eval_ex(e, o, n, loss, term, logit, st));
-  return jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, dz, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, n, st);
-}
-extern "C" int jck_engine_project_ex(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
-                                     float prior, const float* weight, int critic_mode, float critic_weight, float* m, float* v, int t0,
-                                     float* loss_hist, float* term_hist, void* stream) {
-  JCK_TRY(latent_ex_check(e, z, labels, target_nchw, critic_mode, critic_weight, n, "project_ex"));
-  if (steps < 1 || t0 < 0 || !m || !v) JCK_FAIL(JCK_E_ARG, "project_ex: steps >= 1, t0 >= 0 and the Adam state m, v are required");
-  if (!(lr > 0.f) || !(prior >= 0.f)) JCK_FAIL(JCK_E_ARG, "project_ex: lr > 0 and prior >= 0");
-  hipStream_t st = (hipStream_t)stream;
-  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels};
-  JCK_TRY(latent_begin(e, z, labels, n, st));
-  JCK_TRY(latent_ex_begin(e, o, st));
-  for (int s = 0; s < steps; ++s) {
-    JCK_TRY(latent_eval_ex(e, o, n, loss_hist ? loss_hist + (size_t)s * n : e->lat_loss, term_hist ? term_hist + (size_t)s * n : nullptr, nullptr, st));
-    JCK_TRY(jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, z, m, v, lr, prior, t0 + s + 1, e->g_z, z_pad(e->family), n, st));
-  }
-  return JCK_OK;
-}
 
 extern "C" const void* jck_engine_tensor(const jck_engine* e, const char* name, long long* numel) {
   if (!e || !e->bound || !name) return nullptr;

@@ -4,36 +4,6 @@
 #pragma once
 #include "common.hpp"
 
-// One workgroup per image: L_b = mean over the 3 * HW real elements of (x - t)^2, x the stored tanh output (NHWC4, type T), t the
-// caller's NCHW fp32 target read in place; g_raw = 2 (x - t) / (3 HW) * (1 - x^2) in T, padding channel +0.  Thread i takes pixels
-// i, i + 256, ... in that order and the workgroup's 256 partial sums are added in a fixed tree: the same bits on every run, and
-// image b's loss does not depend on N.
-template <typename T>
-__global__ __launch_bounds__(256) void latent_loss_kernel(const T* __restrict__ x, const float* __restrict__ target, T* __restrict__ g_raw,
-                                                          float* __restrict__ loss, int HW) {
-  __shared__ float sm[4];
-  const int b = blockIdx.x;
-  const T* xb = x + (long long)b * HW * 4;
-  T* gb = g_raw + (long long)b * HW * 4;
-  const float* tb = target + (long long)b * 3 * HW;
-  const float k = 2.0f / (3.0f * (float)HW);
-  float s = 0.f;
-  for (int p = threadIdx.x; p < HW; p += 256) {
-    float v[4], g[4];
-    ld4(xb + (long long)p * 4, v);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float d = v[c] - tb[(long long)c * HW + p];
-      s = fmaf(d, d, s);
-      g[c] = k * d * (1.f - v[c] * v[c]);
-    }
-    g[3] = 0.f;
-    st4(gb + (long long)p * 4, g);
-  }
-  s = block_sum256(s, sm);
-  if (threadIdx.x == 0) loss[b] = s / (3.0f * (float)HW);
-}
-
 // One thread per (image, latent column k < zd): g = slab[0][b][k] + slab[1][b][k] + ... (fp32, in slab order) + prior * 2 z / zd, then
 // torch.optim.Adam's update of (z, m, v) with the bias-corrected step - evaluated in fp64 from the fp32 state and rounded once, so the
 // result does not depend on how a compiler contracts the fp32 chain - and z in the element type T into the first zd columns of the
@@ -59,21 +29,26 @@ __global__ void latent_adam_kernel(const float* __restrict__ slab, int Z, long l
   stf(z_operand + (long long)b * zp + k, zn);
 }
 
-// ---- the critic's latent gradient (jck_engine_latent_grad_ex / _project_ex): D(G(z)) differentiated with respect to z under model.eval() ----
-// latent_loss_kernel with a per-pixel weight w [n][HW] (fp32, or null: 1) and an additive image gradient g_x (NHWC4 of T, or null):
-// L_b = sum_p w_p sum_c (x - t)^2 / (3 sum_p w_p), g_raw = (k w_p (x - t) + g_x) (1 - x^2), k = 2 / (3 sum_p w_p).  One workgroup per
-// image, two passes in latent_loss_kernel's fixed order: sum w, then the loss.  sum w = 0: loss 0, no reconstruction gradient.
-// target null (g_x required): L_b = 0, g_raw = g_x (1 - x^2).  With w null and g_x null the arithmetic is latent_loss_kernel's,
-// expression for expression (w d = d, sum w = HW): the same bits.
-template <typename T>
-__global__ __launch_bounds__(256) void latent_loss_ex_kernel(const T* __restrict__ x, const float* __restrict__ target, const float* __restrict__ w,
-                                                             const T* __restrict__ g_x, T* __restrict__ g_raw, float* __restrict__ loss, int HW) {
+// ---- the image loss (jck_latent_loss, jck_latent_loss_ex) and the critic's latent gradient: D(G(z)) differentiated with respect to z under model.eval() ----
+// One workgroup per image.  x is the stored tanh output (NHWC4, type T), t the caller's NCHW fp32 target read in place, w a per-pixel
+// weight [n][HW] (fp32, or null: 1), g_x an additive image gradient (NHWC4 of T, or null):
+// L_b = sum_p w_p sum_c (x - t)^2 / (3 sum_p w_p), g_raw = (k w_p (x - t) + g_x) (1 - x^2) in T, k = 2 / (3 sum_p w_p), padding channel +0.
+// Two passes, sum w and then the loss; thread i takes pixels i, i + 256, ... in that order and the workgroup's 256 partial sums are
+// added in a fixed tree: the same bits on every run, and image b's loss does not depend on N.  sum w = 0: loss 0, no reconstruction
+// gradient.  target null (g_x required): L_b = 0, g_raw = g_x (1 - x^2).  w null and g_x null - jck_latent_loss - is the plain mean:
+// w d = d, sum w = HW, k = 2 / (3 HW), and neither the first pass nor a load of w or g_x runs.
+// PLAIN: the launcher's promise that w and g_x are null and target is not - the same statements with those three tests decided by the
+// compiler.  Tested at run time once per pixel instead, the plain projection measured 0.6-0.8 % slower.
+template <typename T, bool PLAIN>
+__global__ __launch_bounds__(256) void latent_loss_kernel(const T* __restrict__ x, const float* __restrict__ target, const float* __restrict__ w,
+                                                          const T* __restrict__ g_x, T* __restrict__ g_raw, float* __restrict__ loss, int HW) {
   __shared__ float sm[4];
+  if (PLAIN) { w = nullptr; g_x = nullptr; }
   const int b = blockIdx.x;
   const T* xb = x + (long long)b * HW * 4;
   T* gb = g_raw + (long long)b * HW * 4;
   const T* gxb = g_x ? g_x + (long long)b * HW * 4 : nullptr;
-  if (!target) {                                       // critic only
+  if (!PLAIN && !target) {                             // critic only
     for (int p = threadIdx.x; p < HW; p += 256) {
       float v[4], c[4], g[4];
       ld4(xb + (long long)p * 4, v);

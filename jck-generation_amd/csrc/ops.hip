@@ -743,17 +743,29 @@ int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, doubl
 // ---------------------------------------------------------------------------------------------------------
 // latent projection (latent.hpp)
 // ---------------------------------------------------------------------------------------------------------
+// latent_loss_kernel for both entry points below: `id` is the caller's registry label, `bytes` its traffic estimate.  No weight and no
+// image gradient: the PLAIN instantiation of the same body.
+static int launch_latent_loss(KernelId id, double bytes, int prec, const void* x, const float* target, const float* weight, const void* g_x,
+                              void* g_raw, float* loss, int N, int HW, hipStream_t st) {
+  ProfScope prof(id, 0.0, st, bytes);
+  if (target && !weight && !g_x) {
+    DISPATCH_T(prec, hipLaunchKernelGGL((latent_loss_kernel<T, true>), dim3(N), dim3(256), 0, st, (const T*)x, target, nullptr, nullptr, (T*)g_raw,
+                                        loss, HW));
+  } else {
+    DISPATCH_T(prec, hipLaunchKernelGGL((latent_loss_kernel<T, false>), dim3(N), dim3(256), 0, st, (const T*)x, target, weight, (const T*)g_x,
+                                        (T*)g_raw, loss, HW));
+  }
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
 // loss_out[b] = mean((x_b - t_b)^2) over the 3 * HW real elements; g_raw_out = its gradient at the pre-tanh product (NHWC4, element
 // type of prec, padding channel 0).  The target is the caller's NCHW fp32 tensor, read in place.
 extern "C" int jck_latent_loss(int prec, const void* x_nhwc4, const float* target_nchw_f32, void* g_raw_out, float* loss_out, int N,
                                int HW, void* stream) {
   if (!x_nhwc4 || !target_nchw_f32 || !g_raw_out || !loss_out || N < 1 || HW < 1) JCK_FAIL(JCK_E_ARG, "latent_loss: bad arguments");
   if ((((uintptr_t)x_nhwc4 | (uintptr_t)g_raw_out) & 15) != 0) JCK_FAIL(JCK_E_ARG, "latent_loss: the image tensors must be 16-byte aligned");
-  ProfScope prof(K_LATENT_LOSS, 0.0, (hipStream_t)stream, (double)N * HW * (12.0 + 8.0 * (prec_f32_storage(prec) ? 4 : 2)));
-  DISPATCH_T(prec, hipLaunchKernelGGL(latent_loss_kernel<T>, dim3(N), dim3(256), 0, (hipStream_t)stream, (const T*)x_nhwc4, target_nchw_f32,
-                                      (T*)g_raw_out, loss_out, HW));
-  HIPCHK(hipGetLastError());
-  return JCK_OK;
+  return launch_latent_loss(K_LATENT_LOSS, (double)N * HW * (12.0 + 8.0 * (prec_f32_storage(prec) ? 4 : 2)), prec, x_nhwc4, target_nchw_f32,
+                            nullptr, nullptr, g_raw_out, loss_out, N, HW, (hipStream_t)stream);
 }
 // Sums the Z split-K slabs [Z][N][ld] of the dz product in order, adds the prior's gradient 2 * prior * z / 100 and applies
 // torch.optim.Adam(betas = (0.9, 0.999), eps = 1e-8) update number t >= 1 to z, m, v [N][100]; z also goes, in the element type, to
@@ -775,17 +787,14 @@ extern "C" int jck_latent_adam(int prec, const float* slab, int Z, int ld, float
 }
 // jck_latent_loss with a per-pixel weight (fp32 [N][HW], or null: 1) and an additive image gradient g_x (NHWC4, element type, or null):
 // loss_out[b] = sum_p w_p sum_c (x - t)^2 / (3 sum_p w_p), g_raw_out = (k w_p (x - t) + g_x) (1 - x^2) with k = 2 / (3 sum_p w_p).
-// target null (g_x required): loss 0, g_raw_out = g_x (1 - x^2).  weight null and g_x null: jck_latent_loss' bits.
+// target null (g_x required): loss 0, g_raw_out = g_x (1 - x^2).  weight null and g_x null: jck_latent_loss (the same launch).
 extern "C" int jck_latent_loss_ex(int prec, const void* x_nhwc4, const float* target_nchw_f32, const float* weight, const void* g_x,
                                   void* g_raw_out, float* loss_out, int N, int HW, void* stream) {
   if (!x_nhwc4 || !g_raw_out || !loss_out || N < 1 || HW < 1) JCK_FAIL(JCK_E_ARG, "latent_loss_ex: bad arguments");
   if (!target_nchw_f32 && !g_x) JCK_FAIL(JCK_E_ARG, "latent_loss_ex: without a target the image gradient g_x is required");
   if ((((uintptr_t)x_nhwc4 | (uintptr_t)g_raw_out | (uintptr_t)g_x) & 15) != 0) JCK_FAIL(JCK_E_ARG, "latent_loss_ex: the image tensors must be 16-byte aligned");
-  ProfScope prof(K_LATENT_LOSS_EX, 0.0, (hipStream_t)stream, (double)N * HW * (16.0 + 12.0 * (prec_f32_storage(prec) ? 4 : 2)));
-  DISPATCH_T(prec, hipLaunchKernelGGL(latent_loss_ex_kernel<T>, dim3(N), dim3(256), 0, (hipStream_t)stream, (const T*)x_nhwc4, target_nchw_f32,
-                                      weight, (const T*)g_x, (T*)g_raw_out, loss_out, HW));
-  HIPCHK(hipGetLastError());
-  return JCK_OK;
+  return launch_latent_loss(K_LATENT_LOSS_EX, (double)N * HW * (16.0 + 12.0 * (prec_f32_storage(prec) ? 4 : 2)), prec, x_nhwc4, target_nchw_f32,
+                            weight, g_x, g_raw_out, loss_out, N, HW, (hipStream_t)stream);
 }
 // g_y[r, c] = a[r, c] > 0 ? scale[c] g[r, c] : scale[c] g[r, c] slope over `rows` rows of C channels (a power of two >= 8); g_y may be g
 extern "C" int jck_leaky_affine_bwd(int prec, const void* g, const void* a, const float* scale, float slope, void* g_y, long long rows, int C,

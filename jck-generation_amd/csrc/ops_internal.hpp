@@ -1,5 +1,6 @@
-// Host glue shared by the launcher units (ops.hip, ops_gemm.hip) and engine.hip: error and launch macros, the kernel registry, the knobs and the
-// prototypes of the functions that cross a unit.  No kernels: each unit includes the kernel headers it launches from.
+// Host glue shared by the launcher units (ops.hip, ops_gemm.hip) and the engine units (engine.hip, engine_infer.hip): error and launch
+// macros, the kernel registry, the knobs and the prototypes of the functions that cross a unit.  No kernels: each unit includes the
+// kernel headers it launches from.
 #pragma once
 #include <hip/hip_ext.h>
 

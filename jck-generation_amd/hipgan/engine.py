@@ -799,6 +799,27 @@ class DcganEngine:
         self.step_async(real, noise, lr, **kw)
         return self.scalars()
 
+    def _latents(self, what, z, labels):
+        """(n, z as fp32 [n,100] on the device, one-hot int64 labels on the device or None): the latent rows of an inference call"""
+        n = z.shape[0]
+        if n < 1:
+            raise JckError(f"{what}: z is empty")
+        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
+        if zc.shape[0] != n:
+            raise JckError(f"{what}: z must be [n,100]")
+        return n, zc, self._score_labels(what, labels, n)
+
+    def _image_out(self, n, out):
+        """the images of n rows: fp32 NCHW (out="float") or uint8 NHWC (out="uint8")"""
+        if out == "uint8":
+            return torch.empty(n, self.size, self.size, 3, dtype=torch.uint8, device=self.device)
+        return torch.empty(n, 3, self.size, self.size, dtype=torch.float32, device=self.device)
+
+    def _sample_chunk(self, zc, lab, lo, hi, flags, res):
+        """rows [lo, hi) through the generator; res (fp32 NCHW, uint8 NHWC or None) receives their images"""
+        f32, u8 = (None, None) if res is None else (res[lo:hi], None) if res.dtype == torch.float32 else (None, res[lo:hi])
+        lib.jck_engine_sample_ex(self._h, zc[lo:hi], _rows(lab, lo, hi), hi - lo, flags, f32, u8, cur_stream())
+
     def sample(self, z, labels=None, bn="batch", out="float"):
         """G(z) -> NCHW fp32 [n,3,S,S] on the device (out="float") or NHWC uint8 [n,S,S,3] (out="uint8").
 
@@ -812,9 +833,7 @@ class DcganEngine:
             raise JckError(f"sample: bn must be 'batch' or 'running', got {bn!r}")
         if out not in ("float", "uint8"):
             raise JckError(f"sample: out must be 'float' or 'uint8', got {out!r}")
-        n = z.shape[0]
-        if n < 1:
-            raise JckError("sample: z is empty")
+        n, zc, lab = self._latents("sample", z, labels)
         if bn == "batch" and n > self.batch:
             raise JckError(f"sample: {n} latent vectors exceed this engine's batch {self.batch}; bind an engine with batch >= n "
                            f"(DcganEngine(batch=n, share=engine)), or sample with bn='running', which takes any n")
@@ -822,41 +841,22 @@ class DcganEngine:
         self.join()
         if self._packed_version != self._shared["version"]:
             self.repack()
-        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
-        lab = None
-        if self.family == 1:
-            if labels is None or labels.shape != (n, 100):
-                raise JckError("CGAN sample needs one-hot int64 labels [n,100]")
-            lab = labels.to(self.device, torch.int64).contiguous()
-        if out == "uint8":
-            res = torch.empty(n, self.size, self.size, 3, dtype=torch.uint8, device=self.device)
-        else:
-            res = torch.empty(n, 3, self.size, self.size, dtype=torch.float32, device=self.device)
-        if bn == "batch" and out == "float":
-            lib.jck_engine_sample(self._h, zc, lab, n, res, cur_stream())
-        else:
-            flags = SAMPLE_EVAL if bn == "running" else 0
-            for lo, hi in chunk_plan(n, self.batch):
-                lib.jck_engine_sample_ex(self._h, zc[lo:hi], None if lab is None else lab[lo:hi], hi - lo, flags,
-                                         res[lo:hi] if out == "float" else None, res[lo:hi] if out == "uint8" else None, cur_stream())
+        res = self._image_out(n, out)
+        for lo, hi in chunk_plan(n, self.batch):
+            self._sample_chunk(zc, lab, lo, hi, SAMPLE_EVAL if bn == "running" else 0, res)
         self._keep_z = (zc, lab)
         return res
 
-    def _latent_args(self, what, n, target, labels):
-        """Validated device tensors (target fp32 NCHW, one-hot labels or None) of a latent_grad / project call."""
+    def _target(self, what, n, target):
+        """The validated target (fp32 NCHW on the device) of a latent_grad / project call; the engine joined and its operands current."""
         if n < 1:
             raise JckError(f"{what}: no images")
         if target.dim() != 4 or tuple(target.shape) != (n, 3, self.size, self.size):
             raise JckError(f"{what}: target must be [{n},3,{self.size},{self.size}] (NCHW, values in [-1, 1]), got {tuple(target.shape)}")
-        lab = None
-        if self.family == 1:
-            if labels is None or tuple(labels.shape) != (n, 100):
-                raise JckError(f"CGAN {what} needs one-hot int64 labels [n,100]")
-            lab = labels.to(self.device, torch.int64).contiguous()
         self.join()
         if self._packed_version != self._shared["version"]:
             self.repack()
-        return target.to(self.device, torch.float32).contiguous(), lab
+        return target.to(self.device, torch.float32).contiguous()
 
     def _critic_args(self, what, n, weight, critic, critic_weight, has_target=True):
         """(weight fp32 [n,S,S] on the device or None, critic mode 0 / 1 / 2, critic weight) of an _ex call, validated on the host"""
@@ -891,23 +891,14 @@ class DcganEngine:
         weight ([S,S] or [n,S,S], >= 0): L_b becomes the weighted mean sum_p w_p sum_c (.)^2 / (3 sum_p w_p).  critic ("nsgan" |
         "logit") with critic_weight: the eval-mode discriminator's term critic_weight * c(D(G(z_b))) joins the objective, dz is the
         gradient of the sum and the result is (loss, term [n], logit [n], dz)."""
-        n = z.shape[0]
-        t, lab = self._latent_args("latent_grad", n, target, labels)
-        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
-        if zc.shape[0] != n:
-            raise JckError("latent_grad: z must be [n,100]")
+        t = self._target("latent_grad", z.shape[0], target)
+        n, zc, lab = self._latents("latent_grad", z, labels)
+        w, mode, cw = self._critic_args("latent_grad", n, weight, critic, critic_weight)
         loss = torch.empty(n, dtype=torch.float32, device=self.device)
         dz = torch.empty(n, 100, dtype=torch.float32, device=self.device)
-        sub = lambda x, lo, hi: None if x is None else x[lo:hi]
-        if weight is None and critic is None:
-            for lo, hi in chunk_plan(n, self.batch):
-                lib.jck_engine_latent_grad(self._h, zc[lo:hi], sub(lab, lo, hi), t[lo:hi], hi - lo, loss[lo:hi], dz[lo:hi], cur_stream())
-            self._keep_z = (zc, lab, t)
-            return loss, dz
-        w, mode, cw = self._critic_args("latent_grad", n, weight, critic, critic_weight)
         term, logit = torch.zeros_like(loss), torch.full_like(loss, float("nan"))
         for lo, hi in chunk_plan(n, self.batch):
-            lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], sub(lab, lo, hi), t[lo:hi], sub(w, lo, hi), mode, cw, hi - lo, loss[lo:hi],
+            lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], _rows(lab, lo, hi), t[lo:hi], _rows(w, lo, hi), mode, cw, hi - lo, loss[lo:hi],
                                           term[lo:hi] if mode else None, logit[lo:hi] if mode else None, dz[lo:hi], cur_stream())
         self._keep_z = (zc, lab, t, w)
         return (loss, term, logit, dz) if mode else (loss, dz)
@@ -915,20 +906,14 @@ class DcganEngine:
     def critic_grad(self, z, labels=None, mode="nsgan"):
         """(logit [n], term [n], dz [n,100]): D(G(z)), both networks as under model.eval(), the critic's objective c of it - "nsgan":
         softplus(-logit) = -log D, the generator's training loss; "logit": -logit - and dz = dc/dz.  Any n, rows independent."""
-        n = z.shape[0]
-        if n < 1:
-            raise JckError("critic_grad: z is empty")
         if mode not in ("nsgan", "logit"):
             raise JckError(f"critic_grad: mode must be 'nsgan' or 'logit', got {mode!r}")
-        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
-        if zc.shape[0] != n:
-            raise JckError("critic_grad: z must be [n,100]")
-        lab = self._score_labels("critic_grad", labels, n)
+        n, zc, lab = self._latents("critic_grad", z, labels)
         self._score_ready("critic_grad")
         f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=self.device)
         loss, term, logit, dz = f(n), f(n), f(n), f(n, 100)
         for lo, hi in chunk_plan(n, self.batch):
-            lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], None if lab is None else lab[lo:hi], None, None, CRITIC_MODES[mode], 1.0, hi - lo,
+            lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], _rows(lab, lo, hi), None, None, CRITIC_MODES[mode], 1.0, hi - lo,
                                           loss[lo:hi], term[lo:hi], logit[lo:hi], dz[lo:hi], cur_stream())
         self._keep_z = (zc, lab)
         return logit, term, dz
@@ -955,10 +940,8 @@ class DcganEngine:
                 raise JckError("project: no latents")
             t, lab = None, self._score_labels("project", labels, n)
         else:
-            t, lab = self._latent_args("project", n, target, labels)
-        ex = weight is not None or critic is not None or target is None
-        if ex:
-            w, mode, cw = self._critic_args("project", n, weight, critic, critic_weight, target is not None)
+            t, lab = self._target("project", n, target), self._score_labels("project", labels, n)
+        w, mode, cw = self._critic_args("project", n, weight, critic, critic_weight, target is not None)
         if z0 is None:
             z0 = torch.randn(n, 100, generator=torch.Generator().manual_seed(int(seed)))
         if tuple(z0.shape) != (n, 100):
@@ -971,21 +954,17 @@ class DcganEngine:
             if tuple(m.shape) != (n, 100) or tuple(v.shape) != (n, 100) or t0 < 0:
                 raise JckError("project: state must hold m, v [n,100] and t >= 0")
         hist = torch.empty(int(steps), n, dtype=torch.float32, device=self.device)
-        terms = torch.zeros(int(steps), n, dtype=torch.float32, device=self.device) if ex else None
-        sub = lambda x, lo, hi: None if x is None else x[lo:hi]
+        plain = weight is None and critic is None and target is not None
+        terms = None if plain else torch.zeros(int(steps), n, dtype=torch.float32, device=self.device)
         for lo, hi in chunk_plan(n, self.batch):
             h = torch.empty(int(steps), hi - lo, dtype=torch.float32, device=self.device)
-            if not ex:
-                lib.jck_engine_project(self._h, z[lo:hi], sub(lab, lo, hi), t[lo:hi], hi - lo, int(steps), float(lr),
-                                       float(prior), m[lo:hi], v[lo:hi], t0, h, cur_stream())
-            else:
-                th = torch.empty_like(h) if mode else None
-                lib.jck_engine_project_ex(self._h, z[lo:hi], sub(lab, lo, hi), sub(t, lo, hi), hi - lo, int(steps), float(lr), float(prior),
-                                          sub(w, lo, hi), mode, cw, m[lo:hi], v[lo:hi], t0, h, th, cur_stream())
-                if mode:
-                    terms[:, lo:hi] = th
+            th = torch.empty_like(h) if mode else None
+            lib.jck_engine_project_ex(self._h, z[lo:hi], _rows(lab, lo, hi), _rows(t, lo, hi), hi - lo, int(steps), float(lr), float(prior),
+                                      _rows(w, lo, hi), mode, cw, m[lo:hi], v[lo:hi], t0, h, th, cur_stream())
+            if mode:
+                terms[:, lo:hi] = th
             hist[:, lo:hi] = h
-        self._keep_z = (z, lab, t) + ((w,) if ex else ())
+        self._keep_z = (z, lab, t, w)
         self.project_state = {"m": m, "v": v, "t": t0 + int(steps)}
         self.project_term = terms
         return z, hist
@@ -1016,6 +995,18 @@ class DcganEngine:
             raise JckError(f"CGAN {what} needs one-hot int64 labels [n,100]")
         return labels.to(self.device, torch.int64).contiguous()
 
+    def _score_chunks(self, n, lab, zc=None, res=None, x=None, nz=None):
+        """(logit [n], prob [n]) in chunks of at most `batch` rows: the eval-mode generator on zc's rows if given (their images to
+        res, if given), then the discriminator on x's rows (+ the instance noise nz) or, x None, on the images where the generator
+        left them"""
+        logit = torch.empty(n, dtype=torch.float32, device=self.device)
+        prob = torch.empty(n, dtype=torch.float32, device=self.device)
+        for lo, hi in chunk_plan(n, self.batch):
+            if zc is not None:
+                self._sample_chunk(zc, lab, lo, hi, SAMPLE_EVAL, res)
+            lib.jck_engine_score(self._h, _rows(x, lo, hi), _rows(nz, lo, hi), _rows(lab, lo, hi), hi - lo, logit[lo:hi], prob[lo:hi], cur_stream())
+        return logit, prob
+
     def score(self, images, labels=None, noise=None):
         """(logit [n], prob [n]) fp32 on the device: the discriminator as under model.eval() - BatchNorm on its running statistics,
         Dropout the identity - so every image is scored on its own and nothing of the training state is written.
@@ -1035,57 +1026,23 @@ class DcganEngine:
             nz = noise.to(self.device, torch.float32).contiguous()
         self._score_ready("score")
         x = x.to(self.device, torch.float32).contiguous()
-        logit = torch.empty(n, dtype=torch.float32, device=self.device)
-        prob = torch.empty(n, dtype=torch.float32, device=self.device)
-        for lo, hi in chunk_plan(n, self.batch):
-            lib.jck_engine_score(self._h, x[lo:hi], None if nz is None else nz[lo:hi], None if lab is None else lab[lo:hi], hi - lo,
-                                 logit[lo:hi], prob[lo:hi], cur_stream())
         self._keep_score = (x, nz, lab)
-        return logit, prob
+        return self._score_chunks(n, lab, x=x, nz=nz)
 
     def score_latents(self, z, labels=None):
         """(logit [n], prob [n]) of D(G(z)), both networks as under model.eval(): per chunk of at most `batch` rows the eval-mode
         generator (sample(bn="running")) leaves its images on the device and the discriminator scores them where they lie."""
-        n = z.shape[0]
-        if n < 1:
-            raise JckError("score_latents: z is empty")
-        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
-        if zc.shape[0] != n:
-            raise JckError("score_latents: z must be [n,100]")
-        lab = self._score_labels("score_latents", labels, n)
-        self._score_ready("score_latents")
-        logit = torch.empty(n, dtype=torch.float32, device=self.device)
-        prob = torch.empty(n, dtype=torch.float32, device=self.device)
-        for lo, hi in chunk_plan(n, self.batch):
-            lc = None if lab is None else lab[lo:hi]
-            lib.jck_engine_sample_ex(self._h, zc[lo:hi], lc, hi - lo, SAMPLE_EVAL, None, None, cur_stream())
-            lib.jck_engine_score(self._h, None, None, lc, hi - lo, logit[lo:hi], prob[lo:hi], cur_stream())
-        self._keep_score = (zc, lab)
-        return logit, prob
+        return self.sample_scored(z, labels, out=None, _what="score_latents")[1:]
 
-    def sample_scored(self, z, labels=None, out="float"):
+    def sample_scored(self, z, labels=None, out="float", _what="sample_scored"):
         """(images, logit [n], prob [n]): sample(z, bn="running", out=out) and score_latents(z) from ONE generator pass per chunk."""
-        if out not in ("float", "uint8"):
+        if out not in ("float", "uint8") and _what == "sample_scored":
             raise JckError(f"sample_scored: out must be 'float' or 'uint8', got {out!r}")
-        n = z.shape[0]
-        if n < 1:
-            raise JckError("sample_scored: z is empty")
-        zc = z.to(self.device, torch.float32).contiguous().view(-1, 100)
-        if zc.shape[0] != n:
-            raise JckError("sample_scored: z must be [n,100]")
-        lab = self._score_labels("sample_scored", labels, n)
-        self._score_ready("sample_scored")
-        shape, dt = ((n, self.size, self.size, 3), torch.uint8) if out == "uint8" else ((n, 3, self.size, self.size), torch.float32)
-        res = torch.empty(shape, dtype=dt, device=self.device)
-        logit = torch.empty(n, dtype=torch.float32, device=self.device)
-        prob = torch.empty(n, dtype=torch.float32, device=self.device)
-        for lo, hi in chunk_plan(n, self.batch):
-            lc = None if lab is None else lab[lo:hi]
-            lib.jck_engine_sample_ex(self._h, zc[lo:hi], lc, hi - lo, SAMPLE_EVAL, res[lo:hi] if out == "float" else None,
-                                     res[lo:hi] if out == "uint8" else None, cur_stream())
-            lib.jck_engine_score(self._h, None, None, lc, hi - lo, logit[lo:hi], prob[lo:hi], cur_stream())
+        n, zc, lab = self._latents(_what, z, labels)
+        self._score_ready(_what)
+        res = None if out is None else self._image_out(n, out)
         self._keep_score = (zc, lab)
-        return res, logit, prob
+        return (res,) + self._score_chunks(n, lab, zc=zc, res=res)
 
     def score_current(self, n, labels=None):
         """(logit [n], prob [n]) of the n images the generator produced last (sample(...) just before), scored where they lie."""
@@ -1093,11 +1050,8 @@ class DcganEngine:
             raise JckError(f"score_current: n must be in [1, {self.batch}]")
         lab = self._score_labels("score_current", labels, n)
         self._score_ready("score_current")
-        logit = torch.empty(n, dtype=torch.float32, device=self.device)
-        prob = torch.empty(n, dtype=torch.float32, device=self.device)
-        lib.jck_engine_score(self._h, None, None, lab, n, logit, prob, cur_stream())
         self._keep_score = (lab,)
-        return logit, prob
+        return self._score_chunks(n, lab)
 
     def tensor(self, name):
         """Debug/parity view of an internal NHWC tensor as a torch tensor (copy)."""
@@ -1113,6 +1067,11 @@ class DcganEngine:
 
 SAMPLE_EVAL = 1            # include/jckgan.h: JCK_SAMPLE_EVAL
 CRITIC_MODES = {None: 0, "nsgan": 1, "logit": 2}      # jck_engine_latent_grad_ex's critic_mode
+
+
+def _rows(x, lo, hi):
+    """rows [lo, hi) of a tensor, None of None"""
+    return None if x is None else x[lo:hi]
 
 
 def chunk_plan(n, batch):

@@ -14,6 +14,14 @@ Fixtures
   cgan_steps.json   real CGANTrainer.train() for 2 steps, B=8 and B=32, lr 2e-4
   metrics.json      Metrics.inception_score / fid / intra_fid on seeded 100-d features
   selfdiv.json      reference vs itself (8 threads vs 1 thread): long-horizon noise floor
+
+One fixture records the project's own GPU results, not the reference's; it needs an MI355X and no reference, and is written
+only when named:
+
+    python tests/golden/make_golden.py --only latent_plain_bits --commit <the commit the library was built from>
+
+  latent_plain_bits.json   SHA-256 of the raw output bytes of the plain latent entry points (jck_latent_loss,
+                           jck_engine_latent_grad, jck_engine_project); tests/test_latent_plain_bits_gpu.py recomputes them
 """
 import argparse
 import hashlib
@@ -384,10 +392,99 @@ def gen_selfdiv(steps=30, B=64):
             "rel_g": [abs(a - b) / max(abs(a), 1e-12) for a, b in zip(g8, g1)]}
 
 
+# --------------------------------------------------------------------------------------------
+# the plain latent entry points on the GPU, bit for bit (the project's own results at a recorded commit; no reference involved)
+# --------------------------------------------------------------------------------------------
+LATENT_LOSS_CASES = [(n, hw, p) for n, hw in ((1, 64), (5, 4096)) for p in ("f32", "bf16")]
+LATENT_ENGINES = [(f, p) for f in ("dcgan", "cgan") for p in ("bf16", "f32")]          # tests/test_critic_grad_gpu.py ENGINES
+_latent_engines = {}
+
+
+def sha256_bytes(t):
+    """SHA-256 of a tensor's raw bytes (.cpu() waits for the stream that wrote it)"""
+    return hashlib.sha256(t.detach().contiguous().cpu().view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+def latent_loss_bits(n, hw, prec, ex):
+    """{g_raw, loss: digest} of jck_latent_loss (ex: jck_latent_loss_ex without weight and image gradient) on seeded inputs:
+    hw = 64 is less than one pass of the kernel's 256-thread loop, hw = 4096 is 16 passes"""
+    from hipgan import PREC_BF16, PREC_F32, lib
+    from hipgan._lib import cur_stream
+    pc, dt = (PREC_BF16, torch.bfloat16) if prec == "bf16" else (PREC_F32, torch.float32)
+    g = torch.Generator().manual_seed(51)
+    x = torch.tanh(torch.randn(n, hw, 4, generator=g)).to(dt).cuda()
+    t = (torch.rand(n, 3, hw, generator=g) * 2 - 1).cuda()
+    graw, loss = torch.zeros(n, hw, 4, dtype=dt, device="cuda"), torch.zeros(n, device="cuda")
+    if ex:
+        lib.jck_latent_loss_ex(pc, x, t, None, None, graw, loss, n, hw, cur_stream())
+    else:
+        lib.jck_latent_loss(pc, x, t, graw, loss, n, hw, cur_stream())
+    return {"g_raw": sha256_bytes(graw), "loss": sha256_bytes(loss)}
+
+
+def latent_engine(family, prec):
+    """a batch-8 64x64 engine as tools/project_rate.py makes it: the oracle's weights, running statistics after 30 train-mode batches"""
+    if (family, prec) not in _latent_engines:
+        from hipgan.engine import CganEngine, DcganEngine
+        from oracle.gan_oracle import GanOracle
+        orc = GanOracle(family, lr=2e-4, seed=12345)
+        eng = (CganEngine if family == "cgan" else DcganEngine)(batch=8, prec=prec)
+        eng.load_state(orc.g, orc.d)
+        zz = torch.randn(8, 100, generator=torch.Generator().manual_seed(1))
+        lab = synth_onehot(8)[0] if family == "cgan" else None
+        for _ in range(30):
+            eng.sample(zz, lab)
+        _latent_engines[family, prec] = eng
+    return _latent_engines[family, prec]
+
+
+def latent_engine_bits(family, prec, ex):
+    """digests of jck_engine_latent_grad's (loss, dz) and of (z, m, v, loss_hist) after a 3-step jck_engine_project (lr 0.05, prior
+    0.01), n = 5 of 8 (a ragged batch); ex: the same through the _ex entry points with no weight and no critic"""
+    from hipgan import lib
+    from hipgan._lib import cur_stream
+    eng = latent_engine(family, prec)
+    n, steps = 5, 3
+    g = torch.Generator().manual_seed(DATA_SEED + 2)
+    z0 = torch.randn(n, 100, generator=g).cuda()
+    t = (torch.rand(n, 3, 64, 64, generator=g) * 2 - 1).cuda()
+    lab = synth_onehot(n, DATA_SEED + 3)[0].cuda() if family == "cgan" else None
+    f = lambda *sh: torch.zeros(*sh, device="cuda")
+    loss, dz, z, m, v, hist = f(n), f(n, 100), z0.clone(), f(n, 100), f(n, 100), f(steps, n)
+    if ex:
+        lib.jck_engine_latent_grad_ex(eng._h, z0, lab, t, None, 0, 0.0, n, loss, None, None, dz, cur_stream())
+        lib.jck_engine_project_ex(eng._h, z, lab, t, n, steps, 0.05, 0.01, None, 0, 0.0, m, v, 0, hist, None, cur_stream())
+    else:
+        lib.jck_engine_latent_grad(eng._h, z0, lab, t, n, loss, dz, cur_stream())
+        lib.jck_engine_project(eng._h, z, lab, t, n, steps, 0.05, 0.01, m, v, 0, hist, cur_stream())
+    named = {"latent_grad.loss": loss, "latent_grad.dz": dz, "project.z": z, "project.m": m, "project.v": v, "project.loss_hist": hist}
+    return {k: sha256_bytes(x) for k, x in named.items()}
+
+
+def gen_latent_plain_bits(commit):
+    assert torch.cuda.is_available(), "latent_plain_bits records what the GPU computes"
+    assert commit, "--commit: name the commit the library under test was built from"
+    for p in (os.path.dirname(os.path.dirname(HERE)), os.path.join(os.path.dirname(os.path.dirname(HERE)), "jck-generation_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    rec = {"commit": commit, "device": torch.cuda.get_device_name(0), "entry_points": "plain (jck_latent_loss, jck_engine_latent_grad, jck_engine_project)"}
+    rec["latent_loss"] = {f"{n}x{hw}-{p}": latent_loss_bits(n, hw, p, False) for n, hw, p in LATENT_LOSS_CASES}
+    rec["engine"] = {f"{f}-{p}": latent_engine_bits(f, p, False) for f, p in LATENT_ENGINES}
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
+    ap.add_argument("--commit", default="", help="latent_plain_bits: the commit the library was built from")
     a = ap.parse_args()
+    if a.only == "latent_plain_bits":                  # the GPU's results, not the reference's
+        rec = gen_latent_plain_bits(a.commit)
+        rec["_meta"] = {"torch": torch.__version__, "generator": "tests/golden/make_golden.py", "model_seed": MODEL_SEED, "data_seed": DATA_SEED}
+        with open(os.path.join(HERE, "latent_plain_bits.json"), "w") as f:
+            json.dump(rec, f, indent=1)
+        print("latent_plain_bits ->", os.path.getsize(os.path.join(HERE, "latent_plain_bits.json")), "bytes")
+        return
     assert os.path.isdir(REF), "the reference is only mounted in the build container"
     install_stubs()
     sys.path.insert(0, REF)
