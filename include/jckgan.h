@@ -250,6 +250,18 @@ int jck_head_fwd(int prec, const void* a4, const float* wp, const float* bias /*
  * jck_head_fwd), no loss, no gradient, no scalar slots: a row's numbers do not depend on B. */
 int jck_score_head(int prec, const void* x, const float* w, const float* bias /* device scalar or NULL */, int B, int K,
                    float* logit, float* prob /* or NULL */, void* stream);
+/* Discriminator features: a, NHWC [N,H,H,C] of the precision's storage type (bf16, or fp32 for f32 / bf16x3), pooled to a grid x grid
+ * raster of w x w windows (w = H / grid).  For every image b, grid cell (gy,gx) and channel c
+ *   out[b*ld + col0 + (gy*grid + gx)*C + c] = pool over the window of a[b, gy*w+dy, gx*w+dx, c],  as fp32
+ * - cell-major, channel-minor: F.adaptive_max_pool2d(a_nchw, grid).permute(0, 2, 3, 1).flatten(1).
+ * mode 0: max (a NaN in the window gives NaN, as torch's max_pool2d; an all -inf window gives -inf)
+ * mode 1: mean = (fp32 sum in row-major window order) * (1 / w^2)
+ * grid in {1,2,4}, H a multiple of grid, C a multiple of 8, a 16-byte aligned, out, col0 and ld such that every row's column block
+ * is 16-byte aligned and lies inside the row; anything else: JCK_E_ARG with a message and no launch.  Columns outside
+ * [col0, col0 + grid*grid*C) are not written.  One lane per (image, cell, 16 bytes of channels), 16-byte loads and stores, no LDS, no
+ * atomics: row b does not depend on N. */
+int jck_grid_pool(int prec, const void* a, int N, int H, int C, int grid, int mode, float* out, long long ld, long long col0,
+                  void* stream);
 /* G (<= 4) batches of B rows stacked in a4 / prob / ds (the real | fake | penalty groups of a batched D pass), each with its own
  * target, mode and scalar slots, in one launch; the scalar table is indexed by the row inside its group */
 int jck_head_fwd_grouped(int prec, const void* a4, const float* wp, const float* bias, int B, int K, int G, const float* targets,
@@ -525,6 +537,17 @@ int jck_engine_project_ex(jck_engine*, float* z /* in, out */, const int64_t* la
  * have been packed (jck_engine_repack(net 1) after loading its state, or a training step): JCK_E_ARG otherwise. */
 int jck_engine_score(jck_engine*, const float* images_nchw /* fp32 [n,3,S,S] or NULL */, const float* noise_nchw /* or NULL */,
                      const int64_t* labels /* family 1 */, int n, float* logit /* [n] */, float* prob /* [n] or NULL */, void* stream);
+/* The discriminator as a feature extractor (Radford et al. 2016, section 5.1): the conv stack of jck_engine_score - the same input
+ * transform without instance noise, the same fold, the same stage launches - and then, instead of the head, one jck_grid_pool per
+ * stage on that stage's LeakyReLU output: stage i's grid^2 * D_CS[i] columns at col0 = grid^2 * sum_{j<i} D_CS[j] of row b of `out`
+ * (fp32 [n, ld], ld >= the feature dimension, ld % 4 == 0, out 16-byte aligned), stage 0 first.  mode 0: max, 1: mean.  No labels:
+ * a CGAN's conv stack never sees them.  jck_engine_feature_dim: grid^2 * sum_i D_CS[i] (960 grid^2 at 64 x 64, 1984 grid^2 at
+ * 128 x 128); 0 for a null engine or a grid outside {1,2,4}.  Guards, buffers and contract are jck_engine_score's: 1 <= n <= batch,
+ * D's operands packed, the first allocating call not inside a graph capture, nothing of the training state written, D's training
+ * activations, real_noisy and the head's concat buffer untouched, row b bit for bit what a call with that row alone returns. */
+long long jck_engine_feature_dim(const jck_engine*, int grid);
+int jck_engine_features(jck_engine*, const float* images_nchw /* fp32 [n,3,S,S] or NULL: the generator's last output where it lies */,
+                        int n, int grid, int mode, float* out /* fp32 [n, ld] */, long long ld, void* stream);
 /* debug / parity access to internal NHWC tensors: name in {"fake","real_noisy",...}; returns device ptr or NULL */
 const void* jck_engine_tensor(const jck_engine*, const char* name, long long* numel);
 

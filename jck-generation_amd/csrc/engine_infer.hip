@@ -1,4 +1,4 @@
-// Inference beside the step engine: sampling, the latent projection, discriminator scoring and the critic's latent gradient.
+// Inference beside the step engine: sampling, the latent projection, discriminator scoring and features, and the critic's latent gradient.
 // None of it touches the step state except to note that the operand rows hold a caller's z.
 #include "engine_internal.hpp"
 
@@ -115,9 +115,9 @@ static int score_fold(jck_engine* e, hipStream_t st) {
   }
   return jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st);
 }
-// ... and the stages and the head on the NHWC4 images `in`: jck_engine_score, and the forward half of the critic's latent gradient,
-// which reads the stages' activations S.a[i] and aux tables afterwards
-static int score_stages_head(jck_engine* e, const void* in, const int64_t* labels, int n, float* logit, float* prob, hipStream_t st) {
+// ... and the stages on the NHWC4 images `in`, each leaving its activation in S.a[i]: jck_engine_score, jck_engine_features and the
+// forward half of the critic's latent gradient, which reads the activations and aux tables afterwards
+static int score_stages(jck_engine* e, const void* in, int n, hipStream_t st) {
   const jck_engine::ScoreBufs& S = e->sc;
   for (int i = 0; i < TT.NS; ++i) {
     const int hb = TT.D_HB[i], cs = TT.D_CS[i];
@@ -129,6 +129,12 @@ static int score_stages_head(jck_engine* e, const void* in, const int64_t* label
     }
     in = S.a[i];
   }
+  return JCK_OK;
+}
+// the head on the deepest stage's activation
+static int score_head(jck_engine* e, const int64_t* labels, int n, float* logit, float* prob, hipStream_t st) {
+  const jck_engine::ScoreBufs& S = e->sc;
+  const void* in = S.a[TT.NS - 1];
   if (e->family == 0) return jck_score_head(e->prec, in, e->d_head_wp, nullptr, n, TT.FEAT, logit, prob, st);
   JCK_TRY(jck_concat_rows(e->prec, in, TT.FEAT, S.cbuf, L1_KPAD, n, st));
   JCK_TRY(jck_label_embed_fwd(e->prec, labels, e->P(e->LD, e->dp, "label_embedding.weight"), e->P(e->LD, e->dp, "label_embedding.bias"), LRELU, n,
@@ -137,6 +143,10 @@ static int score_stages_head(jck_engine* e, const void* in, const int64_t* label
   // Dropout is the identity under model.eval(): no mask
   JCK_TRY(jck_linear_finish(e->prec, S.slab, L1_KSPLIT, e->P(e->LD, e->dp, "linear1.bias"), nullptr, 1.0f, S.h, nullptr, n, L1_OUT, st));
   return jck_score_head(e->prec, S.h, e->P(e->LD, e->dp, "linear2.weight"), e->P(e->LD, e->dp, "linear2.bias"), n, L1_OUT, logit, prob, st);
+}
+static int score_stages_head(jck_engine* e, const void* in, const int64_t* labels, int n, float* logit, float* prob, hipStream_t st) {
+  JCK_TRY(score_stages(e, in, n, st));
+  return score_head(e, labels, n, logit, prob, st);
 }
 extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const float* noise_nchw, const int64_t* labels, int n, float* logit,
                                 float* prob, void* stream) {
@@ -155,6 +165,43 @@ extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const f
   }
   JCK_TRY(score_fold(e, st));
   return score_stages_head(e, in, labels, n, logit, prob, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// discriminator features: the stages of jck_engine_score, then each stage's activation pooled to a grid x grid raster (jck_grid_pool)
+// into that stage's column block of the caller's rows, stage 0 first; no head, no labels.  The same buffers of its own, the same
+// contract: rows independent, nothing of the training state read or written beyond D's weights and running statistics.
+// ---------------------------------------------------------------------------------------------------------
+static bool feature_grid_ok(int grid) { return grid == 1 || grid == 2 || grid == 4; }
+extern "C" long long jck_engine_feature_dim(const jck_engine* e, int grid) {
+  if (!e || !feature_grid_ok(grid)) return 0;
+  long long c = 0;
+  for (int i = 0; i < TT.NS; ++i) c += TT.D_CS[i];
+  return c * grid * grid;
+}
+extern "C" int jck_engine_features(jck_engine* e, const float* images_nchw, int n, int grid, int mode, float* out, long long ld, void* stream) {
+  if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "features: engine not bound");
+  if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, "features: n must be in [1, batch]");
+  if (!feature_grid_ok(grid)) JCK_FAIL(JCK_E_ARG, "features: grid must be 1, 2 or 4");
+  if (mode != 0 && mode != 1) JCK_FAIL(JCK_E_ARG, "features: mode must be 0 (max) or 1 (mean)");
+  if (!out || (uintptr_t)out % 16) JCK_FAIL(JCK_E_ARG, "features: out must be a 16-byte aligned device pointer");
+  if (ld < jck_engine_feature_dim(e, grid) || ld % 4) JCK_FAIL(JCK_E_ARG, "features: ld must be a multiple of 4 and at least the feature dimension");
+  if (!e->d_packed) JCK_FAIL(JCK_E_ARG, "features: the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
+  hipStream_t st = (hipStream_t)stream;
+  JCK_TRY(score_alloc(e, st));
+  const void* in = e->fake_raw;                                       // NULL images: the generator's last output, where it lies
+  if (images_nchw) {
+    JCK_TRY(jck_img_prep(e->prec, images_nchw, nullptr, 1.0f, 0.0f, e->sc.x, n, TT.HW, st));
+    in = e->sc.x;
+  }
+  JCK_TRY(score_fold(e, st));
+  JCK_TRY(score_stages(e, in, n, st));
+  long long col0 = 0;
+  for (int i = 0; i < TT.NS; ++i) {
+    JCK_TRY(jck_grid_pool(e->prec, e->sc.a[i], n, TT.D_HB[i] / 2, TT.D_CS[i], grid, mode, out, ld, col0, st));
+    col0 += (long long)grid * grid * TT.D_CS[i];
+  }
+  return JCK_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------

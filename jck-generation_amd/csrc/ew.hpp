@@ -819,6 +819,46 @@ __global__ __launch_bounds__(256) void score_head_kernel(const T* __restrict__ x
   }
 }
 
+// Discriminator features (jck_grid_pool): an NHWC activation a [N][H][H][C] pooled to a grid x grid raster of w x w windows (w = H / grid),
+// as fp32 in the activation's own order - cell-major, channel-minor: out[b * ld + col0 + (gy * grid + gx) * C + c].  mode 0: the
+// window's maximum, a NaN in the window giving NaN (as aten's max_pool2d); mode 1: the fp32 sum in row-major window order times
+// 1 / w^2.  One lane per (image, cell, 16 bytes of channels): a 16-byte load per window element, 16-byte stores, neighbouring lanes
+// on neighbouring channels for both.  No LDS, no atomics: an output row depends on its own image alone.  Launched in workgroups of one
+// wave: the shallow stage of a small batch has few lanes with long windows, and one-wave groups spread them over all CUs.
+template <typename T>
+__global__ __launch_bounds__(256) void grid_pool_kernel(const T* __restrict__ a, int H, int C, int grid, int mode, float* __restrict__ out,
+                                                        long long ld, long long col0, long long total) {
+  constexpr int V = 16 / (int)sizeof(T);                             // channels per lane: 8 (bf16) or 4 (fp32)
+  const int w = H / grid, cu = C / V, cells = grid * grid;
+  const float inv = 1.0f / (float)(w * w);
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int u = (int)(i % cu);
+    const int cell = (int)((i / cu) % cells);
+    const long long b = i / ((long long)cu * cells);
+    const int gy = cell / grid, gx = cell - gy * grid;
+    const T* p = a + ((b * H + (long long)gy * w) * H + (long long)gx * w) * C + u * V;
+    float r[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) r[k] = mode == 0 ? -INFINITY : 0.f;
+    for (int dy = 0; dy < w; ++dy) {
+      const T* q = p + (long long)dy * H * C;
+#pragma unroll 4                                                    // four loads of a window row in flight; the order of the sum is kept
+      for (int dx = 0; dx < w; ++dx) {
+        float v[V];
+        if constexpr (V == 8) ld8(q + (long long)dx * C, v); else ld4(q + (long long)dx * C, v);
+#pragma unroll
+        for (int k = 0; k < V; ++k) r[k] = mode == 0 ? ((v[k] > r[k] || v[k] != v[k]) ? v[k] : r[k]) : __fadd_rn(r[k], v[k]);
+      }
+    }
+    if (mode == 1) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) r[k] = __fmul_rn(r[k], inv);
+    }
+    float* o = out + b * ld + col0 + (long long)cell * C + u * V;
+    if constexpr (V == 8) st8(o, r); else st4(o, r);
+  }
+}
+
 // g_a4[n][k] = ds[n] * w[k]
 template <typename T>
 __global__ void head_dgrad_kernel(const float* __restrict__ ds, const float* __restrict__ w, int K, T* __restrict__ g,

@@ -594,6 +594,23 @@ extern "C" int jck_score_head(int prec, const void* x, const float* w, const flo
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }
+// an NHWC activation pooled to a grid x grid raster, as fp32 feature columns (ew.hpp: grid_pool_kernel)
+extern "C" int jck_grid_pool(int prec, const void* a, int N, int H, int C, int grid, int mode, float* out, long long ld, long long col0, void* stream) {
+  if (!a || !out) JCK_FAIL(JCK_E_ARG, "grid_pool: null a / out");
+  if (N < 1 || H < 1 || C < 8 || C % 8) JCK_FAIL(JCK_E_ARG, "grid_pool: N >= 1, H >= 1 and C a multiple of 8");
+  if (grid != 1 && grid != 2 && grid != 4) JCK_FAIL(JCK_E_ARG, "grid_pool: grid must be 1, 2 or 4");
+  if (H % grid) JCK_FAIL(JCK_E_ARG, "grid_pool: H must be a multiple of grid");
+  if (mode != 0 && mode != 1) JCK_FAIL(JCK_E_ARG, "grid_pool: mode must be 0 (max) or 1 (mean)");
+  if (col0 < 0 || ld < col0 + (long long)grid * grid * C) JCK_FAIL(JCK_E_ARG, "grid_pool: the column block [col0, col0 + grid * grid * C) must lie inside a row of ld");
+  if ((uintptr_t)a % 16 || ((uintptr_t)out + 4 * (uintptr_t)col0) % 16 || (N > 1 && ld % 4))
+    JCK_FAIL(JCK_E_ARG, "grid_pool: a and every row's column block must be 16-byte aligned");
+  DISPATCH_T(prec, {
+    const long long total = (long long)N * grid * grid * (C / (16 / (int)sizeof(T)));
+    hipLaunchKernelGGL(grid_pool_kernel<T>, dim3(ew_grid(total, 64)), dim3(64), 0, (hipStream_t)stream, (const T*)a, H, C, grid, mode, out, ld, col0, total);
+  });
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
 // jck_linear_finish + jck_head_fwd_grouped + the input-gradient half of jck_head_bwd + jck_dropout of CGAN's head in one launch
 // (ew.hpp: cg_head_mid_kernel); N = 256 columns; rows = G * B; mask required
 int cg_head_mid(int prec, const float* slab, int ksplit, const float* bias1, const float* mask, float scale, void* h, void* hd, const float* w2,

@@ -9,6 +9,9 @@
     python generate.py -m DCGAN --checkpoint best.pt --num 64 --neighbours train.npz --k 4 --out samples
     python generate.py -m DCGAN --checkpoint best.pt --inpaint samples/images.npz --mask center:32 --out inpainted
     python generate.py -m DCGAN --checkpoint best.pt --num 64 --refine 10 --out refined
+    python generate.py -m DCGAN --checkpoint best.pt --features train.npz --out feats
+    python generate.py -m DCGAN --checkpoint best.pt --probe train.npz --probe_test test.npz --k 5 --out probe
+    python generate.py -m DCGAN --checkpoint best.pt --num 64 --neighbours train.npz --space d --out samples
 
 Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
 BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
@@ -33,7 +36,14 @@ z is fitted to them alone (--project_steps, --project_lr) with --critic_weight W
 discriminator needed), and <out>/inpainted.npz holds z, loss, term, known, images (G(z)) and completed (the known pixels of the input,
 the holes from G); <out>/inpainted.png has one row per picture: masked input, G(z), completed.
 --refine STEPS (with a sampling run) moves every latent STEPS Adam updates (--refine_lr) along the discriminator's gradient before its
-image is made; images.npz then holds the refined z and gains logit_before / logit_after."""
+image is made; images.npz then holds the refined z and gains logit_before / logit_after.
+The discriminator as a feature extractor (Radford et al. 2016, section 5.1; hipgan.probe): --features FILE.npz pools every conv stage's
+activation of the file's pictures (the discriminator's size, or 32x32 data, upscaled as the trainers do) to a --feature_grid raster
+(--feature_pool max|mean) and writes <out>/features.npz (features: fp32 [n,F], unnormalised; layout: int64 [stages,4] rows of stage,
+col0, C, H; grid; pool; labels if the file has them) for an external classifier.  --probe TRAIN.npz --probe_test TEST.npz (both with
+`labels`) classifies every test picture by the majority of its --k (default 5) nearest training pictures in block-normalised feature
+space and writes <out>/probe.json (accuracy, per_class, k, train, test, F, grid, pool).  --neighbours REF.npz --space d looks the
+samples' neighbours up in that feature space instead of pixel space: neighbours.npz then holds idx, d2, ref_nn_d2 and copy, no rmse."""
 import argparse
 import os
 import sys
@@ -65,7 +75,13 @@ def get_arg_parse(argv=None):
     p.add_argument("--oversample", type=int, default=None, metavar="M", help="with --select: draws per image kept (top), per round (drs)")
     p.add_argument("--score_images", default=None, metavar="FILE.npz", help="score the uint8 [n,S,S,3] `images` array of this file")
     p.add_argument("--neighbours", default=None, metavar="REF.npz", help="nearest images of this file's uint8 `images` array for every sample")
-    p.add_argument("--k", type=int, default=4, help="with --neighbours: neighbours per sample (1..8)")
+    p.add_argument("--k", type=int, default=None, help="neighbours per sample, 1..8 (default 4 with --neighbours, 5 with --probe)")
+    p.add_argument("--space", choices=["pixel", "d"], default=None, help="with --neighbours: pixel space (default) or the discriminator's features")
+    p.add_argument("--features", default=None, metavar="FILE.npz", help="the discriminator's pooled activations of this file's uint8 `images` array")
+    p.add_argument("--feature_grid", type=int, choices=[1, 2, 4], default=None, help="with --features, --probe, --space d: the pooling raster (default 4)")
+    p.add_argument("--feature_pool", choices=["max", "mean"], default=None, help="with --features, --probe, --space d (default max)")
+    p.add_argument("--probe", default=None, metavar="TRAIN.npz", help="k-nearest-neighbour probe of the discriminator's features: the labelled training set")
+    p.add_argument("--probe_test", default=None, metavar="TEST.npz", help="with --probe: the labelled test set")
     p.add_argument("--inpaint", default=None, metavar="FILE.npz", help="fill the holes of the uint8 [n,S,S,3] `images` array of this file")
     p.add_argument("--mask", default=None, metavar="SPEC", help="with --inpaint: center:K, half:left|right|top|bottom, or an .npz / .npy with `mask`")
     p.add_argument("--critic_weight", type=float, default=None, metavar="W", help="with --inpaint: weight of -log D(G(z)) (default 0.003; 0: no critic)")
@@ -94,8 +110,24 @@ def get_arg_parse(argv=None):
         p.error("--score scores the eval-mode generator's images: not with --project or --bn batch")
     if a.neighbours and a.project:
         p.error("--neighbours looks up sampled or given images: not with --project")
+    if a.space and not a.neighbours:
+        p.error("--space goes with --neighbours")
+    if bool(a.probe) != bool(a.probe_test):
+        p.error("--probe TRAIN.npz and --probe_test TEST.npz go together")
+    if a.features and a.probe:
+        p.error("--features and --probe are separate runs")
+    if (a.features or a.probe) and (a.interpolate or a.project or a.select or a.score or a.score_images or a.neighbours or a.inpaint or
+                                    a.num is not None or a.truncation is not None or a.refine is not None):
+        p.error("--features and --probe take their images from files; the sampling, projection, scoring and neighbour options do not go with them")
+    if (a.feature_grid is not None or a.feature_pool is not None) and not (a.features or a.probe or a.space == "d"):
+        p.error("--feature_grid and --feature_pool go with --features, --probe or --space d")
+    if a.k is None:
+        a.k = 5 if a.probe else 4
     if not 1 <= a.k <= 8:
         p.error("--k must lie in 1..8")
+    a.space = a.space or "pixel"
+    a.feature_grid = 4 if a.feature_grid is None else a.feature_grid
+    a.feature_pool = a.feature_pool or "max"
     if bool(a.inpaint) != bool(a.mask):
         p.error("--inpaint FILE.npz and --mask SPEC go together")
     if a.inpaint and (a.project or a.interpolate or a.select or a.score or a.score_images or a.neighbours or a.num is not None or
@@ -148,7 +180,8 @@ def parse_interpolate(s):
 
 
 def needs_discriminator(args):
-    return bool(args.score or args.select or args.score_images or args.refine is not None or (args.inpaint and args.critic_weight > 0))
+    return bool(args.score or args.select or args.score_images or args.refine is not None or (args.inpaint and args.critic_weight > 0) or
+                args.features or args.probe or args.space == "d")
 
 
 def check_checkpoint(args, ckpt):
@@ -232,6 +265,9 @@ def main(argv=None):
     job = None
     if args.inpaint:                      # ... and so does a bad picture file or mask
         job = plan_inpaint(args)
+    if args.features or args.probe:       # ... or a feature run's file without pictures, a probe's without labels
+        from hipgan.probe import load_images
+        job = [load_images(f, need_labels=bool(args.probe)) for f in ((args.features,) if args.features else (args.probe, args.probe_test))]
     ckpt = args.checkpoint
     if with_d:
         ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
@@ -243,6 +279,10 @@ def main(argv=None):
         return project_main(args, s)
     if args.inpaint:
         return inpaint_main(args, s, job)
+    if args.features:
+        return features_main(args, s, job)
+    if args.probe:
+        return probe_main(args, s, job)
     if args.score_images:
         return score_main(args, s, ref)
     if ref is not None:                   # ... and one of the wrong size before anything is sampled
@@ -289,14 +329,53 @@ def neighbours_main(args, s, u8, ref):
     from hipgan.neighbours import neighbour_rows, upscale_steps
     from train.gan_trainer import _encode_png
     steps = upscale_steps(ref.shape[1], u8.shape[1], what=args.neighbours)
-    r = s.neighbours(u8, ref, k=args.k)
+    if args.space == "d":
+        r = s.neighbours(u8, ref, k=args.k, space="d", grid=args.feature_grid, pool=args.feature_pool)
+    else:
+        r = s.neighbours(u8, ref, k=args.k)
     os.makedirs(args.out, exist_ok=True)
-    np.savez(os.path.join(args.out, "neighbours.npz"), **{k_: r[k_] for k_ in ("idx", "d2", "rmse", "ref_nn_d2", "copy")})
+    np.savez(os.path.join(args.out, "neighbours.npz"), **{k_: r[k_] for k_ in ("idx", "d2", "rmse", "ref_nn_d2", "copy") if k_ in r})
     with open(os.path.join(args.out, "neighbours.png"), "wb") as f:
         f.write(_encode_png(grid_u8(neighbour_rows(u8, ref, r["idx"], steps), 1 + args.k)))
+    if args.space == "d":
+        near = r["d2"][:, 0]
+        print(f"neighbours (discriminator features): {int(r['copy'].sum())} of {u8.shape[0]} samples flagged as copies, nearest d2 min "
+              f"{float(np.nanmin(near)):.5f} median {float(np.nanmedian(near)):.5f} -> {args.out}/neighbours.npz, neighbours.png")
+        return
     near = r["rmse"][:, 0]
     print(f"neighbours: {int(r['copy'].sum())} of {u8.shape[0]} samples flagged as copies, nearest rmse min {float(np.nanmin(near)):.5f} "
           f"median {float(np.nanmedian(near)):.5f} -> {args.out}/neighbours.npz, neighbours.png")
+
+
+def features_main(args, s, job):
+    """--features: the discriminator's pooled activations of a file's pictures -> <out>/features.npz and one line"""
+    from hipgan.probe import extract, feature_layout
+    (u8, labels), = job
+    f = extract(s.engine, u8, args.feature_grid, args.feature_pool, normalise="none").cpu().numpy()
+    layout, F = feature_layout(s.engine.size, args.feature_grid)
+    arrays = {"features": f, "layout": np.asarray(layout, np.int64), "grid": np.int64(args.feature_grid), "pool": np.str_(args.feature_pool)}
+    if labels is not None:
+        arrays["labels"] = labels
+    os.makedirs(args.out, exist_ok=True)
+    np.savez(os.path.join(args.out, "features.npz"), **arrays)
+    print(f"{f.shape[0]} images -> {F} features each (grid {args.feature_grid}, {args.feature_pool}) -> {args.out}/features.npz")
+    return 0
+
+
+def probe_main(args, s, job):
+    """--probe: a k-nearest-neighbour classifier on the discriminator's features -> <out>/probe.json and one line"""
+    import json
+    from hipgan.probe import feature_layout
+    (train, ltr), (test, lte) = job
+    r = s.knn_probe(train, ltr, test, lte, k=args.k, grid=args.feature_grid, pool=args.feature_pool)
+    res = {"accuracy": r["accuracy"], "per_class": {str(c): a for c, a in r["per_class"].items()}, "k": args.k, "train": int(train.shape[0]),
+           "test": int(test.shape[0]), "F": feature_layout(s.engine.size, args.feature_grid)[1], "grid": args.feature_grid, "pool": args.feature_pool}
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, "probe.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(f"probe: {res['test']} test images against {res['train']} training images, k = {args.k}, F = {res['F']}: accuracy "
+          f"{res['accuracy']:.4f} -> {args.out}/probe.json")
+    return 0
 
 
 def score_main(args, s, ref=None):

@@ -1053,6 +1053,48 @@ class DcganEngine:
         self._keep_score = (lab,)
         return self._score_chunks(n, lab)
 
+    def _feature_args(self, what, grid, pool):
+        """(grid, jck_grid_pool's mode, the feature dimension F) of a features call, validated on the host"""
+        from .probe import POOL_MODES, feature_layout
+        if pool not in POOL_MODES:
+            raise JckError(f"{what}: pool must be 'max' or 'mean', got {pool!r}")
+        return int(grid), POOL_MODES[pool], feature_layout(self.size, grid)[1]
+
+    def _feature_chunks(self, n, grid, mode, F, x=None, zc=None, lab=None):
+        """fp32 [n, F] in chunks of at most `batch` rows: the eval-mode generator on zc's rows if given, then the discriminator's
+        pooled activations of x's rows or, x None, of the images where the generator left them"""
+        out = torch.empty(n, F, dtype=torch.float32, device=self.device)
+        for lo, hi in chunk_plan(n, self.batch):
+            if zc is not None:
+                self._sample_chunk(zc, lab, lo, hi, SAMPLE_EVAL, None)
+            lib.jck_engine_features(self._h, _rows(x, lo, hi), hi - lo, grid, mode, out[lo:hi], F, cur_stream())
+        return out
+
+    def features(self, images, grid=4, pool="max"):
+        """fp32 [n, F] on the device: the discriminator as a feature extractor (Radford et al. 2016, section 5.1).  D runs as under
+        model.eval() (score()), and every conv stage's LeakyReLU output is pooled - pool="max" or "mean" - to a grid x grid raster,
+        flattened cell-major, channel-minor and concatenated, stage 0 first: hipgan.probe.feature_layout(size, grid) names the blocks
+        (F = 960 grid^2 at 64 x 64).  images: fp32 NCHW [n,3,S,S] in [-1, 1] or uint8 NHWC [n,S,S,3].  No labels: a CGAN's conv stack
+        never sees them.  Any n, rows independent bit for bit; nothing of the training state is written."""
+        from .sampler import images_to_target
+        grid, mode, F = self._feature_args("features", grid, pool)
+        x = images_to_target(images)
+        if x.shape[2] != self.size:
+            raise JckError(f"features: images are {x.shape[2]}x{x.shape[2]}, this discriminator takes {self.size}x{self.size}")
+        self._score_ready("features")
+        x = x.to(self.device, torch.float32).contiguous()
+        self._keep_score = (x,)
+        return self._feature_chunks(x.shape[0], grid, mode, F, x=x)
+
+    def features_latents(self, z, labels=None, grid=4, pool="max"):
+        """features() of G(z), both networks as under model.eval(): per chunk the eval-mode generator (sample(bn="running")) leaves
+        its images on the device and the discriminator reads them where they lie.  labels: the generator's, CGAN only."""
+        grid, mode, F = self._feature_args("features_latents", grid, pool)
+        n, zc, lab = self._latents("features_latents", z, labels)
+        self._score_ready("features_latents")
+        self._keep_score = (zc, lab)
+        return self._feature_chunks(n, grid, mode, F, zc=zc, lab=lab)
+
     def tensor(self, name):
         """Debug/parity view of an internal NHWC tensor as a torch tensor (copy)."""
         self.join()

@@ -7,7 +7,9 @@
 Both sides become u8 / 127.5 - 1 fp32 rows on the device, the reference `chunk` images at a time (50 000 x 12 288 fp32 is 2.4 GB),
 and go through jck_knn_index_f32 (csrc/knnindex.hip): candidates from the Gram form, distances recomputed from differences, so a
 near copy's distance keeps its digits.  There is no tuned threshold: the `copy` flag compares a sample's nearest distance with the
-leave-one-out nearest-neighbour distance of that training image inside the training set."""
+leave-one-out nearest-neighbour distance of that training image inside the training set.
+nearest_rows runs the same walk and flag on rows of another space - the discriminator's features (hipgan.probe,
+Sampler.neighbours(space="d")), which also find a shifted, recoloured or mirrored training picture."""
 import numpy as np
 import torch
 
@@ -88,6 +90,33 @@ def nearest_images(query_u8, ref_u8, k=4, chunk=8192, flag=True, device="cuda:0"
             # the matched rows are not consecutive, so the index equality that exclude_self tests cannot name them: take their two
             # nearest rows instead and drop the row itself (a duplicate elsewhere stays, at distance 0)
             mi, md = walk(_rows(r8[torch.as_tensor(rows)], steps, device), 2)
+            mi, md = mi.cpu().numpy(), md.cpu().numpy()
+            loo = np.where(mi[:, 0] == rows, md[:, 1], md[:, 0])
+            nn[first >= 0] = loo[np.searchsorted(rows, first[first >= 0])]
+        out["ref_nn_d2"] = nn
+        with np.errstate(invalid="ignore"):
+            out["copy"] = out["d2"][:, 0] < nn
+    return out
+
+
+def nearest_rows(q, ref, k=4, chunk=8192, flag=True):
+    """The walk of nearest_images on rows that already exist - fp32 device matrices q [n,D] and ref [N,D] of any feature space, the
+    discriminator's for one (hipgan.probe.extract) -> {"idx", "d2"} and, with flag, "ref_nn_d2" and "copy" as nearest_images defines
+    them; no "rmse": a feature distance has no pixel unit."""
+    from metrics import nearest
+    k, chunk = int(k), int(chunk)
+    if not 1 <= k <= 8 or chunk < 1:
+        raise JckError(f"nearest_rows: 1 <= k <= 8 and chunk >= 1, got k = {k}, chunk = {chunk}")
+    n = q.shape[0]
+    idx, d2 = nearest(q, ref, k, chunk=chunk)
+    out = {"idx": idx.cpu().numpy(), "d2": d2.cpu().numpy()}
+    if flag:
+        first = out["idx"][:, 0]
+        rows = np.unique(first[first >= 0])
+        nn = np.full(n, np.nan, np.float32)
+        if rows.size:
+            # as in nearest_images: the matched rows' two nearest rows, the row itself dropped (a duplicate elsewhere stays, at 0)
+            mi, md = nearest(ref[torch.as_tensor(rows, device=ref.device)], ref, 2, chunk=chunk)
             mi, md = mi.cpu().numpy(), md.cpu().numpy()
             loo = np.where(mi[:, 0] == rows, md[:, 1], md[:, 0])
             nn[first >= 0] = loo[np.searchsorted(rows, first[first >= 0])]

@@ -6,6 +6,8 @@
     s = Sampler.from_checkpoint("best.pt", "DCGAN", with_d=True)   # ... with the checkpoint's discriminator
     r = s.inpaint(u8, parse_mask("center:32", 64))             # hipgan.inpaint: z fitted to the known pixels, D as realism prior
     z2, before, after = s.refine(z, steps=10)                  # latents moved along the discriminator's gradient
+    f = s.features(u8)                                         # D's pooled conv activations, fp32 [n,15360] (hipgan.probe)
+    r = s.knn_probe(train_u8, train_labels, test_u8, test_labels)    # what D learned about the classes: r["accuracy"]
 
 Sampling runs with bn="running" by default (DcganEngine.sample): BatchNorm on the running statistics, every image a function of
 its own z, any n.  The running statistics of an AVERAGED generator were never fitted to its weights - they are the live ones at
@@ -401,11 +403,34 @@ class Sampler:
         gen = self.engine.sample(z, lab, bn="running", out="uint8")
         return {"z": z, "loss": loss, "term": term, "generated": gen, "completed": blend(x.to(gen.device), gen, k)}
 
-    def neighbours(self, images, ref, k=4, **kw):
-        """The k nearest reference (training) images of `images` in pixel space, both uint8 NHWC, and the `copy` flags
-        (hipgan.neighbours.nearest_images; on this sampler's device)."""
-        from .neighbours import nearest_images
-        return nearest_images(images, ref, k=k, device=self.engine.device, **kw)
+    def neighbours(self, images, ref, k=4, space="pixel", grid=4, pool="max", normalise="block", **kw):
+        """The k nearest reference (training) images of `images`, both uint8 NHWC, and the `copy` flags, on this sampler's device.
+        space="pixel": in pixel space (hipgan.neighbours.nearest_images).  space="d": the same walk on the discriminator's
+        block-normalised features (hipgan.probe.extract with grid, pool, normalise; needs from_checkpoint(..., with_d=True)), which
+        also finds a shifted, recoloured or mirrored picture: idx, d2, ref_nn_d2 and copy, no rmse."""
+        if space not in ("pixel", "d"):
+            raise JckError(f"neighbours: space must be 'pixel' or 'd', got {space!r}")
+        if space == "pixel":
+            from .neighbours import nearest_images
+            return nearest_images(images, ref, k=k, device=self.engine.device, **kw)
+        from .neighbours import nearest_rows
+        from .probe import extract
+        self._needs_d("neighbours(space='d')")
+        q = extract(self.engine, images, grid, pool, normalise)
+        return nearest_rows(q, extract(self.engine, ref, grid, pool, normalise), k=k, **kw)
+
+    def features(self, images, grid=4, pool="max"):
+        """fp32 [n, F] on the device: the checkpoint's discriminator as a feature extractor on uint8 NHWC or fp32 NCHW images
+        (DcganEngine.features; hipgan.probe.feature_layout names the columns).  Needs from_checkpoint(..., with_d=True)."""
+        self._needs_d("features")
+        return self.engine.features(images, grid=grid, pool=pool)
+
+    def knn_probe(self, train_u8, train_labels, test_u8, test_labels, **kw):
+        """A k-nearest-neighbour classifier on the discriminator's features (hipgan.probe.knn_probe): what D has learned about the
+        classes.  Needs from_checkpoint(..., with_d=True)."""
+        from .probe import knn_probe
+        self._needs_d("knn_probe")
+        return knn_probe(self.engine, train_u8, train_labels, test_u8, test_labels, **kw)
 
     def calibrate(self, batches, seed=0):
         """`batches` train-mode sampling batches (full engine batches of fresh z, uniform random classes for a CGAN) through the
