@@ -144,6 +144,15 @@ int jck_critic_ds(const float* logit, int mode, float weight, int B, float* ds, 
  * weights return the same bits. */
 int jck_latent_loss_ex(int prec, const void* x_nhwc4, const float* target_nchw_f32, const float* weight, const void* g_x, void* g_raw_out,
                        float* loss_out, int N, int HW, void* stream);
+/* Feature matching on a folded eval-mode stage a = leaky(scale[c] * y + shift[c]): fterm[b] = weight / M * sum over image b's M
+ * elements of (a - f)^2, and that term's gradient at the stage's product y in the same pass: d = a - f, t = scale[c] * (2 weight / M * d),
+ * g = a > 0 ? t : t * slope (ATen's leaky_relu_backward on a: a = +-0 and NaN take the slope), all in fp32.  accumulate 0: g_y = g;
+ * accumulate 1: g_y = g_y + g, the old value read in the element type, the sum rounded once - onto a gradient that came down from
+ * the head.  a, f, g_y: NHWC of the element type, M elements per image, M a multiple of C, C a power of two >= 8; scale: device
+ * float[C]; all 16-byte aligned; weight finite and >= 0; anything else is JCK_E_ARG with nothing launched.  One launch, one workgroup
+ * per image, 16 bytes per access, a fixed-order reduction: equal bits on every run, and image b does not depend on N. */
+int jck_feat_match(int prec, const void* a, const void* f, const float* scale, float slope, float weight, void* g_y, int accumulate,
+                   float* fterm, int N, long long M, int C, void* stream);
 size_t jck_g1_wgrad_ws_bytes(int B, int CiPad, int Co);
 int jck_g1_wgrad(int prec, const void* z, const void* dy, float* ws, size_t ws_bytes, float* grad, int accumulate, int B,
                  int Ci, int CiPad, int Co, void* stream);
@@ -522,6 +531,30 @@ int jck_engine_project_ex(jck_engine*, float* z /* in, out */, const int64_t* la
                           int steps, float lr, float prior, const float* weight /* or NULL */, int critic_mode, float critic_weight,
                           float* m, float* v, int t0, float* loss_hist /* [steps][n] or NULL */, float* term_hist /* [steps][n] or NULL */,
                           void* stream);
+/* The same with a feature-matching term on the discriminator's activations: J_b = L_b + term_b + F_b + prior * mean_k(z_bk^2),
+ * F_b = feat_weight / M_k * sum over stage k's elements of (a_k(G(z_b)) - a_k(x_b))^2, a_k the LeakyReLU output of D's conv stage k as
+ * under model.eval() (what jck_engine_features pools), M_k its elements per image, x = feat_target_nchw (fp32 [n,3,S,S] in [-1, 1] on
+ * the device), feat_stage 0 .. NS-1 or -1 for the deepest.  Labels play no part in F.  The term is on iff feat_target_nchw is not NULL
+ * and feat_weight > 0; off, both are the _ex entry points bit for bit (which forward here with NULL, -1, 0, NULL: one implementation).
+ * latent_grad_fm: fterm [n] (or NULL) = F, dz = d(L + term + F)/dz.  project_fm: fterm_hist[s][n] (or NULL) is F before update s.
+ * Once per call the target's activation a_k(x) is computed (the input transform, the stages 0..k) and kept in a buffer of its own.
+ * One evaluation without a critic: the eval generator's products, D's stages 0..k on its output, jck_feat_match into the gradient at
+ * stage k's product, jck_conv_up_mask from stage k down to stage 1, jck_conv_up into the image gradient, jck_latent_loss_ex, the
+ * projection's backward - the head and the stages above k do not run.  With a critic: the _ex chain from the head, and jck_feat_match
+ * (accumulate 1) where the gradient at stage k's product has just been written.  The feature buffer (batch images of stage 0's size
+ * and a row of floats) is ONE allocation made by the first call with a feature term (so: not inside a graph capture) and freed by
+ * jck_engine_destroy; otherwise the contract of the _ex entry points.  JCK_E_ARG, nothing launched: feat_weight negative or not
+ * finite, feat_weight > 0 without a feature target, feat_stage outside [-1, NS-1], a feature term without D's packed operands,
+ * neither a target nor a critic nor a feature term, critic_mode outside 0..2. */
+int jck_engine_latent_grad_fm(jck_engine*, const float* z, const int64_t* labels, const float* target_nchw /* or NULL */,
+                              const float* weight /* or NULL */, int critic_mode, float critic_weight, int n, float* loss /* [n] */,
+                              float* term /* [n] or NULL */, float* logit /* [n] or NULL */, float* dz /* [n,100] */, void* stream,
+                              const float* feat_target_nchw /* or NULL */, int feat_stage, float feat_weight, float* fterm /* [n] or NULL */);
+int jck_engine_project_fm(jck_engine*, float* z /* in, out */, const int64_t* labels, const float* target_nchw /* or NULL */, int n,
+                          int steps, float lr, float prior, const float* weight /* or NULL */, int critic_mode, float critic_weight,
+                          float* m, float* v, int t0, float* loss_hist /* [steps][n] or NULL */, float* term_hist /* [steps][n] or NULL */,
+                          void* stream, const float* feat_target_nchw /* or NULL */, int feat_stage, float feat_weight,
+                          float* fterm_hist /* [steps][n] or NULL */);
 /* The discriminator as under model.eval() (model/DCGAN.py:28-50, model/CGAN.py:18-42 with BatchNorm on its running statistics and
  * Dropout the identity): logit[b] = D's pre-sigmoid output for image b, prob[b] (or NULL) its sigmoid.  images_nchw: fp32 [n,3,S,S]
  * in [-1, 1] on the device, or NULL to score the generator's current output where it lies (jck_engine_sample_ex just before: the images

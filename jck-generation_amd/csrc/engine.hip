@@ -159,6 +159,7 @@ extern "C" void jck_engine_destroy(jck_engine* e) {
   if (e->lat_w) (void)hipFree(e->lat_w);
   if (e->sc.base) (void)hipFree(e->sc.base);
   if (e->cr.base) (void)hipFree(e->cr.base);
+  if (e->fm_fa) (void)hipFree(e->fm_fa);
   delete e;
 }
 extern "C" int jck_engine_num_tensors(int family, int net) { return (int)make_layout(family, net).t.size(); }

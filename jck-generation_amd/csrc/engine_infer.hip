@@ -116,10 +116,12 @@ static int score_fold(jck_engine* e, hipStream_t st) {
   return jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st);
 }
 // ... and the stages on the NHWC4 images `in`, each leaving its activation in S.a[i]: jck_engine_score, jck_engine_features and the
-// forward half of the critic's latent gradient, which reads the activations and aux tables afterwards
-static int score_stages(jck_engine* e, const void* in, int n, hipStream_t st) {
+// forward half of the critic's latent gradient, which reads the activations and aux tables afterwards.  `last`: the last stage to run
+// (the feature term stops at its stage); -1: all of them
+static int score_stages(jck_engine* e, const void* in, int n, hipStream_t st, int last = -1) {
   const jck_engine::ScoreBufs& S = e->sc;
-  for (int i = 0; i < TT.NS; ++i) {
+  if (last < 0) last = TT.NS - 1;
+  for (int i = 0; i <= last; ++i) {
     const int hb = TT.D_HB[i], cs = TT.D_CS[i];
     if (score_stage_fused(e->prec)) {
       JCK_TRY(jck_conv_down_affine(e->prec, in, e->d_down[i], S.aux[i], S.aux[i] + cs, LRELU, S.a[i], n, hb, hb, TT.D_CB[i], cs, st));
@@ -236,36 +238,67 @@ static int critic_alloc(jck_engine* e) {
   return JCK_OK;
 }
 static int latent_check(jck_engine* e, const float* z, const int64_t* labels, const float* target, int critic_mode, float critic_weight,
-                        int n, const char* who) {
+                        const float* feat_target, int feat_stage, float feat_weight, int n, const char* who) {
   const std::string w(who);
   if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, w + ": engine not bound");
   if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, w + ": n must be in [1, batch]");
   if (!z) JCK_FAIL(JCK_E_ARG, w + ": null z");
   if (critic_mode < 0 || critic_mode > 2) JCK_FAIL(JCK_E_ARG, w + ": critic_mode must be 0 (none), 1 (nsgan) or 2 (logit)");
-  if (!target && !critic_mode) JCK_FAIL(JCK_E_ARG, w + ": without a target a critic is required");
+  if (!(feat_weight >= 0.f) || !(feat_weight <= 3.402823466e38f)) JCK_FAIL(JCK_E_ARG, w + ": feat_weight must be finite and >= 0");
+  if (feat_weight > 0.f && !feat_target) JCK_FAIL(JCK_E_ARG, w + ": feat_weight > 0 needs a feature target");
+  if (feat_stage < -1 || feat_stage >= TT.NS) JCK_FAIL(JCK_E_ARG, w + ": feat_stage must be -1 (the deepest stage) or a stage of D");
+  const bool fm = feat_target && feat_weight > 0.f;
+  if (!target && !critic_mode && !fm) JCK_FAIL(JCK_E_ARG, w + ": without a target and without a feature term a critic is required");
   if (!(critic_weight >= 0.f)) JCK_FAIL(JCK_E_ARG, w + ": critic_weight >= 0");
   if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, w + ": CGAN needs labels");
-  if (critic_mode && !e->d_packed)
+  if ((critic_mode || fm) && !e->d_packed)
     JCK_FAIL(JCK_E_ARG, w + ": the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
   if (e->capturing) JCK_FAIL(JCK_E_ARG, w + ": not inside a graph capture");
   return JCK_OK;
 }
-struct LatentEx { const float* target; const float* weight; int mode; float cw; const int64_t* labels; };
-// once per call, behind latent_begin: the critic's buffers and D's BatchNorm fold
-static int latent_ex_begin(jck_engine* e, const LatentEx& o, hipStream_t st) {
-  if (!o.mode) return JCK_OK;
+// feat_target / feat_stage / feat_weight: the feature-matching term F_b = feat_weight * mean((a_k(G(z_b)) - a_k(x_b))^2) on the LeakyReLU
+// output of D's stage k (-1: the deepest); on iff there is a target and a positive weight
+struct LatentEx {
+  const float* target; const float* weight; int mode; float cw; const int64_t* labels;
+  const float* feat_target; int feat_stage; float feat_weight;
+  bool fm() const { return feat_target && feat_weight > 0.f; }
+};
+static int feat_stage_of(const jck_engine* e, const LatentEx& o) { return o.feat_stage < 0 ? TT.NS - 1 : o.feat_stage; }
+static long long feat_elems(const jck_engine* e, int k) { return (long long)(TT.D_HB[k] / 2) * (TT.D_HB[k] / 2) * TT.D_CS[k]; }
+// once per call, behind latent_begin: the critic's buffers and D's BatchNorm fold; with a feature term also its buffer (the first such
+// call allocates it: room for the largest stage, and a row for F), and the target's activation at stage k, which stays there for the call
+static int latent_ex_begin(jck_engine* e, const LatentEx& o, int n, hipStream_t st) {
+  if (!o.mode && !o.fm()) return JCK_OK;
   JCK_TRY(score_alloc(e, st));
   JCK_TRY(critic_alloc(e));
-  return score_fold(e, st);
+  if (o.fm() && !e->fm_fa) {
+    const size_t fb = (size_t)e->B * feat_elems(e, 0) * e->esz;         // a multiple of 256
+    HIPCHK(hipMalloc(&e->fm_fa, fb + (size_t)e->B * sizeof(float)));
+    e->fm_term = reinterpret_cast<float*>((unsigned char*)e->fm_fa + fb);
+  }
+  JCK_TRY(score_fold(e, st));
+  if (!o.fm()) return JCK_OK;
+  const int k = feat_stage_of(e, o);
+  JCK_TRY(jck_img_prep(e->prec, o.feat_target, nullptr, 1.0f, 0.0f, e->sc.x, n, TT.HW, st));
+  JCK_TRY(score_stages(e, e->sc.x, n, st, k));
+  HIPCHK(hipMemcpyAsync(e->fm_fa, e->sc.a[k], (size_t)n * feat_elems(e, k) * e->esz, hipMemcpyDeviceToDevice, st));
+  return JCK_OK;
 }
 // one evaluation: the eval forward's products, the critic's forward and input gradient if there is one, the loss and its gradient, the
 // masked dgrads, the dz product's slabs.  Plain (no weight, no critic): the products, jck_latent_loss_ex, latent_backward.
-static int latent_eval(jck_engine* e, const LatentEx& o, int n, float* loss, float* term, float* logit, hipStream_t st) {
+// With a feature term jck_feat_match puts its gradient where C.g[k] holds (or would hold) the gradient at stage k's product: without a
+// critic D runs up to stage k only and its backward starts there; with one it is added onto what came down from the head.
+static int latent_eval(jck_engine* e, const LatentEx& o, int n, float* loss, float* term, float* logit, float* fterm, hipStream_t st) {
   JCK_TRY(g_eval_products(e, n, st));
   const jck_engine::ScoreBufs& S = e->sc;
   const jck_engine::CriticBufs& C = e->cr;
+  const bool fm = o.fm();
+  const int top = TT.NS - 1, k = feat_stage_of(e, o), from = o.mode ? top : k;
+  auto feat_match = [&](int accumulate) {
+    return jck_feat_match(e->prec, S.a[k], e->fm_fa, S.aux[k], LRELU, o.feat_weight, C.g[k], accumulate, fterm ? fterm : e->fm_term, n,
+                          feat_elems(e, k), TT.D_CS[k], st);
+  };
   if (o.mode) {
-    const int top = TT.NS - 1;
     if (!logit) logit = C.logit;
     JCK_TRY(score_stages_head(e, e->fake_raw, o.labels, n, logit, nullptr, st));
     JCK_TRY(jck_critic_ds(logit, o.mode, o.cw, n, C.ds, term ? term : C.term, st));
@@ -279,63 +312,87 @@ static int latent_eval(jck_engine* e, const LatentEx& o, int n, float* loss, flo
     }
     JCK_TRY(jck_leaky_affine_bwd(e->prec, C.g[top], S.a[top], S.aux[top], LRELU, C.g[top], (long long)n * (TT.D_HB[top] / 2) * (TT.D_HB[top] / 2),
                                  TT.D_CS[top], st));
-    for (int i = top; i >= 1; --i) {            // through conv(i+1) and the folded stage in front of it
+    if (fm && k == top) JCK_TRY(feat_match(1));
+  } else if (fm) {
+    JCK_TRY(score_stages(e, e->fake_raw, n, st, k));
+    JCK_TRY(feat_match(0));
+  }
+  if (o.mode || fm) {
+    for (int i = from; i >= 1; --i) {           // through conv(i+1) and the folded stage in front of it
       const int hs = TT.D_HB[i] / 2;
       JCK_TRY(jck_conv_up_mask(e->prec, C.g[i], e->d_up[i], S.a[i - 1], S.aux[i - 1], LRELU, C.g[i - 1], n, hs, hs, TT.D_CS[i], TT.D_CB[i], st));
+      if (fm && i - 1 == k) JCK_TRY(feat_match(1));
     }
     JCK_TRY(jck_conv_up(e->prec, C.g[0], e->d_up[0], C.gx, nullptr, nullptr, 0, n, TT.D_HB[0] / 2, TT.D_HB[0] / 2, TT.D_CS[0], TT.D_CB[0], st));
   }
-  JCK_TRY(jck_latent_loss_ex(e->prec, e->fake_raw, o.target, o.weight, o.mode ? C.gx : nullptr, e->g_raw, loss, n, TT.HW, st));
+  JCK_TRY(jck_latent_loss_ex(e->prec, e->fake_raw, o.target, o.weight, o.mode || fm ? C.gx : nullptr, e->g_raw, loss, n, TT.HW, st));
   return latent_backward(e, n, st);
 }
 static int latent_grad(const char* who, jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
-                       int critic_mode, float critic_weight, int n, float* loss, float* term, float* logit, float* dz, void* stream) {
-  JCK_TRY(latent_check(e, z, labels, target_nchw, critic_mode, critic_weight, n, who));
+                       int critic_mode, float critic_weight, const float* feat_target, int feat_stage, float feat_weight, int n, float* loss,
+                       float* term, float* logit, float* fterm, float* dz, void* stream) {
+  JCK_TRY(latent_check(e, z, labels, target_nchw, critic_mode, critic_weight, feat_target, feat_stage, feat_weight, n, who));
   if (!loss || !dz) JCK_FAIL(JCK_E_ARG, std::string(who) + ": null loss / dz");
   hipStream_t st = (hipStream_t)stream;
-  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels};
+  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels, feat_target, feat_stage, feat_weight};
   JCK_TRY(latent_begin(e, z, labels, n, st));
-  JCK_TRY(latent_ex_begin(e, o, st));
-  JCK_TRY(latent_eval(e, o, n, loss, term, logit, st));
+  JCK_TRY(latent_ex_begin(e, o, n, st));
+  JCK_TRY(latent_eval(e, o, n, loss, term, logit, fterm, st));
   return jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, dz, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, n, st);
 }
 // `steps` Adam updates of z [n][100] (in, out) on the stream, no host synchronisation: m, v [n][100] are the caller's (zero them for a
-// fresh run), t0 the number of updates they have seen; loss_hist[s][n] / term_hist[s][n] (or null) are the loss and the critic's term
-// BEFORE update s.
+// fresh run), t0 the number of updates they have seen; loss_hist[s][n] / term_hist[s][n] / fterm_hist[s][n] (or null) are the loss, the
+// critic's term and the feature term BEFORE update s.
 static int project(const char* who, jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
-                   float prior, const float* weight, int critic_mode, float critic_weight, float* m, float* v, int t0, float* loss_hist,
-                   float* term_hist, void* stream) {
+                   float prior, const float* weight, int critic_mode, float critic_weight, const float* feat_target, int feat_stage,
+                   float feat_weight, float* m, float* v, int t0, float* loss_hist, float* term_hist, float* fterm_hist, void* stream) {
   const std::string w(who);
-  JCK_TRY(latent_check(e, z, labels, target_nchw, critic_mode, critic_weight, n, who));
+  JCK_TRY(latent_check(e, z, labels, target_nchw, critic_mode, critic_weight, feat_target, feat_stage, feat_weight, n, who));
   if (steps < 1 || t0 < 0 || !m || !v) JCK_FAIL(JCK_E_ARG, w + ": steps >= 1, t0 >= 0 and the Adam state m, v are required");
   if (!(lr > 0.f) || !(prior >= 0.f)) JCK_FAIL(JCK_E_ARG, w + ": lr > 0 and prior >= 0");
   hipStream_t st = (hipStream_t)stream;
-  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels};
+  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels, feat_target, feat_stage, feat_weight};
   JCK_TRY(latent_begin(e, z, labels, n, st));
-  JCK_TRY(latent_ex_begin(e, o, st));
+  JCK_TRY(latent_ex_begin(e, o, n, st));
   for (int s = 0; s < steps; ++s) {
-    JCK_TRY(latent_eval(e, o, n, loss_hist ? loss_hist + (size_t)s * n : e->lat_loss, term_hist ? term_hist + (size_t)s * n : nullptr, nullptr, st));
+    JCK_TRY(latent_eval(e, o, n, loss_hist ? loss_hist + (size_t)s * n : e->lat_loss, term_hist ? term_hist + (size_t)s * n : nullptr, nullptr,
+                        fterm_hist ? fterm_hist + (size_t)s * n : nullptr, st));
     JCK_TRY(jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, z, m, v, lr, prior, t0 + s + 1, e->g_z, z_pad(e->family), n, st));
   }
   return JCK_OK;
 }
-// the four entry points: the plain ones are the _ex ones with no weight and no critic
+// the six entry points: the plain ones are the _ex ones with no weight and no critic, the _ex ones the _fm ones with no feature term
 extern "C" int jck_engine_latent_grad(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, int n, float* loss,
                                       float* dz, void* stream) {
-  return latent_grad("latent_grad", e, z, labels, target_nchw, nullptr, 0, 0.f, n, loss, nullptr, nullptr, dz, stream);
+  return latent_grad("latent_grad", e, z, labels, target_nchw, nullptr, 0, 0.f, nullptr, -1, 0.f, n, loss, nullptr, nullptr, nullptr, dz, stream);
 }
 extern "C" int jck_engine_latent_grad_ex(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
                                          int critic_mode, float critic_weight, int n, float* loss, float* term, float* logit, float* dz,
                                          void* stream) {
-  return latent_grad("latent_grad_ex", e, z, labels, target_nchw, weight, critic_mode, critic_weight, n, loss, term, logit, dz, stream);
+  return latent_grad("latent_grad_ex", e, z, labels, target_nchw, weight, critic_mode, critic_weight, nullptr, -1, 0.f, n, loss, term, logit,
+                     nullptr, dz, stream);
+}
+extern "C" int jck_engine_latent_grad_fm(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
+                                         int critic_mode, float critic_weight, int n, float* loss, float* term, float* logit, float* dz,
+                                         void* stream, const float* feat_target_nchw, int feat_stage, float feat_weight, float* fterm) {
+  return latent_grad("latent_grad_fm", e, z, labels, target_nchw, weight, critic_mode, critic_weight, feat_target_nchw, feat_stage, feat_weight,
+                     n, loss, term, logit, fterm, dz, stream);
 }
 extern "C" int jck_engine_project(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
                                   float prior, float* m, float* v, int t0, float* loss_hist, void* stream) {
-  return project("project", e, z, labels, target_nchw, n, steps, lr, prior, nullptr, 0, 0.f, m, v, t0, loss_hist, nullptr, stream);
+  return project("project", e, z, labels, target_nchw, n, steps, lr, prior, nullptr, 0, 0.f, nullptr, -1, 0.f, m, v, t0, loss_hist, nullptr,
+                 nullptr, stream);
 }
 extern "C" int jck_engine_project_ex(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
                                      float prior, const float* weight, int critic_mode, float critic_weight, float* m, float* v, int t0,
                                      float* loss_hist, float* term_hist, void* stream) {
-  return project("project_ex", e, z, labels, target_nchw, n, steps, lr, prior, weight, critic_mode, critic_weight, m, v, t0, loss_hist, term_hist,
-                 stream);
+  return project("project_ex", e, z, labels, target_nchw, n, steps, lr, prior, weight, critic_mode, critic_weight, nullptr, -1, 0.f, m, v, t0,
+                 loss_hist, term_hist, nullptr, stream);
+}
+extern "C" int jck_engine_project_fm(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
+                                     float prior, const float* weight, int critic_mode, float critic_weight, float* m, float* v, int t0,
+                                     float* loss_hist, float* term_hist, void* stream, const float* feat_target_nchw, int feat_stage,
+                                     float feat_weight, float* fterm_hist) {
+  return project("project_fm", e, z, labels, target_nchw, n, steps, lr, prior, weight, critic_mode, critic_weight, feat_target_nchw, feat_stage,
+                 feat_weight, m, v, t0, loss_hist, term_hist, fterm_hist, stream);
 }

@@ -194,7 +194,10 @@ struct jck_engine {
     void *g[JCK_MAX_STAGES] = {}, *gx = nullptr, *g_h = nullptr, *gc = nullptr;
     float *ds = nullptr, *term = nullptr, *logit = nullptr;
   } cr;
-  bool d_packed = false;                // D's operands were derived from its parameters at least once (jck_engine_repack, a D step)
+  // the feature-matching term (jck_engine_latent_grad_fm / jck_engine_project_fm with a feature target): the target's activation at the
+  // chosen stage, with room for the largest stage (stage 0), and a row for the term - one allocation made by the first such call
+  void* fm_fa = nullptr; float* fm_term = nullptr;
+  bool d_packed = false;               // D's operands were derived from its parameters at least once (jck_engine_repack, a D step)
 
   void carve(unsigned char* base) {
     jck_engine* e = this;

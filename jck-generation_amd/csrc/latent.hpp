@@ -113,6 +113,44 @@ __global__ void leaky_affine_bwd_kernel(const T* g, const T* __restrict__ a, con
   }
 }
 
+// Feature matching on a folded eval-mode stage a = leaky(scale[c] * y + shift[c]): the squared distance between the generated image's
+// activation a and a fixed feature f of the same stage, its gradient and the stage's backward in one pass.  One workgroup per image
+// (M elements, NHWC, a multiple of C; C a power of two >= 8), 8 channels per access; thread i takes groups i, i + 256, ... in that
+// order and the 256 partial sums are added in the fixed tree: the same bits on every run, and image b does not depend on N.
+// d = a - f, s += d^2, t = scale[c] * (kg * d) with kg = 2 weight / M, g = a > 0 ? t : t * slope (ATen's leaky_relu_backward on the
+// generated image's own activation: a = +-0 and NaN take the slope); ACC: g_y = g_y + g (the old value read in T, the sum in fp32, one
+// rounding), else g_y = g.  fterm[b] = (weight / M) * s.
+template <typename T, bool ACC>
+__global__ __launch_bounds__(256) void feat_match_kernel(const T* __restrict__ a, const T* __restrict__ f, const float* __restrict__ scale,
+                                                         float slope, float weight, T* g_y, float* __restrict__ fterm, long long M, int C) {
+  __shared__ float sm[4];
+  const int b = blockIdx.x;
+  const T* ab = a + (long long)b * M;
+  const T* fb = f + (long long)b * M;
+  T* gb = g_y + (long long)b * M;
+  const float wm = weight / (float)M, kg = 2.0f * wm;
+  float s = 0.f;
+  for (long long i = threadIdx.x; i < M / 8; i += 256) {
+    const int c = (int)((i * 8) & (C - 1));
+    float av[8], fv[8], g[8];
+    ld8(ab + i * 8, av);
+    ld8(fb + i * 8, fv);
+    if (ACC) ld8(gb + i * 8, g);
+    const f32x4 s0 = *reinterpret_cast<const f32x4*>(scale + c), s1 = *reinterpret_cast<const f32x4*>(scale + c + 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = av[j] - fv[j];
+      s = fmaf(d, d, s);
+      const float t = (j < 4 ? s0[j] : s1[j - 4]) * (kg * d);
+      const float v = av[j] > 0.f ? t : t * slope;
+      g[j] = ACC ? g[j] + v : v;
+    }
+    st8(gb + i * 8, g);
+  }
+  s = block_sum256(s, sm);
+  if (threadIdx.x == 0) fterm[b] = wm * s;
+}
+
 // The critic's objective on a logit, one thread per row: ds[b] = lambda c'(logit), term[b] = lambda c(logit).
 // mode 1 (nsgan): c = softplus(-logit) = -log sigmoid(logit), the generator's own training loss, c' = -sigmoid(-logit), both from
 // e = exp(-|logit|) <= 1 (no overflow at any logit).  mode 2 (logit): c = -logit, c' = -1.  A non-finite logit: NaN in both.

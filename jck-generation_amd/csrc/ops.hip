@@ -43,7 +43,8 @@ static constexpr KernelInfo KERNELS[] = {
     SAME("wgrad<bf16x3,128,128>"), SAME("wgrad<bf16x3,128,64>"), SAME("wgrad<bf16x3,64,64,img>"), SAME("wgrad<bf16x3,64,64>"),
     {nullptr, "bn_act_fwd"}, {nullptr, "bn_bwd_resident"}, {nullptr, "bn_bwd_3launch"},
     {nullptr, "latent_loss"}, {nullptr, "latent_adam"},
-    {nullptr, "conv_up_mask"}, {nullptr, "leaky_affine_bwd"}, {nullptr, "critic_ds"}, {nullptr, "latent_loss_ex"}};
+    {nullptr, "conv_up_mask"}, {nullptr, "leaky_affine_bwd"}, {nullptr, "critic_ds"}, {nullptr, "latent_loss_ex"},
+    {nullptr, "feat_match"}};
 #undef SAME
 static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "KERNELS and the KernelId offsets disagree");
 // the id arithmetic against the table, row by row: what every launch site's id resolves to (the affine 16 x 256 form with 8..32 gathered
@@ -61,7 +62,7 @@ static_assert(row(kid_igemm<PrecBf16, 128, 128, 1>(), "igemm<bf16,128,128>", "ig
               row(kid_wgrad<PrecBf16x3, 128, 128, 1>(), "wgrad<bf16x3,128,128>", "wgrad<bf16x3,128,128>") && row(kid_wgrad<PrecBf16x3, 128, 64, 1>(), "wgrad<bf16x3,128,64>", "wgrad<bf16x3,128,64>") && row(kid_wgrad<PrecBf16x3, 64, 64, 2>(), "wgrad<bf16x3,64,64,img>", "wgrad<bf16x3,64,64,img>") && row(kid_wgrad<PrecBf16x3, 64, 64, 1>(), "wgrad<bf16x3,64,64>", "wgrad<bf16x3,64,64>") &&
               same_str(KERNELS[K_LATENT_LOSS].label, "latent_loss") && same_str(KERNELS[K_LATENT_ADAM].label, "latent_adam") &&
               same_str(KERNELS[K_CONV_UP_MASK].label, "conv_up_mask") && same_str(KERNELS[K_LEAKY_AFFINE_BWD].label, "leaky_affine_bwd") &&
-              same_str(KERNELS[K_CRITIC_DS].label, "critic_ds") && same_str(KERNELS[K_LATENT_LOSS_EX].label, "latent_loss_ex") &&
+              same_str(KERNELS[K_CRITIC_DS].label, "critic_ds") && same_str(KERNELS[K_LATENT_LOSS_EX].label, "latent_loss_ex") && same_str(KERNELS[K_FEAT_MATCH].label, "feat_match") &&
               same_str(KERNELS[K_BN_ACT_FWD].label, "bn_act_fwd") && same_str(KERNELS[K_BN_BWD_RES].label, "bn_bwd_resident") && same_str(KERNELS[K_BN_BWD_3L].label, "bn_bwd_3launch") &&
               kid_igemm<PrecBf16, 16, 256, 0>() == kid_igemm<PrecBf16, 16, 256, 1>() && !KERNELS[K_IGEMM + 3].launch,
               "KERNELS and the kid_* functions disagree");
@@ -823,6 +824,29 @@ extern "C" int jck_leaky_affine_bwd(int prec, const void* g, const void* a, cons
   ProfScope prof(K_LEAKY_AFFINE_BWD, 0.0, (hipStream_t)stream, (double)rows * C * 3.0 * (prec_f32_storage(prec) ? 4 : 2));
   DISPATCH_T(prec, hipLaunchKernelGGL(leaky_affine_bwd_kernel<T>, dim3(ew_grid(total8)), dim3(256), 0, (hipStream_t)stream, (const T*)g, (const T*)a,
                                       scale, slope, (T*)g_y, total8, C));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// fterm[b] = weight / M * sum (a_b - f_b)^2 over image b's M elements, and g = the gradient of that term through the folded stage
+// a = leaky(scale[c] y + shift[c]): 2 weight / M * (a - f) * scale[c], times slope where a is not > 0; g_y = g, or g_y + g (accumulate)
+extern "C" int jck_feat_match(int prec, const void* a, const void* f, const float* scale, float slope, float weight, void* g_y, int accumulate,
+                              float* fterm, int N, long long M, int C, void* stream) {
+  if (prec != JCK_PREC_BF16 && !prec_f32_storage(prec)) JCK_FAIL(JCK_E_ARG, "feat_match: bad prec");
+  if (!a || !f || !scale || !g_y || !fterm || N < 1) JCK_FAIL(JCK_E_ARG, "feat_match: null tensor or no images");
+  if (!is_pow2(C) || C < 8) JCK_FAIL(JCK_E_ARG, "feat_match: C must be a power of two >= 8");
+  if (M < C || M % C) JCK_FAIL(JCK_E_ARG, "feat_match: M must be a positive multiple of C");
+  if (!(weight >= 0.f) || !(weight <= 3.402823466e38f)) JCK_FAIL(JCK_E_ARG, "feat_match: weight must be finite and >= 0");
+  if (accumulate != 0 && accumulate != 1) JCK_FAIL(JCK_E_ARG, "feat_match: accumulate must be 0 or 1");
+  if ((((uintptr_t)a | (uintptr_t)f | (uintptr_t)g_y | (uintptr_t)scale) & 15) != 0) JCK_FAIL(JCK_E_ARG, "feat_match: tensors and scale must be 16-byte aligned");
+  const hipStream_t st = (hipStream_t)stream;
+  ProfScope prof(K_FEAT_MATCH, 0.0, st, (double)N * M * (accumulate ? 4.0 : 3.0) * (prec_f32_storage(prec) ? 4 : 2));
+  if (accumulate) {
+    DISPATCH_T(prec, hipLaunchKernelGGL((feat_match_kernel<T, true>), dim3(N), dim3(256), 0, st, (const T*)a, (const T*)f, scale, slope, weight,
+                                        (T*)g_y, fterm, M, C));
+  } else {
+    DISPATCH_T(prec, hipLaunchKernelGGL((feat_match_kernel<T, false>), dim3(N), dim3(256), 0, st, (const T*)a, (const T*)f, scale, slope, weight,
+                                        (T*)g_y, fterm, M, C));
+  }
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }

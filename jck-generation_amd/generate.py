@@ -12,6 +12,8 @@
     python generate.py -m DCGAN --checkpoint best.pt --features train.npz --out feats
     python generate.py -m DCGAN --checkpoint best.pt --probe train.npz --probe_test test.npz --k 5 --out probe
     python generate.py -m DCGAN --checkpoint best.pt --num 64 --neighbours train.npz --space d --out samples
+    python generate.py -m DCGAN --checkpoint best.pt --project samples/images.npz --project_feature_weight 10 --out perceptual
+    python generate.py -m DCGAN --checkpoint best.pt --anomaly queries.npz --anomaly_lam 0.1 --out anomaly
 
 Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
 BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
@@ -43,7 +45,15 @@ activation of the file's pictures (the discriminator's size, or 32x32 data, upsc
 col0, C, H; grid; pool; labels if the file has them) for an external classifier.  --probe TRAIN.npz --probe_test TEST.npz (both with
 `labels`) classifies every test picture by the majority of its --k (default 5) nearest training pictures in block-normalised feature
 space and writes <out>/probe.json (accuracy, per_class, k, train, test, F, grid, pool).  --neighbours REF.npz --space d looks the
-samples' neighbours up in that feature space instead of pixel space: neighbours.npz then holds idx, d2, ref_nn_d2 and copy, no rmse."""
+samples' neighbours up in that feature space instead of pixel space: neighbours.npz then holds idx, d2, ref_nn_d2 and copy, no rmse.
+--project_feature_weight W (with --project) adds W times the mean squared distance between the discriminator's deepest-stage activations
+of G(z) and of the picture to the projection's objective (perceptual projection; needs `model_d`).
+--anomaly FILE.npz scores the file's pictures after AnoGAN (Schlegl et al. 2017; Sampler.anomaly): each is projected (--project_steps,
+--project_lr) with a residual term and a feature-matching term on the discriminator's stage --anomaly_stage (default: the deepest),
+and score = (1 - lam) residual + lam feature at the z reached (--anomaly_lam, default 0.1) - mean squared forms, not the paper's L1
+sums.  <out>/anomaly.npz holds z, residual, feature, score, generated (G(z), uint8) and order (indices by falling score);
+<out>/anomaly.png has one row per picture: input, G(z), |input - G(z)|; <out>/anomaly.json (auroc, n, anomalous, lam, stage) is written
+when the file carries a bool `anomalous` [n] array."""
 import argparse
 import os
 import sys
@@ -87,6 +97,11 @@ def get_arg_parse(argv=None):
     p.add_argument("--critic_weight", type=float, default=None, metavar="W", help="with --inpaint: weight of -log D(G(z)) (default 0.003; 0: no critic)")
     p.add_argument("--refine", type=int, default=None, metavar="STEPS", help="Adam updates of every latent along the discriminator's gradient")
     p.add_argument("--refine_lr", type=float, default=None, metavar="LR", help="with --refine (default 0.02)")
+    p.add_argument("--project_feature_weight", type=float, default=None, metavar="W",
+                   help="with --project: weight of the feature-matching term on the discriminator's deepest stage")
+    p.add_argument("--anomaly", default=None, metavar="FILE.npz", help="AnoGAN anomaly scores of the uint8 [n,S,S,3] `images` array of this file")
+    p.add_argument("--anomaly_lam", type=float, default=None, metavar="LAM", help="with --anomaly: weight of the feature term in the score, in [0, 1) (default 0.1)")
+    p.add_argument("--anomaly_stage", type=int, default=None, metavar="K", help="with --anomaly: the discriminator stage matched (default: the deepest)")
     p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     p.add_argument("--out", required=True, help="output directory")
     a = p.parse_args(argv)
@@ -139,6 +154,21 @@ def get_arg_parse(argv=None):
         p.error("--critic_weight must be >= 0")
     if a.inpaint and a.critic_weight is None:
         a.critic_weight = 0.003
+    if a.project_feature_weight is not None and not a.project:
+        p.error("--project_feature_weight goes with --project")
+    if a.project_feature_weight is not None and not 0 <= a.project_feature_weight < float("inf"):
+        p.error("--project_feature_weight must be finite and >= 0")
+    if a.anomaly and (a.project or a.inpaint or a.interpolate or a.select or a.score or a.score_images or a.neighbours or a.features or a.probe or
+                      a.num is not None or a.truncation is not None or a.refine is not None):
+        p.error("--anomaly takes its images from the file; the sampling, projection, inpainting, scoring and feature options do not go with it")
+    if (a.anomaly_lam is not None or a.anomaly_stage is not None) and not a.anomaly:
+        p.error("--anomaly_lam and --anomaly_stage go with --anomaly")
+    if a.anomaly_lam is not None and not 0 <= a.anomaly_lam < 1:
+        p.error("--anomaly_lam must lie in [0, 1)")
+    if a.anomaly_stage is not None and not -1 <= a.anomaly_stage <= 4:
+        p.error("--anomaly_stage must be -1 (the deepest) or a stage of the discriminator")
+    if a.anomaly and a.anomaly_lam is None:
+        a.anomaly_lam = 0.1
     if a.refine_lr is not None and a.refine is None:
         p.error("--refine_lr goes with --refine")
     if a.refine is not None:
@@ -181,7 +211,7 @@ def parse_interpolate(s):
 
 def needs_discriminator(args):
     return bool(args.score or args.select or args.score_images or args.refine is not None or (args.inpaint and args.critic_weight > 0) or
-                args.features or args.probe or args.space == "d")
+                args.features or args.probe or args.space == "d" or args.anomaly or (args.project_feature_weight or 0) > 0)
 
 
 def check_checkpoint(args, ckpt):
@@ -265,6 +295,8 @@ def main(argv=None):
     job = None
     if args.inpaint:                      # ... and so does a bad picture file or mask
         job = plan_inpaint(args)
+    if args.anomaly:                      # ... or an anomaly run's file
+        job = plan_anomaly(args)
     if args.features or args.probe:       # ... or a feature run's file without pictures, a probe's without labels
         from hipgan.probe import load_images
         job = [load_images(f, need_labels=bool(args.probe)) for f in ((args.features,) if args.features else (args.probe, args.probe_test))]
@@ -279,6 +311,8 @@ def main(argv=None):
         return project_main(args, s)
     if args.inpaint:
         return inpaint_main(args, s, job)
+    if args.anomaly:
+        return anomaly_main(args, s, job)
     if args.features:
         return features_main(args, s, job)
     if args.probe:
@@ -447,10 +481,63 @@ def inpaint_main(args, s, job):
     return 0
 
 
+def plan_anomaly(args):
+    """(pictures uint8 [n,S,S,3], class ids [n] or None, anomalous bool [n] or None) of an --anomaly run; JckError for a bad file"""
+    from hipgan._lib import JckError
+    from hipgan.sampler import load_projection_targets
+    u8, labels = load_projection_targets(args.anomaly)
+    n = u8.shape[0]
+    with np.load(args.anomaly) as f:
+        flags = f["anomalous"] if "anomalous" in f.files else None
+    if flags is not None and (flags.dtype != np.bool_ or flags.shape != (n,)):
+        raise JckError(f"{args.anomaly}: 'anomalous' must be bool [{n}], got {flags.dtype} {tuple(flags.shape)}")
+    cls = None
+    if args.model == "CGAN":
+        if args.classes:
+            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(n)])
+        elif labels is not None:
+            cls = labels.to(torch.int64).view(-1)
+        else:
+            raise JckError(f"{args.anomaly} has no 'labels' array: a CGAN needs it, or --classes")
+    return u8, cls, flags
+
+
+def anomaly_main(args, s, job):
+    """--anomaly: AnoGAN scores of a file's pictures -> <out>/anomaly.npz, anomaly.png, anomaly.json (with flags) and one line"""
+    import json
+    from hipgan.anomaly import auroc
+    from train.gan_trainer import _encode_png
+    u8, cls, flags = job
+    r = s.anomaly(u8, cls, steps=args.project_steps, lr=args.project_lr, lam=args.anomaly_lam, stage=args.anomaly_stage, seed=args.seed)
+    gen, score = r["generated"].cpu().numpy(), r["score"].cpu().numpy()
+    order = np.argsort(-score, kind="stable").astype(np.int64)
+    os.makedirs(args.out, exist_ok=True)
+    arrays = {"z": r["z"].cpu().numpy(), "residual": r["residual"].cpu().numpy(), "feature": r["feature"].cpu().numpy(), "score": score,
+              "generated": gen, "order": order}
+    if cls is not None:
+        arrays["labels"] = cls.numpy().astype(np.int64)
+    np.savez(os.path.join(args.out, "anomaly.npz"), **arrays)
+    diff = np.abs(u8.numpy().astype(np.int16) - gen.astype(np.int16)).astype(np.uint8)
+    rows = np.stack([u8.numpy(), gen, diff], axis=1).reshape((-1,) + gen.shape[1:])      # one row per picture: input, G(z), |input - G(z)|
+    with open(os.path.join(args.out, "anomaly.png"), "wb") as f:
+        f.write(_encode_png(grid_u8(rows, 3)))
+    tail = ""
+    if flags is not None:
+        res = {"auroc": auroc(score, flags), "n": int(u8.shape[0]), "anomalous": int(flags.sum()), "lam": args.anomaly_lam,
+               "stage": args.anomaly_stage}
+        with open(os.path.join(args.out, "anomaly.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        tail = f", AUROC {res['auroc']:.4f} -> anomaly.json"
+    print(f"{gen.shape[0]} images scored ({s.which} generator, {args.project_steps} steps, lam {args.anomaly_lam}, mean score "
+          f"{float(score.mean()):.5f}) -> {args.out}/anomaly.npz, anomaly.png{tail}")
+    return 0
+
+
 def project_main(args, s):
     from train.gan_trainer import _encode_png
     targets, z0, cls, per_row = plan_project(args)
-    z, loss = s.project(targets, cls, steps=args.project_steps, lr=args.project_lr, prior=args.project_prior, z0=z0)
+    feat = {"feature_weight": args.project_feature_weight} if (args.project_feature_weight or 0) > 0 else {}
+    z, loss = s.project(targets, cls, steps=args.project_steps, lr=args.project_lr, prior=args.project_prior, z0=z0, **feat)
     recon = s.from_latents(z, cls, bn="running", out="uint8").cpu().numpy()
     os.makedirs(args.out, exist_ok=True)
     arrays = {"z": z.cpu().numpy(), "loss": loss.cpu().numpy(), "images": recon}

@@ -44,6 +44,7 @@ PROTOS = {
     "jck_leaky_affine_bwd": (i32, [i32, vp, vp, vp, f32, vp, i64, i32, vp]),
     "jck_critic_ds": (i32, [vp, i32, f32, i32, vp, vp, vp]),
     "jck_latent_loss_ex": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "jck_feat_match": (i32, [i32, vp, vp, vp, f32, f32, vp, i32, vp, i32, i64, i32, vp]),
     "jck_score_head": (i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "jck_grid_pool": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i64, i64, vp]),
     "jck_latent_loss": (i32, [i32, vp, vp, vp, vp, i32, i32, vp]),
@@ -135,6 +136,8 @@ PROTOS = {
     "jck_engine_project": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, i32, vp, vp]),
     "jck_engine_latent_grad_ex": (i32, [vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp]),
     "jck_engine_project_ex": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, i32, f32, vp, vp, i32, vp, vp, vp]),
+    "jck_engine_latent_grad_fm": (i32, [vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, i32, f32, vp]),
+    "jck_engine_project_fm": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp, i32, f32, vp]),
     "jck_engine_score": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "jck_engine_feature_dim": (i64, [vp, i32]),
     "jck_engine_features": (i32, [vp, vp, i32, i32, i32, vp, i64, vp]),

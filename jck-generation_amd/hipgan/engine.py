@@ -884,24 +884,64 @@ class DcganEngine:
             self._score_ready(what)
         return w, mode, cw
 
-    def latent_grad(self, z, target, labels=None, weight=None, critic=None, critic_weight=0.0):
+    def _feat_args(self, what, n, feature_target, feature_weight, feature_stage):
+        """(feature target fp32 NCHW [n,3,S,S] on the device or None, stage -1 .. NS-1, weight) of an _fm call, validated on the host;
+        the term is on iff the target is given and the weight positive"""
+        fw = float(feature_weight)
+        if not (fw >= 0.0 and fw < float("inf")):
+            raise JckError(f"{what}: feature_weight must be finite and >= 0, got {feature_weight}")
+        if fw > 0.0 and feature_target is None:
+            raise JckError(f"{what}: feature_weight > 0 needs a feature_target")
+        from .probe import feature_layout
+        ns = len(feature_layout(self.size, 1)[0])
+        k = -1 if feature_stage is None else int(feature_stage)
+        if not -1 <= k < ns:
+            raise JckError(f"{what}: feature_stage must be None / -1 (the deepest) or 0..{ns - 1}, got {feature_stage!r}")
+        if feature_target is None or fw == 0.0:
+            return None, k, 0.0
+        from .sampler import images_to_target
+        x = images_to_target(feature_target)
+        if tuple(x.shape) != (n, 3, self.size, self.size):
+            raise JckError(f"{what}: feature_target must be {n} images of {self.size}x{self.size}, got {tuple(x.shape)}")
+        self._score_ready(what)
+        return x.to(self.device, torch.float32).contiguous(), k, fw
+
+    def latent_grad(self, z, target, labels=None, weight=None, critic=None, critic_weight=0.0, feature_target=None, feature_weight=0.0,
+                    feature_stage=None):
         """(loss [n], dz [n,100]): L_b = mean((G(z_b) - target_b)^2) and dL_b/dz_b through the generator as under model.eval()
         (BatchNorm on the running statistics; nothing is written to them).  target: fp32 NCHW [n,3,S,S] in [-1, 1].  Any n: rows
         go through in chunks of at most `batch`, each row's numbers those of a call with that row alone.
         weight ([S,S] or [n,S,S], >= 0): L_b becomes the weighted mean sum_p w_p sum_c (.)^2 / (3 sum_p w_p).  critic ("nsgan" |
         "logit") with critic_weight: the eval-mode discriminator's term critic_weight * c(D(G(z_b))) joins the objective, dz is the
-        gradient of the sum and the result is (loss, term [n], logit [n], dz)."""
-        t = self._target("latent_grad", z.shape[0], target)
+        gradient of the sum and the result is (loss, term [n], logit [n], dz).
+        feature_target (fp32 NCHW or uint8 NHWC images) with feature_weight > 0: the feature-matching term F_b = feature_weight *
+        mean((a_k(G(z_b)) - a_k(x_b))^2) on the LeakyReLU output of D's conv stage k = feature_stage (None / -1: the deepest) joins
+        the objective, target may be None, and the result is the dict {"loss", "term", "logit", "fterm", "dz"} (term 0 and logit NaN
+        without a critic)."""
         n, zc, lab = self._latents("latent_grad", z, labels)
+        fx, fk, fw = self._feat_args("latent_grad", n, feature_target, feature_weight, feature_stage)
+        if target is None and fx is not None:
+            t = None
+            self.join()
+        else:
+            t = self._target("latent_grad", z.shape[0], target)
         w, mode, cw = self._critic_args("latent_grad", n, weight, critic, critic_weight)
         loss = torch.empty(n, dtype=torch.float32, device=self.device)
         dz = torch.empty(n, 100, dtype=torch.float32, device=self.device)
         term, logit = torch.zeros_like(loss), torch.full_like(loss, float("nan"))
+        if fx is None:
+            for lo, hi in chunk_plan(n, self.batch):
+                lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], _rows(lab, lo, hi), t[lo:hi], _rows(w, lo, hi), mode, cw, hi - lo, loss[lo:hi],
+                                              term[lo:hi] if mode else None, logit[lo:hi] if mode else None, dz[lo:hi], cur_stream())
+            self._keep_z = (zc, lab, t, w)
+            return (loss, term, logit, dz) if mode else (loss, dz)
+        fterm = torch.empty_like(loss)
         for lo, hi in chunk_plan(n, self.batch):
-            lib.jck_engine_latent_grad_ex(self._h, zc[lo:hi], _rows(lab, lo, hi), t[lo:hi], _rows(w, lo, hi), mode, cw, hi - lo, loss[lo:hi],
-                                          term[lo:hi] if mode else None, logit[lo:hi] if mode else None, dz[lo:hi], cur_stream())
-        self._keep_z = (zc, lab, t, w)
-        return (loss, term, logit, dz) if mode else (loss, dz)
+            lib.jck_engine_latent_grad_fm(self._h, zc[lo:hi], _rows(lab, lo, hi), _rows(t, lo, hi), _rows(w, lo, hi), mode, cw, hi - lo,
+                                          loss[lo:hi], term[lo:hi] if mode else None, logit[lo:hi] if mode else None, dz[lo:hi],
+                                          cur_stream(), fx[lo:hi], fk, fw, fterm[lo:hi])
+        self._keep_z = (zc, lab, t, w, fx)
+        return {"loss": loss, "term": term, "logit": logit, "fterm": fterm, "dz": dz}
 
     def critic_grad(self, z, labels=None, mode="nsgan"):
         """(logit [n], term [n], dz [n,100]): D(G(z)), both networks as under model.eval(), the critic's objective c of it - "nsgan":
@@ -919,7 +959,7 @@ class DcganEngine:
         return logit, term, dz
 
     def project(self, target, labels=None, steps=200, lr=0.05, prior=0.0, z0=None, seed=0, state=None, weight=None, critic=None,
-                critic_weight=0.0):
+                critic_weight=0.0, feature_target=None, feature_weight=0.0, feature_stage=None):
         """Fits z to `target` (fp32 NCHW [n,3,S,S] in [-1, 1]) through the frozen eval-mode generator: `steps` Adam updates
         (lr, betas (0.9, 0.999)) of z minimising mean((G(z) - target)^2) + prior * mean(z^2) per image, all on the device.
         -> (z [n,100], loss_hist [steps,n]: the loss before each update).  z0: the start (default: randn from `seed` on the host);
@@ -927,7 +967,9 @@ class DcganEngine:
         Any n (chunks of at most `batch` rows; a row's result does not depend on the rows beside it).
         weight / critic / critic_weight: the objective of latent_grad with the same keywords (masked projection: weight 0 on the
         unknown pixels); the critic's term before each update is left in `self.project_term` [steps,n].
-        target None (refinement): the critic's term alone."""
+        target None (refinement): the critic's term alone.
+        feature_target / feature_weight / feature_stage: latent_grad's feature-matching term; it before each update is left in
+        `self.project_fterm` [steps,n] (None without the term).  With it the target may be None as well."""
         if target is None and z0 is None:
             raise JckError("project: without a target the start z0 is required")
         n = (z0 if target is None else target).shape[0]
@@ -941,7 +983,8 @@ class DcganEngine:
             t, lab = None, self._score_labels("project", labels, n)
         else:
             t, lab = self._target("project", n, target), self._score_labels("project", labels, n)
-        w, mode, cw = self._critic_args("project", n, weight, critic, critic_weight, target is not None)
+        fx, fk, fw = self._feat_args("project", n, feature_target, feature_weight, feature_stage)
+        w, mode, cw = self._critic_args("project", n, weight, critic, critic_weight, target is not None or fx is not None)
         if z0 is None:
             z0 = torch.randn(n, 100, generator=torch.Generator().manual_seed(int(seed)))
         if tuple(z0.shape) != (n, 100):
@@ -956,17 +999,25 @@ class DcganEngine:
         hist = torch.empty(int(steps), n, dtype=torch.float32, device=self.device)
         plain = weight is None and critic is None and target is not None
         terms = None if plain else torch.zeros(int(steps), n, dtype=torch.float32, device=self.device)
+        fterms = None if fx is None else torch.empty(int(steps), n, dtype=torch.float32, device=self.device)
         for lo, hi in chunk_plan(n, self.batch):
             h = torch.empty(int(steps), hi - lo, dtype=torch.float32, device=self.device)
             th = torch.empty_like(h) if mode else None
-            lib.jck_engine_project_ex(self._h, z[lo:hi], _rows(lab, lo, hi), _rows(t, lo, hi), hi - lo, int(steps), float(lr), float(prior),
-                                      _rows(w, lo, hi), mode, cw, m[lo:hi], v[lo:hi], t0, h, th, cur_stream())
+            if fx is None:
+                lib.jck_engine_project_ex(self._h, z[lo:hi], _rows(lab, lo, hi), _rows(t, lo, hi), hi - lo, int(steps), float(lr), float(prior),
+                                          _rows(w, lo, hi), mode, cw, m[lo:hi], v[lo:hi], t0, h, th, cur_stream())
+            else:
+                fh = torch.empty_like(h)
+                lib.jck_engine_project_fm(self._h, z[lo:hi], _rows(lab, lo, hi), _rows(t, lo, hi), hi - lo, int(steps), float(lr), float(prior),
+                                          _rows(w, lo, hi), mode, cw, m[lo:hi], v[lo:hi], t0, h, th, cur_stream(), fx[lo:hi], fk, fw, fh)
+                fterms[:, lo:hi] = fh
             if mode:
                 terms[:, lo:hi] = th
             hist[:, lo:hi] = h
-        self._keep_z = (z, lab, t, w)
+        self._keep_z = (z, lab, t, w, fx)
         self.project_state = {"m": m, "v": v, "t": t0 + int(steps)}
         self.project_term = terms
+        self.project_fterm = fterms
         return z, hist
 
     def refine(self, z, labels=None, steps=10, lr=0.02, mode="logit", prior=0.0):

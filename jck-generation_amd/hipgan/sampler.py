@@ -321,13 +321,22 @@ class Sampler:
     def interpolate(self, z0, z1, steps, labels=None, bn="running", out="uint8"):
         return self.from_latents(slerp(z0.reshape(NZ), z1.reshape(NZ), steps).float(), labels, bn, out)
 
-    def project(self, images, labels=None, steps=200, lr=0.05, prior=0.0, seed=0, restarts=1, z0=None):
+    def project(self, images, labels=None, steps=200, lr=0.05, prior=0.0, seed=0, restarts=1, z0=None, feature_weight=0.0,
+                feature_stage=None):
         """The latent z whose image is closest to each of `images` (uint8 NHWC [n,S,S,3] or fp32 NCHW in [-1, 1]): `steps` Adam
         updates through the frozen eval-mode generator (DcganEngine.project) -> (z [n,100], final loss [n]: mean squared error of
         G(z) at the returned z).  restarts=R starts every image from R seeds (seed, seed + 1, ...; run as extra rows) and keeps
-        the start that ends lowest."""
+        the start that ends lowest.
+        feature_weight > 0 (perceptual projection; needs from_checkpoint(..., with_d=True)): feature_weight * the mean squared
+        distance between the discriminator's stage-`feature_stage` activations (None: the deepest) of G(z) and of the image joins
+        the objective (DcganEngine.project(feature_target=images)); the loss returned and compared stays the pixel error."""
         t = images_to_target(images)
         n, R = t.shape[0], int(restarts)
+        fw = float(feature_weight)
+        if not (fw >= 0.0 and fw < float("inf")):
+            raise JckError(f"project: feature_weight must be finite and >= 0, got {feature_weight}")
+        if fw > 0.0:
+            self._needs_d("project(feature_weight > 0)")
         if t.shape[2] != self.engine.size:
             raise JckError(f"images are {t.shape[2]}x{t.shape[2]}, the generator makes {self.engine.size}x{self.engine.size}")
         if R < 1:
@@ -340,7 +349,8 @@ class Sampler:
         ll = None if lab is None else lab.repeat(R, 1)
         if z0 is None:
             z0 = torch.cat([latents(n, int(seed) + r) for r in range(R)])
-        z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, prior=prior, z0=z0.reshape(-1, NZ))
+        feat = dict(feature_target=tt, feature_weight=fw, feature_stage=feature_stage) if fw > 0.0 else {}
+        z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, prior=prior, z0=z0.reshape(-1, NZ), **feat)
         loss, _ = self.engine.latent_grad(z, tt, ll)
         if R > 1:
             best = loss.view(R, n).argmin(0)                            # ties: the lowest seed
@@ -402,6 +412,51 @@ class Sampler:
             z, loss, term = z[pick], loss[pick], term[pick]
         gen = self.engine.sample(z, lab, bn="running", out="uint8")
         return {"z": z, "loss": loss, "term": term, "generated": gen, "completed": blend(x.to(gen.device), gen, k)}
+
+    def anomaly(self, images, labels=None, steps=300, lr=0.05, lam=0.1, stage=None, restarts=1, seed=0):
+        """Anomaly scores after AnoGAN (Schlegl et al. 2017): every image (uint8 NHWC [n,S,S,3] or fp32 NCHW in [-1, 1]) is projected
+        onto the generator with a residual term R = L (the mean squared pixel error) and a feature-matching term D = F_unit (the mean
+        squared distance between the discriminator's stage-`stage` activations of G(z) and of the image; None: the deepest stage),
+        and scored by what remains: score = (1 - lam) R + lam D (hipgan.anomaly.anomaly_score).  `steps` Adam updates minimise
+        L + lam / (1 - lam) * F_unit, which has the minimiser of (1 - lam) R + lam D; one more evaluation at the final z gives the
+        numbers.  -> {"z" [n,100], "residual" [n] = L, "feature" [n] = F / feat_weight, "score" [n] (fp64), "generated" uint8 = G(z)}.
+        restarts=R: R seeds per image (seed, seed + 1, ...), the one ending at the lowest score kept.
+        R and D here are the mean squared forms of this code base's losses, not AnoGAN's L1 sums, so scores are not comparable with
+        the paper's numbers; and whether the discriminator's features separate anything is a property of the run that trained it.
+        Needs from_checkpoint(..., with_d=True)."""
+        from .anomaly import anomaly_score
+        t = images_to_target(images)
+        n, R = t.shape[0], int(restarts)
+        lam = float(lam)
+        if not 0.0 <= lam < 1.0:
+            raise JckError(f"anomaly: lam must lie in [0, 1), got {lam}")
+        if R < 1:
+            raise JckError(f"anomaly: restarts must be >= 1, got {restarts}")
+        self._needs_d("anomaly")
+        if t.shape[2] != self.engine.size:
+            raise JckError(f"images are {t.shape[2]}x{t.shape[2]}, the generator makes {self.engine.size}x{self.engine.size}")
+        lab = self._labels(labels, n)
+        t = t.to(self.engine.device)
+        tt = t.repeat(R, 1, 1, 1) if R > 1 else t
+        ll = lab if lab is None or R == 1 else lab.repeat(R, 1)
+        z0 = torch.cat([latents(n, int(seed) + r) for r in range(R)])
+        fw = lam / (1.0 - lam)
+        if fw > 0.0:
+            feat = dict(feature_target=tt, feature_weight=fw, feature_stage=stage)
+            z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, z0=z0, **feat)
+            res = self.engine.latent_grad(z, tt, ll, **feat)
+            residual, feature = res["loss"], res["fterm"] / fw
+        else:                                                            # lam = 0: the residual alone decides; D is still reported
+            z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, z0=z0)
+            residual = self.engine.latent_grad(z, tt, ll)[0]
+            feature = self.engine.latent_grad(z, tt, ll, feature_target=tt, feature_weight=1.0, feature_stage=stage)["fterm"]
+        score = anomaly_score(residual, feature, lam)
+        if R > 1:
+            best = score.view(R, n).argmin(0)                           # ties: the lowest seed
+            pick = best * n + torch.arange(n, device=best.device)
+            z, residual, feature, score = z[pick], residual[pick], feature[pick], score[pick]
+        gen = self.engine.sample(z, lab, bn="running", out="uint8")
+        return {"z": z, "residual": residual, "feature": feature, "score": score, "generated": gen}
 
     def neighbours(self, images, ref, k=4, space="pixel", grid=4, pool="max", normalise="block", **kw):
         """The k nearest reference (training) images of `images`, both uint8 NHWC, and the `copy` flags, on this sampler's device.
