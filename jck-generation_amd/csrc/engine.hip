@@ -156,10 +156,7 @@ extern "C" int jck_engine_create_ex(jck_engine** out, int family, int prec, int 
 extern "C" void jck_engine_destroy(jck_engine* e) {
   if (!e) return;
   if (e->overlap) destroy_side_streams(e, true);
-  if (e->lat_w) (void)hipFree(e->lat_w);
-  if (e->sc.base) (void)hipFree(e->sc.base);
-  if (e->cr.base) (void)hipFree(e->cr.base);
-  if (e->fm_fa) (void)hipFree(e->fm_fa);
+  infer_free(e);
   delete e;
 }
 extern "C" int jck_engine_num_tensors(int family, int net) { return (int)make_layout(family, net).t.size(); }

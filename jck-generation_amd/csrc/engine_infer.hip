@@ -17,6 +17,31 @@ extern "C" int jck_engine_sample(jck_engine* e, const float* z, const int64_t* l
   return jck_engine_sample_ex(e, z, labels, n, 0, out_nchw, nullptr, stream);
 }
 
+// One of the engine's inference buffer groups (LatentBufs, ScoreBufs, CriticBufs, FeatBufs), allocated by the first call that needs it:
+// `carve` takes the group's buffers from a Carver and runs twice - without memory for the size, then on the allocation.  `clear`: the
+// group must read as zero from the start, and the call waits on that stream for the clear (score_alloc says why).
+template <typename Bufs, typename Carve>
+static int infer_alloc(Bufs& group, Carve carve, const hipStream_t* clear = nullptr) {
+  if (group.base) return JCK_OK;
+  Carver c;
+  Bufs b;
+  carve(c, b);                                                       // sizes
+  void* base = nullptr;
+  HIPCHK(hipMalloc(&base, c.off));
+  if (clear && (hipMemsetAsync(base, 0, c.off, *clear) != hipSuccess || hipStreamSynchronize(*clear) != hipSuccess)) {
+    (void)hipFree(base);
+    JCK_FAIL(JCK_E_HIP, "score: clearing the buffers failed");
+  }
+  c = Carver{0, reinterpret_cast<unsigned char*>(base)};
+  carve(c, b);
+  b.base = base;
+  group = b;
+  return JCK_OK;
+}
+void infer_free(jck_engine* e) {
+  for (void* base : {e->lat.base, e->sc.base, e->cr.base, e->fm.base}) if (base) (void)hipFree(base);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // latent projection: dL/dz through the frozen generator under model.eval(), L_b = mean((G(z_b) - t_b)^2), and Adam on z.
 // Beside the step: it uses only buffers that every step rewrites before reading (g_z, g_a, g_gr, g_raw, fake_raw, the stages' aux) -
@@ -28,12 +53,11 @@ constexpr int LAT_KSPLIT = 16, LAT_LD = 128;          // 16 * G_C1 / 64 = 128 (6
 // operand rows from z (and the labels), the BatchNorm fold and the pack of G.conv1's weight for the dz product: once per call
 static int latent_begin(jck_engine* e, const float* z, const int64_t* labels, int n, hipStream_t st) {
   const int K = 16 * TT.G_C1, zp = z_pad(e->family);
-  if (!e->lat_w) {
-    const size_t wb = (size_t)LAT_LD * K * e->esz, sb = (size_t)LAT_KSPLIT * e->B * LAT_LD * sizeof(float);      // both multiples of 256
-    HIPCHK(hipMalloc(&e->lat_w, wb + sb + (size_t)e->B * sizeof(float)));
-    e->lat_slab = reinterpret_cast<float*>((unsigned char*)e->lat_w + wb);
-    e->lat_loss = reinterpret_cast<float*>((unsigned char*)e->lat_w + wb + sb);
-  }
+  JCK_TRY(infer_alloc(e->lat, [&](Carver& c, jck_engine::LatentBufs& b) {
+    b.w = c.take<unsigned char>((size_t)LAT_LD * K * e->esz);
+    b.slab = c.take<float>((size_t)LAT_KSPLIT * e->B * LAT_LD);
+    b.loss = c.take<float>(e->B);
+  }));
   if (e->family == 1) JCK_TRY(jck_cgan_z(e->prec, z, labels, n, 100, N_CLASS, zp, e->g_z, st));
   else {
     e->ss.gz_step = -1;                        // the operand rows now hold somebody else's z
@@ -42,7 +66,7 @@ static int latent_begin(jck_engine* e, const float* z, const int64_t* labels, in
   }
   JCK_TRY(g_eval_fold(e, st));
   // conv1.weight [z_dim][G_C1][4][4]: its first 100 rows as a Linear weight [100][G_C1 * 16] whose columns go from (c, pos) to (pos, c)
-  return jck_pack_linear(e->prec, e->P(e->LG, e->gp, CWN[0]), 100, K, LAT_LD, K, 0, TT.G_C1, 16, e->lat_w, st);
+  return jck_pack_linear(e->prec, e->P(e->LG, e->gp, CWN[0]), 100, K, LAT_LD, K, 0, TT.G_C1, 16, e->lat.w, st);
 }
 // from g_raw, the gradient at the pre-tanh product: the masked dgrads and the dz product's slabs
 static int latent_backward(jck_engine* e, int n, hipStream_t st) {
@@ -52,7 +76,7 @@ static int latent_backward(jck_engine* e, int n, hipStream_t st) {
     JCK_TRY(jck_conv_down_mask(e->prec, gbig, e->g_down[i], e->g_a[i], e->g_bn[i].aux, e->g_gr[i], n, 2 * hs, 2 * hs, TT.G_CB[i], TT.G_CS[i], st));
     gbig = e->g_gr[i];
   }
-  return jck_linear_fwd(e->prec, e->g_gr[0], e->lat_w, nullptr, e->lat_slab, n, 16 * TT.G_C1, 100, LAT_LD, LAT_KSPLIT, st);
+  return jck_linear_fwd(e->prec, e->g_gr[0], e->lat.w, nullptr, e->lat.slab, n, 16 * TT.G_C1, 100, LAT_LD, LAT_KSPLIT, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -69,11 +93,10 @@ static int latent_backward(jck_engine* e, int n, hipStream_t st) {
 // epilogue only) gives up, and the whole call measured 4 % faster that way at batch 64 and 256 (tools/score_rate.py).
 static bool score_stage_fused(int prec) { return prec_f32_storage(prec); }
 static int score_alloc(jck_engine* e, hipStream_t st) {
-  if (e->sc.base) return JCK_OK;
-  if (e->capturing) JCK_FAIL(JCK_E_ARG, "score: the first scoring call allocates and cannot run inside a graph capture");
-  Carver c;
-  auto carve = [&](jck_engine::ScoreBufs& b) {
-    c.off = 0;
+  if (!e->sc.base && e->capturing) JCK_FAIL(JCK_E_ARG, "score: the first scoring call allocates and cannot run inside a graph capture");
+  // the concat buffer's padding columns are a GEMM operand: they read as zero from the start - for a later call on ANY stream, so this
+  // one call, which allocates anyway, waits for the clear
+  return infer_alloc(e->sc, [&](Carver& c, jck_engine::ScoreBufs& b) {
     b.x = c.take<unsigned char>((size_t)e->B * TT.HW * 4 * e->esz);
     if (!score_stage_fused(e->prec)) b.y = c.take<unsigned char>((size_t)e->B * (TT.S / 2) * (TT.S / 2) * TT.D_CS[0] * e->esz);   // the largest stage's
     for (int i = 0; i < TT.NS; ++i) {
@@ -85,22 +108,7 @@ static int score_alloc(jck_engine* e, hipStream_t st) {
       b.slab = c.take<float>((size_t)L1_KSPLIT * e->B * L1_OUT);
       b.h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
     }
-  };
-  jck_engine::ScoreBufs b;
-  carve(b);                                                          // sizes
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, c.off));
-  // the concat buffer's padding columns are a GEMM operand: they read as zero from the start - for a later call on ANY stream, so this
-  // one call, which allocates anyway, waits for the clear
-  if (hipMemsetAsync(base, 0, c.off, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    (void)hipFree(base);
-    JCK_FAIL(JCK_E_HIP, "score: clearing the buffers failed");
-  }
-  c.base = reinterpret_cast<unsigned char*>(base);
-  carve(b);
-  b.base = base;
-  e->sc = b;
-  return JCK_OK;
+  }, &st);
 }
 // the fold of D's BatchNorm layers (gamma, beta and the running statistics) into the stages' aux tables: one launch ...
 static int score_fold(jck_engine* e, hipStream_t st) {
@@ -114,6 +122,14 @@ static int score_fold(jck_engine* e, hipStream_t st) {
     aux[i] = S.aux[i]; Cs[i] = TT.D_CS[i];
   }
   return jck_bn_eval_aux(TT.NS, gamma, beta, rm, rv, aux, Cs, BN_EPS, st);
+}
+// D's input and the fold, the head of jck_engine_score and jck_engine_features: the buffers, *in = the images (and their instance noise)
+// transformed into S.x or - NULL images - the generator's last output, where it lies, then score_fold
+static int score_input(jck_engine* e, const float* images_nchw, const float* noise_nchw, int n, const void** in, hipStream_t st) {
+  JCK_TRY(score_alloc(e, st));
+  *in = images_nchw ? e->sc.x : e->fake_raw;
+  if (images_nchw) JCK_TRY(jck_img_prep(e->prec, images_nchw, noise_nchw, noise_nchw ? 0.9f : 1.0f, noise_nchw ? 0.1f : 0.0f, e->sc.x, n, TT.HW, st));
+  return score_fold(e, st);
 }
 // ... and the stages on the NHWC4 images `in`, each leaving its activation in S.a[i]: jck_engine_score, jck_engine_features and the
 // forward half of the critic's latent gradient, which reads the activations and aux tables afterwards.  `last`: the last stage to run
@@ -159,13 +175,8 @@ extern "C" int jck_engine_score(jck_engine* e, const float* images_nchw, const f
   if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, "score: CGAN discriminator needs labels");
   if (!e->d_packed) JCK_FAIL(JCK_E_ARG, "score: the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
   hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(score_alloc(e, st));
-  const void* in = e->fake_raw;                                       // NULL images: the generator's last output, where it lies
-  if (images_nchw) {
-    JCK_TRY(jck_img_prep(e->prec, images_nchw, noise_nchw, noise_nchw ? 0.9f : 1.0f, noise_nchw ? 0.1f : 0.0f, e->sc.x, n, TT.HW, st));
-    in = e->sc.x;
-  }
-  JCK_TRY(score_fold(e, st));
+  const void* in;
+  JCK_TRY(score_input(e, images_nchw, noise_nchw, n, &in, st));
   return score_stages_head(e, in, labels, n, logit, prob, st);
 }
 
@@ -190,13 +201,8 @@ extern "C" int jck_engine_features(jck_engine* e, const float* images_nchw, int 
   if (ld < jck_engine_feature_dim(e, grid) || ld % 4) JCK_FAIL(JCK_E_ARG, "features: ld must be a multiple of 4 and at least the feature dimension");
   if (!e->d_packed) JCK_FAIL(JCK_E_ARG, "features: the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
   hipStream_t st = (hipStream_t)stream;
-  JCK_TRY(score_alloc(e, st));
-  const void* in = e->fake_raw;                                       // NULL images: the generator's last output, where it lies
-  if (images_nchw) {
-    JCK_TRY(jck_img_prep(e->prec, images_nchw, nullptr, 1.0f, 0.0f, e->sc.x, n, TT.HW, st));
-    in = e->sc.x;
-  }
-  JCK_TRY(score_fold(e, st));
+  const void* in;
+  JCK_TRY(score_input(e, images_nchw, nullptr, n, &in, st));
   JCK_TRY(score_stages(e, in, n, st));
   long long col0 = 0;
   for (int i = 0; i < TT.NS; ++i) {
@@ -215,10 +221,7 @@ extern "C" int jck_engine_features(jck_engine* e, const float* images_nchw, int 
 // buffers (DActs, real_noisy, the head's cbuf, any gradient arena) is read or written.
 // ---------------------------------------------------------------------------------------------------------
 static int critic_alloc(jck_engine* e) {
-  if (e->cr.base) return JCK_OK;
-  Carver c;
-  auto carve = [&](jck_engine::CriticBufs& b) {
-    c.off = 0;
+  return infer_alloc(e->cr, [&](Carver& c, jck_engine::CriticBufs& b) {
     for (int i = 0; i < TT.NS; ++i) b.g[i] = c.take<unsigned char>((size_t)e->B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i] * e->esz);
     b.gx = c.take<unsigned char>((size_t)e->B * TT.HW * 4 * e->esz);
     b.ds = c.take<float>(e->B); b.term = c.take<float>(e->B); b.logit = c.take<float>(e->B);
@@ -226,82 +229,81 @@ static int critic_alloc(jck_engine* e) {
       b.g_h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
       b.gc = c.take<unsigned char>((size_t)e->B * L1_KPAD * e->esz);
     }
-  };
-  jck_engine::CriticBufs b;
-  carve(b);                                                          // sizes
-  void* base = nullptr;
-  HIPCHK(hipMalloc(&base, c.off));
-  c.base = reinterpret_cast<unsigned char*>(base);
-  carve(b);
-  b.base = base;
-  e->cr = b;
-  return JCK_OK;
+  });
 }
-static int latent_check(jck_engine* e, const float* z, const int64_t* labels, const float* target, int critic_mode, float critic_weight,
-                        const float* feat_target, int feat_stage, float feat_weight, int n, const char* who) {
-  const std::string w(who);
+// The objective of a latent call, as the six entry points build it: the image loss on `target` under the per-pixel `weight` (either may be
+// null), the critic's term (mode 0: none) at weight cw, and
+// feat_target / feat_stage / feat_weight: the feature-matching term F_b = feat_weight * mean((a_k(G(z_b)) - a_k(x_b))^2) on the LeakyReLU
+// output of D's stage k (-1: the deepest); on iff there is a target and a positive weight
+struct LatentEx {
+  const int64_t* labels; const float* target; const float* weight; int mode; float cw;
+  const float* feat_target; int feat_stage; float feat_weight;
+  bool fm() const { return feat_target && feat_weight > 0.f; }
+};
+// What a call reports per image: rows [n] of one evaluation, or (project) histories [steps][n] of which row(s) is update s's; null: not wanted
+struct LatentOut {
+  float *loss, *term, *logit, *fterm;
+  LatentOut row(int s, int n) const {
+    auto at = [&](float* p) { return p ? p + (size_t)s * n : nullptr; };
+    return {at(loss), at(term), at(logit), at(fterm)};
+  }
+};
+struct LatentAdam { int steps; float lr, prior; float *m, *v; int t0; };      // project's schedule and the caller's Adam state
+static int latent_check(jck_engine* e, const float* z, const LatentEx& o, int n, const std::string& w) {
   if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, w + ": engine not bound");
   if (n < 1 || n > e->B) JCK_FAIL(JCK_E_ARG, w + ": n must be in [1, batch]");
   if (!z) JCK_FAIL(JCK_E_ARG, w + ": null z");
-  if (critic_mode < 0 || critic_mode > 2) JCK_FAIL(JCK_E_ARG, w + ": critic_mode must be 0 (none), 1 (nsgan) or 2 (logit)");
-  if (!(feat_weight >= 0.f) || !(feat_weight <= 3.402823466e38f)) JCK_FAIL(JCK_E_ARG, w + ": feat_weight must be finite and >= 0");
-  if (feat_weight > 0.f && !feat_target) JCK_FAIL(JCK_E_ARG, w + ": feat_weight > 0 needs a feature target");
-  if (feat_stage < -1 || feat_stage >= TT.NS) JCK_FAIL(JCK_E_ARG, w + ": feat_stage must be -1 (the deepest stage) or a stage of D");
-  const bool fm = feat_target && feat_weight > 0.f;
-  if (!target && !critic_mode && !fm) JCK_FAIL(JCK_E_ARG, w + ": without a target and without a feature term a critic is required");
-  if (!(critic_weight >= 0.f)) JCK_FAIL(JCK_E_ARG, w + ": critic_weight >= 0");
-  if (e->family == 1 && !labels) JCK_FAIL(JCK_E_ARG, w + ": CGAN needs labels");
-  if ((critic_mode || fm) && !e->d_packed)
+  if (o.mode < 0 || o.mode > 2) JCK_FAIL(JCK_E_ARG, w + ": critic_mode must be 0 (none), 1 (nsgan) or 2 (logit)");
+  if (!(o.feat_weight >= 0.f) || !(o.feat_weight <= 3.402823466e38f)) JCK_FAIL(JCK_E_ARG, w + ": feat_weight must be finite and >= 0");
+  if (o.feat_weight > 0.f && !o.feat_target) JCK_FAIL(JCK_E_ARG, w + ": feat_weight > 0 needs a feature target");
+  if (o.feat_stage < -1 || o.feat_stage >= TT.NS) JCK_FAIL(JCK_E_ARG, w + ": feat_stage must be -1 (the deepest stage) or a stage of D");
+  if (!o.target && !o.mode && !o.fm()) JCK_FAIL(JCK_E_ARG, w + ": without a target and without a feature term a critic is required");
+  if (!(o.cw >= 0.f)) JCK_FAIL(JCK_E_ARG, w + ": critic_weight >= 0");
+  if (e->family == 1 && !o.labels) JCK_FAIL(JCK_E_ARG, w + ": CGAN needs labels");
+  if ((o.mode || o.fm()) && !e->d_packed)
     JCK_FAIL(JCK_E_ARG, w + ": the discriminator's weights were never packed (load a discriminator state and repack net 1 first)");
   if (e->capturing) JCK_FAIL(JCK_E_ARG, w + ": not inside a graph capture");
   return JCK_OK;
 }
-// feat_target / feat_stage / feat_weight: the feature-matching term F_b = feat_weight * mean((a_k(G(z_b)) - a_k(x_b))^2) on the LeakyReLU
-// output of D's stage k (-1: the deepest); on iff there is a target and a positive weight
-struct LatentEx {
-  const float* target; const float* weight; int mode; float cw; const int64_t* labels;
-  const float* feat_target; int feat_stage; float feat_weight;
-  bool fm() const { return feat_target && feat_weight > 0.f; }
-};
 static int feat_stage_of(const jck_engine* e, const LatentEx& o) { return o.feat_stage < 0 ? TT.NS - 1 : o.feat_stage; }
 static long long feat_elems(const jck_engine* e, int k) { return (long long)(TT.D_HB[k] / 2) * (TT.D_HB[k] / 2) * TT.D_CS[k]; }
-// once per call, behind latent_begin: the critic's buffers and D's BatchNorm fold; with a feature term also its buffer (the first such
-// call allocates it: room for the largest stage, and a row for F), and the target's activation at stage k, which stays there for the call
+// once per call, behind latent_begin: the critic's buffers and D's BatchNorm fold; with a feature term also its buffers (room for the
+// largest stage, and a row for F), and the target's activation at stage k, which stays there for the call
 static int latent_ex_begin(jck_engine* e, const LatentEx& o, int n, hipStream_t st) {
   if (!o.mode && !o.fm()) return JCK_OK;
   JCK_TRY(score_alloc(e, st));
   JCK_TRY(critic_alloc(e));
-  if (o.fm() && !e->fm_fa) {
-    const size_t fb = (size_t)e->B * feat_elems(e, 0) * e->esz;         // a multiple of 256
-    HIPCHK(hipMalloc(&e->fm_fa, fb + (size_t)e->B * sizeof(float)));
-    e->fm_term = reinterpret_cast<float*>((unsigned char*)e->fm_fa + fb);
-  }
+  if (o.fm()) JCK_TRY(infer_alloc(e->fm, [&](Carver& c, jck_engine::FeatBufs& b) {
+    b.fa = c.take<unsigned char>((size_t)e->B * feat_elems(e, 0) * e->esz);
+    b.term = c.take<float>(e->B);
+  }));
   JCK_TRY(score_fold(e, st));
   if (!o.fm()) return JCK_OK;
   const int k = feat_stage_of(e, o);
   JCK_TRY(jck_img_prep(e->prec, o.feat_target, nullptr, 1.0f, 0.0f, e->sc.x, n, TT.HW, st));
   JCK_TRY(score_stages(e, e->sc.x, n, st, k));
-  HIPCHK(hipMemcpyAsync(e->fm_fa, e->sc.a[k], (size_t)n * feat_elems(e, k) * e->esz, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->fm.fa, e->sc.a[k], (size_t)n * feat_elems(e, k) * e->esz, hipMemcpyDeviceToDevice, st));
   return JCK_OK;
 }
 // one evaluation: the eval forward's products, the critic's forward and input gradient if there is one, the loss and its gradient, the
 // masked dgrads, the dz product's slabs.  Plain (no weight, no critic): the products, jck_latent_loss_ex, latent_backward.
 // With a feature term jck_feat_match puts its gradient where C.g[k] holds (or would hold) the gradient at stage k's product: without a
 // critic D runs up to stage k only and its backward starts there; with one it is added onto what came down from the head.
-static int latent_eval(jck_engine* e, const LatentEx& o, int n, float* loss, float* term, float* logit, float* fterm, hipStream_t st) {
+static int latent_eval(jck_engine* e, const LatentEx& o, int n, const LatentOut& out, hipStream_t st) {
   JCK_TRY(g_eval_products(e, n, st));
   const jck_engine::ScoreBufs& S = e->sc;
   const jck_engine::CriticBufs& C = e->cr;
+  // a row the caller does not want goes to one of the engine's own
+  float *loss = out.loss ? out.loss : e->lat.loss, *term = out.term ? out.term : C.term, *logit = out.logit ? out.logit : C.logit;
   const bool fm = o.fm();
   const int top = TT.NS - 1, k = feat_stage_of(e, o), from = o.mode ? top : k;
   auto feat_match = [&](int accumulate) {
-    return jck_feat_match(e->prec, S.a[k], e->fm_fa, S.aux[k], LRELU, o.feat_weight, C.g[k], accumulate, fterm ? fterm : e->fm_term, n,
+    return jck_feat_match(e->prec, S.a[k], e->fm.fa, S.aux[k], LRELU, o.feat_weight, C.g[k], accumulate, out.fterm ? out.fterm : e->fm.term, n,
                           feat_elems(e, k), TT.D_CS[k], st);
   };
   if (o.mode) {
-    if (!logit) logit = C.logit;
     JCK_TRY(score_stages_head(e, e->fake_raw, o.labels, n, logit, nullptr, st));
-    JCK_TRY(jck_critic_ds(logit, o.mode, o.cw, n, C.ds, term ? term : C.term, st));
+    JCK_TRY(jck_critic_ds(logit, o.mode, o.cw, n, C.ds, term, st));
     if (e->family == 0) {
       JCK_TRY(jck_head_bwd_conv(e->prec, C.ds, e->d_head_wp, S.a[top], n, TT.G_C1, C.g[top], nullptr, nullptr, st));
     } else {
@@ -328,71 +330,65 @@ static int latent_eval(jck_engine* e, const LatentEx& o, int n, float* loss, flo
   JCK_TRY(jck_latent_loss_ex(e->prec, e->fake_raw, o.target, o.weight, o.mode || fm ? C.gx : nullptr, e->g_raw, loss, n, TT.HW, st));
   return latent_backward(e, n, st);
 }
-static int latent_grad(const char* who, jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
-                       int critic_mode, float critic_weight, const float* feat_target, int feat_stage, float feat_weight, int n, float* loss,
-                       float* term, float* logit, float* fterm, float* dz, void* stream) {
-  JCK_TRY(latent_check(e, z, labels, target_nchw, critic_mode, critic_weight, feat_target, feat_stage, feat_weight, n, who));
-  if (!loss || !dz) JCK_FAIL(JCK_E_ARG, std::string(who) + ": null loss / dz");
+static int latent_grad(const std::string& who, jck_engine* e, const float* z, const LatentEx& o, int n, const LatentOut& out, float* dz,
+                       void* stream) {
+  JCK_TRY(latent_check(e, z, o, n, who));
+  if (!out.loss || !dz) JCK_FAIL(JCK_E_ARG, who + ": null loss / dz");
   hipStream_t st = (hipStream_t)stream;
-  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels, feat_target, feat_stage, feat_weight};
-  JCK_TRY(latent_begin(e, z, labels, n, st));
+  JCK_TRY(latent_begin(e, z, o.labels, n, st));
   JCK_TRY(latent_ex_begin(e, o, n, st));
-  JCK_TRY(latent_eval(e, o, n, loss, term, logit, fterm, st));
-  return jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, dz, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, n, st);
+  JCK_TRY(latent_eval(e, o, n, out, st));
+  return jck_latent_adam(e->prec, e->lat.slab, LAT_KSPLIT, LAT_LD, dz, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, n, st);
 }
-// `steps` Adam updates of z [n][100] (in, out) on the stream, no host synchronisation: m, v [n][100] are the caller's (zero them for a
-// fresh run), t0 the number of updates they have seen; loss_hist[s][n] / term_hist[s][n] / fterm_hist[s][n] (or null) are the loss, the
+// a.steps Adam updates of z [n][100] (in, out) on the stream, no host synchronisation: a.m, a.v [n][100] are the caller's (zero them for
+// a fresh run), a.t0 the number of updates they have seen; hist's loss[s][n] / term[s][n] / fterm[s][n] (or null) are the loss, the
 // critic's term and the feature term BEFORE update s.
-static int project(const char* who, jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
-                   float prior, const float* weight, int critic_mode, float critic_weight, const float* feat_target, int feat_stage,
-                   float feat_weight, float* m, float* v, int t0, float* loss_hist, float* term_hist, float* fterm_hist, void* stream) {
-  const std::string w(who);
-  JCK_TRY(latent_check(e, z, labels, target_nchw, critic_mode, critic_weight, feat_target, feat_stage, feat_weight, n, who));
-  if (steps < 1 || t0 < 0 || !m || !v) JCK_FAIL(JCK_E_ARG, w + ": steps >= 1, t0 >= 0 and the Adam state m, v are required");
-  if (!(lr > 0.f) || !(prior >= 0.f)) JCK_FAIL(JCK_E_ARG, w + ": lr > 0 and prior >= 0");
+static int project(const std::string& who, jck_engine* e, float* z, const LatentEx& o, int n, const LatentAdam& a, const LatentOut& hist,
+                   void* stream) {
+  JCK_TRY(latent_check(e, z, o, n, who));
+  if (a.steps < 1 || a.t0 < 0 || !a.m || !a.v) JCK_FAIL(JCK_E_ARG, who + ": steps >= 1, t0 >= 0 and the Adam state m, v are required");
+  if (!(a.lr > 0.f) || !(a.prior >= 0.f)) JCK_FAIL(JCK_E_ARG, who + ": lr > 0 and prior >= 0");
   hipStream_t st = (hipStream_t)stream;
-  const LatentEx o = {target_nchw, weight, critic_mode, critic_weight, labels, feat_target, feat_stage, feat_weight};
-  JCK_TRY(latent_begin(e, z, labels, n, st));
+  JCK_TRY(latent_begin(e, z, o.labels, n, st));
   JCK_TRY(latent_ex_begin(e, o, n, st));
-  for (int s = 0; s < steps; ++s) {
-    JCK_TRY(latent_eval(e, o, n, loss_hist ? loss_hist + (size_t)s * n : e->lat_loss, term_hist ? term_hist + (size_t)s * n : nullptr, nullptr,
-                        fterm_hist ? fterm_hist + (size_t)s * n : nullptr, st));
-    JCK_TRY(jck_latent_adam(e->prec, e->lat_slab, LAT_KSPLIT, LAT_LD, z, m, v, lr, prior, t0 + s + 1, e->g_z, z_pad(e->family), n, st));
+  for (int s = 0; s < a.steps; ++s) {
+    JCK_TRY(latent_eval(e, o, n, hist.row(s, n), st));
+    JCK_TRY(jck_latent_adam(e->prec, e->lat.slab, LAT_KSPLIT, LAT_LD, z, a.m, a.v, a.lr, a.prior, a.t0 + s + 1, e->g_z, z_pad(e->family), n, st));
   }
   return JCK_OK;
 }
 // the six entry points: the plain ones are the _ex ones with no weight and no critic, the _ex ones the _fm ones with no feature term
 extern "C" int jck_engine_latent_grad(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, int n, float* loss,
                                       float* dz, void* stream) {
-  return latent_grad("latent_grad", e, z, labels, target_nchw, nullptr, 0, 0.f, nullptr, -1, 0.f, n, loss, nullptr, nullptr, nullptr, dz, stream);
+  return latent_grad("latent_grad", e, z, {labels, target_nchw, nullptr, 0, 0.f, nullptr, -1, 0.f}, n, {loss, nullptr, nullptr, nullptr}, dz, stream);
 }
 extern "C" int jck_engine_latent_grad_ex(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
                                          int critic_mode, float critic_weight, int n, float* loss, float* term, float* logit, float* dz,
                                          void* stream) {
-  return latent_grad("latent_grad_ex", e, z, labels, target_nchw, weight, critic_mode, critic_weight, nullptr, -1, 0.f, n, loss, term, logit,
-                     nullptr, dz, stream);
+  return latent_grad("latent_grad_ex", e, z, {labels, target_nchw, weight, critic_mode, critic_weight, nullptr, -1, 0.f}, n,
+                     {loss, term, logit, nullptr}, dz, stream);
 }
 extern "C" int jck_engine_latent_grad_fm(jck_engine* e, const float* z, const int64_t* labels, const float* target_nchw, const float* weight,
                                          int critic_mode, float critic_weight, int n, float* loss, float* term, float* logit, float* dz,
                                          void* stream, const float* feat_target_nchw, int feat_stage, float feat_weight, float* fterm) {
-  return latent_grad("latent_grad_fm", e, z, labels, target_nchw, weight, critic_mode, critic_weight, feat_target_nchw, feat_stage, feat_weight,
-                     n, loss, term, logit, fterm, dz, stream);
+  return latent_grad("latent_grad_fm", e, z, {labels, target_nchw, weight, critic_mode, critic_weight, feat_target_nchw, feat_stage, feat_weight},
+                     n, {loss, term, logit, fterm}, dz, stream);
 }
 extern "C" int jck_engine_project(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
                                   float prior, float* m, float* v, int t0, float* loss_hist, void* stream) {
-  return project("project", e, z, labels, target_nchw, n, steps, lr, prior, nullptr, 0, 0.f, nullptr, -1, 0.f, m, v, t0, loss_hist, nullptr,
-                 nullptr, stream);
+  return project("project", e, z, {labels, target_nchw, nullptr, 0, 0.f, nullptr, -1, 0.f}, n, {steps, lr, prior, m, v, t0},
+                 {loss_hist, nullptr, nullptr, nullptr}, stream);
 }
 extern "C" int jck_engine_project_ex(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
                                      float prior, const float* weight, int critic_mode, float critic_weight, float* m, float* v, int t0,
                                      float* loss_hist, float* term_hist, void* stream) {
-  return project("project_ex", e, z, labels, target_nchw, n, steps, lr, prior, weight, critic_mode, critic_weight, nullptr, -1, 0.f, m, v, t0,
-                 loss_hist, term_hist, nullptr, stream);
+  return project("project_ex", e, z, {labels, target_nchw, weight, critic_mode, critic_weight, nullptr, -1, 0.f}, n, {steps, lr, prior, m, v, t0},
+                 {loss_hist, term_hist, nullptr, nullptr}, stream);
 }
 extern "C" int jck_engine_project_fm(jck_engine* e, float* z, const int64_t* labels, const float* target_nchw, int n, int steps, float lr,
                                      float prior, const float* weight, int critic_mode, float critic_weight, float* m, float* v, int t0,
                                      float* loss_hist, float* term_hist, void* stream, const float* feat_target_nchw, int feat_stage,
                                      float feat_weight, float* fterm_hist) {
-  return project("project_fm", e, z, labels, target_nchw, n, steps, lr, prior, weight, critic_mode, critic_weight, feat_target_nchw, feat_stage,
-                 feat_weight, m, v, t0, loss_hist, term_hist, fterm_hist, stream);
+  return project("project_fm", e, z, {labels, target_nchw, weight, critic_mode, critic_weight, feat_target_nchw, feat_stage, feat_weight}, n,
+                 {steps, lr, prior, m, v, t0}, {loss_hist, term_hist, nullptr, fterm_hist}, stream);
 }

@@ -175,28 +175,36 @@ struct jck_engine {
   void *d_v[JCK_MAX_STAGES], *d_xdir[JCK_MAX_STAGES], *d_u0;
   float* bn2_ws[JCK_MAX_STAGES]; float* bn2_ws_rev;
   const int64_t* cur_labels = nullptr;
-  // latent projection (jck_engine_latent_grad / jck_engine_project): memory of its own, allocated by the first such call and freed
-  // with the engine - G.conv1's weight as the dz product's operand [128][16 * G_C1], that product's split-K slabs, a loss row (one allocation)
-  void* lat_w = nullptr; float *lat_slab = nullptr, *lat_loss = nullptr;
-  // discriminator inference (jck_engine_score): memory of its own as well, one allocation made by the first scoring call - the
-  // transformed input, a stage's activations and folded aux table each, one pre-activation tensor that the stages share (bf16: see
-  // jck_engine_score), and CGAN's head rows (concat buffer, split-K slabs, hidden row)
+  // The four buffer groups of the inference side (engine_infer.hip): each is memory of its own, ONE allocation made by the first call
+  // that needs the group (infer_alloc carves it) and freed with the engine (infer_free).
+  // latent projection (jck_engine_latent_grad / jck_engine_project): G.conv1's weight as the dz product's operand [128][16 * G_C1], that
+  // product's split-K slabs, a loss row
+  struct LatentBufs {
+    void* base = nullptr;
+    void* w = nullptr; float *slab = nullptr, *loss = nullptr;
+  } lat;
+  // discriminator inference (jck_engine_score): the transformed input, a stage's activations and folded aux table each, one
+  // pre-activation tensor that the stages share (bf16: see jck_engine_score), and CGAN's head rows (concat buffer, split-K slabs,
+  // hidden row)
   struct ScoreBufs {
     void* base = nullptr;
     void *x = nullptr, *y = nullptr, *a[JCK_MAX_STAGES] = {}, *cbuf = nullptr, *h = nullptr;
     float *aux[JCK_MAX_STAGES] = {}, *slab = nullptr;
   } sc;
-  // the critic's latent gradient (jck_engine_latent_grad_ex / jck_engine_project_ex with critic_mode != 0): memory of its own too, one
-  // allocation made by the first such call - the gradient at every stage's pre-activation, the image gradient (NHWC4), the rows
-  // ds / term / logit, and CGAN's gradient rows at the Linear(8392,256) output and at the concat buffer
+  // the critic's latent gradient (jck_engine_latent_grad_ex / jck_engine_project_ex with critic_mode != 0, or a feature term): the
+  // gradient at every stage's pre-activation, the image gradient (NHWC4), the rows ds / term / logit, and CGAN's gradient rows at the
+  // Linear(8392,256) output and at the concat buffer
   struct CriticBufs {
     void* base = nullptr;
     void *g[JCK_MAX_STAGES] = {}, *gx = nullptr, *g_h = nullptr, *gc = nullptr;
     float *ds = nullptr, *term = nullptr, *logit = nullptr;
   } cr;
   // the feature-matching term (jck_engine_latent_grad_fm / jck_engine_project_fm with a feature target): the target's activation at the
-  // chosen stage, with room for the largest stage (stage 0), and a row for the term - one allocation made by the first such call
-  void* fm_fa = nullptr; float* fm_term = nullptr;
+  // chosen stage, with room for the largest stage (stage 0), and a row for the term
+  struct FeatBufs {
+    void* base = nullptr;
+    void* fa = nullptr; float* term = nullptr;
+  } fm;
   bool d_packed = false;               // D's operands were derived from its parameters at least once (jck_engine_repack, a D step)
 
   void carve(unsigned char* base) {
@@ -326,3 +334,5 @@ static void launch_pad_rows(const float* z, int B, int zd, int zp, void* out, hi
 JCK_INTERNAL int g_eval_fold(jck_engine* e, hipStream_t st);
 JCK_INTERNAL int g_eval_products(jck_engine* e, int B, hipStream_t st);
 JCK_INTERNAL int g_forward(jck_engine* e, const float* z, const int64_t* labels, int B, hipStream_t st, bool z_in_place = false, bool eval = false);
+// engine_infer.hip: frees the inference side's buffer groups (jck_engine_destroy)
+JCK_INTERNAL void infer_free(jck_engine* e);

@@ -153,6 +153,31 @@ def images_to_target(images):
     return x
 
 
+def fit_images(images, size, what):
+    """images_to_target(images), refused unless they are `size` x `size`: what an engine's generator makes and its discriminator takes"""
+    x = images_to_target(images)
+    if x.shape[2] != size:
+        raise JckError(f"{what}: images are {x.shape[2]}x{x.shape[2]}, this engine's networks are {size}x{size}")
+    return x
+
+
+def restart_rows(n, restarts, seed, *rows):
+    """R = restarts starts per image, run as extra rows: (z0 [R*n,100], whose block r is latents(n, seed + r), then every tensor of
+    `rows` ([n,...] or None) tiled R times) - row r * n + i is image i from seed + r"""
+    z0 = torch.cat([latents(n, int(seed) + r) for r in range(restarts)])
+    return (z0,) + tuple(a if a is None or restarts == 1 else a.repeat(restarts, *([1] * (a.dim() - 1))) for a in rows)
+
+
+def pick_best(score, n, *rows):
+    """`rows` ([R*n,...] each, laid out as restart_rows leaves them) cut to the start with the lowest score [R*n] per image: [n,...]
+    each.  Ties go to the lowest seed; R = 1 returns the rows as they are."""
+    if score.shape[0] == n:
+        return rows
+    best = score.view(-1, n).argmin(0)                                  # the first minimum: the lowest seed
+    pick = best * n + torch.arange(n, device=best.device)
+    return tuple(a[pick] for a in rows)
+
+
 def load_projection_targets(path):
     """The `images` array of an .npz (generate.py's images.npz, or any uint8 [n,S,S,3]) -> (uint8 tensor, labels or None)."""
     import numpy as np
@@ -330,33 +355,26 @@ class Sampler:
         feature_weight > 0 (perceptual projection; needs from_checkpoint(..., with_d=True)): feature_weight * the mean squared
         distance between the discriminator's stage-`feature_stage` activations (None: the deepest) of G(z) and of the image joins
         the objective (DcganEngine.project(feature_target=images)); the loss returned and compared stays the pixel error."""
-        t = images_to_target(images)
-        n, R = t.shape[0], int(restarts)
         fw = float(feature_weight)
         if not (fw >= 0.0 and fw < float("inf")):
             raise JckError(f"project: feature_weight must be finite and >= 0, got {feature_weight}")
         if fw > 0.0:
             self._needs_d("project(feature_weight > 0)")
-        if t.shape[2] != self.engine.size:
-            raise JckError(f"images are {t.shape[2]}x{t.shape[2]}, the generator makes {self.engine.size}x{self.engine.size}")
-        if R < 1:
-            raise JckError(f"restarts must be >= 1, got {restarts}")
+        t, n, R = self._targets("project", images, restarts)
         if z0 is not None and R != 1:
             raise JckError("z0 fixes the start: restarts must be 1")
-        lab = self._labels(labels, n)
-        t = t.to(self.engine.device)
-        tt = t.repeat(R, 1, 1, 1) if R > 1 else t                     # row r * n + i: image i from seed + r
-        ll = None if lab is None else lab.repeat(R, 1)
-        if z0 is None:
-            z0 = torch.cat([latents(n, int(seed) + r) for r in range(R)])
+        zr, tt, ll = restart_rows(n, R, seed, t, self._labels(labels, n))
         feat = dict(feature_target=tt, feature_weight=fw, feature_stage=feature_stage) if fw > 0.0 else {}
-        z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, prior=prior, z0=z0.reshape(-1, NZ), **feat)
+        z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, prior=prior, z0=(zr if z0 is None else z0).reshape(-1, NZ), **feat)
         loss, _ = self.engine.latent_grad(z, tt, ll)
-        if R > 1:
-            best = loss.view(R, n).argmin(0)                            # ties: the lowest seed
-            pick = best * n + torch.arange(n, device=best.device)
-            z, loss = z[pick], loss[pick]
-        return z, loss
+        return pick_best(loss, n, z, loss)
+
+    def _targets(self, what, images, restarts):
+        """(the images as fp32 NCHW on the engine's device, n, R) of a call that fits latents to images from R = restarts starts each"""
+        t = fit_images(images, self.engine.size, what)
+        if int(restarts) < 1:
+            raise JckError(f"{what}: restarts must be >= 1, got {restarts}")
+        return t.to(self.engine.device), t.shape[0], int(restarts)
 
     def _needs_d(self, what):
         if not self.engine._shared.get("d_loaded"):
@@ -379,13 +397,8 @@ class Sampler:
         x = torch.as_tensor(images_u8)
         if x.dtype != torch.uint8:
             raise JckError(f"inpaint: images must be uint8 [n,S,S,3], got {x.dtype}")
-        t = images_to_target(x)
-        n, R, S = t.shape[0], int(restarts), self.engine.size
-        if t.shape[2] != S:
-            raise JckError(f"images are {t.shape[2]}x{t.shape[2]}, the generator makes {S}x{S}")
-        if R < 1:
-            raise JckError(f"restarts must be >= 1, got {restarts}")
-        k = _check_known(torch.as_tensor(known).cpu(), S, "inpaint")
+        t, n, R = self._targets("inpaint", x, restarts)
+        k = _check_known(torch.as_tensor(known).cpu(), self.engine.size, "inpaint")
         if k.dim() == 3 and k.shape[0] != n:
             raise JckError(f"inpaint: {k.shape[0]} masks for {n} images")
         cw = float(critic_weight)
@@ -399,17 +412,11 @@ class Sampler:
         if bool((w.reshape(n, -1).sum(1) <= 0).any()):
             raise JckError("inpaint: the importance weights of an image are all zero (no known pixel has a hole within the window)")
         lab = self._labels(labels, n)
-        t = t.to(self.engine.device)
-        rep = lambda a, *ones: a if a is None or R == 1 else a.repeat(R, *ones)
-        tt, ww, ll = rep(t, 1, 1, 1), rep(w.contiguous(), 1, 1), rep(lab, 1)
-        z0 = torch.cat([latents(n, int(seed) + r) for r in range(R)])
+        z0, tt, ww, ll = restart_rows(n, R, seed, t, w.contiguous(), lab)
         z, _ = self.engine.project(tt, ll, steps=steps, lr=lr, z0=z0, weight=ww, critic=critic, critic_weight=cw)
         res = self.engine.latent_grad(z, tt, ll, weight=ww, critic=critic, critic_weight=cw)
         loss, term = (res[0], res[1]) if critic else (res[0], torch.zeros_like(res[0]))
-        if R > 1:
-            best = (loss + term).view(R, n).argmin(0)
-            pick = best * n + torch.arange(n, device=best.device)
-            z, loss, term = z[pick], loss[pick], term[pick]
+        z, loss, term = pick_best(loss + term if R > 1 else loss, n, z, loss, term)      # (one start: nothing to add up for)
         gen = self.engine.sample(z, lab, bn="running", out="uint8")
         return {"z": z, "loss": loss, "term": term, "generated": gen, "completed": blend(x.to(gen.device), gen, k)}
 
@@ -425,21 +432,13 @@ class Sampler:
         the paper's numbers; and whether the discriminator's features separate anything is a property of the run that trained it.
         Needs from_checkpoint(..., with_d=True)."""
         from .anomaly import anomaly_score
-        t = images_to_target(images)
-        n, R = t.shape[0], int(restarts)
         lam = float(lam)
         if not 0.0 <= lam < 1.0:
             raise JckError(f"anomaly: lam must lie in [0, 1), got {lam}")
-        if R < 1:
-            raise JckError(f"anomaly: restarts must be >= 1, got {restarts}")
+        t, n, R = self._targets("anomaly", images, restarts)
         self._needs_d("anomaly")
-        if t.shape[2] != self.engine.size:
-            raise JckError(f"images are {t.shape[2]}x{t.shape[2]}, the generator makes {self.engine.size}x{self.engine.size}")
         lab = self._labels(labels, n)
-        t = t.to(self.engine.device)
-        tt = t.repeat(R, 1, 1, 1) if R > 1 else t
-        ll = lab if lab is None or R == 1 else lab.repeat(R, 1)
-        z0 = torch.cat([latents(n, int(seed) + r) for r in range(R)])
+        z0, tt, ll = restart_rows(n, R, seed, t, lab)
         fw = lam / (1.0 - lam)
         if fw > 0.0:
             feat = dict(feature_target=tt, feature_weight=fw, feature_stage=stage)
@@ -451,10 +450,7 @@ class Sampler:
             residual = self.engine.latent_grad(z, tt, ll)[0]
             feature = self.engine.latent_grad(z, tt, ll, feature_target=tt, feature_weight=1.0, feature_stage=stage)["fterm"]
         score = anomaly_score(residual, feature, lam)
-        if R > 1:
-            best = score.view(R, n).argmin(0)                           # ties: the lowest seed
-            pick = best * n + torch.arange(n, device=best.device)
-            z, residual, feature, score = z[pick], residual[pick], feature[pick], score[pick]
+        z, residual, feature, score = pick_best(score, n, z, residual, feature, score)
         gen = self.engine.sample(z, lab, bn="running", out="uint8")
         return {"z": z, "residual": residual, "feature": feature, "score": score, "generated": gen}
 

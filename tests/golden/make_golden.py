@@ -15,13 +15,17 @@ Fixtures
   metrics.json      Metrics.inception_score / fid / intra_fid on seeded 100-d features
   selfdiv.json      reference vs itself (8 threads vs 1 thread): long-horizon noise floor
 
-One fixture records the project's own GPU results, not the reference's; it needs an MI355X and no reference, and is written
+Two fixtures record the project's own GPU results, not the reference's; they need an MI355X and no reference, and are written
 only when named:
 
     python tests/golden/make_golden.py --only latent_plain_bits --commit <the commit the library was built from>
+    python tests/golden/make_golden.py --only infer_bits --commit <the commit the library was built from>
 
   latent_plain_bits.json   SHA-256 of the raw output bytes of the plain latent entry points (jck_latent_loss,
                            jck_engine_latent_grad, jck_engine_project); tests/test_latent_plain_bits_gpu.py recomputes them
+  infer_bits.json          the same of the _ex / _fm latent entry points with a weight, a critic and a feature term, of
+                           jck_engine_score and jck_engine_features, and of the engine's Python methods over them; every digest is
+                           computed twice and written only if the two agree; tests/test_infer_bits_gpu.py recomputes them
 """
 import argparse
 import hashlib
@@ -473,17 +477,119 @@ def gen_latent_plain_bits(commit):
     return rec
 
 
+# --------------------------------------------------------------------------------------------
+# the inference paths beside the plain ones, bit for bit: the _ex / _fm latent entry points with their objective terms on,
+# jck_engine_score, jck_engine_features and the Python layer over them (again the project's own results at a recorded commit)
+# --------------------------------------------------------------------------------------------
+INFER_ENGINES = LATENT_ENGINES + [(f, "bf16x3") for f in ("dcgan", "cgan") if (f, "bf16x3") not in LATENT_ENGINES]
+INFER_GROUPS = ("latent_ex", "latent_fm", "score", "features", "python")
+# name: (target, per-pixel weight, critic mode, critic weight)
+INFER_EX_CASES = {"weight": (True, True, 0, 0.0), "nsgan": (True, False, 1, 0.003), "logit_no_target": (False, False, 2, 1.0),
+                  "weight_nsgan": (True, True, 1, 0.003)}
+# name: (target, feature stage, critic mode, critic weight); the feature weight is 0.5
+INFER_FM_CASES = {"stage0": (True, 0, 0, 0.0), "deepest_no_target": (False, -1, 0, 0.0), "stage1_nsgan": (True, 1, 1, 0.003)}
+
+
+def infer_inputs(family, n=5):
+    """seeded rows of an inference call: z, target, per-pixel weight (a block of unknown pixels), feature target, instance noise, labels"""
+    g = torch.Generator().manual_seed(DATA_SEED + 4)
+    z = torch.randn(n, 100, generator=g)
+    t, ft = torch.rand(n, 3, 64, 64, generator=g) * 2 - 1, torch.rand(n, 3, 64, 64, generator=g) * 2 - 1
+    w = torch.rand(n, 64, 64, generator=g)
+    w[:, 16:40, 20:48] = 0.0
+    nz = torch.randn(n, 3, 64, 64, generator=g)
+    lab = synth_onehot(n, DATA_SEED + 5)[0].cuda() if family == "cgan" else None
+    return z.cuda(), t.cuda(), w.cuda(), ft.cuda(), nz.cuda(), lab
+
+
+def infer_bits(family, prec, group):
+    """{"case.output": digest} of one group of calls on latent_engine(family, prec), n = 5 of 8; a 3-step projection at lr 0.05, prior 0.01"""
+    from hipgan import lib
+    from hipgan._lib import cur_stream
+    eng = latent_engine(family, prec)
+    n, steps, out = 5, 3, {}
+    z0, t, w, ft, nz, lab = infer_inputs(family, n)
+    f = lambda *sh: torch.zeros(*sh, device="cuda")
+    put = lambda case, named: out.update({f"{case}.{k}": sha256_bytes(x) for k, x in named.items()})
+
+    def latent(case, tt, ww, mode, cw, fm=None):
+        loss, term, logit, fterm, dz = f(n), f(n), f(n), f(n), f(n, 100)
+        z, m, v, hist, thist, fhist = z0.clone(), f(n, 100), f(n, 100), f(steps, n), f(steps, n), f(steps, n)
+        if fm is None:
+            lib.jck_engine_latent_grad_ex(eng._h, z0, lab, tt, ww, mode, cw, n, loss, term, logit, dz, cur_stream())
+            lib.jck_engine_project_ex(eng._h, z, lab, tt, n, steps, 0.05, 0.01, ww, mode, cw, m, v, 0, hist, thist, cur_stream())
+        else:
+            lib.jck_engine_latent_grad_fm(eng._h, z0, lab, tt, ww, mode, cw, n, loss, term, logit, dz, cur_stream(), ft, fm, 0.5, fterm)
+            lib.jck_engine_project_fm(eng._h, z, lab, tt, n, steps, 0.05, 0.01, ww, mode, cw, m, v, 0, hist, thist, cur_stream(), ft, fm, 0.5,
+                                      fhist)
+        named = {"loss": loss, "term": term, "logit": logit, "dz": dz, "z": z, "m": m, "v": v, "loss_hist": hist, "term_hist": thist}
+        if fm is not None:
+            named.update({"fterm": fterm, "fterm_hist": fhist})
+        put(case, named)
+
+    if group == "latent_ex":
+        for case, (has_t, has_w, mode, cw) in INFER_EX_CASES.items():
+            latent(case, t if has_t else None, w if has_w else None, mode, cw)
+    elif group == "latent_fm":
+        for case, (has_t, stage, mode, cw) in INFER_FM_CASES.items():
+            latent(case, t if has_t else None, None, mode, cw, fm=stage)
+    elif group == "score":
+        for case, (x, noise) in {"images": (t, None), "images_noise": (t, nz), "current": (None, None)}.items():
+            if x is None:
+                lib.jck_engine_sample_ex(eng._h, z0, lab, n, 1, None, None, cur_stream())          # JCK_SAMPLE_EVAL
+            logit, prob = f(n), f(n)
+            lib.jck_engine_score(eng._h, x, noise, lab, n, logit, prob, cur_stream())
+            put(case, {"logit": logit, "prob": prob})
+    elif group == "features":
+        for case, (grid, mode) in {"grid1_max": (1, 0), "grid4_mean": (4, 1)}.items():
+            F = lib.jck_engine_feature_dim(eng._h, grid)
+            rows = f(n, F)
+            lib.jck_engine_features(eng._h, t, n, grid, mode, rows, F, cur_stream())
+            put(case, {"rows": rows})
+    elif group == "python":
+        put("latent_grad", dict(zip(("loss", "dz"), eng.latent_grad(z0, t, lab))))
+        put("latent_grad_critic", dict(zip(("loss", "term", "logit", "dz"),
+                                           eng.latent_grad(z0, t, lab, weight=w, critic="nsgan", critic_weight=0.003))))
+        put("latent_grad_feature", eng.latent_grad(z0, t, lab, feature_target=ft, feature_weight=0.5, feature_stage=1))
+        put("critic_grad", dict(zip(("logit", "term", "dz"), eng.critic_grad(z0, lab))))
+        z, hist = eng.project(t, lab, steps=steps, lr=0.05, prior=0.01, z0=z0, critic="nsgan", critic_weight=0.003, feature_target=ft,
+                              feature_weight=0.5, feature_stage=1)
+        put("project", {"z": z, "loss_hist": hist, "state.m": eng.project_state["m"], "state.v": eng.project_state["v"],
+                        "term": eng.project_term, "fterm": eng.project_fterm})
+        put("refine", dict(zip(("z", "before", "after"), eng.refine(z0, lab, steps=2))))
+    else:
+        raise KeyError(group)
+    return out
+
+
+def gen_infer_bits(commit):
+    assert torch.cuda.is_available(), "infer_bits records what the GPU computes"
+    assert commit, "--commit: name the commit the library under test was built from"
+    for p in (os.path.dirname(os.path.dirname(HERE)), os.path.join(os.path.dirname(os.path.dirname(HERE)), "jck-generation_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    rec = {"commit": commit, "device": torch.cuda.get_device_name(0), "engine": {}, "not_reproducible": []}
+    for fam, prec in INFER_ENGINES:
+        for group in INFER_GROUPS:
+            a, b = infer_bits(fam, prec, group), infer_bits(fam, prec, group)      # a key whose two digests differ is not written
+            rec["not_reproducible"] += [f"{fam}-{prec}.{group}.{k}" for k in a if a[k] != b[k]]
+            rec["engine"].setdefault(f"{fam}-{prec}", {})[group] = {k: d for k, d in a.items() if d == b[k]}
+    for k in rec["not_reproducible"]:
+        print("NOT REPRODUCIBLE, left out:", k)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
-    ap.add_argument("--commit", default="", help="latent_plain_bits: the commit the library was built from")
+    ap.add_argument("--commit", default="", help="latent_plain_bits, infer_bits: the commit the library was built from")
     a = ap.parse_args()
-    if a.only == "latent_plain_bits":                  # the GPU's results, not the reference's
-        rec = gen_latent_plain_bits(a.commit)
+    if a.only in ("latent_plain_bits", "infer_bits"):  # the GPU's results, not the reference's
+        rec = gen_latent_plain_bits(a.commit) if a.only == "latent_plain_bits" else gen_infer_bits(a.commit)
         rec["_meta"] = {"torch": torch.__version__, "generator": "tests/golden/make_golden.py", "model_seed": MODEL_SEED, "data_seed": DATA_SEED}
-        with open(os.path.join(HERE, "latent_plain_bits.json"), "w") as f:
+        with open(os.path.join(HERE, a.only + ".json"), "w") as f:
             json.dump(rec, f, indent=1)
-        print("latent_plain_bits ->", os.path.getsize(os.path.join(HERE, "latent_plain_bits.json")), "bytes")
+        print(a.only, "->", os.path.getsize(os.path.join(HERE, a.only + ".json")), "bytes")
         return
     assert os.path.isdir(REF), "the reference is only mounted in the build container"
     install_stubs()

@@ -206,6 +206,30 @@ def test_engine_and_sampler_refuse_on_the_host(monkeypatch):
         s.images(2, select="best")
 
 
+def test_restart_rows_and_the_pick_of_the_best_start():
+    """restarts run as extra rows: row r * n + i is image i from seed + r, and the pick per image is the lowest score, ties to the lowest seed"""
+    from hipgan.sampler import latents, pick_best, restart_rows
+    n, R, seed = 2, 3, 7
+    t = torch.arange(n * 3.0).view(n, 3, 1, 1)
+    lab = torch.tensor([[1, 0], [0, 1]])
+    z0, tt, none, ll = restart_rows(n, R, seed, t, None, lab)
+    assert z0.shape == (R * n, 100) and tt.shape == (R * n, 3, 1, 1) and ll.shape == (R * n, 2) and none is None
+    for r in range(R):
+        zr = latents(n, seed + r)
+        for i in range(n):
+            assert torch.equal(z0[r * n + i], zr[i]) and torch.equal(tt[r * n + i], t[i]) and torch.equal(ll[r * n + i], lab[i])
+    z1, t1, l1 = restart_rows(n, 1, seed, t, lab)                               # one start: the rows as they are
+    assert torch.equal(z1, latents(n, seed)) and t1 is t and l1 is lab
+    # image 0: seeds 7 and 8 tie at the minimum -> seed 7 (row 0); image 1: seed 9 is the lowest (row 5)
+    score = torch.tensor([1.0, 5.0, 1.0, 4.0, 2.0, 3.0])
+    rows = torch.arange(R * n)
+    z, s = pick_best(score, n, rows, score)
+    assert z.tolist() == [0, 5] and s.tolist() == [1.0, 3.0]
+    score = torch.tensor([2.0, 3.0, 1.0, 3.0, 1.0, 3.0])                        # image 0: seeds 8 and 9 tie; image 1: all three tie
+    assert pick_best(score, n, rows)[0].tolist() == [2, 1]
+    assert pick_best(score[:n], n, rows[:n])[0] is not None and pick_best(score[:n], n, rows[:n])[0].tolist() == [0, 1]
+
+
 def test_abi_declares_and_exports_the_entry_points():
     from hipgan import _lib
     if not os.path.exists(_lib.LIB_PATH):
