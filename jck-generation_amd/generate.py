@@ -1,4 +1,13 @@
-"""Images from a trained generator, outside the trainer.  Run from this directory:
+import argparse
+import json
+import os
+import sys
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+HEAD = """Images from a trained generator, outside the trainer.  Run from this directory:
 
     python generate.py -m DCGAN --checkpoint ../model/DCGAN/fid/best.pt --num 64 --out samples
     python generate.py -m CGAN --checkpoint best.pt --num 8 --classes 3,17,42 --truncation 0.7 --out samples
@@ -15,177 +24,96 @@
     python generate.py -m DCGAN --checkpoint best.pt --project samples/images.npz --project_feature_weight 10 --out perceptual
     python generate.py -m DCGAN --checkpoint best.pt --anomaly queries.npz --anomaly_lam 0.1 --out anomaly
 
-Writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN only) and <out>/grid.png.
-BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z, and --num is not
-bounded by the batch.  --bn batch is the trainers' evaluation sampling: each chunk of -b images is one train-mode BatchNorm batch.
+A run is exactly one mode: one record of MODES below, which holds the mode's arguments, defaults, checks, host-side plan, run and the
+paragraph that describes it here.  The options outside the modes (-b, --seed, --bn, --which, --calibrate, --classes, --k, --project_steps,
+--project_lr, --project_prior, --prec) are taken by every mode, and ignored by a mode that has no use for one.
 An averaged generator (--which ema, or auto when the file has one) wants --calibrate K first: K train-mode batches that fit the
 running statistics to the averaged weights (in this process only; the file is not touched).
---project FILE.npz fits a latent to every picture of the file's `images` array (uint8 [n,S,S,3]: an images.npz of this tool, or any
-such array; a CGAN takes the file's `labels` or cycles through --classes) by Adam through the frozen eval-mode generator and writes
-<out>/projected.npz (z: fp32 [n,100]; loss: the mean squared error of each reconstruction in [-1, 1] units; images: the
-reconstructions, uint8) and <out>/projected.png, each row of targets above the row of their reconstructions.
-The checkpoint's discriminator (`model_d`), as under Discriminator.eval(): --score adds `logit` and `prob` fp32 [N] to images.npz;
---select top|drs with --oversample M keeps the --num best of M * --num draws, or runs discriminator rejection sampling with rounds
-of that size (Sampler.images; a CGAN ranks within one class: --classes ID, else one drawn from the seed); --score_images FILE.npz scores an existing uint8 `images` array into <out>/scores.npz (logit, prob).
-Whether the discriminator's running statistics make it a good ranker is a property of the run that trained it.
---neighbours REF.npz (with a sampling run, or with --score_images, whose images it then takes) looks up the --k nearest images of
-REF's uint8 `images` array (the samples' size, or 32x32 training data, upscaled as the trainers do) for every sample, in pixel space:
-<out>/neighbours.npz (idx int64 [n,k]; d2 squared distance in [-1, 1] units; rmse = sqrt(d2 / D); ref_nn_d2: the nearest other
-reference image's d2 from the image idx[:,0]; copy = d2[:,0] < ref_nn_d2) and <out>/neighbours.png, each sample followed by its neighbours.
---inpaint FILE.npz --mask SPEC is semantic inpainting (Yeh et al. 2017; Sampler.inpaint): SPEC names the KNOWN pixels of the file's
-pictures ("center:K": a centred K x K hole; "half:left|right|top|bottom": that half is the hole; an .npz / .npy file holding `mask`),
-z is fitted to them alone (--project_steps, --project_lr) with --critic_weight W times -log D(G(z)) as the realism prior (0: none, no
-discriminator needed), and <out>/inpainted.npz holds z, loss, term, known, images (G(z)) and completed (the known pixels of the input,
-the holes from G); <out>/inpainted.png has one row per picture: masked input, G(z), completed.
---refine STEPS (with a sampling run) moves every latent STEPS Adam updates (--refine_lr) along the discriminator's gradient before its
-image is made; images.npz then holds the refined z and gains logit_before / logit_after.
-The discriminator as a feature extractor (Radford et al. 2016, section 5.1; hipgan.probe): --features FILE.npz pools every conv stage's
-activation of the file's pictures (the discriminator's size, or 32x32 data, upscaled as the trainers do) to a --feature_grid raster
-(--feature_pool max|mean) and writes <out>/features.npz (features: fp32 [n,F], unnormalised; layout: int64 [stages,4] rows of stage,
-col0, C, H; grid; pool; labels if the file has them) for an external classifier.  --probe TRAIN.npz --probe_test TEST.npz (both with
-`labels`) classifies every test picture by the majority of its --k (default 5) nearest training pictures in block-normalised feature
-space and writes <out>/probe.json (accuracy, per_class, k, train, test, F, grid, pool).  --neighbours REF.npz --space d looks the
-samples' neighbours up in that feature space instead of pixel space: neighbours.npz then holds idx, d2, ref_nn_d2 and copy, no rmse.
---project_feature_weight W (with --project) adds W times the mean squared distance between the discriminator's deepest-stage activations
-of G(z) and of the picture to the projection's objective (perceptual projection; needs `model_d`).
---anomaly FILE.npz scores the file's pictures after AnoGAN (Schlegl et al. 2017; Sampler.anomaly): each is projected (--project_steps,
---project_lr) with a residual term and a feature-matching term on the discriminator's stage --anomaly_stage (default: the deepest),
-and score = (1 - lam) residual + lam feature at the z reached (--anomaly_lam, default 0.1) - mean squared forms, not the paper's L1
-sums.  <out>/anomaly.npz holds z, residual, feature, score, generated (G(z), uint8) and order (indices by falling score);
-<out>/anomaly.png has one row per picture: input, G(z), |input - G(z)|; <out>/anomaly.json (auroc, n, anomalous, lam, stage) is written
-when the file carries a bool `anomalous` [n] array."""
-import argparse
-import os
-import sys
+The checkpoint's discriminator (`model_d`) is used as under Discriminator.eval(); whether its running statistics make it a good ranker,
+and whether its features separate anything, is a property of the run that trained it."""
 
-import numpy as np
-import torch
+
+@dataclass
+class Mode:
+    """One kind of run.  get_arg_parse declares `arguments` in a group of the mode's own, selects the mode whose `flag` was given
+    (`sample` when none was), refuses every option of another mode, runs `check` and fills in `defaults`; main calls `plan`, then `run`."""
+    name: str
+    doc: str                                          # the mode's paragraph of the module docstring and of --help
+    arguments: tuple = ()                             # ((flag, add_argument keywords), ...): the options that go only with this mode
+    flag: str = None                                  # the attribute of the selecting option; None: the run without a selector
+    companions: tuple = ()                            # attributes that must come with the selector
+    shares: tuple = ()                                # options of another mode's group that go with this mode too
+    defaults: dict = field(default_factory=dict)      # attribute: value, or a function of args (None: leave it), where it was not given
+    check: object = lambda a, p: None                 # check(args, parser): value ranges and the rules inside the mode
+    needs_d: object = lambda a: True                  # needs_d(args): does this run need the checkpoint's discriminator
+    plan: object = lambda a: None                     # plan(args): host only; reads and checks the run's files -> job; JckError for a bad one
+    run: object = None                                # run(args, sampler, job)
+
+    def options(self):
+        return tuple(flag.lstrip("-") for flag, _ in self.arguments) + tuple(self.shares)
+
+    def title(self):
+        return f"--{self.flag}" if self.flag else "a sampling run"
+
+
+# what an option that no mode set rests at, in every mode
+RESTING = {"num": 64, "k": 4, "space": "pixel", "feature_grid": 4, "feature_pool": "max"}
+
+
+def _given(a, name):
+    v = getattr(a, name)
+    return v is not None and v is not False and v != ""
 
 
 def get_arg_parse(argv=None):
-    p = argparse.ArgumentParser(description="sample a trained DCGAN / CGAN generator")
+    p = argparse.ArgumentParser(description="sample a trained DCGAN / CGAN generator", formatter_class=argparse.RawDescriptionHelpFormatter,
+                                epilog="\n".join(m.doc for m in MODES))
     p.add_argument("-m", "--model", choices=["DCGAN", "CGAN"], default="DCGAN")
     p.add_argument("--checkpoint", required=True, help="a checkpoint written by the trainers (or the reference's)")
-    p.add_argument("--num", type=int, default=None, help="images, per class with --classes (default 64; not with --interpolate)")
     p.add_argument("-b", "--batch_size", type=int, default=64, help="images per launch sequence")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--truncation", type=float, default=None, help="draw z from a normal truncated to [-T, T]")
     p.add_argument("--bn", choices=["running", "batch"], default="running")
     p.add_argument("--which", choices=["auto", "live", "ema"], default="auto")
     p.add_argument("--calibrate", type=int, default=0, metavar="K", help="train-mode sampling batches before sampling")
     p.add_argument("--classes", type=parse_classes, default=None, metavar="3,17,...", help="CGAN: one grid row of --num images per class")
-    p.add_argument("--interpolate", type=parse_interpolate, default=None, metavar="PAIRS:STEPS",
-                   help="PAIRS spherical interpolations of STEPS points each between random z (one grid row per pair)")
-    p.add_argument("--project", default=None, metavar="FILE.npz", help="fit z to the uint8 [n,S,S,3] `images` array of this file")
+    p.add_argument("--k", type=int, default=None, help="neighbours per sample, 1..8 (default 4 with --neighbours, 5 with --probe)")
     p.add_argument("--project_steps", type=int, default=200, help="Adam updates per image")
     p.add_argument("--project_lr", type=float, default=0.05)
     p.add_argument("--project_prior", type=float, default=0.0, help="weight of mean(z^2) beside the image loss")
-    p.add_argument("--score", action="store_true", help="add the discriminator's logit and prob of every image to images.npz")
-    p.add_argument("--select", choices=["top", "drs"], default=None, help="keep the best / rejection-sample by the discriminator's score")
-    p.add_argument("--oversample", type=int, default=None, metavar="M", help="with --select: draws per image kept (top), per round (drs)")
-    p.add_argument("--score_images", default=None, metavar="FILE.npz", help="score the uint8 [n,S,S,3] `images` array of this file")
-    p.add_argument("--neighbours", default=None, metavar="REF.npz", help="nearest images of this file's uint8 `images` array for every sample")
-    p.add_argument("--k", type=int, default=None, help="neighbours per sample, 1..8 (default 4 with --neighbours, 5 with --probe)")
-    p.add_argument("--space", choices=["pixel", "d"], default=None, help="with --neighbours: pixel space (default) or the discriminator's features")
-    p.add_argument("--features", default=None, metavar="FILE.npz", help="the discriminator's pooled activations of this file's uint8 `images` array")
-    p.add_argument("--feature_grid", type=int, choices=[1, 2, 4], default=None, help="with --features, --probe, --space d: the pooling raster (default 4)")
-    p.add_argument("--feature_pool", choices=["max", "mean"], default=None, help="with --features, --probe, --space d (default max)")
-    p.add_argument("--probe", default=None, metavar="TRAIN.npz", help="k-nearest-neighbour probe of the discriminator's features: the labelled training set")
-    p.add_argument("--probe_test", default=None, metavar="TEST.npz", help="with --probe: the labelled test set")
-    p.add_argument("--inpaint", default=None, metavar="FILE.npz", help="fill the holes of the uint8 [n,S,S,3] `images` array of this file")
-    p.add_argument("--mask", default=None, metavar="SPEC", help="with --inpaint: center:K, half:left|right|top|bottom, or an .npz / .npy with `mask`")
-    p.add_argument("--critic_weight", type=float, default=None, metavar="W", help="with --inpaint: weight of -log D(G(z)) (default 0.003; 0: no critic)")
-    p.add_argument("--refine", type=int, default=None, metavar="STEPS", help="Adam updates of every latent along the discriminator's gradient")
-    p.add_argument("--refine_lr", type=float, default=None, metavar="LR", help="with --refine (default 0.02)")
-    p.add_argument("--project_feature_weight", type=float, default=None, metavar="W",
-                   help="with --project: weight of the feature-matching term on the discriminator's deepest stage")
-    p.add_argument("--anomaly", default=None, metavar="FILE.npz", help="AnoGAN anomaly scores of the uint8 [n,S,S,3] `images` array of this file")
-    p.add_argument("--anomaly_lam", type=float, default=None, metavar="LAM", help="with --anomaly: weight of the feature term in the score, in [0, 1) (default 0.1)")
-    p.add_argument("--anomaly_stage", type=int, default=None, metavar="K", help="with --anomaly: the discriminator stage matched (default: the deepest)")
     p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     p.add_argument("--out", required=True, help="output directory")
+    for m in MODES:
+        g = p.add_argument_group(f"{m.name} ({m.title()})")
+        for flag, kw in m.arguments:
+            g.add_argument(flag, **{"default": None, **kw})
     a = p.parse_args(argv)
-    if a.interpolate and a.num is not None:
-        p.error("--interpolate PAIRS:STEPS sets the number of images; --num does not go with it")
-    if a.project and (a.interpolate or a.num is not None or a.truncation is not None):
-        p.error("--project takes its images from the file; --num, --interpolate and --truncation do not go with it")
+    picked = [m for m in MODES if m.flag and _given(a, m.flag)]
+    if len(picked) > 1:
+        p.error(f"{' and '.join(m.title() for m in picked)} are separate runs")
+    mode = picked[0] if picked else next(m for m in MODES if m.flag is None)
+    for c in mode.companions:
+        if not _given(a, c):
+            p.error(f"--{mode.flag} and --{c} go together")
+    homes = {}                            # option: the modes it goes with
+    for m in MODES:
+        for o in m.options():
+            homes.setdefault(o, []).append(m)
+    for o, ms in homes.items():
+        if _given(a, o) and mode not in ms:
+            p.error(f"--{o} goes with {' or '.join(m.title() for m in ms)}, not with {mode.title()}")
     if a.project_steps < 1 or not a.project_lr > 0 or a.project_prior < 0:
         p.error("--project_steps must be >= 1, --project_lr > 0, --project_prior >= 0")
-    if a.select and (a.oversample is None or a.oversample < 1):
-        p.error("--select needs --oversample M with M >= 1")
-    if a.oversample is not None and not a.select:
-        p.error("--oversample goes with --select")
-    if a.select and (a.interpolate or a.project or a.bn != "running"):
-        p.error("--select draws its own latents under --bn running; --interpolate, --project and --bn batch do not go with it")
-    if a.select and a.classes and len(a.classes) != 1:
-        p.error("--select ranks within ONE class: give --classes a single id (scores of different classes do not compare)")
-    if a.score_images and (a.interpolate or a.project or a.select or a.score or a.num is not None or a.truncation is not None):
-        p.error("--score_images takes its images from the file; the sampling options do not go with it")
-    if a.score and (a.project or a.bn != "running"):
-        p.error("--score scores the eval-mode generator's images: not with --project or --bn batch")
-    if a.neighbours and a.project:
-        p.error("--neighbours looks up sampled or given images: not with --project")
-    if a.space and not a.neighbours:
-        p.error("--space goes with --neighbours")
-    if bool(a.probe) != bool(a.probe_test):
-        p.error("--probe TRAIN.npz and --probe_test TEST.npz go together")
-    if a.features and a.probe:
-        p.error("--features and --probe are separate runs")
-    if (a.features or a.probe) and (a.interpolate or a.project or a.select or a.score or a.score_images or a.neighbours or a.inpaint or
-                                    a.num is not None or a.truncation is not None or a.refine is not None):
-        p.error("--features and --probe take their images from files; the sampling, projection, scoring and neighbour options do not go with them")
-    if (a.feature_grid is not None or a.feature_pool is not None) and not (a.features or a.probe or a.space == "d"):
-        p.error("--feature_grid and --feature_pool go with --features, --probe or --space d")
-    if a.k is None:
-        a.k = 5 if a.probe else 4
-    if not 1 <= a.k <= 8:
+    if a.k is not None and not 1 <= a.k <= 8:
         p.error("--k must lie in 1..8")
-    a.space = a.space or "pixel"
-    a.feature_grid = 4 if a.feature_grid is None else a.feature_grid
-    a.feature_pool = a.feature_pool or "max"
-    if bool(a.inpaint) != bool(a.mask):
-        p.error("--inpaint FILE.npz and --mask SPEC go together")
-    if a.inpaint and (a.project or a.interpolate or a.select or a.score or a.score_images or a.neighbours or a.num is not None or
-                      a.truncation is not None or a.refine is not None):
-        p.error("--inpaint takes its images from the file; the sampling, projection and scoring options do not go with it")
-    if a.critic_weight is not None and not a.inpaint:
-        p.error("--critic_weight goes with --inpaint")
-    if a.critic_weight is not None and not a.critic_weight >= 0:
-        p.error("--critic_weight must be >= 0")
-    if a.inpaint and a.critic_weight is None:
-        a.critic_weight = 0.003
-    if a.project_feature_weight is not None and not a.project:
-        p.error("--project_feature_weight goes with --project")
-    if a.project_feature_weight is not None and not 0 <= a.project_feature_weight < float("inf"):
-        p.error("--project_feature_weight must be finite and >= 0")
-    if a.anomaly and (a.project or a.inpaint or a.interpolate or a.select or a.score or a.score_images or a.neighbours or a.features or a.probe or
-                      a.num is not None or a.truncation is not None or a.refine is not None):
-        p.error("--anomaly takes its images from the file; the sampling, projection, inpainting, scoring and feature options do not go with it")
-    if (a.anomaly_lam is not None or a.anomaly_stage is not None) and not a.anomaly:
-        p.error("--anomaly_lam and --anomaly_stage go with --anomaly")
-    if a.anomaly_lam is not None and not 0 <= a.anomaly_lam < 1:
-        p.error("--anomaly_lam must lie in [0, 1)")
-    if a.anomaly_stage is not None and not -1 <= a.anomaly_stage <= 4:
-        p.error("--anomaly_stage must be -1 (the deepest) or a stage of the discriminator")
-    if a.anomaly and a.anomaly_lam is None:
-        a.anomaly_lam = 0.1
-    if a.refine_lr is not None and a.refine is None:
-        p.error("--refine_lr goes with --refine")
-    if a.refine is not None:
-        if a.refine < 1 or (a.refine_lr is not None and not a.refine_lr > 0):
-            p.error("--refine STEPS must be >= 1 and --refine_lr > 0")
-        if a.project or a.score_images or a.select or a.interpolate or a.bn != "running":
-            p.error("--refine moves the latents of a plain sampling run under --bn running: not with --project, --score_images, --select, --interpolate or --bn batch")
-        if a.refine_lr is None:
-            a.refine_lr = 0.02
-    if a.num is None:
-        a.num = 64
-    if a.num < 1 or a.batch_size < 1 or a.calibrate < 0:
-        p.error("--num and -b must be >= 1, --calibrate >= 0")
-    if a.truncation is not None and not a.truncation > 0:
-        p.error("--truncation must be > 0")
+    if a.batch_size < 1 or a.calibrate < 0:
+        p.error("-b must be >= 1, --calibrate >= 0")
     if a.classes is not None and a.model != "CGAN":
         p.error("--classes needs -m CGAN")
+    mode.check(a, p)
+    for name, v in {**RESTING, **mode.defaults}.items():
+        if getattr(a, name) is None:
+            setattr(a, name, v(a) if callable(v) else v)
+    a.mode = mode.name
     return a
 
 
@@ -209,9 +137,12 @@ def parse_interpolate(s):
     return pairs, steps
 
 
+def mode_of(args):
+    return next(m for m in MODES if m.name == args.mode)
+
+
 def needs_discriminator(args):
-    return bool(args.score or args.select or args.score_images or args.refine is not None or (args.inpaint and args.critic_weight > 0) or
-                args.features or args.probe or args.space == "d" or args.anomaly or (args.project_feature_weight or 0) > 0)
+    return bool(mode_of(args).needs_d(args))
 
 
 def check_checkpoint(args, ckpt):
@@ -219,6 +150,89 @@ def check_checkpoint(args, ckpt):
     from hipgan.sampler import pick_discriminator_state
     if needs_discriminator(args):
         pick_discriminator_state(ckpt)
+
+
+def class_ids(args, n, labels, path):
+    """Class ids [n] of a run on the n pictures of file `path` (None for a DCGAN): --classes cycled, else the file's `labels`"""
+    from hipgan._lib import JckError
+    if args.model != "CGAN":
+        return None
+    if args.classes:
+        return torch.tensor([args.classes[k % len(args.classes)] for k in range(n)])
+    if labels is None:
+        raise JckError(f"{path} has no 'labels' array: a CGAN needs it, or --classes")
+    return labels.to(torch.int64).view(-1)
+
+
+def pair_rows(targets_u8, recon_u8, per_row):
+    """[targets of row 0 | reconstructions of row 0 | targets of row 1 | ...], each row padded to per_row with black images: the
+    order in which grid_u8 puts every target above its reconstruction."""
+    t, r = np.asarray(targets_u8), np.asarray(recon_u8)
+    out = []
+    for lo in range(0, t.shape[0], per_row):
+        for part in (t[lo:lo + per_row], r[lo:lo + per_row]):
+            pad = np.zeros((per_row - part.shape[0],) + part.shape[1:], np.uint8)
+            out += [part, pad]
+    return np.concatenate(out)
+
+
+def grid_u8(images_u8, per_row, padding=2):
+    """uint8 [N,H,W,3] -> one uint8 [H',W',3] sheet, `per_row` images a row on black."""
+    from train.gan_trainer import _make_grid
+    x = torch.as_tensor(images_u8).permute(0, 3, 1, 2).float()
+    g = _make_grid(x, nrow=per_row, padding=padding, normalize=False)
+    return g.permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).numpy()
+
+
+def write_outputs(out, npz=None, arrays=None, cls=None, sheet=None, record=None):
+    """A run's files in directory `out`: `npz` of `arrays` (and `labels` where there are class ids), sheet = (uint8 images, images per
+    row, .png name) through grid_u8, record = (.json name, dict)."""
+    from train.gan_trainer import _encode_png
+    os.makedirs(out, exist_ok=True)
+    if npz:
+        if cls is not None:
+            arrays = {**arrays, "labels": cls.numpy().astype(np.int64)}
+        np.savez(os.path.join(out, npz), **arrays)
+    if sheet:
+        images, per_row, png = sheet
+        with open(os.path.join(out, png), "wb") as f:
+            f.write(_encode_png(grid_u8(images, per_row)))
+    if record:
+        with open(os.path.join(out, record[0]), "w") as f:
+            json.dump(record[1], f, indent=1)
+
+
+def check_lookup(a, p):
+    """the rules of --neighbours and its options, for the two modes that take it"""
+    if a.space and not a.neighbours:
+        p.error("--space goes with --neighbours")
+    if (a.feature_grid is not None or a.feature_pool is not None) and a.space != "d":
+        p.error("--feature_grid and --feature_pool go with --features, --probe or --space d")
+
+
+def check_sample(a, p):
+    if a.interpolate and a.num is not None:
+        p.error("--interpolate PAIRS:STEPS sets the number of images; --num does not go with it")
+    if (a.num is not None and a.num < 1) or (a.truncation is not None and not a.truncation > 0):
+        p.error("--num must be >= 1, --truncation > 0")
+    if a.select and (a.oversample is None or a.oversample < 1):
+        p.error("--select needs --oversample M with M >= 1")
+    if a.oversample is not None and not a.select:
+        p.error("--oversample goes with --select")
+    if a.select and (a.interpolate or a.bn != "running"):
+        p.error("--select draws its own latents under --bn running; --interpolate and --bn batch do not go with it")
+    if a.select and a.classes and len(a.classes) != 1:
+        p.error("--select ranks within ONE class: give --classes a single id (scores of different classes do not compare)")
+    if a.score and a.bn != "running":
+        p.error("--score scores the eval-mode generator's images: not with --bn batch")
+    if a.refine_lr is not None and a.refine is None:
+        p.error("--refine_lr goes with --refine")
+    if a.refine is not None:
+        if a.refine < 1 or (a.refine_lr is not None and not a.refine_lr > 0):
+            p.error("--refine STEPS must be >= 1 and --refine_lr > 0")
+        if a.select or a.interpolate or a.bn != "running":
+            p.error("--refine moves the latents of a plain sampling run under --bn running: not with --select, --interpolate or --bn batch")
+    check_lookup(a, p)
 
 
 def plan(args):
@@ -246,82 +260,23 @@ def plan(args):
     return z.float(), cls, per_row
 
 
-def plan_project(args):
-    """(target images uint8 [n,S,S,3], start z0 [n,100], class ids [n] or None, images per grid row) of a --project run."""
-    from hipgan._lib import JckError
-    from hipgan.sampler import latents, load_projection_targets
-    u8, labels = load_projection_targets(args.project)
-    n = u8.shape[0]
-    cls = None
-    if args.model == "CGAN":
-        if args.classes:
-            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(n)])
-        elif labels is not None:
-            cls = labels.to(torch.int64).view(-1)
-        else:
-            raise JckError(f"{args.project} has no 'labels' array: a CGAN projection needs it, or --classes")
-    return u8, latents(n, args.seed), cls, min(n, 8)
+def load_reference(args):
+    """the pictures of --neighbours REF.npz, or None: a bad reference file ends the run before an engine exists"""
+    from hipgan.neighbours import load_reference_images
+    return load_reference_images(args.neighbours) if args.neighbours else None
 
 
-def pair_rows(targets_u8, recon_u8, per_row):
-    """[targets of row 0 | reconstructions of row 0 | targets of row 1 | ...], each row padded to per_row with black images: the
-    order in which grid_u8 puts every target above its reconstruction."""
-    t, r = np.asarray(targets_u8), np.asarray(recon_u8)
-    out = []
-    for lo in range(0, t.shape[0], per_row):
-        for part in (t[lo:lo + per_row], r[lo:lo + per_row]):
-            pad = np.zeros((per_row - part.shape[0],) + part.shape[1:], np.uint8)
-            out += [part, pad]
-    return np.concatenate(out)
+def plan_sample(args):
+    """(plan(args), or None for --select, whose latents Sampler.images draws; the reference pictures of --neighbours or None)"""
+    return None if args.select else plan(args), load_reference(args)
 
 
-def grid_u8(images_u8, per_row, padding=2):
-    """uint8 [N,H,W,3] -> one uint8 [H',W',3] sheet, `per_row` images a row on black."""
-    from train.gan_trainer import _make_grid
-    x = torch.as_tensor(images_u8).permute(0, 3, 1, 2).float()
-    g = _make_grid(x, nrow=per_row, padding=padding, normalize=False)
-    return g.permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).numpy()
-
-
-def main(argv=None):
-    args = get_arg_parse(argv)
-    from hipgan.sampler import Sampler
-    from train.gan_trainer import _encode_png
-    with_d = needs_discriminator(args)
-    ref = None
-    if args.neighbours:                   # a bad reference file ends the run before an engine exists
-        from hipgan.neighbours import load_reference_images
-        ref = load_reference_images(args.neighbours)
-    job = None
-    if args.inpaint:                      # ... and so does a bad picture file or mask
-        job = plan_inpaint(args)
-    if args.anomaly:                      # ... or an anomaly run's file
-        job = plan_anomaly(args)
-    if args.features or args.probe:       # ... or a feature run's file without pictures, a probe's without labels
-        from hipgan.probe import load_images
-        job = [load_images(f, need_labels=bool(args.probe)) for f in ((args.features,) if args.features else (args.probe, args.probe_test))]
-    ckpt = args.checkpoint
-    if with_d:
-        ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
-        check_checkpoint(args, ckpt)
-    s = Sampler.from_checkpoint(ckpt, args.model, which=args.which, prec=args.prec, batch=args.batch_size, **({"with_d": True} if with_d else {}))
-    if args.calibrate:
-        s.calibrate(args.calibrate, seed=args.seed + 2)
-    if args.project:
-        return project_main(args, s)
-    if args.inpaint:
-        return inpaint_main(args, s, job)
-    if args.anomaly:
-        return anomaly_main(args, s, job)
-    if args.features:
-        return features_main(args, s, job)
-    if args.probe:
-        return probe_main(args, s, job)
-    if args.score_images:
-        return score_main(args, s, ref)
-    if ref is not None:                   # ... and one of the wrong size before anything is sampled
+def run_sample(args, s, job):
+    planned, ref = job
+    if ref is not None:                   # a reference of the wrong size ends the run before anything is sampled
         from hipgan.neighbours import upscale_steps
         upscale_steps(ref.shape[1], s.engine.size, what=args.neighbours)
+    more = {}
     if args.select:
         cls = None
         if args.model == "CGAN":          # one class for the whole run (--classes ID, else drawn from the seed): scores of different classes do not compare
@@ -331,46 +286,33 @@ def main(argv=None):
         u8, z, per_row, scores = img.cpu().numpy(), info["z"], 8, (info["logit"], info["prob"])
         cls = None if cls is None else cls.repeat(args.num)
     else:
-        z, cls, per_row = plan(args)
-        refined = None
+        z, cls, per_row = planned
         if args.refine is not None:       # the pictures are those of the refined latents
             zr, before, after = s.refine(z, cls, steps=args.refine, lr=args.refine_lr)
-            z, refined = zr.cpu(), (before.cpu().numpy(), after.cpu().numpy())
+            z, more = zr.cpu(), {"logit_before": before.cpu().numpy(), "logit_after": after.cpu().numpy()}
         if args.score:                    # the scores of exactly these pictures, from the generator pass that made them
             img, *scores = s.from_latents_scored(z, cls, out="uint8")
             u8 = img.cpu().numpy()
         else:
             u8 = s.from_latents(z, cls, bn=args.bn, out="uint8").cpu().numpy()
-    os.makedirs(args.out, exist_ok=True)
-    arrays = {"images": u8, "z": z.numpy()}
-    if cls is not None:
-        arrays["labels"] = cls.numpy().astype(np.int64)
     if args.score:
-        arrays["logit"], arrays["prob"] = scores[0].cpu().numpy(), scores[1].cpu().numpy()
-    if args.refine is not None:
-        arrays["logit_before"], arrays["logit_after"] = refined
-    np.savez(os.path.join(args.out, "images.npz"), **arrays)
-    with open(os.path.join(args.out, "grid.png"), "wb") as f:
-        f.write(_encode_png(grid_u8(u8, per_row)))
+        more.update(logit=scores[0].cpu().numpy(), prob=scores[1].cpu().numpy())
+    write_outputs(args.out, "images.npz", {"images": u8, "z": z.numpy(), **more}, cls, sheet=(u8, per_row, "grid.png"))
     print(f"{u8.shape[0]} images ({s.which} generator, bn={args.bn}) -> {args.out}/images.npz, grid.png")
     if ref is not None:
-        neighbours_main(args, s, u8, ref)
-    return 0
+        write_neighbours(args, s, u8, ref)
 
 
-def neighbours_main(args, s, u8, ref):
+def write_neighbours(args, s, u8, ref):
     """--neighbours: the samples' nearest reference images -> <out>/neighbours.npz, neighbours.png and one line"""
     from hipgan.neighbours import neighbour_rows, upscale_steps
-    from train.gan_trainer import _encode_png
     steps = upscale_steps(ref.shape[1], u8.shape[1], what=args.neighbours)
     if args.space == "d":
         r = s.neighbours(u8, ref, k=args.k, space="d", grid=args.feature_grid, pool=args.feature_pool)
     else:
         r = s.neighbours(u8, ref, k=args.k)
-    os.makedirs(args.out, exist_ok=True)
-    np.savez(os.path.join(args.out, "neighbours.npz"), **{k_: r[k_] for k_ in ("idx", "d2", "rmse", "ref_nn_d2", "copy") if k_ in r})
-    with open(os.path.join(args.out, "neighbours.png"), "wb") as f:
-        f.write(_encode_png(grid_u8(neighbour_rows(u8, ref, r["idx"], steps), 1 + args.k)))
+    write_outputs(args.out, "neighbours.npz", {k_: r[k_] for k_ in ("idx", "d2", "rmse", "ref_nn_d2", "copy") if k_ in r},
+                  sheet=(neighbour_rows(u8, ref, r["idx"], steps), 1 + args.k, "neighbours.png"))
     if args.space == "d":
         near = r["d2"][:, 0]
         print(f"neighbours (discriminator features): {int(r['copy'].sum())} of {u8.shape[0]} samples flagged as copies, nearest d2 min "
@@ -381,62 +323,88 @@ def neighbours_main(args, s, u8, ref):
           f"median {float(np.nanmedian(near)):.5f} -> {args.out}/neighbours.npz, neighbours.png")
 
 
-def features_main(args, s, job):
-    """--features: the discriminator's pooled activations of a file's pictures -> <out>/features.npz and one line"""
-    from hipgan.probe import extract, feature_layout
-    (u8, labels), = job
-    f = extract(s.engine, u8, args.feature_grid, args.feature_pool, normalise="none").cpu().numpy()
-    layout, F = feature_layout(s.engine.size, args.feature_grid)
-    arrays = {"features": f, "layout": np.asarray(layout, np.int64), "grid": np.int64(args.feature_grid), "pool": np.str_(args.feature_pool)}
-    if labels is not None:
-        arrays["labels"] = labels
-    os.makedirs(args.out, exist_ok=True)
-    np.savez(os.path.join(args.out, "features.npz"), **arrays)
-    print(f"{f.shape[0]} images -> {F} features each (grid {args.feature_grid}, {args.feature_pool}) -> {args.out}/features.npz")
-    return 0
+SAMPLE = Mode(
+    name="sample",
+    doc="""sample (no selecting option): writes <out>/images.npz (images: uint8 [N,S,S,3]; z: fp32 [N,100]; labels: int64 class ids [N], CGAN
+only) and <out>/grid.png.  BatchNorm runs on the running statistics by default (--bn running): every image is a function of its own z,
+and --num is not bounded by the batch.  --bn batch is the trainers' evaluation sampling: each chunk of -b images is one train-mode
+BatchNorm batch.
+--score adds the discriminator's `logit` and `prob` fp32 [N] to images.npz; --select top|drs with --oversample M keeps the --num best of
+M * --num draws, or runs discriminator rejection sampling with rounds of that size (Sampler.images; a CGAN ranks within one class:
+--classes ID, else one drawn from the seed).
+--refine STEPS moves every latent STEPS Adam updates (--refine_lr) along the discriminator's gradient before its image is made;
+images.npz then holds the refined z and gains logit_before / logit_after.
+--neighbours REF.npz (here, or with --score_images, whose images it then takes) looks up the --k nearest images of REF's uint8 `images`
+array (the samples' size, or 32x32 training data, upscaled as the trainers do) for every sample, in pixel space: <out>/neighbours.npz
+(idx int64 [n,k]; d2 squared distance in [-1, 1] units; rmse = sqrt(d2 / D); ref_nn_d2: the nearest other reference image's d2 from
+the image idx[:,0]; copy = d2[:,0] < ref_nn_d2) and <out>/neighbours.png, each sample followed by its neighbours.  --space d looks the
+neighbours up in the discriminator's block-normalised feature space (--feature_grid, --feature_pool) instead: neighbours.npz then
+holds idx, d2, ref_nn_d2 and copy, no rmse.""",
+    arguments=(
+        ("--num", dict(type=int, help="images, per class with --classes (default 64; not with --interpolate)")),
+        ("--truncation", dict(type=float, help="draw z from a normal truncated to [-T, T]")),
+        ("--interpolate", dict(type=parse_interpolate, metavar="PAIRS:STEPS",
+                               help="PAIRS spherical interpolations of STEPS points each between random z (one grid row per pair)")),
+        ("--score", dict(action="store_true", default=False, help="add the discriminator's logit and prob of every image to images.npz")),
+        ("--select", dict(choices=["top", "drs"], help="keep the best / rejection-sample by the discriminator's score")),
+        ("--oversample", dict(type=int, metavar="M", help="with --select: draws per image kept (top), per round (drs)")),
+        ("--refine", dict(type=int, metavar="STEPS", help="Adam updates of every latent along the discriminator's gradient")),
+        ("--refine_lr", dict(type=float, metavar="LR", help="with --refine (default 0.02)")),
+        ("--neighbours", dict(metavar="REF.npz", help="nearest images of this file's uint8 `images` array for every sample")),
+        ("--space", dict(choices=["pixel", "d"], help="with --neighbours: pixel space (default) or the discriminator's features"))),
+    shares=("feature_grid", "feature_pool"),
+    defaults={"refine_lr": lambda a: None if a.refine is None else 0.02},
+    check=check_sample,
+    needs_d=lambda a: a.score or a.select or a.refine is not None or a.space == "d",
+    plan=plan_sample,
+    run=run_sample)
 
 
-def probe_main(args, s, job):
-    """--probe: a k-nearest-neighbour classifier on the discriminator's features -> <out>/probe.json and one line"""
-    import json
-    from hipgan.probe import feature_layout
-    (train, ltr), (test, lte) = job
-    r = s.knn_probe(train, ltr, test, lte, k=args.k, grid=args.feature_grid, pool=args.feature_pool)
-    res = {"accuracy": r["accuracy"], "per_class": {str(c): a for c, a in r["per_class"].items()}, "k": args.k, "train": int(train.shape[0]),
-           "test": int(test.shape[0]), "F": feature_layout(s.engine.size, args.feature_grid)[1], "grid": args.feature_grid, "pool": args.feature_pool}
-    os.makedirs(args.out, exist_ok=True)
-    with open(os.path.join(args.out, "probe.json"), "w") as f:
-        json.dump(res, f, indent=1)
-    print(f"probe: {res['test']} test images against {res['train']} training images, k = {args.k}, F = {res['F']}: accuracy "
-          f"{res['accuracy']:.4f} -> {args.out}/probe.json")
-    return 0
+def check_project(a, p):
+    if a.project_feature_weight is not None and not 0 <= a.project_feature_weight < float("inf"):
+        p.error("--project_feature_weight must be finite and >= 0")
 
 
-def score_main(args, s, ref=None):
-    from hipgan._lib import JckError
-    from hipgan.sampler import load_projection_targets
-    u8, labels = load_projection_targets(args.score_images)
-    if ref is not None:
-        from hipgan.neighbours import upscale_steps
-        upscale_steps(ref.shape[1], u8.shape[1], what=args.neighbours)
-    cls = None
-    if args.model == "CGAN":
-        if args.classes:
-            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(u8.shape[0])])
-        elif labels is not None:
-            cls = labels.to(torch.int64).view(-1)
-        else:
-            raise JckError(f"{args.score_images} has no 'labels' array: a CGAN discriminator needs it, or --classes")
-    logit, prob = s.score(u8, cls)
-    os.makedirs(args.out, exist_ok=True)
-    arrays = {"logit": logit.cpu().numpy(), "prob": prob.cpu().numpy()}
-    if cls is not None:
-        arrays["labels"] = cls.numpy().astype(np.int64)
-    np.savez(os.path.join(args.out, "scores.npz"), **arrays)
-    print(f"{u8.shape[0]} images scored (mean prob {float(prob.mean()):.4f}) -> {args.out}/scores.npz")
-    if ref is not None:
-        neighbours_main(args, s, u8.numpy(), ref)
-    return 0
+def plan_project(args):
+    """(target images uint8 [n,S,S,3], start z0 [n,100], class ids [n] or None, images per grid row) of a --project run."""
+    from hipgan.sampler import latents, load_projection_targets
+    u8, labels = load_projection_targets(args.project)
+    n = u8.shape[0]
+    return u8, latents(n, args.seed), class_ids(args, n, labels, args.project), min(n, 8)
+
+
+def run_project(args, s, job):
+    targets, z0, cls, per_row = job
+    feat = {"feature_weight": args.project_feature_weight} if (args.project_feature_weight or 0) > 0 else {}
+    z, loss = s.project(targets, cls, steps=args.project_steps, lr=args.project_lr, prior=args.project_prior, z0=z0, **feat)
+    recon = s.from_latents(z, cls, bn="running", out="uint8").cpu().numpy()
+    write_outputs(args.out, "projected.npz", {"z": z.cpu().numpy(), "loss": loss.cpu().numpy(), "images": recon}, cls,
+                  sheet=(pair_rows(targets.numpy(), recon, per_row), per_row, "projected.png"))
+    print(f"{recon.shape[0]} images projected ({s.which} generator, {args.project_steps} steps, mean loss {float(loss.mean()):.5f}) "
+          f"-> {args.out}/projected.npz, projected.png")
+
+
+PROJECT = Mode(
+    name="project", flag="project",
+    doc="""--project FILE.npz fits a latent to every picture of the file's `images` array (uint8 [n,S,S,3]: an images.npz of this tool, or any
+such array; a CGAN takes the file's `labels` or cycles through --classes) by Adam through the frozen eval-mode generator
+(--project_steps, --project_lr, --project_prior) and writes <out>/projected.npz (z: fp32 [n,100]; loss: the mean squared error of each
+reconstruction in [-1, 1] units; images: the reconstructions, uint8) and <out>/projected.png, each row of targets above the row of
+their reconstructions.  --project_feature_weight W adds W times the mean squared distance between the discriminator's deepest-stage
+activations of G(z) and of the picture to the objective (perceptual projection; needs `model_d`).""",
+    arguments=(
+        ("--project", dict(metavar="FILE.npz", help="fit z to the uint8 [n,S,S,3] `images` array of this file")),
+        ("--project_feature_weight", dict(type=float, metavar="W",
+                                          help="with --project: weight of the feature-matching term on the discriminator's deepest stage"))),
+    check=check_project,
+    needs_d=lambda a: (a.project_feature_weight or 0) > 0,
+    plan=plan_project,
+    run=run_project)
+
+
+def check_inpaint(a, p):
+    if a.critic_weight is not None and not a.critic_weight >= 0:
+        p.error("--critic_weight must be >= 0")
 
 
 def plan_inpaint(args):
@@ -449,36 +417,46 @@ def plan_inpaint(args):
     known = parse_mask(args.mask, u8.shape[1])
     if known.dim() == 3 and known.shape[0] != n:
         raise JckError(f"{args.mask}: {known.shape[0]} masks for {n} images")
-    cls = None
-    if args.model == "CGAN":
-        if args.classes:
-            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(n)])
-        elif labels is not None:
-            cls = labels.to(torch.int64).view(-1)
-        else:
-            raise JckError(f"{args.inpaint} has no 'labels' array: a CGAN needs it, or --classes")
-    return u8, known, cls
+    return u8, known, class_ids(args, n, labels, args.inpaint)
 
 
-def inpaint_main(args, s, job):
-    from train.gan_trainer import _encode_png
+def run_inpaint(args, s, job):
     u8, known, cls = job
     r = s.inpaint(u8, known, cls, steps=args.project_steps, lr=args.project_lr, critic_weight=args.critic_weight, seed=args.seed)
     gen, done = r["generated"].cpu().numpy(), r["completed"].cpu().numpy()
     k3 = (known if known.dim() == 3 else known.unsqueeze(0).expand(u8.shape[0], -1, -1)).numpy()
     masked = u8.numpy() * k3[..., None].astype(np.uint8)              # the holes black
-    os.makedirs(args.out, exist_ok=True)
     arrays = {"z": r["z"].cpu().numpy(), "loss": r["loss"].cpu().numpy(), "term": r["term"].cpu().numpy(), "known": known.numpy(),
               "images": gen, "completed": done}
-    if cls is not None:
-        arrays["labels"] = cls.numpy().astype(np.int64)
-    np.savez(os.path.join(args.out, "inpainted.npz"), **arrays)
     rows = np.stack([masked, gen, done], axis=1).reshape((-1,) + gen.shape[1:])      # one row per picture: masked input, G(z), completed
-    with open(os.path.join(args.out, "inpainted.png"), "wb") as f:
-        f.write(_encode_png(grid_u8(rows, 3)))
+    write_outputs(args.out, "inpainted.npz", arrays, cls, sheet=(rows, 3, "inpainted.png"))
     print(f"{gen.shape[0]} images inpainted ({s.which} generator, {args.project_steps} steps, critic weight {args.critic_weight}, "
           f"mean loss {float(r['loss'].mean()):.5f}) -> {args.out}/inpainted.npz, inpainted.png")
-    return 0
+
+
+INPAINT = Mode(
+    name="inpaint", flag="inpaint", companions=("mask",),
+    doc="""--inpaint FILE.npz --mask SPEC is semantic inpainting (Yeh et al. 2017; Sampler.inpaint): SPEC names the KNOWN pixels of the file's
+pictures ("center:K": a centred K x K hole; "half:left|right|top|bottom": that half is the hole; an .npz / .npy file holding `mask`),
+z is fitted to them alone (--project_steps, --project_lr) with --critic_weight W times -log D(G(z)) as the realism prior (0: none, no
+discriminator needed), and <out>/inpainted.npz holds z, loss, term, known, images (G(z)) and completed (the known pixels of the input,
+the holes from G); <out>/inpainted.png has one row per picture: masked input, G(z), completed.""",
+    arguments=(
+        ("--inpaint", dict(metavar="FILE.npz", help="fill the holes of the uint8 [n,S,S,3] `images` array of this file")),
+        ("--mask", dict(metavar="SPEC", help="with --inpaint: center:K, half:left|right|top|bottom, or an .npz / .npy with `mask`")),
+        ("--critic_weight", dict(type=float, metavar="W", help="with --inpaint: weight of -log D(G(z)) (default 0.003; 0: no critic)"))),
+    defaults={"critic_weight": 0.003},
+    check=check_inpaint,
+    needs_d=lambda a: a.critic_weight > 0,
+    plan=plan_inpaint,
+    run=run_inpaint)
+
+
+def check_anomaly(a, p):
+    if a.anomaly_lam is not None and not 0 <= a.anomaly_lam < 1:
+        p.error("--anomaly_lam must lie in [0, 1)")
+    if a.anomaly_stage is not None and not -1 <= a.anomaly_stage <= 4:
+        p.error("--anomaly_stage must be -1 (the deepest) or a stage of the discriminator")
 
 
 def plan_anomaly(args):
@@ -491,63 +469,153 @@ def plan_anomaly(args):
         flags = f["anomalous"] if "anomalous" in f.files else None
     if flags is not None and (flags.dtype != np.bool_ or flags.shape != (n,)):
         raise JckError(f"{args.anomaly}: 'anomalous' must be bool [{n}], got {flags.dtype} {tuple(flags.shape)}")
-    cls = None
-    if args.model == "CGAN":
-        if args.classes:
-            cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(n)])
-        elif labels is not None:
-            cls = labels.to(torch.int64).view(-1)
-        else:
-            raise JckError(f"{args.anomaly} has no 'labels' array: a CGAN needs it, or --classes")
-    return u8, cls, flags
+    return u8, class_ids(args, n, labels, args.anomaly), flags
 
 
-def anomaly_main(args, s, job):
-    """--anomaly: AnoGAN scores of a file's pictures -> <out>/anomaly.npz, anomaly.png, anomaly.json (with flags) and one line"""
-    import json
+def run_anomaly(args, s, job):
     from hipgan.anomaly import auroc
-    from train.gan_trainer import _encode_png
     u8, cls, flags = job
     r = s.anomaly(u8, cls, steps=args.project_steps, lr=args.project_lr, lam=args.anomaly_lam, stage=args.anomaly_stage, seed=args.seed)
     gen, score = r["generated"].cpu().numpy(), r["score"].cpu().numpy()
     order = np.argsort(-score, kind="stable").astype(np.int64)
-    os.makedirs(args.out, exist_ok=True)
     arrays = {"z": r["z"].cpu().numpy(), "residual": r["residual"].cpu().numpy(), "feature": r["feature"].cpu().numpy(), "score": score,
               "generated": gen, "order": order}
-    if cls is not None:
-        arrays["labels"] = cls.numpy().astype(np.int64)
-    np.savez(os.path.join(args.out, "anomaly.npz"), **arrays)
     diff = np.abs(u8.numpy().astype(np.int16) - gen.astype(np.int16)).astype(np.uint8)
     rows = np.stack([u8.numpy(), gen, diff], axis=1).reshape((-1,) + gen.shape[1:])      # one row per picture: input, G(z), |input - G(z)|
-    with open(os.path.join(args.out, "anomaly.png"), "wb") as f:
-        f.write(_encode_png(grid_u8(rows, 3)))
-    tail = ""
+    res, tail = None, ""
     if flags is not None:
         res = {"auroc": auroc(score, flags), "n": int(u8.shape[0]), "anomalous": int(flags.sum()), "lam": args.anomaly_lam,
                "stage": args.anomaly_stage}
-        with open(os.path.join(args.out, "anomaly.json"), "w") as f:
-            json.dump(res, f, indent=1)
         tail = f", AUROC {res['auroc']:.4f} -> anomaly.json"
+    write_outputs(args.out, "anomaly.npz", arrays, cls, sheet=(rows, 3, "anomaly.png"), record=res and ("anomaly.json", res))
     print(f"{gen.shape[0]} images scored ({s.which} generator, {args.project_steps} steps, lam {args.anomaly_lam}, mean score "
           f"{float(score.mean()):.5f}) -> {args.out}/anomaly.npz, anomaly.png{tail}")
-    return 0
 
 
-def project_main(args, s):
-    from train.gan_trainer import _encode_png
-    targets, z0, cls, per_row = plan_project(args)
-    feat = {"feature_weight": args.project_feature_weight} if (args.project_feature_weight or 0) > 0 else {}
-    z, loss = s.project(targets, cls, steps=args.project_steps, lr=args.project_lr, prior=args.project_prior, z0=z0, **feat)
-    recon = s.from_latents(z, cls, bn="running", out="uint8").cpu().numpy()
-    os.makedirs(args.out, exist_ok=True)
-    arrays = {"z": z.cpu().numpy(), "loss": loss.cpu().numpy(), "images": recon}
-    if cls is not None:
-        arrays["labels"] = cls.numpy().astype(np.int64)
-    np.savez(os.path.join(args.out, "projected.npz"), **arrays)
-    with open(os.path.join(args.out, "projected.png"), "wb") as f:
-        f.write(_encode_png(grid_u8(pair_rows(targets.numpy(), recon, per_row), per_row)))
-    print(f"{recon.shape[0]} images projected ({s.which} generator, {args.project_steps} steps, mean loss {float(loss.mean()):.5f}) "
-          f"-> {args.out}/projected.npz, projected.png")
+ANOMALY = Mode(
+    name="anomaly", flag="anomaly",
+    doc="""--anomaly FILE.npz scores the file's pictures after AnoGAN (Schlegl et al. 2017; Sampler.anomaly): each is projected (--project_steps,
+--project_lr) with a residual term and a feature-matching term on the discriminator's stage --anomaly_stage (default: the deepest),
+and score = (1 - lam) residual + lam feature at the z reached (--anomaly_lam, default 0.1) - mean squared forms, not the paper's L1
+sums.  <out>/anomaly.npz holds z, residual, feature, score, generated (G(z), uint8) and order (indices by falling score);
+<out>/anomaly.png has one row per picture: input, G(z), |input - G(z)|; <out>/anomaly.json (auroc, n, anomalous, lam, stage) is written
+when the file carries a bool `anomalous` [n] array.""",
+    arguments=(
+        ("--anomaly", dict(metavar="FILE.npz", help="AnoGAN anomaly scores of the uint8 [n,S,S,3] `images` array of this file")),
+        ("--anomaly_lam", dict(type=float, metavar="LAM", help="with --anomaly: weight of the feature term in the score, in [0, 1) (default 0.1)")),
+        ("--anomaly_stage", dict(type=int, metavar="K", help="with --anomaly: the discriminator stage matched (default: the deepest)"))),
+    defaults={"anomaly_lam": 0.1},
+    check=check_anomaly,
+    plan=plan_anomaly,
+    run=run_anomaly)
+
+
+def plan_feature_files(args):
+    """[(pictures uint8 [n,S,S,3], labels or None)] of a --features run's file, or of a --probe run's two, which must both have labels"""
+    from hipgan.probe import load_images
+    return [load_images(f, need_labels=bool(args.probe)) for f in ((args.features,) if args.features else (args.probe, args.probe_test))]
+
+
+def run_features(args, s, job):
+    from hipgan.probe import extract, feature_layout
+    (u8, labels), = job
+    f = extract(s.engine, u8, args.feature_grid, args.feature_pool, normalise="none").cpu().numpy()
+    layout, F = feature_layout(s.engine.size, args.feature_grid)
+    arrays = {"features": f, "layout": np.asarray(layout, np.int64), "grid": np.int64(args.feature_grid), "pool": np.str_(args.feature_pool)}
+    if labels is not None:                # the file's labels as they are, for a DCGAN too
+        arrays["labels"] = labels
+    write_outputs(args.out, "features.npz", arrays)
+    print(f"{f.shape[0]} images -> {F} features each (grid {args.feature_grid}, {args.feature_pool}) -> {args.out}/features.npz")
+
+
+FEATURES = Mode(
+    name="features", flag="features",
+    doc="""The discriminator as a feature extractor (Radford et al. 2016, section 5.1; hipgan.probe): --features FILE.npz pools every conv stage's
+activation of the file's pictures (the discriminator's size, or 32x32 data, upscaled as the trainers do) to a --feature_grid raster
+(--feature_pool max|mean) and writes <out>/features.npz (features: fp32 [n,F], unnormalised; layout: int64 [stages,4] rows of stage,
+col0, C, H; grid; pool; labels if the file has them) for an external classifier.""",
+    arguments=(
+        ("--features", dict(metavar="FILE.npz", help="the discriminator's pooled activations of this file's uint8 `images` array")),
+        ("--feature_grid", dict(type=int, choices=[1, 2, 4], help="with --features, --probe, --space d: the pooling raster (default 4)")),
+        ("--feature_pool", dict(choices=["max", "mean"], help="with --features, --probe, --space d (default max)"))),
+    plan=plan_feature_files,
+    run=run_features)
+
+
+def run_probe(args, s, job):
+    from hipgan.probe import feature_layout
+    (train, ltr), (test, lte) = job
+    r = s.knn_probe(train, ltr, test, lte, k=args.k, grid=args.feature_grid, pool=args.feature_pool)
+    res = {"accuracy": r["accuracy"], "per_class": {str(c): a for c, a in r["per_class"].items()}, "k": args.k, "train": int(train.shape[0]),
+           "test": int(test.shape[0]), "F": feature_layout(s.engine.size, args.feature_grid)[1], "grid": args.feature_grid, "pool": args.feature_pool}
+    write_outputs(args.out, record=("probe.json", res))
+    print(f"probe: {res['test']} test images against {res['train']} training images, k = {args.k}, F = {res['F']}: accuracy "
+          f"{res['accuracy']:.4f} -> {args.out}/probe.json")
+
+
+PROBE = Mode(
+    name="probe", flag="probe", companions=("probe_test",),
+    doc="""--probe TRAIN.npz --probe_test TEST.npz (both with `labels`) classifies every test picture by the majority of its --k (default 5)
+nearest training pictures in block-normalised feature space (--feature_grid, --feature_pool) and writes <out>/probe.json (accuracy,
+per_class, k, train, test, F, grid, pool).""",
+    arguments=(
+        ("--probe", dict(metavar="TRAIN.npz", help="k-nearest-neighbour probe of the discriminator's features: the labelled training set")),
+        ("--probe_test", dict(metavar="TEST.npz", help="with --probe: the labelled test set"))),
+    shares=("feature_grid", "feature_pool"),
+    defaults={"k": 5},
+    plan=plan_feature_files,
+    run=run_probe)
+
+
+def plan_score_images(args):
+    """(pictures uint8 [n,S,S,3], class ids [n] or None, the reference pictures of --neighbours or None)"""
+    from hipgan.sampler import load_projection_targets
+    ref = load_reference(args)
+    u8, labels = load_projection_targets(args.score_images)
+    if ref is not None:
+        from hipgan.neighbours import upscale_steps
+        upscale_steps(ref.shape[1], u8.shape[1], what=args.neighbours)
+    return u8, class_ids(args, u8.shape[0], labels, args.score_images), ref
+
+
+def run_score_images(args, s, job):
+    u8, cls, ref = job
+    logit, prob = s.score(u8, cls)
+    write_outputs(args.out, "scores.npz", {"logit": logit.cpu().numpy(), "prob": prob.cpu().numpy()}, cls)
+    print(f"{u8.shape[0]} images scored (mean prob {float(prob.mean()):.4f}) -> {args.out}/scores.npz")
+    if ref is not None:
+        write_neighbours(args, s, u8.numpy(), ref)
+
+
+SCORE_IMAGES = Mode(
+    name="score_images", flag="score_images",
+    doc="""--score_images FILE.npz scores an existing uint8 `images` array into <out>/scores.npz (logit, prob: fp32 [n]; labels for a CGAN);
+--neighbours REF.npz then looks up the neighbours of these pictures, as in a sampling run.""",
+    arguments=(("--score_images", dict(metavar="FILE.npz", help="score the uint8 [n,S,S,3] `images` array of this file")),),
+    shares=("neighbours", "space", "feature_grid", "feature_pool"),
+    check=check_lookup,
+    plan=plan_score_images,
+    run=run_score_images)
+
+
+MODES = [SAMPLE, PROJECT, INPAINT, ANOMALY, FEATURES, PROBE, SCORE_IMAGES]
+__doc__ = HEAD + "\n" + "\n".join(m.doc for m in MODES)
+
+
+def main(argv=None):
+    args = get_arg_parse(argv)
+    from hipgan.sampler import Sampler
+    mode = mode_of(args)
+    job = mode.plan(args)                 # a bad file ends the run before a checkpoint is read or an engine exists
+    with_d = needs_discriminator(args)
+    ckpt = args.checkpoint
+    if with_d:
+        ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
+        check_checkpoint(args, ckpt)
+    s = Sampler.from_checkpoint(ckpt, args.model, which=args.which, prec=args.prec, batch=args.batch_size, **({"with_d": True} if with_d else {}))
+    if args.calibrate:
+        s.calibrate(args.calibrate, seed=args.seed + 2)
+    mode.run(args, s, job)
     return 0
 
 

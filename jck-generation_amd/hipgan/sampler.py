@@ -240,7 +240,7 @@ class Sampler:
         lab = self._labels(labels, z.shape[0])
         if bn != "batch" or z.shape[0] <= self.engine.batch:
             return self.engine.sample(z, lab, bn=bn, out=out)
-        from .engine import chunk_plan
+        from .engine_infer import chunk_plan
         return torch.cat([self.engine.sample(z[lo:hi], None if lab is None else lab[lo:hi], bn=bn, out=out)
                           for lo, hi in chunk_plan(z.shape[0], self.engine.batch)])
 
@@ -260,12 +260,7 @@ class Sampler:
         if select == "refine":
             if bn != "running":
                 raise JckError("refinement follows the eval-mode discriminator's gradient: bn must be 'running'")
-            z0 = latents(int(n), seed, truncation)
-            lab = self._labels(labels, int(n))
-            z, before, after = self.refine(z0, lab, steps=refine_steps, lr=refine_lr)
-            img = self.engine.sample(z, lab, bn="running", out=out)
-            info = {"z": z.cpu(), "logit": after.cpu(), "prob": torch.sigmoid(after).cpu(), "drawn": int(n), "logit_before": before.cpu(),
-                    "logit_after": after.cpu()}
+            img, info = self._images_refine(int(n), seed, truncation, labels, out, refine_steps, refine_lr)
             return (img, info) if return_info else img
         if select is None:
             z = latents(n, seed, truncation)
@@ -282,49 +277,61 @@ class Sampler:
             raise JckError(f"gamma_percentile must lie in [0, 100], got {gamma_percentile}")
         if select == "drs" and m > 50:
             raise JckError(f"select='drs': oversample {m} exceeds the cap of 50 * n draws in its first round; use oversample <= 50")
-        g = torch.Generator().manual_seed(int(seed))
-        draw = lambda k: latents(k, seed, truncation, generator=g)          # successive pieces of ONE seeded stream
-
-        def lab_for(k):
-            if not self.conditional:
-                return None
-            if labels is None:
-                raise JckError("a CGAN sampler needs labels (one class id or one one-hot row for score-guided sampling)")
-            lab = torch.as_tensor(labels)
-            lab = one_hot(lab.view(-1)) if lab.dim() <= 1 else lab.to(torch.int64)
-            if lab.shape != (1, N_CLASS):
-                raise JckError("score-guided sampling of a CGAN takes ONE class (an id or a [1,100] one-hot row)")
-            return lab.expand(k, N_CLASS).contiguous()
-
-        info = {}
-        if select == "top":
-            z = draw(m * n)
-            logit, prob = (t.cpu() for t in self.engine.score_latents(z, lab_for(m * n)))
-            idx = select_top(logit, n)
-            zk, lk, pk, drawn = z[idx], logit[idx], prob[idx], m * n
-        else:
-            burn = self.engine.score_latents(draw(m * n), lab_for(m * n))[0].cpu()
-            finite = burn[~torch.isnan(burn)].double()
-            if finite.numel() == 0:
-                raise JckError("select='drs': every burn-in logit is NaN")
-            M = float(finite.max())
-            gamma = float(torch.quantile(drs_f(finite, M, 0.0), float(gamma_percentile) / 100.0))
-            zs, ls, ps, drawn, kept = [], [], [], 0, 0
-            while kept < n:
-                if drawn + m * n > 50 * n:
-                    raise JckError(f"select='drs': {kept} of {n} accepted after {drawn} draws (cap 50 * n); lower gamma_percentile")
-                z = draw(m * n)
-                u = torch.rand(m * n, generator=g, dtype=torch.float64)
-                logit, prob = (t.cpu() for t in self.engine.score_latents(z, lab_for(m * n)))
-                acc = drs_accept(logit, M, gamma, u)
-                zs.append(z[acc]); ls.append(logit[acc]); ps.append(prob[acc])
-                drawn += m * n
-                kept += int(acc.sum())
-            zk, lk, pk = torch.cat(zs)[:n], torch.cat(ls)[:n], torch.cat(ps)[:n]
-            info.update(max_logit=M, gamma=gamma, burn_in=m * n)
-        img = self.from_latents(zk, None if not self.conditional else lab_for(n), "running", out)
-        info.update(z=zk, logit=lk, prob=pk, drawn=drawn)
+        g = torch.Generator().manual_seed(int(seed))                        # ONE seeded stream: latents, then uniforms, per round
+        info = self._images_top(n, m, g, truncation, labels) if select == "top" else self._images_drs(n, m, g, truncation, labels, gamma_percentile)
+        img = self.from_latents(info["z"], self._one_class(labels, n), "running", out)
         return (img, info) if return_info else img
+
+    def _one_class(self, labels, k):
+        """one-hot [k,100] of the ONE class (an id or a one-hot row) all k draws of a score-guided CGAN run share; None for a DCGAN"""
+        if not self.conditional:
+            return None
+        if labels is None:
+            raise JckError("a CGAN sampler needs labels (one class id or one one-hot row for score-guided sampling)")
+        lab = torch.as_tensor(labels)
+        lab = one_hot(lab.view(-1)) if lab.dim() <= 1 else lab.to(torch.int64)
+        if lab.shape != (1, N_CLASS):
+            raise JckError("score-guided sampling of a CGAN takes ONE class (an id or a [1,100] one-hot row)")
+        return lab.expand(k, N_CLASS).contiguous()
+
+    def _images_refine(self, n, seed, truncation, labels, out, steps, lr):
+        z0 = latents(n, seed, truncation)
+        lab = self._labels(labels, n)
+        z, before, after = self.refine(z0, lab, steps=steps, lr=lr)
+        img = self.engine.sample(z, lab, bn="running", out=out)
+        return img, {"z": z.cpu(), "logit": after.cpu(), "prob": torch.sigmoid(after).cpu(), "drawn": n, "logit_before": before.cpu(),
+                     "logit_after": after.cpu()}
+
+    def _images_top(self, n, m, g, truncation, labels):
+        """the n best of m * n draws of the stream g, best first -> info"""
+        z = latents(m * n, 0, truncation, generator=g)
+        logit, prob = (t.cpu() for t in self.engine.score_latents(z, self._one_class(labels, m * n)))
+        idx = select_top(logit, n)
+        return {"z": z[idx], "logit": logit[idx], "prob": prob[idx], "drawn": m * n}
+
+    def _images_drs(self, n, m, g, truncation, labels, gamma_percentile):
+        """discriminator rejection sampling: a burn-in of m * n draws of the stream g fixes M and gamma, then rounds of m * n latents
+        and as many uniforms are accepted where u < sigmoid(F) until n are kept -> info"""
+        lab = self._one_class(labels, m * n)
+        burn = self.engine.score_latents(latents(m * n, 0, truncation, generator=g), lab)[0].cpu()
+        finite = burn[~torch.isnan(burn)].double()
+        if finite.numel() == 0:
+            raise JckError("select='drs': every burn-in logit is NaN")
+        M = float(finite.max())
+        gamma = float(torch.quantile(drs_f(finite, M, 0.0), float(gamma_percentile) / 100.0))
+        zs, ls, ps, drawn, kept = [], [], [], 0, 0
+        while kept < n:
+            if drawn + m * n > 50 * n:
+                raise JckError(f"select='drs': {kept} of {n} accepted after {drawn} draws (cap 50 * n); lower gamma_percentile")
+            z = latents(m * n, 0, truncation, generator=g)
+            u = torch.rand(m * n, generator=g, dtype=torch.float64)
+            logit, prob = (t.cpu() for t in self.engine.score_latents(z, lab))
+            acc = drs_accept(logit, M, gamma, u)
+            zs.append(z[acc]); ls.append(logit[acc]); ps.append(prob[acc])
+            drawn += m * n
+            kept += int(acc.sum())
+        return {"max_logit": M, "gamma": gamma, "burn_in": m * n, "z": torch.cat(zs)[:n], "logit": torch.cat(ls)[:n], "prob": torch.cat(ps)[:n],
+                "drawn": drawn}
 
     def from_latents_scored(self, z, labels=None, out="uint8"):
         """(images, logit [n], prob [n]): the eval-mode generator's images of z and the discriminator's scores of exactly those

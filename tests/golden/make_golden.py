@@ -26,6 +26,16 @@ only when named:
   infer_bits.json          the same of the _ex / _fm latent entry points with a weight, a critic and a feature term, of
                            jck_engine_score and jck_engine_features, and of the engine's Python methods over them; every digest is
                            computed twice and written only if the two agree; tests/test_infer_bits_gpu.py recomputes them
+
+Two more record generate.py at a commit, the first on the CPU, the second on an MI355X:
+
+    python tests/golden/make_golden.py --only generate_cli --commit <the commit checked out>
+    python tests/golden/make_golden.py --only generate_bits --commit <the commit checked out and built>
+
+  generate_cli.json        which of 8758 command lines the parser refuses, and a digest of the namespace of each it accepts;
+                           tests/test_generate_table_cpu.py reproduces it
+  generate_bits.json       SHA-256 of every array, .png, .json and printed line of one generate.main run per mode and sampling
+                           strategy, each run twice as above; tests/test_generate_bits_gpu.py reproduces it
 """
 import argparse
 import hashlib
@@ -579,13 +589,200 @@ def gen_infer_bits(commit):
     return rec
 
 
+# --------------------------------------------------------------------------------------------
+# generate.py's parser as a table: which command lines it accepts, and the namespace of each (the project's own, on the CPU)
+# --------------------------------------------------------------------------------------------
+CLI_MODELS = ("DCGAN", "CGAN")
+CLI_UNITS_A = [
+    "--num 5", "--num 0", "-b 8", "-b 0", "--seed 3", "--truncation 0.7", "--truncation 0", "--bn batch", "--which ema", "--calibrate 2",
+    "--calibrate -1", "--classes 3,17", "--classes 3", "--interpolate 2:4", "--project f.npz", "--project_steps 7", "--project_steps 0",
+    "--project_lr 0.1", "--project_lr 0", "--project_prior 0.5", "--project_prior -1", "--score", "--select top", "--select top --oversample 4",
+    "--select drs --oversample 4", "--oversample 4", "--select top --oversample 0", "--score_images f.npz", "--neighbours r.npz", "--k 3", "--k 9",
+    "--space d", "--space pixel", "--features f.npz", "--feature_grid 2", "--feature_pool mean", "--probe tr.npz", "--probe_test te.npz",
+    "--probe tr.npz --probe_test te.npz", "--inpaint f.npz", "--mask center:32", "--inpaint f.npz --mask center:32", "--critic_weight 0",
+    "--critic_weight 0.5", "--critic_weight -1", "--refine 5", "--refine 0", "--refine_lr 0.1", "--refine_lr 0", "--project_feature_weight 10",
+    "--project_feature_weight -1", "--project_feature_weight inf", "--anomaly f.npz", "--anomaly_lam 0.3", "--anomaly_lam 1", "--anomaly_stage 2",
+    "--anomaly_stage 5", "--prec f32"]
+CLI_SELECTORS_B = [
+    "--project f.npz", "--score_images f.npz", "--features f.npz", "--probe tr.npz --probe_test te.npz", "--inpaint f.npz --mask center:32",
+    "--anomaly f.npz", "--interpolate 2:4", "--select top --oversample 4", "--select drs --oversample 4", "--refine 5", "--score",
+    "--neighbours r.npz"]
+CLI_UNITS_B = [
+    "--num 5", "--truncation 0.7", "--bn batch", "--calibrate 2", "--classes 3", "--project_steps 7", "--project_prior 0.5", "--score",
+    "--neighbours r.npz", "--k 3", "--space d", "--feature_grid 2", "--feature_pool mean", "--critic_weight 0.5", "--refine 5", "--refine_lr 0.1",
+    "--project_feature_weight 10", "--anomaly_lam 0.3", "--anomaly_stage 2", "--interpolate 2:4", "--select top --oversample 4", "--prec f32"]
+
+
+def cli_lines(which):
+    """the command lines of set "A" (every 0, 1 or 2 of CLI_UNITS_A) or "B" (a complete selector and every pair of CLI_UNITS_B but
+    itself) as strings of units, in the fixture's order; each is tried under -m DCGAN and -m CGAN"""
+    from itertools import combinations
+    if which == "A":
+        return [" ".join(c) for r in (0, 1, 2) for c in combinations(CLI_UNITS_A, r)]
+    return [" ".join((s,) + c) for s in CLI_SELECTORS_B for c in combinations([u for u in CLI_UNITS_B if u != s], 2)]
+
+
+def cli_namespace(model, line):
+    """{attribute: repr(value)} of generate.get_arg_parse on one command line, or None where the parser refuses it"""
+    import contextlib
+    import io
+    import generate
+    argv = ["-m", model, "--checkpoint", "c.pt", "--out", "o"] + line.split()
+    try:
+        with contextlib.redirect_stderr(io.StringIO()):
+            a = generate.get_arg_parse(argv)
+    except SystemExit:
+        return None
+    return {k: repr(v) for k, v in vars(a).items()}
+
+
+def cli_digest(ns, attrs):
+    """"x" for a refused line, else 12 hex digits of the SHA-256 of the namespace's `attrs` as sorted JSON of repr values"""
+    if ns is None:
+        return "x"
+    return hashlib.sha256(json.dumps({k: ns[k] for k in attrs}, sort_keys=True).encode()).hexdigest()[:12]
+
+
+def cli_table(attrs=None):
+    """{"attrs", "A": {model: [digest per line of cli_lines("A")]}, "B": ..., "full": {"model: line": namespace or "x"}} - the full
+    namespace only of the empty and the one-unit lines, so that a difference can be read.  attrs None: every attribute the namespace has."""
+    if attrs is None:
+        attrs = sorted(cli_namespace("DCGAN", ""))
+    rec = {"attrs": list(attrs), "A": {}, "B": {}, "full": {}}
+    for which in ("A", "B"):
+        for model in CLI_MODELS:
+            nss = [cli_namespace(model, line) for line in cli_lines(which)]
+            rec[which][model] = [cli_digest(ns, attrs) for ns in nss]
+            if which == "A":
+                for line, ns in zip(cli_lines("A"), nss):
+                    if line in [""] + CLI_UNITS_A:
+                        rec["full"][f"{model}: {line}"] = "x" if ns is None else {k: ns[k] for k in attrs}
+    return rec
+
+
+def _project_paths():
+    root = os.path.dirname(os.path.dirname(HERE))
+    for p in (root, os.path.join(root, "jck-generation_amd"), os.path.join(root, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+
+
+def gen_generate_cli(commit):
+    assert commit, "--commit: name the commit whose parser is recorded"
+    _project_paths()
+    rec = {"commit": commit, **cli_table()}
+    for which in ("A", "B"):
+        n = sum(len(v) for v in rec[which].values())
+        print(f"set {which}: {n} lines, {sum(d != 'x' for v in rec[which].values() for d in v)} accepted")
+    return rec
+
+
+# --------------------------------------------------------------------------------------------
+# generate.py end to end on the GPU, bit for bit: every file and the stdout line of one run per mode and sampling strategy
+# (the project's own results at a recorded commit).  Shapes: -b 8, 64x64, 5 or 20 images cross a chunk edge; 3 projection steps.
+# --------------------------------------------------------------------------------------------
+# name: (checkpoint, arguments; "@a" / "@c" / "@q": the images.npz of run a / c, and a's pictures with an `anomalous` array)
+GENERATE_RUNS = {
+    "a": ("plain", "--num 20 --seed 3 --truncation 0.7"),
+    "b": ("plain", "--num 20 --seed 3 --truncation 0.7 --bn batch"),
+    "c": ("cgan", "-m CGAN --num 3 --classes 3,17"),
+    "d": ("cgan", "-m CGAN --interpolate 3:4 --classes 3,17"),
+    "e": ("ema", "--which ema --calibrate 2 --num 5"),
+    "f": ("plain", "--num 5 --score"),
+    "g": ("plain", "--num 5 --select top --oversample 3 --score"),
+    "h": ("plain", "--num 5 --select drs --oversample 4"),
+    "i": ("plain", "--num 5 --refine 2"),
+    "j": ("plain", "--project @a --project_steps 3"),
+    "k": ("plain", "--project @a --project_steps 3 --project_feature_weight 10"),
+    "l": ("cgan", "-m CGAN --project @c"),
+    "m": ("plain", "--inpaint @a --mask center:32 --project_steps 3"),
+    "n": ("plain", "--inpaint @a --mask center:32 --project_steps 3 --critic_weight 0"),
+    "o": ("plain", "--anomaly @q --project_steps 3 --anomaly_lam 0.3 --anomaly_stage 1"),
+    "p": ("plain", "--score_images @a --neighbours @a --k 2"),
+    "q": ("plain", "--num 5 --neighbours @a --space d --feature_grid 2 --k 2"),
+    "r": ("plain", "--features @a --feature_grid 2 --feature_pool mean"),
+    "s": ("plain", "--probe @c --probe_test @c --k 3"),
+}
+GENERATE_HOST_ARRAYS = ("z", "labels", "known", "order", "layout")      # (of these only a sampling run's z is never touched by the device)
+DRAW_CAP = "(cap 50 * n)"
+
+
+def generate_workdir(d):
+    """Makes directory d the place the runs of GENERATE_RUNS are started from: the three checkpoints of gpu_util.make_checkpoints, the
+    outputs of runs a and c (which the other runs read) and q.npz -> {"a": digests of run a, "c": of run c}"""
+    from gpu_util import make_checkpoints
+    make_checkpoints(d)
+    done = {k: generate_run(d, k) for k in ("a", "c")}
+    with np.load(os.path.join(str(d), "a", "images.npz")) as f:
+        np.savez(os.path.join(str(d), "q.npz"), images=f["images"], anomalous=np.arange(f["images"].shape[0]) % 3 == 0)
+    return done
+
+
+def generate_run(d, name):
+    """{"file.npz:array" | "file.png" | "file.json" | "stdout": SHA-256} of run `name`, started in directory d (generate_workdir) with
+    relative paths, so that the printed line names no temporary directory.  An array's digest covers dtype, shape and raw bytes."""
+    import contextlib
+    import io
+    import generate
+    ck, line = GENERATE_RUNS[name]
+    argv = ["--checkpoint", ck + ".pt", "-b", "8", "--out", name] + [{"@a": "a/images.npz", "@c": "c/images.npz", "@q": "q.npz"}.get(t, t)
+                                                                    for t in line.split()]
+    cwd, buf = os.getcwd(), io.StringIO()
+    os.chdir(str(d))
+    try:
+        with contextlib.redirect_stdout(buf):
+            assert generate.main(argv) == 0
+        out = {"stdout": hashlib.sha256(buf.getvalue().encode()).hexdigest()}
+        for fn in sorted(os.listdir(name)):
+            path = os.path.join(name, fn)
+            if fn.endswith(".npz"):
+                with np.load(path) as f:
+                    for k in f.files:
+                        a = np.ascontiguousarray(f[k])
+                        out[f"{fn}:{k}"] = hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
+            else:
+                out[fn] = hashlib.sha256(open(path, "rb").read()).hexdigest()
+    finally:
+        os.chdir(cwd)
+    return out
+
+
+def gen_generate_bits(commit):
+    import tempfile
+    assert torch.cuda.is_available(), "generate_bits records what the GPU computes"
+    assert commit, "--commit: name the commit the library and generate.py are those of"
+    _project_paths()
+    from hipgan._lib import JckError
+    rec = {"commit": commit, "device": torch.cuda.get_device_name(0), "runs": {}, "not_reproducible": [], "left_out": {}}
+    with tempfile.TemporaryDirectory() as d:
+        first = generate_workdir(d)
+        for name in GENERATE_RUNS:
+            try:
+                a, b = first.get(name) or generate_run(d, name), generate_run(d, name)      # a key whose two digests differ is not written
+            except JckError as e:
+                assert name == "h" and DRAW_CAP in str(e), (name, e)                       # only rejection sampling's draw cap excuses a run
+                rec["left_out"][name] = str(e)
+                continue
+            assert set(a) == set(b), (name, sorted(set(a) ^ set(b)))
+            rec["not_reproducible"] += [f"{name}.{k}" for k in a if a[k] != b[k]]
+            rec["runs"][name] = {k: v for k, v in a.items() if v == b[k]}
+    bad, total = rec["not_reproducible"], sum(len(r) for r in rec["runs"].values()) + len(rec["not_reproducible"])
+    for k in bad:
+        print("NOT REPRODUCIBLE, left out:", k)
+    assert not [k for k in bad if k.split(":")[-1] in GENERATE_HOST_ARRAYS], "a host-made array did not repeat"
+    assert len(bad) <= 0.05 * total, f"{len(bad)} of {total} digests did not repeat"
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
-    ap.add_argument("--commit", default="", help="latent_plain_bits, infer_bits: the commit the library was built from")
+    ap.add_argument("--commit", default="", help="the project's own fixtures: the commit the code recorded is that of")
     a = ap.parse_args()
-    if a.only in ("latent_plain_bits", "infer_bits"):  # the GPU's results, not the reference's
-        rec = gen_latent_plain_bits(a.commit) if a.only == "latent_plain_bits" else gen_infer_bits(a.commit)
+    own = {"latent_plain_bits": gen_latent_plain_bits, "infer_bits": gen_infer_bits, "generate_cli": gen_generate_cli,
+           "generate_bits": gen_generate_bits}
+    if a.only in own:                                  # the project's own results, not the reference's
+        rec = own[a.only](a.commit)
         rec["_meta"] = {"torch": torch.__version__, "generator": "tests/golden/make_golden.py", "model_seed": MODEL_SEED, "data_seed": DATA_SEED}
         with open(os.path.join(HERE, a.only + ".json"), "w") as f:
             json.dump(rec, f, indent=1)

@@ -69,3 +69,30 @@ def check(got, ref, tol, what=""):
                              f"got {got[tuple(idx)].item():.6g} ref {ref[tuple(idx)].item():.6g}; "
                              f"rel-l2 {((got-ref).norm()/ref.norm()).item():.3e}")
     return m / scale
+
+
+def make_checkpoints(d):
+    """Writes plain.pt (no average), ema.pt (an average whose weights differ from the live ones) and cgan.pt into directory d, each
+    from a fresh batch-8 engine with the oracle's weights -> (plain, ema, cgan) paths."""
+    import os
+    from hipgan.engine import CganEngine, DcganEngine
+    from oracle.gan_oracle import GanOracle
+    orc = GanOracle("dcgan", lr=2e-4, seed=12345)
+    eng = DcganEngine(batch=8, prec="bf16")
+    eng.load_state(orc.g, orc.d)
+    gen = torch.Generator().manual_seed(9)
+    for _ in range(30):          # running statistics that belong to the weights (the initial (0, 1) give a flat grey image in eval mode)
+        eng.sample(torch.randn(8, 100, generator=gen))
+    g, dd = eng.state_dicts()
+    plain, both, cgan = (os.path.join(str(d), f) for f in ("plain.pt", "ema.pt", "cgan.pt"))
+    torch.save({"model_g": g, "model_d": dd}, plain)
+    co = GanOracle("cgan", lr=2e-4, seed=12345)
+    ce = CganEngine(batch=8, prec="bf16")
+    ce.load_state(co.g, co.d)
+    for _ in range(30):
+        ce.sample(torch.randn(8, 100, generator=gen), torch.nn.functional.one_hot(torch.randint(0, 100, (8,), generator=gen), 100))
+    cg, cd = ce.state_dicts()
+    torch.save({"model_g": cg, "model_d": cd}, cgan)
+    ema = {k: (v * 0.5 if k.endswith("conv3.weight") else v.clone()) for k, v in g.items()}
+    torch.save({"model_g": g, "model_d": dd, "model_g_ema": ema}, both)
+    return plain, both, cgan
