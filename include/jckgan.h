@@ -223,6 +223,38 @@ int jck_img_prep(int prec, const float* img_nchw, const float* noise_nchw, float
  * (the transformed image without noise); either may be NULL. */
 int jck_img_prep_u8(int prec, const unsigned char* data, const int64_t* idx, const float* noise, float keep, float mix,
                     void* out_nhwc4, float* out_nchw, int B, int Hs, int Ws, void* stream);
+/* The same pipeline for any source size: Resize((S, S)) of an Hs x Ws image exactly as PIL.Image.resize(BILINEAR) computes it
+ * (what transforms.Resize does to a PIL image) - a horizontal and then a vertical pass of fixed-point taps, each rounded to uint8 -
+ * then ToTensor, Normalize(0.5, 0.5) and the noise mix as above.  S = 64 or 128, 1 <= Hs, Ws <= JCK_RESIZE_MAX_SRC.
+ *
+ * The taps come from a table that the HOST builds (no device call, works without a GPU) and the caller copies to the device once
+ * per geometry.  jck_resize_taps_bytes: its size in bytes, or JCK_E_ARG (negative) for an unsupported geometry.
+ * jck_resize_taps_build fills host_buf (that many bytes) with int32 words:
+ *   [0..7]   header: JCK_RESIZE_TAPS_MAGIC, Hs, Ws, S, KX, KY, 0, 0       (KX, KY: taps per output column / row, see below)
+ *   x axis (source length L = Ws, K = KX), then y axis (L = Hs, K = KY), each (2 + K) * S words:
+ *     lo[S]      first source index of output o
+ *     cnt[S]     taps of output o, 1 <= cnt <= K, lo + cnt <= L
+ *     k[K][S]    k[j][o] = weight of source index lo[o] + j in units of 2^-22 (0 for j >= cnt[o]); tap-major, so neighbouring
+ *                outputs read neighbouring words
+ *   with, in IEEE double and in this order, never contracted: scale = L / S, support = max(scale, 1), K = (int)ceil(support) * 2 + 1,
+ *   center = (o + 0.5) * scale, lo = max((int)(center - support + 0.5), 0), cnt = min((int)(center + support + 0.5), L) - lo,
+ *   w_j = max(1 - |(j + lo - center + 0.5) * (1 / support)|, 0) divided by their sum, k_j = (int)(0.5 + w_j * 2^22).
+ *   out[o] = clip((2^21 + sum_j k_j * src[lo + j]) >> 22, 0, 255); an axis with L == S has the single weight 2^22.
+ *
+ * jck_img_prep_u8_any: data uint8 [Ntot][3][Hs][Ws]; idx int64 [B] or NULL (the first B); flip uint8 [B] or NULL, non-zero = the
+ * image is mirrored left-right in the source (column x reads Ws-1-x) before the resize; noise fp32 [B][3][S][S] or NULL; rng device
+ * uint32[4] or NULL (in-kernel Philox noise keyed on the output pixel, as jck_img_prep_u8_rng; noise wins when both are given);
+ * out_nhwc4 [B][S][S][4] T and / or out_nchw fp32 [B][3][S][S] (the transformed image without noise), either may be NULL;
+ * taps_dev: the table above in device memory.  A table built for another geometry leaves the outputs untouched.  One workgroup
+ * per (image, band of output rows): horizontal pass of the band's source rows into LDS, vertical pass out of it; integer
+ * arithmetic up to the uint8 result, no atomics.  At 32x32 -> 64 the result is jck_img_prep_u8's bit for bit. */
+#define JCK_RESIZE_MAX_SRC 1024
+#define JCK_RESIZE_TAPS_MAGIC 0x7a736572
+long long jck_resize_taps_bytes(int Hs, int Ws, int S);
+int jck_resize_taps_build(int Hs, int Ws, int S, void* host_buf);
+int jck_img_prep_u8_any(int prec, const unsigned char* data, const int64_t* idx, const unsigned char* flip, const float* noise,
+                        const unsigned* rng, int tensor_id, float keep, float mix, void* out_nhwc4, float* out_nchw, int B, int Hs,
+                        int Ws, int S, const void* taps_dev, void* stream);
 /* Evaluation branch (train/dcgan_trainer.py:202-206, train/cgan_trainer.py:227-231): out = (resize(pre_scale*in + pre_shift,
  * [OH,OW]) - mean[c]) / std[c], bilinear with align_corners = False exactly as aten::upsample_bilinear2d (what
  * torchvision.transforms.functional.resize does to a tensor; an upscale, so antialiasing is moot).  NCHW fp32 in / out;
@@ -468,6 +500,13 @@ typedef struct jck_step_inputs {
    * indices int64 [B]; the step applies the input transform itself (jck_img_prep_u8) */
   const unsigned char* real_u8;
   const int64_t* real_idx;
+  /* any-size dataset (optional; all zero = the 32x32 -> 64 path above): real_u8 is uint8 [Ntot,3,real_h,real_w], real_taps the
+   * device copy of jck_resize_taps_build(real_h, real_w, S) for the engine's image size S, real_flip uint8 [B] (or NULL) mirrors
+   * images left-right before the resize; the step then applies jck_img_prep_u8_any.  Caller's device memory: the step neither
+   * allocates nor copies. */
+  int real_h, real_w;
+  const unsigned char* real_flip;
+  const void* real_taps;
 } jck_step_inputs;
 int jck_engine_phase(jck_engine*, int phase, const jck_step_inputs* in, void* stream);
 /* device pointer to float[8]: loss_d, loss_g, D(x), D(G(z))_1, D(G(z))_2, gp, loss_real, loss_fake (valid after PHASE_G_STEP) */

@@ -6,6 +6,7 @@
 #include "ew_optim.hpp"
 #include "bnres.hpp"
 #include "latent.hpp"
+#include "resize.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -44,7 +45,7 @@ static constexpr KernelInfo KERNELS[] = {
     {nullptr, "bn_act_fwd"}, {nullptr, "bn_bwd_resident"}, {nullptr, "bn_bwd_3launch"},
     {nullptr, "latent_loss"}, {nullptr, "latent_adam"},
     {nullptr, "conv_up_mask"}, {nullptr, "leaky_affine_bwd"}, {nullptr, "critic_ds"}, {nullptr, "latent_loss_ex"},
-    {nullptr, "feat_match"}};
+    {nullptr, "feat_match"}, {nullptr, "img_prep_u8_any"}};
 #undef SAME
 static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "KERNELS and the KernelId offsets disagree");
 // the id arithmetic against the table, row by row: what every launch site's id resolves to (the affine 16 x 256 form with 8..32 gathered
@@ -62,7 +63,7 @@ static_assert(row(kid_igemm<PrecBf16, 128, 128, 1>(), "igemm<bf16,128,128>", "ig
               row(kid_wgrad<PrecBf16x3, 128, 128, 1>(), "wgrad<bf16x3,128,128>", "wgrad<bf16x3,128,128>") && row(kid_wgrad<PrecBf16x3, 128, 64, 1>(), "wgrad<bf16x3,128,64>", "wgrad<bf16x3,128,64>") && row(kid_wgrad<PrecBf16x3, 64, 64, 2>(), "wgrad<bf16x3,64,64,img>", "wgrad<bf16x3,64,64,img>") && row(kid_wgrad<PrecBf16x3, 64, 64, 1>(), "wgrad<bf16x3,64,64>", "wgrad<bf16x3,64,64>") &&
               same_str(KERNELS[K_LATENT_LOSS].label, "latent_loss") && same_str(KERNELS[K_LATENT_ADAM].label, "latent_adam") &&
               same_str(KERNELS[K_CONV_UP_MASK].label, "conv_up_mask") && same_str(KERNELS[K_LEAKY_AFFINE_BWD].label, "leaky_affine_bwd") &&
-              same_str(KERNELS[K_CRITIC_DS].label, "critic_ds") && same_str(KERNELS[K_LATENT_LOSS_EX].label, "latent_loss_ex") && same_str(KERNELS[K_FEAT_MATCH].label, "feat_match") &&
+              same_str(KERNELS[K_CRITIC_DS].label, "critic_ds") && same_str(KERNELS[K_LATENT_LOSS_EX].label, "latent_loss_ex") && same_str(KERNELS[K_FEAT_MATCH].label, "feat_match") && same_str(KERNELS[K_IMG_PREP_ANY].label, "img_prep_u8_any") &&
               same_str(KERNELS[K_BN_ACT_FWD].label, "bn_act_fwd") && same_str(KERNELS[K_BN_BWD_RES].label, "bn_bwd_resident") && same_str(KERNELS[K_BN_BWD_3L].label, "bn_bwd_3launch") &&
               kid_igemm<PrecBf16, 16, 256, 0>() == kid_igemm<PrecBf16, 16, 256, 1>() && !KERNELS[K_IGEMM + 3].launch,
               "KERNELS and the kid_* functions disagree");
@@ -459,6 +460,87 @@ extern "C" int jck_img_prep_u8(int prec, const unsigned char* data, const int64_
   DISPATCH_T(prec, hipLaunchKernelGGL(img_prep_u8_kernel<T>, dim3(ew_grid((long long)B * 4 * Hs * Ws)), dim3(256), 0,
                                       (hipStream_t)stream, data, (const long long*)idx, noise, keep, mix, (T*)out_nhwc4, out_nchw, B,
                                       Hs, Ws));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// ---- any-size input pipeline (resize.hpp): the tap tables are made on the host, in Pillow's double arithmetic and order
+// (ImagingResample's precompute_coeffs + normalize_coeffs_8bpc with the bilinear filter) ----
+static int resize_geometry_ok(int Hs, int Ws, int S) {
+  return (S == 64 || S == 128) && Hs >= 1 && Ws >= 1 && Hs <= JCK_RESIZE_MAX_SRC && Ws <= JCK_RESIZE_MAX_SRC;
+}
+static int resize_ksize(int L, int S) {
+  const double scale = (double)L / (double)S, support = scale < 1.0 ? 1.0 : scale;
+  return (int)std::ceil(support) * 2 + 1;
+}
+extern "C" long long jck_resize_taps_bytes(int Hs, int Ws, int S) {
+  if (!resize_geometry_ok(Hs, Ws, S)) JCK_FAIL(JCK_E_ARG, "resize taps: S must be 64 or 128 and 1 <= Hs, Ws <= " + std::to_string(JCK_RESIZE_MAX_SRC));
+  return 4ll * (RESIZE_HDR + (long long)S * (2 + resize_ksize(Ws, S)) + (long long)S * (2 + resize_ksize(Hs, S)));
+}
+// one axis: lo[S], cnt[S], k[K][S] (include/jckgan.h); every product, sum and quotient below is rounded on its own
+static void resize_axis_taps(int L, int S, int K, int* lo_out, int* cnt_out, int* k_out) {
+#pragma clang fp contract(off)
+  const double scale = (double)L / (double)S;
+  const double filterscale = scale < 1.0 ? 1.0 : scale;
+  const double support = 1.0 * filterscale;
+  const double ss = 1.0 / filterscale;
+  double w[2 * JCK_RESIZE_MAX_SRC / 64 + 3];                  // K <= 2 * ceil(1024 / 64) + 1
+  for (int o = 0; o < S; ++o) {
+    const double center = (o + 0.5) * scale;
+    int lo = (int)(center - support + 0.5);
+    if (lo < 0) lo = 0;
+    int hi = (int)(center + support + 0.5);
+    if (hi > L) hi = L;
+    const int cnt = hi - lo;
+    double ww = 0.0;
+    for (int j = 0; j < cnt; ++j) {
+      double a = (j + lo - center + 0.5) * ss;
+      if (a < 0.0) a = -a;
+      w[j] = a < 1.0 ? 1.0 - a : 0.0;
+      ww += w[j];
+    }
+    for (int j = 0; j < K; ++j) {
+      double v = 0.0;
+      if (j < cnt) v = ww != 0.0 ? w[j] / ww : w[j];
+      k_out[j * S + o] = j < cnt ? (int)(0.5 + v * (double)(1 << 22)) : 0;      // bilinear weights are never negative
+    }
+    lo_out[o] = lo;
+    cnt_out[o] = cnt;
+  }
+}
+extern "C" int jck_resize_taps_build(int Hs, int Ws, int S, void* host_buf) {
+  if (!resize_geometry_ok(Hs, Ws, S)) JCK_FAIL(JCK_E_ARG, "resize taps: S must be 64 or 128 and 1 <= Hs, Ws <= " + std::to_string(JCK_RESIZE_MAX_SRC));
+  if (!host_buf) JCK_FAIL(JCK_E_ARG, "resize taps: host_buf is NULL");
+  const int KX = resize_ksize(Ws, S), KY = resize_ksize(Hs, S);
+  int* t = (int*)host_buf;
+  const int hdr[RESIZE_HDR] = {(int)JCK_RESIZE_TAPS_MAGIC, Hs, Ws, S, KX, KY, 0, 0};
+  memcpy(t, hdr, sizeof(hdr));
+  int* ax = t + RESIZE_HDR;
+  resize_axis_taps(Ws, S, KX, ax, ax + S, ax + 2 * S);
+  ax += (2 + KX) * S;
+  resize_axis_taps(Hs, S, KY, ax, ax + S, ax + 2 * S);
+  return JCK_OK;
+}
+extern "C" int jck_img_prep_u8_any(int prec, const unsigned char* data, const int64_t* idx, const unsigned char* flip, const float* noise,
+                                   const unsigned* rng, int tensor_id, float keep, float mix, void* out_nhwc4, float* out_nchw, int B,
+                                   int Hs, int Ws, int S, const void* taps_dev, void* stream) {
+  if (!data || !taps_dev || B < 1 || B > (1 << 24)) JCK_FAIL(JCK_E_ARG, "img_prep_u8_any: data and taps_dev must be set, 1 <= B <= 2^24");
+  if (!resize_geometry_ok(Hs, Ws, S)) JCK_FAIL(JCK_E_ARG, "img_prep_u8_any: S must be 64 or 128 and 1 <= Hs, Ws <= " + std::to_string(JCK_RESIZE_MAX_SRC));
+  if (prec != JCK_PREC_BF16 && !prec_f32_storage(prec)) JCK_FAIL(JCK_E_ARG, "bad prec");
+  if ((uintptr_t)taps_dev % 4) JCK_FAIL(JCK_E_ARG, "img_prep_u8_any: taps_dev must be 4-byte aligned");
+  if (!out_nhwc4 && !out_nchw) return JCK_OK;
+  // source rows a band of output rows can touch: (band - 1) * scale + 2 * support + 1 <= band * Hs / S + 2 * ceil(Hs / S) + 2
+  int band = RESIZE_BAND, rows = 0;
+  for (;; band >>= 1) {
+    rows = std::min(band * Hs / S + 2 * ((Hs + S - 1) / S) + 2, Hs);
+    if ((long long)rows * 3 * S <= 65536 || band == 1) break;
+  }
+  if ((long long)rows * 3 * S > 65536) JCK_FAIL(JCK_E_ARG, "img_prep_u8_any: no band of output rows fits 64 KiB of LDS");
+  const hipStream_t st = (hipStream_t)stream;
+  ProfScope prof(K_IMG_PREP_ANY, 0.0, st, (double)B * (3.0 * Hs * Ws + (double)S * S * (out_nhwc4 ? (prec == JCK_PREC_BF16 ? 8 : 16) : 12)));
+  DISPATCH_T(prec, hipLaunchKernelGGL(img_prep_u8_any_kernel<T>, dim3((unsigned)B * (S / band)), dim3(RESIZE_THREADS), (size_t)rows * 3 * S, st,
+                                      data, (const long long*)idx, flip, noise, rng, (unsigned)tensor_id, keep, mix, (T*)out_nhwc4, out_nchw,
+                                      Hs, Ws, S, resize_ksize(Ws, S), resize_ksize(Hs, S), band, rows, (unsigned)JCK_RESIZE_TAPS_MAGIC,
+                                      (const int*)taps_dev));
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }

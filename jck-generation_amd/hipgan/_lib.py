@@ -14,7 +14,8 @@ vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_d
 class StepInputs(C.Structure):
     _fields_ = [("real_nchw", vp), ("noise_real", vp), ("z", vp), ("noise_fake", vp), ("alpha", vp),
                 ("lr", f32), ("grad_scale", f32), ("step", i32), ("labels", vp), ("drop_mask", vp * 4),
-                ("real_u8", vp), ("real_idx", vp)]
+                ("real_u8", vp), ("real_idx", vp),
+                ("real_h", i32), ("real_w", i32), ("real_flip", vp), ("real_taps", vp)]
 
 
 # name -> (restype, argtypes)      (keep in sync with include/jckgan.h; tests/test_abi.py checks the symbol list)
@@ -69,6 +70,9 @@ PROTOS = {
     "jck_img_prep": (i32, [i32, vp, vp, f32, f32, vp, i32, i32, vp]),
     "jck_resize_norm": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp]),
     "jck_img_prep_u8": (i32, [i32, vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
+    "jck_resize_taps_bytes": (i64, [i32, i32, i32]),
+    "jck_resize_taps_build": (i32, [i32, i32, i32, vp]),
+    "jck_img_prep_u8_any": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "jck_nhwc4_to_nchw": (i32, [i32, vp, vp, i32, i32, vp]),
     "jck_axpy_noise": (i32, [i32, vp, vp, f32, f32, vp, i32, i32, vp]),
     "jck_interp": (i32, [i32, vp, vp, vp, vp, i32, i32, vp]),

@@ -72,25 +72,70 @@ class _GraphUnavailable(JckError):
     """Capture of a step segment failed before anything of the step ran: the engine falls back to eager launches."""
 
 
-class DeviceBatch:
-    """A training batch as indices into a uint8 image dataset that lives in HBM ([N,3,32,32], the CIFAR pickle layout).
-    The step gathers and transforms it on the device (jck_img_prep_u8: the reference's Resize(64) / ToTensor /
-    Normalize(0.5, 0.5), preprocess/dcgan_data_preprocessor.py:38-43, bit-exact) - no per-step host->device image copy."""
+RESIZE_MAX_SRC = 1024              # include/jckgan.h: JCK_RESIZE_MAX_SRC
+_TAPS = {}
 
-    def __init__(self, data_u8, idx):
+
+def resize_taps_host(hs, ws, size):
+    """The tap table of Resize((size, size)) for hs x ws sources (jck_resize_taps_build; layout in include/jckgan.h) as an int32
+    host tensor.  Pure host arithmetic: works without a GPU."""
+    dll = load_library()
+    nbytes = dll.jck_resize_taps_bytes(int(hs), int(ws), int(size))
+    if nbytes < 0:
+        raise JckError(dll.jck_last_error().decode())
+    buf = torch.zeros(nbytes // 4, dtype=torch.int32)
+    if dll.jck_resize_taps_build(int(hs), int(ws), int(size), buf.data_ptr()) != 0:
+        raise JckError(dll.jck_last_error().decode())
+    return buf
+
+
+def resize_taps(hs, ws, size, device):
+    """That table in `device`'s memory: one upload per (hs, ws, size, device), kept for the life of the process."""
+    device = torch.device(device)
+    key = (int(hs), int(ws), int(size), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _TAPS:
+        _TAPS[key] = resize_taps_host(hs, ws, size).to(device)
+    return _TAPS[key]
+
+
+class DeviceBatch:
+    """A training batch as indices into a uint8 image dataset that lives in HBM ([N,3,H,W] planar; [N,3,32,32] is the CIFAR
+    pickle layout).  The step gathers and transforms it on the device - the reference's Resize / ToTensor / Normalize(0.5, 0.5),
+    preprocess/dcgan_data_preprocessor.py:38-43, bit-exact against Pillow - with no per-step host->device image copy.
+    size: the output side, 64 or 128 (a non-square source is resized to size x size).  flip: uint8 [B] or None, non-zero mirrors
+    the image left-right before the resize.  A [N,3,32,32] dataset with size 64 and no flips runs jck_img_prep_u8 (the 2x special
+    case, as before); everything else runs jck_img_prep_u8_any with the tap table of its geometry."""
+
+    def __init__(self, data_u8, idx, size=64, flip=None):
         if data_u8.dtype != torch.uint8 or not data_u8.is_cuda or not data_u8.is_contiguous():
             raise JckError("DeviceBatch: dataset must be a contiguous uint8 CUDA tensor")
+        if data_u8.dim() != 4 or data_u8.shape[1] != 3 or not (1 <= data_u8.shape[2] <= RESIZE_MAX_SRC and 1 <= data_u8.shape[3] <= RESIZE_MAX_SRC):
+            raise JckError(f"DeviceBatch: dataset must be uint8 [N,3,H,W] with 1 <= H, W <= {RESIZE_MAX_SRC}, got {tuple(data_u8.shape)}")
+        if size not in (64, 128):
+            raise JckError(f"DeviceBatch: size must be 64 or 128, got {size}")
         self.data = data_u8
         self.idx = idx.to(data_u8.device, torch.int64).contiguous()
+        self.out_size = int(size)
+        self.flip = None
+        if flip is not None:
+            self.flip = flip.to(data_u8.device, torch.uint8).contiguous()
+            if self.flip.numel() != self.idx.numel():
+                raise JckError(f"DeviceBatch: flip has {self.flip.numel()} entries for {self.idx.numel()} indices")
+        h, w = int(data_u8.shape[2]), int(data_u8.shape[3])
+        self.taps = None if (h, w, self.out_size) == (32, 32, 64) and flip is None else resize_taps(h, w, self.out_size, data_u8.device)
 
     def size(self, dim=0):
-        return (self.idx.numel(), 3, 64, 64)[dim]
+        return (self.idx.numel(), 3, self.out_size, self.out_size)[dim]
 
     def materialize(self):
-        """The transformed batch as fp32 NCHW [B,3,64,64] (what the reference's DataLoader would have yielded)."""
-        b = self.idx.numel()
-        out = torch.empty(b, 3, 64, 64, dtype=torch.float32, device=self.data.device)
-        lib.jck_img_prep_u8(PREC_F32, self.data, self.idx, None, 1.0, 0.0, None, out, b, 32, 32, cur_stream())
+        """The transformed batch as fp32 NCHW [B,3,size,size] (what the reference's DataLoader would have yielded)."""
+        b, s = self.idx.numel(), self.out_size
+        out = torch.empty(b, 3, s, s, dtype=torch.float32, device=self.data.device)
+        if self.taps is None:
+            lib.jck_img_prep_u8(PREC_F32, self.data, self.idx, None, 1.0, 0.0, None, out, b, 32, 32, cur_stream())
+        else:
+            lib.jck_img_prep_u8_any(PREC_F32, self.data, self.idx, self.flip, None, None, 0, 1.0, 0.0, None, out, b, self.data.shape[2],
+                                    self.data.shape[3], s, self.taps, cur_stream())
         return out
 
 
@@ -353,10 +398,14 @@ class DcganEngine(EngineInference):
         si = StepInputs()
         keep = []
         if isinstance(real, DeviceBatch):           # indices into a uint8 dataset resident in HBM: the step transforms them itself
-            if real.size(0) != B or tuple(real.data.shape[1:]) != (3, 32, 32):
-                raise JckError(f"DeviceBatch must index {B} images of a uint8 [N,3,32,32] dataset")
+            if real.size(0) != B or (real.taps is not None and real.size(2) != S):
+                raise JckError(f"DeviceBatch must index {B} images and resize them to {S}x{S}, got {real.size(0)} to {real.size(2)}x{real.size(2)}")
             keep += [real.data, real.idx]
             si.real_u8, si.real_idx = real.data.data_ptr(), real.idx.data_ptr()
+            if real.taps is not None:               # any other geometry or flips: the general kernel with its tap table
+                keep += [real.taps, real.flip]
+                si.real_h, si.real_w, si.real_taps = real.data.shape[2], real.data.shape[3], real.taps.data_ptr()
+                si.real_flip = real.flip.data_ptr() if real.flip is not None else None
             real = None
         elif real is not None and (real.shape != (B, 3, S, S) or real.dtype != torch.float32):
             raise JckError(f"real must be float32 [{B},3,{S},{S}], got {tuple(real.shape)} {real.dtype}")
@@ -470,7 +519,8 @@ class DcganEngine(EngineInference):
             f32 = dict(dtype=torch.float32, device=dev)
             sb = {"nbuf": torch.empty(2 * B * 3 * S * S + B * 100, **f32), "alpha": torch.empty(B, 1, 1, 1, **f32),
                   "z": torch.empty(B, 100, 1, 1, **f32),
-                  "real": torch.empty(B, 3, S, S, **f32), "idx": torch.empty(B, dtype=torch.int64, device=dev)}
+                  "real": torch.empty(B, 3, S, S, **f32), "idx": torch.empty(B, dtype=torch.int64, device=dev),
+                  "flip": torch.empty(B, dtype=torch.uint8, device=dev)}
             if self.family == 1:
                 sb["labels"] = torch.empty(B, 100, dtype=torch.int64, device=dev)
                 sb["u"] = torch.empty(4, B, 256, **f32)
@@ -516,7 +566,8 @@ class DcganEngine(EngineInference):
         if isinstance(real, DeviceBatch):
             if real.size(0) != B:
                 raise JckError(f"DeviceBatch must index {B} images")
-            real = DeviceBatch(real.data, sb["idx"].copy_(real.idx, non_blocking=True))
+            flip = sb["flip"].copy_(real.flip, non_blocking=True) if real.flip is not None else None
+            real = DeviceBatch(real.data, sb["idx"].copy_(real.idx, non_blocking=True), real.out_size, flip)
         else:
             if real.shape != (B, 3, S, S) or real.dtype != torch.float32:
                 raise JckError(f"real must be float32 [{B},3,{S},{S}], got {tuple(real.shape)} {real.dtype}")
@@ -546,7 +597,9 @@ class DcganEngine(EngineInference):
                 segs = ([[PHASE_D_LOSS, PHASE_D_GP]], [[PHASE_D_STEP, PHASE_G_LOSS]], [[PHASE_G_STEP]])
             else:
                 segs = ([[PHASE_D_LOSS, PHASE_D_GP, PHASE_D_STEP, PHASE_G_LOSS, PHASE_G_STEP]], [], [])
-            kind = (("u8", real.data.data_ptr()) if isinstance(real, DeviceBatch) else ("f32",)) + (nz.get("n1") is None, nz.get("z") is None, nz.get("alpha") is None, nz.get("m1") is None)
+            # (a captured graph bakes the dataset's address, its geometry, the tap table and whether a flip vector is read)
+            kind = (("u8", real.data.data_ptr(), tuple(real.data.shape[2:]), real.out_size, real.taps.data_ptr() if real.taps is not None else 0,
+                     real.flip is not None) if isinstance(real, DeviceBatch) else ("f32",)) + (nz.get("n1") is None, nz.get("z") is None, nz.get("alpha") is None, nz.get("m1") is None)
             handle = None
 
             launched = []

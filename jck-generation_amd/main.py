@@ -53,7 +53,21 @@ def get_arg_parse(argv=None):
     p.add_argument("--extra_metrics", type=int, choices=(0, 1), default=argparse.SUPPRESS,
                    help="1: every evaluation also reports KID, improved precision / recall (CGAN: intra-KID too) on one more log "
                         "line and keeps 'kid' (CGAN: 'intra_kid') best checkpoints; absent or 0 = the reference's scores only")
-    return p.parse_args(argv)
+    p.add_argument("--data", type=str, default=argparse.SUPPRESS, metavar="FILE.npz",
+                   help="train on this dataset instead of CIFAR-100: `images` uint8 [N,H,W,3] (any H, W up to 1024; what generate.py "
+                        "writes) and `labels` int [N] (CGAN: required, 0..99; DCGAN: optional).  Every image is resized to "
+                        "image_size x image_size exactly as transforms.Resize((S, S)) would: a non-square source is squeezed, so crop "
+                        "first if the aspect matters")
+    p.add_argument("--image_size", type=int, choices=(64, 128), default=argparse.SUPPRESS,
+                   help="DCGAN: side of the generated and the training images; 128 builds the nets with one more stride-2 stage "
+                        "(absent = 64, the reference)")
+    p.add_argument("--mirror", type=int, choices=(0, 1), default=argparse.SUPPRESS,
+                   help="1: mirror every training image left-right with probability 1/2, drawn anew each epoch (needs the "
+                        "device-resident input pipeline); absent or 0 = the reference, which has no augmentation")
+    args = p.parse_args(argv)
+    if getattr(args, "image_size", 64) != 64 and args.model != ModelEnum.DCGAN:
+        p.error("--image_size 128: the 128x128 topology exists for DCGAN only (CGAN's Linear(8392,256) fixes 64x64)")
+    return args
 
 
 def main(args: argparse.Namespace):
@@ -77,7 +91,8 @@ def main(args: argparse.Namespace):
         from train.dcgan_trainer import DCGANTrainer
         data_pre = DCGANDataPreprocessor(args)
         data_pre.transform_data()
-        trainer = DCGANTrainer(args, DCGAN.Generator(), DCGAN.Discriminator(), data_pre)
+        size = {"image_size": args.image_size} if getattr(args, "image_size", 64) != 64 else {}
+        trainer = DCGANTrainer(args, DCGAN.Generator(**size), DCGAN.Discriminator(**size), data_pre)
     else:
         from model import CGAN
         from preprocess.cgan_data_preprocessor import CGANDataPreprocessor

@@ -23,11 +23,13 @@ class OneHotEncoder:
 
 
 class CGANDataPreprocessor(DCGANDataPreprocessor):
+    NEED_LABELS = True          # --data: the file must carry `labels` in 0..99
+
     def __init__(self, args, synthetic_size=None):
         super().__init__(args, synthetic_size)
         self.idx_to_labels = {i: str(i) for i in range(100)}
         meta = os.path.join(CIFAR_DIR, "meta")
-        if synthetic_size is None and os.path.exists(meta):
+        if synthetic_size is None and self.data_file is None and os.path.exists(meta):
             with open(meta, "rb") as f:
                 names = pickle.load(f, encoding="latin1")["fine_label_names"]
             self.idx_to_labels = {i: n for i, n in enumerate(names)}
@@ -37,7 +39,7 @@ class CGANDataPreprocessor(DCGANDataPreprocessor):
             self.transform_data()
         onehot = torch.nn.functional.one_hot(torch.tensor(self.targets, dtype=torch.int64), 100).to(torch.int64)
         if self._train.dtype == torch.uint8:                                       # device-resident dataset: labels live in HBM too
-            return DeviceLoader(self._train, self.batch_size, onehot=onehot.to(self._train.device), seed=12345), self._metric
+            return self._device_loader(onehot=onehot.to(self._train.device)), self._metric
         ds = torch.utils.data.TensorDataset(self._train, onehot)
         sampler = None
         if torch.distributed.is_available() and torch.distributed.is_initialized():

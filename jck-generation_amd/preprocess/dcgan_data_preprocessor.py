@@ -11,7 +11,13 @@ MI355X-first layout: the uint8 dataset (150 MB for CIFAR) is copied to HBM ONCE;
 workers.  The transform is bit-exact against the reference's: transforms.Resize on a PIL image is PIL's bilinear resize,
 whose 2x upscale is a horizontal and a vertical 3:1 pass each rounded to uint8 (`resize2x_pil_u8`, pinned to PIL by
 tests/golden/resize_u8.json).  Without a GPU (and with JCKGAN_DEVICE_DATA=0) the same arithmetic runs as tensor ops on the
-host and a torch DataLoader is returned, as in the reference."""
+host and a torch DataLoader is returned, as in the reference.
+
+Opt-in (main.py --data / --image_size / --mirror): any uint8 image set from an `images.npz` (`load_npz_dataset`) instead of CIFAR-100,
+resized to 64x64 or 128x128 from any source size with Pillow's general bilinear taps (`resize_pil_u8` on the host,
+jck_img_prep_u8_any in the step; pinned to PIL by tests/golden/resize_any_u8.json), and left-right flips drawn per epoch
+(`DeviceLoader(mirror=True)`, device-resident pipeline only)."""
+import math
 import os
 import pickle
 
@@ -21,6 +27,7 @@ import torch
 from logger.main_logger import MainLogger
 
 CIFAR_DIR = os.path.join(".", "data", "cifar-100-python")
+RESIZE_MAX_SRC = 1024              # include/jckgan.h: JCK_RESIZE_MAX_SRC
 
 
 class _TensorSource:
@@ -52,21 +59,65 @@ def resize2x_pil_u8(x):
     return up(up(x, -1), -2).to(torch.uint8)
 
 
+def _axis_taps(length, size):
+    """Pillow's bilinear taps of one axis (ImagingResample: precompute_coeffs + normalize_coeffs_8bpc) -> (lo [size], k [size, K]
+    int64 weights in units of 2^-22, zero past an output's last tap).  Python floats are IEEE doubles and every operation below is
+    rounded on its own, as in Pillow's C: the same integers (jck_resize_taps_build computes them for the device kernel)."""
+    scale = length / size
+    support = max(scale, 1.0)
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / support
+    lo = torch.zeros(size, dtype=torch.int64)
+    k = torch.zeros(size, ksize, dtype=torch.int64)
+    for o in range(size):
+        center = (o + 0.5) * scale
+        first = max(int(center - support + 0.5), 0)
+        cnt = min(int(center + support + 0.5), length) - first
+        w = [max(1.0 - abs((j + first - center + 0.5) * ss), 0.0) for j in range(cnt)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        lo[o] = first
+        for j, v in enumerate(w):
+            k[o, j] = int(0.5 + (v / ww if ww != 0.0 else v) * (1 << 22))
+    return lo, k
+
+
+def resize_pil_u8(x, size):
+    """uint8 [..., H, W] -> uint8 [..., size, size] exactly as PIL.Image.resize((size, size), BILINEAR) (what transforms.Resize does
+    to a PIL image): a horizontal pass, then a vertical pass on its result, each a fixed-point weighted sum rounded to uint8:
+    out[o] = clip((2^21 + sum_j k[o][j] * src[lo[o] + j]) >> 22, 0, 255).  Any H, W >= 1; an axis that already has `size` entries is
+    reproduced.  The host statement of the device kernel img_prep_u8_any_kernel; at 2x it is resize2x_pil_u8."""
+    def one_axis(t, dim):
+        t = t.to(torch.int64).movedim(dim, -1)
+        length = t.shape[-1]
+        lo, k = _axis_taps(length, size)
+        acc = torch.full(t.shape[:-1] + (size,), 1 << 21, dtype=torch.int64)
+        for j in range(k.shape[1]):
+            acc += k[:, j] * t[..., (lo + j).clamp_(max=length - 1)]          # (a tap past the last one has weight 0)
+        return (acc >> 22).clamp_(0, 255).movedim(-1, dim)
+    return one_axis(one_axis(x, -1), -2).to(torch.uint8)
+
+
 class DeviceLoader:
     """Iterable with the DataLoader surface the trainers use (`len()`, iteration over `[images, (labels)]` batches): images
     are `DeviceBatch`es over the uint8 dataset in HBM, labels (CGAN: int64 one-hot [B,100]) are gathered on the device.
     Shuffles every epoch like DataLoader(shuffle=True); under torch.distributed every rank takes a strided share of the same
-    permutation (DistributedSampler semantics, padded by wrap-around)."""
+    permutation (DistributedSampler semantics, padded by wrap-around).
+    size: the side the step resizes to (64 or 128).  mirror: every drawn index also draws a left-right flip with probability 1/2
+    (RandomHorizontalFlip) from a SECOND generator, so the index order of a seed is the same with and without it."""
 
-    def __init__(self, data_u8, batch_size, onehot=None, seed=0):
+    def __init__(self, data_u8, batch_size, onehot=None, seed=0, size=64, mirror=False):
         from hipgan.engine import DeviceBatch
         self._DeviceBatch = DeviceBatch
         self.data, self.onehot, self.batch_size = data_u8, onehot, batch_size
+        self.size, self.mirror = size, bool(mirror)
         self.rank, self.world = 0, 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.rank, self.world = torch.distributed.get_rank(), torch.distributed.get_world_size()
         self.n_local = (data_u8.shape[0] + self.world - 1) // self.world
         self.gen = torch.Generator().manual_seed(seed)
+        self.flip_gen = torch.Generator().manual_seed(seed + 0x6d6972) if self.mirror else None
 
     def __len__(self):
         return (self.n_local + self.batch_size - 1) // self.batch_size
@@ -74,28 +125,75 @@ class DeviceLoader:
     def __iter__(self):
         n = self.data.shape[0]
         perm = torch.randperm(n, generator=self.gen)
+        flips = torch.randint(0, 2, (n,), generator=self.flip_gen, dtype=torch.uint8) if self.mirror else None      # one per drawn index, new every epoch
         if self.world > 1:
             total = self.n_local * self.world
             perm = torch.cat([perm, perm[:total - n]])[self.rank:total:self.world]
+            if flips is not None:
+                flips = torch.cat([flips, flips[:total - n]])[self.rank:total:self.world]
         perm = perm.to(self.data.device)
+        flips = flips.to(self.data.device) if flips is not None else None
         for i in range(0, perm.numel(), self.batch_size):
             idx = perm[i:i + self.batch_size]
-            batch = [self._DeviceBatch(self.data, idx)]
+            batch = [self._DeviceBatch(self.data, idx, self.size, flips[i:i + self.batch_size] if flips is not None else None)]
             if self.onehot is not None:
                 batch.append(self.onehot[idx])
             yield batch
 
 
+def load_npz_dataset(path, need_labels=False):
+    """--data FILE.npz, the format generate.py writes: `images` uint8 [N,H,W,3] (1 <= H, W <= 1024) and optionally `labels` int [N]
+    -> (uint8 [N,3,H,W] planar host tensor, list of int labels or None).  need_labels (CGAN): `labels` must be there, all within
+    0..99.  Everything is checked here, on the host, before anything is allocated on the device."""
+    with np.load(path, allow_pickle=False) as z:
+        if "images" not in z.files:
+            raise ValueError(f"{path}: no `images` array (expected uint8 [N,H,W,3], as generate.py writes it)")
+        img = z["images"]
+        lab = z["labels"] if "labels" in z.files else None
+    if img.dtype != np.uint8 or img.ndim != 4 or img.shape[3] != 3 or img.shape[0] < 1:
+        raise ValueError(f"{path}: `images` must be uint8 [N,H,W,3] with N >= 1, got {img.dtype} {img.shape}")
+    if not (1 <= img.shape[1] <= RESIZE_MAX_SRC and 1 <= img.shape[2] <= RESIZE_MAX_SRC):
+        raise ValueError(f"{path}: images of {img.shape[1]}x{img.shape[2]}: the input pipeline takes 1..{RESIZE_MAX_SRC} pixels a side")
+    if lab is None:
+        if need_labels:
+            raise ValueError(f"{path}: no `labels` array: the conditional model needs one class in 0..99 per image")
+        labels = None
+    else:
+        if lab.ndim != 1 or lab.shape[0] != img.shape[0] or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError(f"{path}: `labels` must be int [{img.shape[0]}], got {lab.dtype} {lab.shape}")
+        if need_labels and (int(lab.min()) < 0 or int(lab.max()) > 99):
+            raise ValueError(f"{path}: `labels` must lie in 0..99, got {int(lab.min())}..{int(lab.max())}")
+        labels = [int(t) for t in lab]
+    return torch.from_numpy(np.ascontiguousarray(img.transpose(0, 3, 1, 2))), labels
+
+
 class DCGANDataPreprocessor:
+    NEED_LABELS = False
+
     def __init__(self, args, synthetic_size=None):
         self._logger = MainLogger(args)
         self.batch_size = args.batch_size
         self.num_worker = args.num_worker
+        # the opt-in flags of main.py (absent from the namespace unless given): another dataset, the 128x128 topology, flips
+        self.data_file = getattr(args, "data", None)
+        self.image_size = int(getattr(args, "image_size", 64))
+        self.mirror = bool(int(getattr(args, "mirror", 0)))
+        if self.image_size not in (64, 128):
+            raise ValueError(f"image_size must be 64 or 128, got {self.image_size}")
+        self.metric_cache = None
         self.images, self.targets = self._load(synthetic_size)
         self._train, self._metric = None, None
         self._logger.debug("data preprocessor init")
 
     def _load(self, synthetic_size):
+        if self.data_file is not None:
+            x, labels = load_npz_dataset(self.data_file, self.NEED_LABELS)
+            # the real-feature cache of metrics.Metrics belongs to ONE dataset: ./data/metric_data.pikl holds CIFAR-100's
+            st = os.stat(self.data_file)
+            stem = os.path.splitext(os.path.basename(self.data_file))[0]
+            self.metric_cache = os.path.join(".", "data", f"metric_{stem}_{st.st_size}_{st.st_mtime_ns}.pikl")
+            self._logger.debug(f"dataset loaded from {self.data_file}: {tuple(x.shape)}" + ("" if labels is not None else ", no labels"))
+            return x, labels if labels is not None else [0] * x.shape[0]
         path = os.path.join(CIFAR_DIR, "train")
         if synthetic_size is None and os.path.exists(path):
             with open(path, "rb") as f:
@@ -123,15 +221,24 @@ class DCGANDataPreprocessor:
         if self.device_resident():
             self._train = self.images.cuda().contiguous()                         # uint8, transformed inside the step
         else:
-            up = resize2x_pil_u8(self.images)                                     # Resize(64) on the PIL image (:39)
+            if self.mirror:
+                raise ValueError("--mirror 1 needs the device-resident pipeline (a GPU, JCKGAN_DEVICE_DATA not 0): the host "
+                                 "loader transforms the dataset once, before training, and has no per-step flip")
+            if tuple(self.images.shape[2:]) == (32, 32) and self.image_size == 64:
+                up = resize2x_pil_u8(self.images)                                 # Resize(64) on the PIL image (:39)
+            else:
+                up = resize_pil_u8(self.images, self.image_size)                  # Resize((S, S)) of any source size
             self._train = (up.float() / 255.0 - 0.5) / 0.5                        # ToTensor, Normalize(0.5, 0.5)
         self._logger.debug("data transform")
+
+    def _device_loader(self, onehot=None):
+        return DeviceLoader(self._train, self.batch_size, onehot=onehot, seed=12345, size=self.image_size, mirror=self.mirror)
 
     def get_data_loader(self):
         if self._train is None:
             self.transform_data()
         if self._train.dtype == torch.uint8:
-            return DeviceLoader(self._train, self.batch_size, seed=12345), self._metric
+            return self._device_loader(), self._metric
         ds = torch.utils.data.TensorDataset(self._train)
         sampler = None
         if torch.distributed.is_available() and torch.distributed.is_initialized():

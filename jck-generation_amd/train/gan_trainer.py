@@ -201,7 +201,10 @@ class GANTrainer(Trainer):
     def _make_metrics(self, metric_loader):
         try:
             from metrics import Metrics
-            return Metrics(metric_loader)
+            # --data: the cache of the real features is named after that file (preprocess/dcgan_data_preprocessor.py), never the
+            # default ./data/metric_data.pikl, which holds CIFAR-100's and would be reused silently
+            cache = getattr(self.data_pre, "metric_cache", None)
+            return Metrics(metric_loader, cache=cache) if cache else Metrics(metric_loader)
         except Exception as e:
             self.logger.warning(f"Inception-score / FID evaluation disabled: {e}")
             return None
