@@ -620,7 +620,9 @@ int jck_engine_score(jck_engine*, const float* images_nchw /* fp32 [n,3,S,S] or 
 long long jck_engine_feature_dim(const jck_engine*, int grid);
 int jck_engine_features(jck_engine*, const float* images_nchw /* fp32 [n,3,S,S] or NULL: the generator's last output where it lies */,
                         int n, int grid, int mode, float* out /* fp32 [n, ld] */, long long ld, void* stream);
-/* debug / parity access to internal NHWC tensors: name in {"fake","real_noisy",...}; returns device ptr or NULL */
+/* debug / parity access to internal NHWC tensors: name in {"fake","real_noisy",...}; returns device ptr or NULL.  The packed GEMM
+ * operands are in the table too, numel = their allocated element count (padding included): "d_down{i}", "d_up{i}", "g_up{i}",
+ * "g_down{i}" (stage i, the engine's storage type), "g1_w", "d_head_wp" (always fp32), CGAN's "l1_w" and "l1_wT". */
 const void* jck_engine_tensor(const jck_engine*, const char* name, long long* numel);
 
 /* ---- evaluation branch: the metric network (reference metrics.py:46-51,80-94: torchvision inception_v3 with a

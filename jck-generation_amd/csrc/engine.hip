@@ -1381,5 +1381,21 @@ extern "C" const void* jck_engine_tensor(const jck_engine* e, const char* name, 
       {"g_y1", e->g_y[0], (long long)e->B * TT.FEAT}, {"g_a4", e->g_a[TT.NS - 1], (long long)e->B * (TT.S / 2) * (TT.S / 2) * 64}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) { if (numel) *numel = t.c; return t.p; }
+  // the packed GEMM operands, with the element counts carve() allocates (padding included): "d_down0", "g_up3", ...
+  auto hit = [&](const void* p, long long c) { if (numel) *numel = c; return p; };
+  for (int i = 0; i < TT.NS; ++i) {
+    const long long d_dn = (long long)jck_pad_rows(TT.D_CS[i]) * 16 * jck_pad_chan(TT.D_CB[i]), d_up = 4ll * jck_pad_rows(TT.D_CB[i]) * 4 * TT.D_CS[i];
+    const long long g_dn = (long long)jck_pad_rows(TT.G_CS[i]) * 16 * jck_pad_chan(TT.G_CB[i]), g_up = 4ll * jck_pad_rows(TT.G_CB[i]) * 4 * TT.G_CS[i];
+    const struct { const char* pre; const void* p; long long c; } ops[] = {
+        {"d_down", e->d_down[i], d_dn}, {"d_up", e->d_up[i], d_up}, {"g_up", e->g_up[i], g_up}, {"g_down", e->g_down[i], g_dn}};
+    for (auto& o : ops) {
+      const size_t l = strlen(o.pre);
+      if (!strncmp(name, o.pre, l) && name[l] == (char)('0' + i) && name[l + 1] == '\0') return hit(o.p, o.c);
+    }
+  }
+  if (!strcmp(name, "d_head_wp")) return hit(e->d_head_wp, TT.FEAT);
+  if (!strcmp(name, "g1_w")) return hit(e->g1_w, 16ll * TT.G_C1 * z_pad(e->family));
+  if (e->family == 1 && !strcmp(name, "l1_w")) return hit(e->l1_w, (long long)L1_OUT * L1_KPAD);
+  if (e->family == 1 && !strcmp(name, "l1_wT")) return hit(e->l1_wT, (long long)L1_KPAD * L1_OUT);
   return nullptr;
 }

@@ -859,13 +859,14 @@ class DcganEngine(EngineInference):
         return self.scalars()
 
     def tensor(self, name):
-        """Debug/parity view of an internal NHWC tensor as a torch tensor (copy)."""
+        """Debug/parity view of an internal NHWC tensor as a torch tensor (copy).  The packed GEMM operands are there too, over their
+        whole allocation: d_down{i}, d_up{i}, g_up{i}, g_down{i}, g1_w, d_head_wp (always fp32), CGAN's l1_w and l1_wT."""
         self.join()
         n = C.c_longlong()
         p = load_library().jck_engine_tensor(self._h, name.encode(), C.byref(n))
         if not p:
             raise KeyError(name)
-        f32 = name in ("prob", "ds", "norms", "acc", "rs", "prob_gp")
+        f32 = name in ("prob", "ds", "norms", "acc", "rs", "prob_gp", "d_head_wp")
         dt = torch.bfloat16 if (self.prec == PREC_BF16 and not f32) else torch.float32
         return self._ws_view(p, n.value, dt).clone()
 

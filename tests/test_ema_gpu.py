@@ -70,6 +70,26 @@ def test_adam_ema_op_against_the_recurrence(off, decay):
 
 
 @pytest.mark.parametrize("off", [0, 1])
+def test_adam_ema_op_past_the_grid_cap(off):
+    """One step whose launch passes the cap of 8192 workgroups of 256 threads: n = 8192 * 256 + 5 element by element (off = 1),
+    n = 4 * 8192 * 256 + 7 on the vector path (off = 0: one quad of the second sweep and the 3-element tail).  decay 0.4; the
+    average against the recurrence, p, m, v bitwise as jck_adam leaves them."""
+    from hipgan import lib
+    from hipgan._lib import cur_stream
+    n = 8192 * 256 + 5 if off else 4 * 8192 * 256 + 7
+    a, b = _op_inputs(n, off), _op_inputs(n, off)
+    w = _w(0.4)
+    e0 = a["ema"].double().cpu()
+    M = max(a["p"].abs().max().item(), a["ema"].abs().max().item())
+    lib.jck_adam_ema(a["p"], a["g"], a["m"], a["v"], a["ema"], n, 2e-4, 0.5, 0.999, 1e-8, 1, 0.5, w, None, cur_stream())
+    lib.jck_adam(b["p"], b["g"], b["m"], b["v"], n, 2e-4, 0.5, 0.999, 1e-8, 1, 0.5, cur_stream())
+    for k in ("p", "m", "v"):
+        assert torch.equal(a[k], b[k]), k
+    p = a["p"].double().cpu()
+    _check_recurrence(a["ema"], e0 + w * (p - e0), 1, max(M, p.abs().max().item()), f"op past the grid cap off={off}")
+
+
+@pytest.mark.parametrize("off", [0, 1])
 def test_adam_ema_op_weight_one_and_skip(off):
     from hipgan import lib
     from hipgan._lib import cur_stream

@@ -429,7 +429,18 @@ def test_head_clamp(G):
 @pytest.mark.parametrize("off", [0, 1])
 def test_adam(G, off):
     """off = 0: 16-byte aligned arenas (four elements per thread + a scalar tail, n % 4 = 3); off = 1: views that start one
-    element into their buffers (the element-by-element path)."""
+    element into their buffers (the element-by-element path).
+
+    Then p, m AND v of single steps against torch.optim.Adam in float64 started from the kernel's own float32 state (so every
+    comparison sees one step's rounding): beta1 0.5 / 0.9 / 0.0 (lerp's second branch, its first, and w1 = 1), grad_scale 1 and 1/8,
+    gradients with exact zeros, the first step against zero moments.  p keeps the 3e-7 absolute bound.  v is within 4 ulp of the
+    reference value: two or three float32 operations (omb2 * g, * g, the product with beta2 and the sum, possibly one fma) on
+    positive terms, plus float32(beta2).  m likewise (difference, product, sum) wherever gradient and old moment do not have opposite
+    signs - zero moments included; where they do, the sum can cancel and no float32 lerp stays within ulps of the RESULT, so there the
+    bound is 4 ulp of the larger operand max(|grad_scale * g|, |m_old|): the difference (<= 2 M) rounds to 1 ulp(M), its product
+    with w1 <= 1 to another, the result to half of one.
+    Last, one step whose launch passes ew_grid's cap of 8192 workgroups of 256: n = 8192 * 256 + 5 on the element-by-element path
+    (off = 1), n = 4 * 8192 * 256 + 7 on the vector path (off = 0: one quad of the second sweep, and the 3-element tail)."""
     g = torch.Generator().manual_seed(7)
     n = 10007
     p0 = torch.randn(n, generator=g)
@@ -444,6 +455,61 @@ def test_adam(G, off):
         G.lib.jck_adam(pd, buf(gr), m, v, n, 2e-4, 0.5, 0.999, 1e-8, step, 1.0, G.cur_stream())
         torch.cuda.synchronize()
         assert (pd.cpu() - p.detach()).abs().max().item() < 3e-7, step
+    for beta1 in (0.5, 0.9, 0.0):
+        for gs in (1.0, 0.125):
+            _adam_single_steps(G, off, n, beta1, gs, steps=3, seed=11)
+    _adam_single_steps(G, off, 8192 * 256 + 5 if off else 4 * 8192 * 256 + 7, 0.5, 1.0, steps=1, seed=12, first_step=3)
+
+
+def _adam_ref64(p, g, m, v, step, beta1, gs):
+    """one torch.optim.Adam step in float64 from float32 state -> p, m, v (float64)"""
+    p64 = p.double().clone().requires_grad_(True)
+    opt = torch.optim.Adam([p64], lr=2e-4, betas=(beta1, 0.999), eps=1e-8)
+    opt.state[p64] = {"step": torch.tensor(float(step - 1)), "exp_avg": m.double().clone(), "exp_avg_sq": v.double().clone()}
+    p64.grad = g.double() * gs
+    opt.step()
+    st = opt.state[p64]
+    assert int(st["step"]) == step
+    return p64.detach(), st["exp_avg"], st["exp_avg_sq"]
+
+
+def _ulp32(x):
+    """spacing of float32 at |x| (x float64 tensor)"""
+    import numpy as np
+    return torch.from_numpy(np.spacing(np.abs(x.numpy()).astype(np.float32)).astype(np.float64))
+
+
+def _adam_single_steps(G, off, n, beta1, gs, steps, seed, first_step=1):
+    gen = torch.Generator().manual_seed(seed)
+    buf = lambda t: torch.cat([torch.zeros(off), t]).cuda()[off:]
+    p0 = torch.randn(n, generator=gen)
+    if first_step == 1:
+        m0, v0 = torch.zeros(n), torch.zeros(n)
+    else:
+        m0, v0 = torch.randn(n, generator=gen) * 0.01, torch.rand(n, generator=gen) * 1e-4
+    pd, md, vd = buf(p0), buf(m0), buf(v0)
+    assert (pd.data_ptr() % 16 == 0) == (off == 0)
+    for step in range(first_step, first_step + steps):
+        gr = torch.randn(n, generator=gen) * (10.0 ** (step - 2))
+        gr[torch.rand(n, generator=gen) < 0.25] = 0.0                     # exact zeros
+        p_old, m_old, v_old = pd.cpu().clone(), md.cpu().clone(), vd.cpu().clone()
+        pr, mr, vr = _adam_ref64(p_old, gr, m_old, v_old, step, beta1, gs)
+        G.lib.jck_adam(pd, buf(gr), md, vd, n, 2e-4, beta1, 0.999, 1e-8, step, gs, G.cur_stream())
+        torch.cuda.synchronize()
+        what = (off, n, beta1, gs, step)
+        assert (pd.cpu().double() - pr).abs().max().item() < 3e-7, what
+        ev = (vd.cpu().double() - vr).abs()
+        assert bool((ev <= 4 * _ulp32(vr)).all()), (what, "v", (ev / _ulp32(vr)).max().item())
+        em = (md.cpu().double() - mr).abs()
+        gsc = gr.double() * gs
+        same = gsc * m_old.double() >= 0                                   # no cancellation: zero moments, zero gradients, equal signs
+        if first_step == 1 and step == 1:
+            assert bool(same.all())
+        assert bool((em[same] <= 4 * _ulp32(mr)[same]).all()), (what, "m", (em[same] / _ulp32(mr)[same]).max().item())
+        big = torch.maximum(gsc.abs(), m_old.double().abs())
+        assert bool((em <= 4 * _ulp32(big)).all()), (what, "m, opposite signs", (em / _ulp32(big)).max().item())
+        if beta1 == 0.0:
+            assert torch.equal(md.cpu(), (gr * gs)), what                  # w1 = 1: the moment IS the scaled gradient
 
 
 @pytest.mark.parametrize("prec", PRECS)
