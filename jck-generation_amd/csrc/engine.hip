@@ -302,7 +302,7 @@ static int d_convs_forward(jck_engine* e, const DActs& S, const void* x_in, int 
     if (slots % n) JCK_FAIL(JCK_E_ARG, "batched D pass: statistic slots do not split by group");
     const bool cb = to_cbuf && i == TT.NS - 1;
     void* out = cb ? (unsigned char*)e->cbuf + (size_t)S.g0 * B * L1_KPAD * e->esz : S.a[i];
-    bool fused = false;                           // finalize + apply as one launch where the statistics rows are few (ops.hip)
+    bool fused = false;                           // finalize + apply as one launch where the statistics rows are few (ops_bn.hip)
     JCK_TRY(bn_fwd_fused(e->prec, S.y[i], S.stats[i], slots / n, (float)rows, e->P(e->LD, e->dp, NWN[i]), e->P(e->LD, e->dp, NBN[i]), BN_EPS, LRELU, out,
                          S.aux[i], rec, nullptr, nullptr, nullptr, BN_MOM, rows, cs, n, cb ? TT.FEAT : 0, cb ? L1_KPAD : 0, st, &fused));
     if (!fused) {

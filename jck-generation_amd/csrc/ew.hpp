@@ -1,7 +1,6 @@
-// Memory-bound kernels of the DCGAN/CGAN step: layout conversion + instance noise, BatchNorm
-// (statistics finalise, normalise+activation, backward reduce/apply), D head (4x4 valid conv to one
+// Memory-bound kernels of the DCGAN/CGAN step: layout conversion + instance noise, D head (4x4 valid conv to one
 // logit + sigmoid + BCE with the -100 log clamp + gradient), tanh backward, gradient-penalty norm, the CGAN
-// pieces (Adam and weight packing: ew_optim.hpp).  Everything is 16-byte vectorised along the NHWC channel axis; per-channel
+// pieces (BatchNorm: bn.hpp, bn2.hpp; Adam and weight packing: ew_optim.hpp).  Everything is 16-byte vectorised along the NHWC channel axis; per-channel
 // reductions use registers -> LDS -> per-workgroup partial rows summed in a fixed order (no float atomics anywhere:
 // two runs of a step give bitwise identical gradients and scalars).
 #pragma once
@@ -235,502 +234,6 @@ __global__ __launch_bounds__(256) void gp_norm_kernel(const T* __restrict__ g, i
     const float nr = sqrtf(s);
     if (norms) norms[blockIdx.x] = nr;
     if (scal && slot >= 0) scal[(long long)slot * scal_ld + blockIdx.x] = (nr - 1.f) * (nr - 1.f);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// BatchNorm (training mode always - the reference never switches G/D to eval)
-// ------------------------------------------------------------------------------------------------------
-// The streaming BatchNorm kernels run at wave priority 3: in the backward passes they share the chip with the weight-gradient
-// products of the second stream, whose waves otherwise win the issue arbitration by age (step 1.8535 -> 1.8466 ms, two A/B
-// rounds on one box; -DJCK_BN_PRIO=0 to compare)
-#ifndef JCK_BN_PRIO
-#define JCK_BN_PRIO 3
-#endif
-// stats: [slots][2][C] partial sums / sums of squares written by the GEMM epilogue (every slot complete).
-// aux layout (floats): [0,C) scale = gamma*invstd   [C,2C) shift = beta - mean*scale
-//                      [2C,3C) mean                 [3C,4C) invstd
-// One workgroup per 4 channels: 256 slot-lanes, 16-byte loads, double accumulation, wavefront + LDS reduction.
-static __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ stats, int slots, float count,
-                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                 float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                                 long long* __restrict__ nbt, float momentum, float eps,
-                                                                 float* __restrict__ aux, int C, float* __restrict__ stat_out = nullptr) {
-  __shared__ double sh[4][8];
-  const int c0 = blockIdx.x * 4;
-  // grouped launch (gridDim.y > 1): group g owns slots [g*slots, (g+1)*slots), aux block g and record g (independent
-  // BatchNorm batches that went through ONE conv launch - the D passes that share weights)
-  stats += (long long)blockIdx.y * slots * 2 * C;
-  aux += (long long)blockIdx.y * 4 * C;
-  if (stat_out) stat_out += (long long)blockIdx.y * 2 * C;
-  double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
-  // eight rows of this thread's sequence in flight (the rows are 2C floats apart: every load is a line of its own, and a launch with
-  // a thousand rows was four to sixteen DEPENDENT memory round trips long - 5-9 us for a kernel that moves a megabyte); the adds
-  // stay in sequence order: the same sums, bit for bit
-  constexpr int FU = 8;
-  for (int k0 = threadIdx.x; k0 < slots; k0 += 256 * FU) {
-    f32x4 a[FU], b[FU];
-#pragma unroll
-    for (int u = 0; u < FU; ++u) {
-      const int k = k0 + u * 256;
-      if (k < slots) {
-        a[u] = *reinterpret_cast<const f32x4*>(stats + (long long)k * 2 * C + c0);
-        b[u] = *reinterpret_cast<const f32x4*>(stats + (long long)k * 2 * C + C + c0);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < FU; ++u) {
-      if (k0 + u * 256 >= slots) break;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { s[i] += (double)a[u][i]; q[i] += (double)b[u][i]; }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { s[i] = wave_sum_d(s[i]); q[i] = wave_sum_d(q[i]); }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { sh[threadIdx.x >> 6][i] = s[i]; sh[threadIdx.x >> 6][4 + i] = q[i]; }
-  }
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
-  if (threadIdx.x >= 4) return;
-  const int i = threadIdx.x, c = c0 + i;
-  const double sd = sh[0][i] + sh[1][i] + sh[2][i] + sh[3][i], qd = sh[0][4 + i] + sh[1][4 + i] + sh[2][4 + i] + sh[3][4 + i];
-  const double meand = sd / (double)count;
-  double vard = qd / (double)count - meand * meand;
-  if (vard < 0.0) vard = 0.0;
-  const float mean = (float)meand, var = (float)vard;
-  const float invstd = 1.0f / sqrtf(var + eps);
-  const float sc = gamma[c] * invstd;
-  aux[c] = sc;
-  aux[C + c] = beta[c] - mean * sc;
-  aux[2 * C + c] = mean;
-  aux[3 * C + c] = invstd;
-  const float unbiased = var * (count / fmaxf(count - 1.f, 1.f));
-  if (stat_out) {             // deferred running-stat update (passes that run concurrently on different streams)
-    stat_out[c] = mean;
-    stat_out[C + c] = unbiased;
-  }
-  if (running_mean) {
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-  }
-}
-
-// Eval-mode BatchNorm folded into the aux table above from the RUNNING statistics (aten::native_batch_norm, training = false:
-// invstd = 1 / sqrt(var + eps), scale = gamma * invstd, shift = beta - mean * scale, each product and sum rounded once:
-// contraction is off in the kernel).  Every BatchNorm layer of a network in one launch: a job per layer, a thread
-// per channel, block b belongs to the job with first_block[j] <= b < first_block[j + 1].  Nothing but aux is written.
-#define BN_EVAL_MAX_JOBS 8
-struct BnEvalJob { const float *gamma, *beta, *mean, *var; float* aux; int C; };
-struct BnEvalJobs { BnEvalJob j[BN_EVAL_MAX_JOBS]; int first_block[BN_EVAL_MAX_JOBS + 1]; int n; float eps; };
-static __global__ __launch_bounds__(256) void bn_eval_aux_kernel(const BnEvalJobs jobs) {
-#pragma clang fp contract(off)
-  int k = 0;
-  while (k + 1 < jobs.n && (int)blockIdx.x >= jobs.first_block[k + 1]) ++k;
-  const BnEvalJob& q = jobs.j[k];
-  const int c = ((int)blockIdx.x - jobs.first_block[k]) * 256 + (int)threadIdx.x;
-  if (c >= q.C) return;
-  const float mean = q.mean[c];
-  const float invstd = 1.0f / sqrtf(q.var[c] + jobs.eps);
-  const float sc = q.gamma[c] * invstd;
-  q.aux[c] = sc;
-  q.aux[q.C + c] = q.beta[c] - mean * sc;
-  q.aux[2 * q.C + c] = mean;
-  q.aux[3 * q.C + c] = invstd;
-}
-
-// a = act(scale[c]*y + shift[c]), act = x>0 ? x : slope*x
-// pitch > 0: the output rows of 2^log_row elements are written `pitch` elements apart - the last layer of CGAN's D lands in the
-// concat buffer of the Linear head ([rows][8448], model/CGAN.py:119-121) without a copy
-template <typename T>
-__global__ void bn_act_fwd_kernel(const T* __restrict__ y, const float* __restrict__ aux, float slope,
-                                  T* __restrict__ a, long long total8, int C, int log_row = 0, long long pitch = 0) {
-  __builtin_amdgcn_s_setprio(JCK_BN_PRIO);
-  const long long g0 = (long long)blockIdx.y * total8 * 8;      // first element of this group
-  y += g0; aux += (long long)blockIdx.y * 4 * C;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)((i * 8) & (C - 1));
-    float v[8];
-    ld8(y + i * 8, v);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float z = v[k] * aux[c + k] + aux[C + c + k];
-      v[k] = z > 0.f ? z : slope * z;
-    }
-    const long long e = g0 + i * 8;
-    st8(a + (pitch ? (e >> log_row) * pitch + (e & ((1ll << log_row) - 1)) : e), v);
-  }
-}
-
-// BatchNorm finalize + apply as ONE launch with no hand-over between workgroups (round 5): a workgroup owns a 64-channel SLICE of a
-// pixel range (128 contiguous bytes per row in bf16), sums the statistics rows of ITS 64 channels itself - rows of 2 x 64 floats,
-// double accumulation in an order fixed by the geometry - forms scale / shift in LDS and streams its pixels.  What bn_finalize did for
-// everybody in a launch of its own (4.2 us of the step each, measured by skipping them: DESIGN.md section 7.2) every workgroup does
-// for itself in ~2 us that overlap its first loads; it pays while the rows are few (the gather-GEMMs write one per workgroup).  The
-// workgroups with blockIdx.x == 0 also write the aux table the backward reads, the deferred running-statistics record / the
-// running statistics themselves.  aux, stats, stat_out: as bn_finalize_kernel; a: as bn_act_fwd_kernel (pitched output included).
-#define BNF_THREADS 256
-template <typename T>
-__global__ __launch_bounds__(BNF_THREADS) void bn_fwd_fused_kernel(const T* __restrict__ y, const float* __restrict__ stats, int slots, float count,
-                                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float slope,
-                                                                   T* __restrict__ a, float* __restrict__ aux, float* __restrict__ stat_out,
-                                                                   float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                                   long long* __restrict__ nbt, float momentum, long long rows, int C,
-                                                                   int log_row, long long pitch) {
-  __shared__ double part[8][128];
-  __shared__ float tab[2][64];
-  __builtin_amdgcn_s_setprio(JCK_BN_PRIO);
-  const int t = threadIdx.x, s = blockIdx.y, grp = blockIdx.z;
-  stats += (long long)grp * slots * 2 * C;
-  aux += (long long)grp * 4 * C;
-  if (stat_out) stat_out += (long long)grp * 2 * C;
-  const long long g0 = (long long)grp * rows * C;              // first element of this group
-  // the first rows of this thread are requested BEFORE the table is formed: their latency hides under the row sums
-  constexpr int BU = 4;
-  const int u8 = t & 7;
-  const long long rstep = (long long)gridDim.x * 32, rfirst = (long long)blockIdx.x * 32 + (t >> 3);
-  Raw8<T> raw[BU];
-#pragma unroll
-  for (int u = 0; u < BU; ++u)
-    if (rfirst + u * rstep < rows) ldraw(y + g0 + (rfirst + u * rstep) * C + s * 64 + u8 * 8, raw[u]);
-  // ---- the slice's sums: thread = (row lane 0..7, stat, 4 channels)
-  {
-    const int q4 = t & 31, rl = t >> 5;
-    const float* col = stats + (q4 >> 4) * C + s * 64 + (q4 & 15) * 4;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    constexpr int RU = 16;                                       // rows of this thread in flight (256 rows: two round trips)
-    for (int r0 = rl; r0 < slots; r0 += 8 * RU) {
-      f32x4 v[RU];
-#pragma unroll
-      for (int u = 0; u < RU; ++u)
-        if (r0 + u * 8 < slots) v[u] = *reinterpret_cast<const f32x4*>(col + (long long)(r0 + u * 8) * 2 * C);
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        if (r0 + u * 8 >= slots) break;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] += (double)v[u][i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[rl][q4 * 4 + i] = acc[i];
-  }
-  __syncthreads();
-  if (t < 64) {
-    double sd = 0.0, qd = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sd += part[k][t]; qd += part[k][64 + t]; }
-    const int c = s * 64 + t;
-    const double meand = sd / (double)count;
-    double vard = qd / (double)count - meand * meand;
-    if (vard < 0.0) vard = 0.0;
-    const float mean = (float)meand, var = (float)vard;
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float sc = gamma[c] * invstd, sh = beta[c] - mean * sc;
-    tab[0][t] = sc; tab[1][t] = sh;
-    if (blockIdx.x == 0) {
-      aux[c] = sc; aux[C + c] = sh; aux[2 * C + c] = mean; aux[3 * C + c] = invstd;
-      const float unbiased = var * (count / fmaxf(count - 1.f, 1.f));
-      if (stat_out) { stat_out[c] = mean; stat_out[C + c] = unbiased; }
-      if (running_mean) {
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-      }
-      if (nbt && s == 0 && grp == 0 && t == 0) *nbt += 1;
-    }
-  }
-  __syncthreads();
-  // ---- stream: 8 threads per row slice (8 channels = 16 / 32 bytes each), 32 rows per pass
-  float sc[8], sh[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { sc[k] = tab[0][u8 * 8 + k]; sh[k] = tab[1][u8 * 8 + k]; }
-  // four rows of this thread in flight (few workgroups - each paid for its own table - so the bytes in flight come from the unroll)
-  for (long long r0 = rfirst; r0 < rows; r0 += rstep * BU) {
-    if (r0 != rfirst) {
-#pragma unroll
-      for (int u = 0; u < BU; ++u)
-        if (r0 + u * rstep < rows) ldraw(y + g0 + (r0 + u * rstep) * C + s * 64 + u8 * 8, raw[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < BU; ++u) {
-      if (r0 + u * rstep >= rows) break;
-      const long long e = g0 + (r0 + u * rstep) * C + s * 64 + u8 * 8;
-      float v[8];
-      unraw(raw[u], v);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float z = v[k] * sc[k] + sh[k];
-        v[k] = z > 0.f ? z : slope * z;
-      }
-      st8(a + (pitch ? (e >> log_row) * pitch + (e & ((1ll << log_row) - 1)) : e), v);
-    }
-  }
-}
-
-// stage 1: partial[blk][0..C) = sum g_z,  partial[blk][C..2C) = sum g_z * xhat over this workgroup's rows,
-// g_z = g_a * act'(z).  Register accumulation per (row-lane, 8-channel unit), one LDS pass over the row-lanes; no atomics:
-// the summation order per (thread, channel) is fixed by the launch geometry alone, so the result is bitwise reproducible.
-// Geometry (measured in the step, round 2): <= 256 workgroups per group.  A variant with 1024 workgroups and 4 rows in flight per
-// thread (8x the bytes in flight) was SLOWER in the step (29.3 vs 22.1 us average): the kernel runs beside the weight-gradient
-// product of the previous layer on the second stream and both are bound by the same memory system.  Two rows in flight at the
-// same 256 workgroups (UNR = 2, the default; same summation order, same bits) is the optimum: step 1.867 -> 1.837 ms, UNR 4: 1.853.
-#define BN_BWD_MAX_BLOCKS 256
-template <typename T, int UNR = 1>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ ga, const T* __restrict__ y,
-                                                            const float* __restrict__ aux, float slope,
-                                                            float* __restrict__ partial, long long rows, int C,
-                                                            long long group_stride = 0) {
-  extern __shared__ float lsum[];                         // [rstep][2][C]
-  __builtin_amdgcn_s_setprio(JCK_BN_PRIO);
-  ga += (long long)blockIdx.y * rows * C; y += (long long)blockIdx.y * rows * C;                    // group
-  aux += (long long)blockIdx.y * 4 * C; partial += (long long)blockIdx.y * group_stride;
-  const int upr = C >> 3;                                 // 8-channel units per row
-  const int u = threadIdx.x % upr, r0 = threadIdx.x / upr, rstep = 256 / upr;
-  const int c = u * 8;
-  float sc[8], sh[8], mu[8], is[8], s1[8], s2[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    sc[k] = aux[c + k]; sh[k] = aux[C + c + k]; mu[k] = aux[2 * C + c + k]; is[k] = aux[3 * C + c + k];
-    s1[k] = 0.f; s2[k] = 0.f;
-  }
-  // UNR rows of this thread's sequence are loaded together and accumulated in sequence order: the same sums, bit for bit,
-  // with UNR times the bytes in flight
-  const long long stride = (long long)gridDim.x * rstep;
-  for (long long r = (long long)blockIdx.x * rstep + r0; r < rows; r += stride * UNR) {
-    float vg[UNR][8], vy[UNR][8];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const long long ru = r + u * stride;
-      if (ru < rows) { ld8(ga + ru * C + c, vg[u]); ld8(y + ru * C + c, vy[u]); }
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      if (r + u * stride >= rows) break;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float z = vy[u][k] * sc[k] + sh[k];
-        const float gz = z > 0.f ? vg[u][k] : slope * vg[u][k];
-        s1[k] += gz;
-        s2[k] += gz * ((vy[u][k] - mu[k]) * is[k]);
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { lsum[(r0 * 2) * C + c + k] = s1[k]; lsum[(r0 * 2 + 1) * C + c + k] = s2[k]; }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += 256) {
-    float t = 0.f;
-    for (int rr = 0; rr < rstep; ++rr) t += lsum[rr * 2 * C + i];
-    partial[(long long)blockIdx.x * 2 * C + i] = t;
-  }
-}
-
-// stage 2: sums[g][0..2C) = sum over workgroups for every group g; dgamma += sum_{g < grad_groups} s2, dbeta likewise (when
-// given) - the groups are walked in order inside the workgroup, so the gradient does not depend on any arrival order.
-// One workgroup per 4 channels.
-static __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float* __restrict__ partial, int nblk, float* __restrict__ sums,
-                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta, int C,
-                                                                 long long group_stride = 0, int groups = 1, int grad_groups = 1,
-                                                                 long long partial_group_stride = -1) {
-  // groups in chunks of four: the loads of a chunk's groups are in flight together and one barrier pair serves them (the
-  // grouped D pass has 3: one memory round trip instead of three; same summation order per group - same bits)
-  __shared__ float sh[4][4][8];
-  const int c0 = blockIdx.x * 4;
-  const long long pgs = partial_group_stride >= 0 ? partial_group_stride : group_stride;
-  float dg = 0.f, db = 0.f;
-  for (int g0 = 0; g0 < groups; g0 += 4) {
-    float s[4][4], q[4][4];
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { s[gg][i] = 0.f; q[gg][i] = 0.f; }
-    for (int k = threadIdx.x; k < nblk; k += 256) {
-#pragma unroll
-      for (int gg = 0; gg < 4; ++gg) {
-        if (g0 + gg >= groups) continue;
-        const float* pp = partial + (long long)(g0 + gg) * pgs;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(pp + (long long)k * 2 * C + c0);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(pp + (long long)k * 2 * C + C + c0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { s[gg][i] += a[i]; q[gg][i] += b[i]; }
-      }
-    }
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-      if (g0 + gg >= groups) continue;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { s[gg][i] = wave_sum(s[gg][i]); q[gg][i] = wave_sum(q[gg][i]); }
-    }
-    __syncthreads();                                        // the previous chunk's sh[] has been read
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int gg = 0; gg < 4; ++gg) {
-        if (g0 + gg >= groups) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { sh[gg][threadIdx.x >> 6][i] = s[gg][i]; sh[gg][threadIdx.x >> 6][4 + i] = q[gg][i]; }
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      const int i = threadIdx.x, c = c0 + i;
-      for (int gg = 0; gg < 4 && g0 + gg < groups; ++gg) {
-        const int g = g0 + gg;
-        const float s1 = sh[gg][0][i] + sh[gg][1][i] + sh[gg][2][i] + sh[gg][3][i];
-        const float s2 = sh[gg][0][4 + i] + sh[gg][1][4 + i] + sh[gg][2][4 + i] + sh[gg][3][4 + i];
-        sums[(long long)g * group_stride + c] = s1;
-        sums[(long long)g * group_stride + C + c] = s2;
-        if (g < grad_groups) { dg += s2; db += s1; }
-      }
-    }
-  }
-  if (threadIdx.x < 4) {
-    const int c = c0 + threadIdx.x;
-    if (dgamma) dgamma[c] += dg;
-    if (dbeta) dbeta[c] += db;
-  }
-}
-
-// g_y = scale * (g_z - s1/n - xhat * s2/n)
-template <typename T>
-__global__ void bn_bwd_apply_kernel(const T* __restrict__ ga, const T* __restrict__ y, const float* __restrict__ aux,
-                                    const float* __restrict__ sums, float slope, float inv_count,
-                                    T* __restrict__ gy, long long total8, int C, long long group_stride = 0) {
-  __builtin_amdgcn_s_setprio(JCK_BN_PRIO);
-  ga += (long long)blockIdx.y * total8 * 8; y += (long long)blockIdx.y * total8 * 8; gy += (long long)blockIdx.y * total8 * 8;   // group
-  aux += (long long)blockIdx.y * 4 * C; sums += (long long)blockIdx.y * group_stride;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)((i * 8) & (C - 1));
-    float vg[8], vy[8];
-    ld8(ga + i * 8, vg);
-    ld8(y + i * 8, vy);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float sc = aux[c + k];
-      const float z = vy[k] * sc + aux[C + c + k];
-      const float gz = z > 0.f ? vg[k] : slope * vg[k];
-      const float xh = (vy[k] - aux[2 * C + c + k]) * aux[3 * C + c + k];
-      vg[k] = sc * (gz - sums[c + k] * inv_count - xh * (sums[C + c + k] * inv_count));
-    }
-    st8(gy + i * 8, vg);
-  }
-}
-
-// Backward sums + apply as ONE launch (round 5, the backward twin of bn_fwd_fused_kernel): the three-launch form's middle launch -
-// bn_bwd_sums_kernel, 10-13 us on the main stream's chain between two streaming kernels - is done by every workgroup for itself.
-// A workgroup owns a 64-channel slice of a pixel range of ONE group, sums the partial rows bn_bwd_reduce_kernel wrote for ITS 64
-// channels ([blk][2][C] floats: <= 256 rows of 512 bytes, L2-resident; double accumulation in an order fixed by the geometry),
-// keeps s1/n, s2/n in LDS and streams its pixels.  The workgroups with blockIdx.x == 0 write the group's sums (CGAN's v-chain
-// reads them); those of group 0 also form the parameter gradients: dgamma += sum_{g < grad_groups} s2_g, dbeta likewise, the
-// groups walked in order.  Its first rows are requested before the sums are formed.
-template <typename T>
-__global__ __launch_bounds__(BNF_THREADS) void bn_bwd_apply_fused_kernel(const T* __restrict__ ga, const T* __restrict__ y, const float* __restrict__ aux,
-                                                                         const float* __restrict__ partial, int nblk, float* __restrict__ sums,
-                                                                         float* __restrict__ dgamma, float* __restrict__ dbeta, float slope,
-                                                                         float inv_count, T* __restrict__ gy, long long rows, int C,
-                                                                         long long group_stride, int grad_groups) {
-  __shared__ double part[8][128];
-  __shared__ float tab[2][64];
-  __builtin_amdgcn_s_setprio(JCK_BN_PRIO);
-  const int t = threadIdx.x, s = blockIdx.y, grp = blockIdx.z;
-  const long long g0 = (long long)grp * rows * C;              // first element of this group
-  constexpr int BU = 2;
-  const int u8 = t & 7;
-  const long long rstep = (long long)gridDim.x * 32, rfirst = (long long)blockIdx.x * 32 + (t >> 3);
-  Raw8<T> rg[BU], ry[BU];
-#pragma unroll
-  for (int u = 0; u < BU; ++u)
-    if (rfirst + u * rstep < rows) {
-      ldraw(ga + g0 + (rfirst + u * rstep) * C + s * 64 + u8 * 8, rg[u]);
-      ldraw(y + g0 + (rfirst + u * rstep) * C + s * 64 + u8 * 8, ry[u]);
-    }
-  // ---- the slice's sums of group g: thread = (row lane 0..7, stat, 4 channels); result of thread t < 64: (s1, s2) of channel s*64 + t
-  const int q4 = t & 31, rl = t >> 5;
-  auto slice_sums = [&](int g, double& s1, double& s2) {
-    const float* col = partial + (long long)g * group_stride + (q4 >> 4) * C + s * 64 + (q4 & 15) * 4;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    constexpr int RU = 16;
-    for (int r0 = rl; r0 < nblk; r0 += 8 * RU) {
-      f32x4 v[RU];
-#pragma unroll
-      for (int u = 0; u < RU; ++u)
-        if (r0 + u * 8 < nblk) v[u] = *reinterpret_cast<const f32x4*>(col + (long long)(r0 + u * 8) * 2 * C);
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        if (r0 + u * 8 >= nblk) break;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] += (double)v[u][i];
-      }
-    }
-    __syncthreads();                                           // part[] of the previous call has been read
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[rl][q4 * 4 + i] = acc[i];
-    __syncthreads();
-    s1 = 0.0; s2 = 0.0;
-    if (t < 64) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { s1 += part[k][t]; s2 += part[k][64 + t]; }
-    }
-  };
-  double s1d, s2d;
-  slice_sums(grp, s1d, s2d);
-  if (t < 64) {
-    const float s1 = (float)s1d, s2 = (float)s2d;
-    tab[0][t] = s1 * inv_count; tab[1][t] = s2 * inv_count;
-    if (blockIdx.x == 0) {
-      const int c = s * 64 + t;
-      sums[(long long)grp * group_stride + c] = s1;
-      sums[(long long)grp * group_stride + C + c] = s2;
-    }
-  }
-  __syncthreads();
-  // ---- stream: 8 threads per row slice, 32 rows per pass, BU rows of this thread in flight
-  float sc[8], sh[8], mu[8], is[8], m1[8], m2[8];
-  {
-    const float* ax = aux + (long long)grp * 4 * C + s * 64 + u8 * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      sc[k] = ax[k]; sh[k] = ax[C + k]; mu[k] = ax[2 * C + k]; is[k] = ax[3 * C + k];
-      m1[k] = tab[0][u8 * 8 + k]; m2[k] = tab[1][u8 * 8 + k];
-    }
-  }
-  for (long long r0 = rfirst; r0 < rows; r0 += rstep * BU) {
-    if (r0 != rfirst) {
-#pragma unroll
-      for (int u = 0; u < BU; ++u)
-        if (r0 + u * rstep < rows) {
-          ldraw(ga + g0 + (r0 + u * rstep) * C + s * 64 + u8 * 8, rg[u]);
-          ldraw(y + g0 + (r0 + u * rstep) * C + s * 64 + u8 * 8, ry[u]);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < BU; ++u) {
-      if (r0 + u * rstep >= rows) break;
-      float vg[8], vy[8];
-      unraw(rg[u], vg);
-      unraw(ry[u], vy);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float z = vy[k] * sc[k] + sh[k];
-        const float gz = z > 0.f ? vg[k] : slope * vg[k];
-        const float xh = (vy[k] - mu[k]) * is[k];
-        vg[k] = sc[k] * (gz - m1[k] - xh * m2[k]);
-      }
-      st8(gy + g0 + (r0 + u * rstep) * C + s * 64 + u8 * 8, vg);
-    }
-  }
-  // ---- parameter gradients: the first workgroup of a slice in group 0 walks the gradient groups in order
-  if (blockIdx.x == 0 && grp == 0 && (dgamma || dbeta) && grad_groups > 0) {      // (uniform per workgroup)
-    float dg = (float)s2d, db = (float)s1d;
-    for (int g = 1; g < grad_groups; ++g) {
-      double a1, a2;
-      slice_sums(g, a1, a2);
-      dg += (float)a2; db += (float)a1;
-    }
-    if (t < 64) {
-      const int c = s * 64 + t;
-      if (dgamma) dgamma[c] += dg;
-      if (dbeta) dbeta[c] += db;
-    }
   }
 }
 
@@ -1312,328 +815,6 @@ __global__ __launch_bounds__(256) void cg_gp_head_mid_kernel(const float* __rest
   stf(&tg, srs * w2[j]);
   g_hd[i] = tg;
   stf(g_h + i, ldf(&tg) * mask[i] * scale);
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Second-order BatchNorm terms of the back-propagated gradient penalty (CGAN, train/cgan_trainer.py:200-203).
-// Notation (tests/test_gp_double_backward_math.py): first backward gy = (gamma/sigma) (gz - m1 - xhat*m2),
-// gz = g_a*act'(z), m1 = mean gz, m2 = mean gz*xhat.  The adjoint sweep carries v = adj(gy) forward through D
-// ("v-chain") and then the usual reverse sweep with two extra inputs per layer (xdir, sigexp).
-// Generic per-channel reduction: NA accumulators per channel, per-workgroup partials [blk][NA][C] (no atomics).
-// ------------------------------------------------------------------------------------------------------
-struct BnAux { const float* aux; int C; };       // aux = scale | shift | mean | invstd
-
-// MODE 1 (v-chain):  acc = { v, v*xhat, v*gy }             inputs a = v, b = y, c = gy
-// MODE 2 (reverse):  acc = { uz, uz*xhat, xdir, xdir*xhat } inputs a = ua, b = y, c = xdir;  uz = ua*act'(z)
-template <typename T, int MODE>
-__global__ __launch_bounds__(256) void bn2_reduce_kernel(const T* __restrict__ a, const T* __restrict__ b, const T* __restrict__ c,
-                                                         const float* __restrict__ aux, float slope, float* __restrict__ partial,
-                                                         long long rows, int C) {
-  constexpr int NA = MODE == 1 ? 3 : 4;
-  extern __shared__ float lsum[];                         // [rstep][NA][C]
-  const int upr = C >> 3;
-  const int u = threadIdx.x % upr, r0 = threadIdx.x / upr, rstep = 256 / upr;
-  const int ch = u * 8;
-  float sc[8], sh[8], mu[8], is[8], acc[NA][8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    sc[k] = aux[ch + k]; sh[k] = aux[C + ch + k]; mu[k] = aux[2 * C + ch + k]; is[k] = aux[3 * C + ch + k];
-#pragma unroll
-    for (int q = 0; q < NA; ++q) acc[q][k] = 0.f;
-  }
-  // two rows of this thread's sequence in flight, accumulated in sequence order (same sums, bit for bit; see bn_bwd_reduce_kernel)
-  constexpr int UNR = 2;
-  const long long stride = (long long)gridDim.x * rstep;
-  for (long long r = (long long)blockIdx.x * rstep + r0; r < rows; r += stride * UNR) {
-    float va[UNR][8], vb[UNR][8], vc[UNR][8];
-#pragma unroll
-    for (int q = 0; q < UNR; ++q) {
-      const long long rq = r + q * stride;
-      if (rq < rows) { ld8(a + rq * C + ch, va[q]); ld8(b + rq * C + ch, vb[q]); ld8(c + rq * C + ch, vc[q]); }
-    }
-#pragma unroll
-    for (int q = 0; q < UNR; ++q) {
-      if (r + q * stride >= rows) break;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float xh = (vb[q][k] - mu[k]) * is[k];
-        if (MODE == 1) {
-          acc[0][k] += va[q][k]; acc[1][k] += va[q][k] * xh; acc[2][k] += va[q][k] * vc[q][k];
-        } else {
-          const float z = vb[q][k] * sc[k] + sh[k];
-          const float uz = z > 0.f ? va[q][k] : slope * va[q][k];
-          acc[0][k] += uz; acc[1][k] += uz * xh; acc[2][k] += vc[q][k]; acc[NA - 1][k] += vc[q][k] * xh;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < NA; ++q)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) lsum[(r0 * NA + q) * C + ch + k] = acc[q][k];
-  __syncthreads();
-  for (int i = threadIdx.x; i < NA * C; i += 256) {
-    float t = 0.f;
-    for (int r = 0; r < rstep; ++r) t += lsum[r * NA * C + i];
-    partial[(long long)blockIdx.x * NA * C + i] = t;
-  }
-}
-
-// sums[i] = sum over workgroups of partial[blk][i], i < NA*C (a multiple of 4): one workgroup per 4 outputs, 256 lanes over
-// the partials with 16-byte loads (one thread per output looping over 256 strided partials took 64 us for C = 64)
-// mode 1 (v-chain): dgamma[c] += sum(v*gy)[c] / gamma[c] (the direct parameter gradient of the v-chain);  mode 2 (reverse sweep):
-// dgamma[c] += sum uz*xhat, dbeta[c] += sum uz - by the thread that owns that sum, instead of a launch of their own
-static __global__ __launch_bounds__(256) void bn2_sums_kernel(const float* __restrict__ partial, int nblk, int NA, int C,
-                                                              float* __restrict__ sums, int mode = 0, const float* __restrict__ gamma = nullptr,
-                                                              float* __restrict__ dgamma = nullptr, float* __restrict__ dbeta = nullptr) {
-  __shared__ float sh[4][4];
-  const int i0 = blockIdx.x * 4, n = NA * C;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  for (int k = threadIdx.x; k < nblk; k += 256) s += *reinterpret_cast<const f32x4*>(partial + (long long)k * n + i0);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s[j] = wave_sum(s[j]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[threadIdx.x >> 6][j] = s[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const int i = i0 + threadIdx.x;
-    const float t = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-    sums[i] = t;
-    if (mode == 1 && i >= 2 * C && i < 3 * C) dgamma[i - 2 * C] += t / gamma[i - 2 * C];
-    if (mode == 2 && i < C) dbeta[i] += t;
-    if (mode == 2 && i >= C && i < 2 * C) dgamma[i - C] += t;
-  }
-}
-
-// v-chain apply:  u = act'(z) * (gamma/sigma) (v - mean v - xhat * mean(v xhat))                 (may overwrite v)
-//                 xdir = -(gamma/sigma) (v*m2 + gz * mean(v xhat)),  gz = gy*sigma/gamma + m1 + xhat*m2
-// s1 = sums of the FIRST backward (sum gz, sum gz*xhat), s3 = {sum v, sum v*xhat, sum v*gy}
-template <typename T>
-__global__ void bn2_vchain_apply_kernel(const T* __restrict__ v, const T* __restrict__ y, const T* __restrict__ gy,
-                                        const float* __restrict__ aux, const float* __restrict__ s1, const float* __restrict__ s3,
-                                        float slope, float inv_count, T* __restrict__ u, T* __restrict__ xdir, long long total8, int C) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)((i * 8) & (C - 1));
-    float vv[8], vy[8], vg[8], ou[8], ox[8];
-    ld8(v + i * 8, vv);
-    ld8(y + i * 8, vy);
-    ld8(gy + i * 8, vg);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float sc = aux[c + k];                           // gamma / sigma
-      const float z = vy[k] * sc + aux[C + c + k];
-      const float xh = (vy[k] - aux[2 * C + c + k]) * aux[3 * C + c + k];
-      const float m1 = s1[c + k] * inv_count, m2 = s1[C + c + k] * inv_count;
-      const float mv = s3[c + k] * inv_count, mvx = s3[C + c + k] * inv_count;
-      const float gz = vg[k] / sc + m1 + xh * m2;
-      ox[k] = -sc * (vv[k] * m2 + gz * mvx);
-      const float ugz = sc * (vv[k] - mv - xh * mvx);
-      ou[k] = z > 0.f ? ugz : slope * ugz;
-    }
-    st8(u + i * 8, ou);
-    st8(xdir + i * 8, ox);
-  }
-}
-// reverse-sweep apply with the penalty's extra inputs:
-//   q = gamma*uz + xdir;  uy = (q - mean q - xhat*mean(q xhat)) / sigma  -  (sum(v*gy)/sigma) * xhat / n
-// s4 = {sum uz, sum uz*xhat, sum xdir, sum xdir*xhat};  vgy = sum v*gy (from the v-chain).  dgamma += sum uz*xhat, dbeta += sum uz
-template <typename T>
-__global__ void bn2_reverse_apply_kernel(const T* __restrict__ ua, const T* __restrict__ y, const T* __restrict__ xdir,
-                                         const float* __restrict__ aux, const float* __restrict__ gamma, const float* __restrict__ s4,
-                                         const float* __restrict__ vgy, float slope, float inv_count, T* __restrict__ uy,
-                                         long long total8, int C) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)((i * 8) & (C - 1));
-    float va[8], vy[8], vx[8], o[8];
-    ld8(ua + i * 8, va);
-    ld8(y + i * 8, vy);
-    ld8(xdir + i * 8, vx);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float g = gamma[c + k], is = aux[3 * C + c + k];
-      const float z = vy[k] * aux[c + k] + aux[C + c + k];
-      const float xh = (vy[k] - aux[2 * C + c + k]) * is;
-      const float uz = z > 0.f ? va[k] : slope * va[k];
-      const float q = g * uz + vx[k];
-      const float mq = (g * s4[c + k] + s4[2 * C + c + k]) * inv_count;
-      const float mqx = (g * s4[C + c + k] + s4[3 * C + c + k]) * inv_count;
-      o[k] = (q - mq - xh * mqx) * is - vgy[c + k] * is * xh * inv_count;
-    }
-    st8(uy + i * 8, o);
-  }
-}
-// The second-order chains as two launches instead of three (round 5; the backward twin bn_bwd_apply_fused_kernel above): the apply
-// kernel's workgroups own a 64-channel slice of a pixel range and sum the partial rows of bn2_reduce_kernel for THEIR channels
-// themselves ([blk][NA][C] floats; double accumulation in an order fixed by the geometry) - bn2_sums_kernel, ~6 us on the main
-// stream's chain eight times per CGAN step, is gone.  The first workgroup of a slice writes the sums (ws[q*C + c], as bn2_sums_kernel
-// did: the reverse sweep reads the v-chain's) and the direct parameter gradients.
-// -> LDS tot[q][j] = sum over the nblk rows of accumulator q, channel slice*64 + j   (q < NA)
-template <int NA>
-__device__ __forceinline__ void bn2_slice_sums(const float* __restrict__ partial, int nblk, int C, int slice, double (*part)[NA * 64], float (*tot)[64]) {
-  constexpr int NCOL = NA * 16, RL = 256 / NCOL;            // float4 columns of a slice row, row lanes (5 or 4)
-  const int t = threadIdx.x, q4 = t % NCOL, rl = t / NCOL;
-  if (rl < RL) {
-    const float* col = partial + (q4 >> 4) * C + slice * 64 + (q4 & 15) * 4;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    constexpr int RU = 8;
-    for (int r0 = rl; r0 < nblk; r0 += RL * RU) {
-      f32x4 v[RU];
-#pragma unroll
-      for (int u = 0; u < RU; ++u)
-        if (r0 + u * RL < nblk) v[u] = *reinterpret_cast<const f32x4*>(col + (long long)(r0 + u * RL) * NA * C);
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        if (r0 + u * RL >= nblk) break;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] += (double)v[u][i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[rl][q4 * 4 + i] = acc[i];
-  }
-  __syncthreads();
-  if (t < NA * 64) {
-    double sd = 0.0;
-#pragma unroll
-    for (int k = 0; k < RL; ++k) sd += part[k][t];
-    tot[t >> 6][t & 63] = (float)sd;
-  }
-  __syncthreads();
-}
-
-// v-chain apply (bn2_vchain_apply_kernel's arithmetic) with the sums of ITS slice formed in the prologue
-template <typename T>
-__global__ __launch_bounds__(256) void bn2_vchain_apply_fused_kernel(const T* __restrict__ v, const T* __restrict__ y, const T* __restrict__ gy,
-                                                                     const float* __restrict__ aux, const float* __restrict__ s1,
-                                                                     const float* __restrict__ partial, int nblk, float* __restrict__ ws,
-                                                                     const float* __restrict__ gamma, float* __restrict__ dgamma, float slope,
-                                                                     float inv_count, T* __restrict__ u, T* __restrict__ xdir, long long rows, int C) {
-  __shared__ double part[5][3 * 64];
-  __shared__ float tot[3][64];
-  __builtin_amdgcn_s_setprio(JCK_BN_PRIO);
-  const int t = threadIdx.x, s = blockIdx.y, u8 = t & 7;
-  const long long rstep = (long long)gridDim.x * 32, rfirst = (long long)blockIdx.x * 32 + (t >> 3);
-  constexpr int BU = 2;
-  Raw8<T> rv[BU], ry[BU], rg[BU];
-#pragma unroll
-  for (int q = 0; q < BU; ++q)
-    if (rfirst + q * rstep < rows) {
-      const long long e = (rfirst + q * rstep) * C + s * 64 + u8 * 8;
-      ldraw(v + e, rv[q]); ldraw(y + e, ry[q]); ldraw(gy + e, rg[q]);
-    }
-  bn2_slice_sums<3>(partial, nblk, C, s, part, tot);
-  if (blockIdx.x == 0 && t < 64) {
-    const int c = s * 64 + t;
-    ws[c] = tot[0][t]; ws[C + c] = tot[1][t]; ws[2 * C + c] = tot[2][t];
-    if (dgamma) dgamma[c] += tot[2][t] / gamma[c];
-  }
-  float sc[8], sh[8], mu[8], is[8], m1[8], m2[8], mv[8], mvx[8];
-  {
-    const int c0 = s * 64 + u8 * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      sc[k] = aux[c0 + k]; sh[k] = aux[C + c0 + k]; mu[k] = aux[2 * C + c0 + k]; is[k] = aux[3 * C + c0 + k];
-      m1[k] = s1[c0 + k] * inv_count; m2[k] = s1[C + c0 + k] * inv_count;
-      mv[k] = tot[0][u8 * 8 + k] * inv_count; mvx[k] = tot[1][u8 * 8 + k] * inv_count;
-    }
-  }
-  for (long long r0 = rfirst; r0 < rows; r0 += rstep * BU) {
-    if (r0 != rfirst) {
-#pragma unroll
-      for (int q = 0; q < BU; ++q)
-        if (r0 + q * rstep < rows) {
-          const long long e = (r0 + q * rstep) * C + s * 64 + u8 * 8;
-          ldraw(v + e, rv[q]); ldraw(y + e, ry[q]); ldraw(gy + e, rg[q]);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < BU; ++q) {
-      if (r0 + q * rstep >= rows) break;
-      float vv[8], vy[8], vg[8], ou[8], ox[8];
-      unraw(rv[q], vv); unraw(ry[q], vy); unraw(rg[q], vg);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float z = vy[k] * sc[k] + sh[k];
-        const float xh = (vy[k] - mu[k]) * is[k];
-        const float gz = vg[k] / sc[k] + m1[k] + xh * m2[k];
-        ox[k] = -sc[k] * (vv[k] * m2[k] + gz * mvx[k]);
-        const float ugz = sc[k] * (vv[k] - mv[k] - xh * mvx[k]);
-        ou[k] = z > 0.f ? ugz : slope * ugz;
-      }
-      const long long e = (r0 + q * rstep) * C + s * 64 + u8 * 8;
-      st8(u + e, ou);
-      st8(xdir + e, ox);
-    }
-  }
-}
-
-// reverse-sweep apply (bn2_reverse_apply_kernel's arithmetic) with the sums of ITS slice formed in the prologue
-template <typename T>
-__global__ __launch_bounds__(256) void bn2_reverse_apply_fused_kernel(const T* __restrict__ ua, const T* __restrict__ y, const T* __restrict__ xdir,
-                                                                      const float* __restrict__ aux, const float* __restrict__ gamma,
-                                                                      const float* __restrict__ partial, int nblk, float* __restrict__ ws,
-                                                                      const float* __restrict__ vgy, float* __restrict__ dgamma,
-                                                                      float* __restrict__ dbeta, float slope, float inv_count, T* __restrict__ uy,
-                                                                      long long rows, int C) {
-  __shared__ double part[4][4 * 64];
-  __shared__ float tot[4][64];
-  __builtin_amdgcn_s_setprio(JCK_BN_PRIO);
-  const int t = threadIdx.x, s = blockIdx.y, u8 = t & 7;
-  const long long rstep = (long long)gridDim.x * 32, rfirst = (long long)blockIdx.x * 32 + (t >> 3);
-  constexpr int BU = 2;
-  Raw8<T> ra[BU], ry[BU], rx[BU];
-#pragma unroll
-  for (int q = 0; q < BU; ++q)
-    if (rfirst + q * rstep < rows) {
-      const long long e = (rfirst + q * rstep) * C + s * 64 + u8 * 8;
-      ldraw(ua + e, ra[q]); ldraw(y + e, ry[q]); ldraw(xdir + e, rx[q]);
-    }
-  bn2_slice_sums<4>(partial, nblk, C, s, part, tot);
-  if (blockIdx.x == 0 && t < 64) {
-    const int c = s * 64 + t;
-    ws[c] = tot[0][t]; ws[C + c] = tot[1][t]; ws[2 * C + c] = tot[2][t]; ws[3 * C + c] = tot[3][t];
-    if (dbeta) dbeta[c] += tot[0][t];
-    if (dgamma) dgamma[c] += tot[1][t];
-  }
-  float g[8], sc[8], sh[8], mu[8], is[8], mq[8], mqx[8], kv[8];
-  {
-    const int c0 = s * 64 + u8 * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      g[k] = gamma[c0 + k];
-      sc[k] = aux[c0 + k]; sh[k] = aux[C + c0 + k]; mu[k] = aux[2 * C + c0 + k]; is[k] = aux[3 * C + c0 + k];
-      mq[k] = (g[k] * tot[0][u8 * 8 + k] + tot[2][u8 * 8 + k]) * inv_count;
-      mqx[k] = (g[k] * tot[1][u8 * 8 + k] + tot[3][u8 * 8 + k]) * inv_count;
-      kv[k] = vgy[c0 + k];
-    }
-  }
-  for (long long r0 = rfirst; r0 < rows; r0 += rstep * BU) {
-    if (r0 != rfirst) {
-#pragma unroll
-      for (int q = 0; q < BU; ++q)
-        if (r0 + q * rstep < rows) {
-          const long long e = (r0 + q * rstep) * C + s * 64 + u8 * 8;
-          ldraw(ua + e, ra[q]); ldraw(y + e, ry[q]); ldraw(xdir + e, rx[q]);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < BU; ++q) {
-      if (r0 + q * rstep >= rows) break;
-      float va[8], vy[8], vx[8], o[8];
-      unraw(ra[q], va); unraw(ry[q], vy); unraw(rx[q], vx);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float z = vy[k] * sc[k] + sh[k];
-        const float xh = (vy[k] - mu[k]) * is[k];
-        const float uz = z > 0.f ? va[k] : slope * va[k];
-        const float qq = g[k] * uz + vx[k];
-        o[k] = (qq - mq[k] - xh * mqx[k]) * is[k] - kv[k] * is[k] * xh * inv_count;
-      }
-      st8(uy + (r0 + q * rstep) * C + s * 64 + u8 * 8, o);
-    }
-  }
 }
 
 // h[b][j] = sum_z slab[z][b][j] + bias[j];  hd = h * mask * scale     (Linear(8392,256) finish + Dropout, model/CGAN.py:104-105,122)

@@ -1,4 +1,4 @@
-// Host glue shared by the launcher units (ops.hip, ops_gemm.hip) and the engine units (engine.hip, engine_infer.hip): error and launch
+// Host glue shared by the launcher units (ops.hip, ops_bn.hip, ops_gemm.hip) and the engine units (engine.hip, engine_infer.hip): error and launch
 // macros, the kernel registry, the knobs and the prototypes of the functions that cross a unit.  No kernels: each unit includes the
 // kernel headers it launches from.
 #pragma once
@@ -131,8 +131,8 @@ int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, doubl
                 float grad_scale, const float* hp, hipStream_t st, float* zero = nullptr, long long nzero = 0,
                 const unsigned* skip_if = nullptr,       // skip_if: device word; non-zero = leave p, m, v untouched (a grid barrier of the step timed out)
                 float* ema = nullptr);                   // ema: moving average of p, advanced in the same launch with the weight in hp[2]
-const unsigned* jck_grid_sync_error_word(const void* sync_ws);
-// BatchNorm finalize + apply as one launch where the statistics rows are few (ops.hip); *fused = false: nothing was launched
+const unsigned* jck_grid_sync_error_word(const void* sync_ws);      // (ops_bn.hip)
+// BatchNorm finalize + apply as one launch where the statistics rows are few (ops_bn.hip); *fused = false: nothing was launched
 int bn_fwd_fused(int prec, const void* y, const float* stats, int slots_per_group, float count, const float* gamma, const float* beta,
                  float eps, float slope, void* a, float* aux, float* stat_out, float* running_mean, float* running_var, int64_t* nbt,
                  float momentum, long long rows_per_group, int C, int groups, long long out_row, long long out_pitch, hipStream_t stream,
@@ -141,6 +141,7 @@ int bn_fwd_fused(int prec, const void* y, const float* stats, int slots_per_grou
 // that writes the result - the dispatch packet's own completion signal (hipExtLaunchKernel's stop event) instead of a
 // hipEventRecord behind it, whose marker packet costs the launch stream ~6-7 us of idle time on this runtime.  The event is an
 // explicit argument (round 3 handed it over through a thread-local "armed" slot that the next armable launch consumed).
+// (bn_act_bwd_res_ev, bn_act_fwd_pitched: ops_bn.hip; the others: ops.hip)
 int bn_act_bwd_res_ev(int prec, const void* g_a, const void* y, const float* aux, float slope, float* sums, void* g_y, float* dgamma,
                       float* dbeta, long long rows_per_group, int C, int groups, int grad_groups, void* sync_ws, hipStream_t stream,
                       hipEvent_t done);

@@ -68,7 +68,7 @@ class _RndW(Function):
 class _BnAct(Function):
     """BatchNorm2d (train) + (Leaky)ReLU exactly as the kernels compute it: statistics from the fp32 conv accumulators,
     y stored bf16, a = act(scale*y + shift) stored bf16; backward from the bf16 g_a and y with the saved mean / invstd:
-    g_z = g_a*act'(z), g_y = scale*(g_z - mean g_z - xhat*mean(g_z xhat)) stored bf16 (csrc/ew.hpp: bn_finalize_kernel,
+    g_z = g_a*act'(z), g_y = scale*(g_z - mean g_z - xhat*mean(g_z xhat)) stored bf16 (csrc/bn.hpp: bn_finalize_kernel,
     bn_act_fwd_kernel, bn_bwd_reduce_kernel, bn_bwd_apply_kernel)."""
 
     @staticmethod

@@ -3,7 +3,7 @@ for tests/test_bn2_math.py, tests/test_bn2_gpu.py and tests/test_bn_edges_gpu.py
 
   xhat = (y - mean) / sigma, sigma = sqrt(biased var + eps), z = gamma * xhat + beta, a = z > 0 ? z : slope * z, s = act'(z)
   first backward:   gz = ga * s, m1 = mean gz, m2 = mean gz*xhat, gy = (gamma / sigma) (gz - m1 - xhat * m2)
-  second backward of S = <v, gy> + <ua, a> (the notation above the bn2 kernels in csrc/ew.hpp):
+  second backward of S = <v, gy> + <ua, a> (the notation above the bn2 kernels in csrc/bn2.hpp):
     xdir = -(gamma / sigma) (v * m2 + gz * mean(v xhat))
     u    = dS/dga = s (gamma / sigma) (v - mean v - xhat * mean(v xhat))
     q    = gamma * uz + xdir, uz = ua * s

@@ -127,7 +127,7 @@ def test_bn2_chain_vs_fp64(G, shape, prec, slope, kind):
 @pytest.mark.parametrize("prec", [1, 0])
 def test_bn2_aliasing_and_optional_gradients(G, prec, fuse):
     """At (700, 64): u written over v (the header allows it); jck_bn2_vchain without dgamma; jck_bn2_reverse with only one of
-    dgamma / dbeta, which writes neither (csrc/ops.hip) - the outputs and the sums are what they are with everything passed."""
+    dgamma / dbeta, which writes neither (csrc/ops_bn.hip) - the outputs and the sums are what they are with everything passed."""
     rows, c = 700, 64
     inp = storage_round(bn_ref.inputs(rows, c, seed=7), prec)
     ref = bn_ref.second_order(slope=0.2, **inp)

@@ -73,7 +73,7 @@ def test_every_term_is_visible_in_bf16(shape):
 
 
 def emulate(inp, slope, bf16):
-    """The chain as the kernels run it (csrc/ew.hpp), in fp32 on the CPU: statistics rows rounded once from fp64, finalize in double,
+    """The chain as the kernels run it (csrc/bn.hpp, csrc/bn2.hpp), in fp32 on the CPU: statistics rows rounded once from fp64, finalize in double,
     everything else in fp32; y, ga, v, ua arrive in the storage type and gy, xdir, u, uy are rounded to it where the kernels store
     them.  The sums are torch's fp32 sums: the order of a summation is the kernels' own business."""
     st = (lambda t: t.float().bfloat16().float()) if bf16 else (lambda t: t.float())
