@@ -255,6 +255,23 @@ int jck_resize_taps_build(int Hs, int Ws, int S, void* host_buf);
 int jck_img_prep_u8_any(int prec, const unsigned char* data, const int64_t* idx, const unsigned char* flip, const float* noise,
                         const unsigned* rng, int tensor_id, float keep, float mix, void* out_nhwc4, float* out_nchw, int B, int Hs,
                         int Ws, int S, const void* taps_dev, void* stream);
+/* The same transform of a BOX of the source: PIL.Image.crop((x0, y0, x0 + Wc, y0 + Hc)).resize((S, S), BILINEAR) - the resize of
+ * the cropped array, not Pillow's resize(box=...) - then ToTensor, Normalize and the noise mix as above.  The box is Hc x Wc source
+ * pixels with its top-left corner at (y0, x0): 1 <= Hc <= Hs, 1 <= Wc <= Ws, 0 <= y0 <= Hs - Hc, 0 <= x0 <= Ws - Wc.  taps_dev is
+ * the table of jck_resize_taps_build(Hc, Wc, S); a flip mirrors inside the box (box column x reads x0 + Wc - 1 - x).  origin:
+ * device int32 [B][2] = (y0, x0) per image, or NULL for the scalar (y0, x0) of the call.  A scalar origin outside its range is
+ * JCK_E_ARG; per-image origins cannot be checked without a sync, so the kernel clamps each to its range and no origin makes it read
+ * outside its image.  Every other argument, refusal and the arithmetic are jck_img_prep_u8_any's: a whole-image box gives its bits.
+ * The kernel is jck_img_prep_u8_any's with the corner added to its addresses.
+ * jck_resize_lds_bytes: the dynamic LDS in bytes that either launch takes for Hs source rows (of the image, or of the box; never
+ * more than 65536), and through the pointers that are not NULL the output rows per workgroup and the source rows they can touch;
+ * host arithmetic only.  JCK_E_ARG (negative) for an unsupported geometry. */
+long long jck_resize_lds_bytes(int Hs, int S, int* band, int* rows);
+int jck_img_prep_u8_box(int prec, const unsigned char* data, const int64_t* idx, const unsigned char* flip,
+                        const int* origin /* device int32 [B][2] = (y0, x0) per image, or NULL */, const float* noise,
+                        const unsigned* rng, int tensor_id, float keep, float mix, void* out_nhwc4, float* out_nchw,
+                        int B, int Hs, int Ws, int Hc, int Wc, int y0, int x0 /* used when origin is NULL */, int S,
+                        const void* taps_dev /* table of (Hc, Wc, S) */, void* stream);
 /* Evaluation branch (train/dcgan_trainer.py:202-206, train/cgan_trainer.py:227-231): out = (resize(pre_scale*in + pre_shift,
  * [OH,OW]) - mean[c]) / std[c], bilinear with align_corners = False exactly as aten::upsample_bilinear2d (what
  * torchvision.transforms.functional.resize does to a tensor; an upscale, so antialiasing is moot).  NCHW fp32 in / out;
@@ -507,6 +524,11 @@ typedef struct jck_step_inputs {
   int real_h, real_w;
   const unsigned char* real_flip;
   const void* real_taps;
+  /* a box of every image (optional; all zero = the whole image, as above): real_box_h x real_box_w source pixels at (real_y0,
+   * real_x0), or at real_origin's int32 [B][2] = (y0, x0) per image when that is set; real_taps is then the table of
+   * (real_box_h, real_box_w, S) and the step applies jck_img_prep_u8_box. */
+  int real_box_h, real_box_w, real_y0, real_x0;
+  const int* real_origin;
 } jck_step_inputs;
 int jck_engine_phase(jck_engine*, int phase, const jck_step_inputs* in, void* stream);
 /* device pointer to float[8]: loss_d, loss_g, D(x), D(G(z))_1, D(G(z))_2, gp, loss_real, loss_fake (valid after PHASE_G_STEP) */

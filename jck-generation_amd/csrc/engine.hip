@@ -766,6 +766,10 @@ static int g_backward(jck_engine* e, const void* g_fake, int B, hipStream_t st, 
 // the real batch -> NHWC4 with instance noise (:160): from an fp32 NCHW tensor, or gathered from the device-resident uint8
 // dataset with the input transform applied on the fly
 static int prep_real(jck_engine* e, const jck_step_inputs* in, int B, hipStream_t st) {
+  if (in->real_u8 && in->real_box_h)     // a box of every image: real_taps is the box's table (the launcher refuses a missing one)
+    return jck_img_prep_u8_box(e->prec, in->real_u8, in->real_idx, in->real_flip, in->real_origin, in->noise_real, in->noise_real ? nullptr : e->rng(),
+                               0, 0.9f, 0.1f, e->real_noisy, nullptr, B, in->real_h, in->real_w, in->real_box_h, in->real_box_w, in->real_y0,
+                               in->real_x0, TT.S, in->real_taps, st);
   if (in->real_u8 && in->real_taps)      // any source size, either engine size, optional mirror: Pillow's general bilinear taps
     return jck_img_prep_u8_any(e->prec, in->real_u8, in->real_idx, in->real_flip, in->noise_real, in->noise_real ? nullptr : e->rng(), 0,
                                0.9f, 0.1f, e->real_noisy, nullptr, B, in->real_h, in->real_w, TT.S, in->real_taps, st);

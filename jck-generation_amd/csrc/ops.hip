@@ -44,7 +44,7 @@ static constexpr KernelInfo KERNELS[] = {
     {nullptr, "bn_act_fwd"}, {nullptr, "bn_bwd_resident"}, {nullptr, "bn_bwd_3launch"},
     {nullptr, "latent_loss"}, {nullptr, "latent_adam"},
     {nullptr, "conv_up_mask"}, {nullptr, "leaky_affine_bwd"}, {nullptr, "critic_ds"}, {nullptr, "latent_loss_ex"},
-    {nullptr, "feat_match"}, {nullptr, "img_prep_u8_any"}};
+    {nullptr, "feat_match"}, {nullptr, "img_prep_u8_any"}, {nullptr, "img_prep_u8_box"}};
 #undef SAME
 static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "KERNELS and the KernelId offsets disagree");
 // the id arithmetic against the table, row by row: what every launch site's id resolves to (the affine 16 x 256 form with 8..32 gathered
@@ -62,7 +62,7 @@ static_assert(row(kid_igemm<PrecBf16, 128, 128, 1>(), "igemm<bf16,128,128>", "ig
               row(kid_wgrad<PrecBf16x3, 128, 128, 1>(), "wgrad<bf16x3,128,128>", "wgrad<bf16x3,128,128>") && row(kid_wgrad<PrecBf16x3, 128, 64, 1>(), "wgrad<bf16x3,128,64>", "wgrad<bf16x3,128,64>") && row(kid_wgrad<PrecBf16x3, 64, 64, 2>(), "wgrad<bf16x3,64,64,img>", "wgrad<bf16x3,64,64,img>") && row(kid_wgrad<PrecBf16x3, 64, 64, 1>(), "wgrad<bf16x3,64,64>", "wgrad<bf16x3,64,64>") &&
               same_str(KERNELS[K_LATENT_LOSS].label, "latent_loss") && same_str(KERNELS[K_LATENT_ADAM].label, "latent_adam") &&
               same_str(KERNELS[K_CONV_UP_MASK].label, "conv_up_mask") && same_str(KERNELS[K_LEAKY_AFFINE_BWD].label, "leaky_affine_bwd") &&
-              same_str(KERNELS[K_CRITIC_DS].label, "critic_ds") && same_str(KERNELS[K_LATENT_LOSS_EX].label, "latent_loss_ex") && same_str(KERNELS[K_FEAT_MATCH].label, "feat_match") && same_str(KERNELS[K_IMG_PREP_ANY].label, "img_prep_u8_any") &&
+              same_str(KERNELS[K_CRITIC_DS].label, "critic_ds") && same_str(KERNELS[K_LATENT_LOSS_EX].label, "latent_loss_ex") && same_str(KERNELS[K_FEAT_MATCH].label, "feat_match") && same_str(KERNELS[K_IMG_PREP_ANY].label, "img_prep_u8_any") && same_str(KERNELS[K_IMG_PREP_BOX].label, "img_prep_u8_box") &&
               same_str(KERNELS[K_BN_ACT_FWD].label, "bn_act_fwd") && same_str(KERNELS[K_BN_BWD_RES].label, "bn_bwd_resident") && same_str(KERNELS[K_BN_BWD_3L].label, "bn_bwd_3launch") &&
               kid_igemm<PrecBf16, 16, 256, 0>() == kid_igemm<PrecBf16, 16, 256, 1>() && !KERNELS[K_IGEMM + 3].launch,
               "KERNELS and the kid_* functions disagree");
@@ -273,6 +273,26 @@ extern "C" int jck_resize_taps_build(int Hs, int Ws, int S, void* host_buf) {
   resize_axis_taps(Hs, S, KY, ax, ax + S, ax + 2 * S);
   return JCK_OK;
 }
+// The band of output rows of one workgroup and the dynamic LDS it takes, for Hs source rows (of the image, or of the box): the source
+// rows a band can touch are (band - 1) * scale + 2 * support + 1 <= band * Hs / S + 2 * ceil(Hs / S) + 2, each 3 * S bytes after the
+// horizontal pass; the band is halved while that exceeds 64 KiB
+static long long resize_band_lds(int Hs, int S, int* band_out, int* rows_out) {
+  int band = RESIZE_BAND, rows = 0;
+  for (;; band >>= 1) {
+    rows = std::min(band * Hs / S + 2 * ((Hs + S - 1) / S) + 2, Hs);
+    if ((long long)rows * 3 * S <= 65536 || band == 1) break;
+  }
+  *band_out = band, *rows_out = rows;
+  return (long long)rows * 3 * S;
+}
+extern "C" long long jck_resize_lds_bytes(int Hs, int S, int* band, int* rows) {
+  if (!resize_geometry_ok(Hs, 1, S)) JCK_FAIL(JCK_E_ARG, "resize_lds_bytes: S must be 64 or 128 and 1 <= Hs <= " + std::to_string(JCK_RESIZE_MAX_SRC));
+  int b, r;
+  const long long bytes = resize_band_lds(Hs, S, &b, &r);
+  if (band) *band = b;
+  if (rows) *rows = r;
+  return bytes;
+}
 extern "C" int jck_img_prep_u8_any(int prec, const unsigned char* data, const int64_t* idx, const unsigned char* flip, const float* noise,
                                    const unsigned* rng, int tensor_id, float keep, float mix, void* out_nhwc4, float* out_nchw, int B,
                                    int Hs, int Ws, int S, const void* taps_dev, void* stream) {
@@ -281,19 +301,41 @@ extern "C" int jck_img_prep_u8_any(int prec, const unsigned char* data, const in
   if (prec != JCK_PREC_BF16 && !prec_f32_storage(prec)) JCK_FAIL(JCK_E_ARG, "bad prec");
   if ((uintptr_t)taps_dev % 4) JCK_FAIL(JCK_E_ARG, "img_prep_u8_any: taps_dev must be 4-byte aligned");
   if (!out_nhwc4 && !out_nchw) return JCK_OK;
-  // source rows a band of output rows can touch: (band - 1) * scale + 2 * support + 1 <= band * Hs / S + 2 * ceil(Hs / S) + 2
-  int band = RESIZE_BAND, rows = 0;
-  for (;; band >>= 1) {
-    rows = std::min(band * Hs / S + 2 * ((Hs + S - 1) / S) + 2, Hs);
-    if ((long long)rows * 3 * S <= 65536 || band == 1) break;
-  }
-  if ((long long)rows * 3 * S > 65536) JCK_FAIL(JCK_E_ARG, "img_prep_u8_any: no band of output rows fits 64 KiB of LDS");
+  int band, rows;
+  if (resize_band_lds(Hs, S, &band, &rows) > 65536) JCK_FAIL(JCK_E_ARG, "img_prep_u8_any: no band of output rows fits 64 KiB of LDS");
   const hipStream_t st = (hipStream_t)stream;
   ProfScope prof(K_IMG_PREP_ANY, 0.0, st, (double)B * (3.0 * Hs * Ws + (double)S * S * (out_nhwc4 ? (prec == JCK_PREC_BF16 ? 8 : 16) : 12)));
   DISPATCH_T(prec, hipLaunchKernelGGL(img_prep_u8_any_kernel<T>, dim3((unsigned)B * (S / band)), dim3(RESIZE_THREADS), (size_t)rows * 3 * S, st,
                                       data, (const long long*)idx, flip, noise, rng, (unsigned)tensor_id, keep, mix, (T*)out_nhwc4, out_nchw,
                                       Hs, Ws, S, resize_ksize(Ws, S), resize_ksize(Hs, S), band, rows, (unsigned)JCK_RESIZE_TAPS_MAGIC,
                                       (const int*)taps_dev));
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+// ---- the same transform of a box of the source (img_prep_u8_box_kernel): the table, the band and the LDS are those of a source of
+// Hc x Wc; the kernel adds the box's corner to its addresses ----
+extern "C" int jck_img_prep_u8_box(int prec, const unsigned char* data, const int64_t* idx, const unsigned char* flip, const int* origin,
+                                   const float* noise, const unsigned* rng, int tensor_id, float keep, float mix, void* out_nhwc4,
+                                   float* out_nchw, int B, int Hs, int Ws, int Hc, int Wc, int y0, int x0, int S, const void* taps_dev,
+                                   void* stream) {
+  if (!data || !taps_dev || B < 1 || B > (1 << 24)) JCK_FAIL(JCK_E_ARG, "img_prep_u8_box: data and taps_dev must be set, 1 <= B <= 2^24");
+  if (!resize_geometry_ok(Hs, Ws, S)) JCK_FAIL(JCK_E_ARG, "img_prep_u8_box: S must be 64 or 128 and 1 <= Hs, Ws <= " + std::to_string(JCK_RESIZE_MAX_SRC));
+  if (Hc < 1 || Wc < 1 || Hc > Hs || Wc > Ws)
+    JCK_FAIL(JCK_E_ARG, "img_prep_u8_box: a box of " + std::to_string(Hc) + "x" + std::to_string(Wc) + " does not lie in a source of " + std::to_string(Hs) + "x" + std::to_string(Ws));
+  if (!origin && (y0 < 0 || x0 < 0 || y0 > Hs - Hc || x0 > Ws - Wc))
+    JCK_FAIL(JCK_E_ARG, "img_prep_u8_box: origin (" + std::to_string(y0) + ", " + std::to_string(x0) + ") puts the box outside the source");
+  if (prec != JCK_PREC_BF16 && !prec_f32_storage(prec)) JCK_FAIL(JCK_E_ARG, "bad prec");
+  if ((uintptr_t)taps_dev % 4 || (uintptr_t)origin % 4) JCK_FAIL(JCK_E_ARG, "img_prep_u8_box: taps_dev and origin must be 4-byte aligned");
+  if (!out_nhwc4 && !out_nchw) return JCK_OK;
+  int band, rows;
+  const long long lds = resize_band_lds(Hc, S, &band, &rows);
+  if (lds > 65536) JCK_FAIL(JCK_E_ARG, "img_prep_u8_box: no band of output rows fits 64 KiB of LDS");
+  const hipStream_t st = (hipStream_t)stream;
+  ProfScope prof(K_IMG_PREP_BOX, 0.0, st, (double)B * (3.0 * Hc * Wc + (double)S * S * (out_nhwc4 ? (prec == JCK_PREC_BF16 ? 8 : 16) : 12)));
+  DISPATCH_T(prec, hipLaunchKernelGGL(img_prep_u8_box_kernel<T>, dim3((unsigned)B * (S / band)), dim3(RESIZE_THREADS), (size_t)lds, st, data,
+                                      (const long long*)idx, flip, origin, noise, rng, (unsigned)tensor_id, keep, mix, (T*)out_nhwc4,
+                                      out_nchw, Hs, Ws, Hc, Wc, y0, x0, S, resize_ksize(Wc, S), resize_ksize(Hc, S), band, rows,
+                                      (unsigned)JCK_RESIZE_TAPS_MAGIC, (const int*)taps_dev));
   HIPCHK(hipGetLastError());
   return JCK_OK;
 }

@@ -82,6 +82,7 @@ enum KernelId : int {
   K_CONV_UP_MASK, K_LEAKY_AFFINE_BWD, K_CRITIC_DS, K_LATENT_LOSS_EX,
   K_FEAT_MATCH,                                   // feature matching on D's activations (latent.hpp): a label without a launch name
   K_IMG_PREP_ANY,                                 // any-size input pipeline (resize.hpp): a label without a launch name, like img_prep_u8_kernel beside it
+  K_IMG_PREP_BOX,                                 // the same transform of a box of the source (resize.hpp), likewise a label only
   K_COUNT
 };
 template <class P> constexpr int kid_prec() { return P::SPLIT ? 2 : P::IS_F32 ? 1 : 0; }

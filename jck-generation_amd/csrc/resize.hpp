@@ -10,6 +10,10 @@
 // Stage 2, behind the one barrier: the vertical pass out of LDS.  A wave holds 64 neighbouring x of ONE output row, so a tap's
 // weight is the same in every lane and its read is 64 consecutive bytes of one LDS row = 16 distinct dwords in 16 distinct banks,
 // four lanes sharing each: no bank conflict at any row stride, no padding.  No atomics; an output row depends on its own image only.
+//
+// Both kernels are resize_band: the resize of the box of Hc x Wc source pixels whose top-left corner is (oy, ox) inside the Hs x Ws
+// image, with the tap table of (Hc, Wc, S).  img_prep_u8_any_kernel is the whole image (Hc = Hs, Wc = Ws, corner 0, 0: the offsets
+// fold away); img_prep_u8_box_kernel takes the box and one corner for all images or one per image, clamped into the image.
 #pragma once
 #include "common.hpp"
 #include "philox.hpp"
@@ -22,23 +26,21 @@ constexpr int RESIZE_BAND = 16;          // output rows per workgroup (the launc
 __device__ __forceinline__ int resize_u8(int acc) { return min(max(acc >> 22, 0), 255); }
 
 template <typename T>
-__global__ __launch_bounds__(RESIZE_THREADS) void img_prep_u8_any_kernel(
+__device__ __forceinline__ void resize_band(
     const unsigned char* __restrict__ data, const long long* __restrict__ idx, const unsigned char* __restrict__ flip,
     const float* __restrict__ noise, const unsigned* __restrict__ rng, unsigned rng_tensor, float keep, float mix,
-    T* __restrict__ out_nhwc4, float* __restrict__ out_nchw, int Hs, int Ws, int S, int KX, int KY, int band, int max_rows,
-    unsigned magic, const int* __restrict__ taps) {
+    T* __restrict__ out_nhwc4, float* __restrict__ out_nchw, int Hs, int Ws, int Hc, int Wc, int oy, int ox, int S, int KX, int KY,
+    int band, int max_rows, const int* __restrict__ taps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hrow[];      // [rows][3][S]: the band's source rows after the horizontal pass
-  // a table of another geometry (KX, KY are the launcher's own count for this one): nothing is read past it, nothing is written
-  if ((unsigned)taps[0] != magic || taps[1] != Hs || taps[2] != Ws || taps[3] != S || taps[4] != KX || taps[5] != KY) return;
   const int *xlo = taps + RESIZE_HDR, *xcnt = xlo + S, *xk = xcnt + S;
   const int *ylo = xk + KX * S, *ycnt = ylo + S, *yk = ycnt + S;
   const int bands = S / band;
   const long long n = blockIdx.x / bands;
   const int y0 = (int)(blockIdx.x % bands) * band;
-  const int r0 = min(max(ylo[y0], 0), Hs - 1);
-  const int nrows = min(min(max(ylo[y0 + band - 1] + ycnt[y0 + band - 1] - r0, 1), max_rows), Hs - r0);
+  const int r0 = min(max(ylo[y0], 0), Hc - 1);
+  const int nrows = min(min(max(ylo[y0 + band - 1] + ycnt[y0 + band - 1] - r0, 1), max_rows), Hc - r0);
   const int x = threadIdx.x % S, g = threadIdx.x / S, G = RESIZE_THREADS / S;
-  const unsigned char* src = data + (idx ? idx[n] : n) * 3ll * Hs * Ws;
+  const unsigned char* src = data + (idx ? idx[n] : n) * 3ll * Hs * Ws + (long long)oy * Ws + ox;      // the box's first pixel, channel 0
   const bool mirror = flip && flip[n];
 
   // ---- stage 1: horizontal pass of source rows r0 .. r0 + nrows - 1, three channels each ----
@@ -55,8 +57,8 @@ __global__ __launch_bounds__(RESIZE_THREADS) void img_prep_u8_any_kernel(
       }
       for (int j = 0; j < cnt; ++j) {
         const int w = xk[j * S + x];
-        int col = min(max(lo + j, 0), Ws - 1);
-        if (mirror) col = Ws - 1 - col;
+        int col = min(max(lo + j, 0), Wc - 1);
+        if (mirror) col = Wc - 1 - col;                                // a flip mirrors inside the box
 #pragma unroll
         for (int u = 0; u < RESIZE_ROWS; ++u) acc[u] += w * (int)rp[u][col];
       }
@@ -96,4 +98,34 @@ __global__ __launch_bounds__(RESIZE_THREADS) void img_prep_u8_any_kernel(
     v[3] = 0.f;
     if (out_nhwc4) st4(out_nhwc4 + i * 4, v);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(RESIZE_THREADS) void img_prep_u8_any_kernel(
+    const unsigned char* __restrict__ data, const long long* __restrict__ idx, const unsigned char* __restrict__ flip,
+    const float* __restrict__ noise, const unsigned* __restrict__ rng, unsigned rng_tensor, float keep, float mix,
+    T* __restrict__ out_nhwc4, float* __restrict__ out_nchw, int Hs, int Ws, int S, int KX, int KY, int band, int max_rows,
+    unsigned magic, const int* __restrict__ taps) {
+  // a table of another geometry (KX, KY are the launcher's own count for this one): nothing is read past it, nothing is written
+  if ((unsigned)taps[0] != magic || taps[1] != Hs || taps[2] != Ws || taps[3] != S || taps[4] != KX || taps[5] != KY) return;
+  resize_band<T>(data, idx, flip, noise, rng, rng_tensor, keep, mix, out_nhwc4, out_nchw, Hs, Ws, Hs, Ws, 0, 0, S, KX, KY, band, max_rows, taps);
+}
+
+// origin: int32 [B][2] = (y0, x0) per image, or NULL for the call's (oy, ox).  Nobody can check a device vector without a sync, so
+// every corner is clamped to [0, Hs - Hc] x [0, Ws - Wc] here: no origin makes the kernel read outside its image.
+template <typename T>
+__global__ __launch_bounds__(RESIZE_THREADS) void img_prep_u8_box_kernel(
+    const unsigned char* __restrict__ data, const long long* __restrict__ idx, const unsigned char* __restrict__ flip,
+    const int* __restrict__ origin, const float* __restrict__ noise, const unsigned* __restrict__ rng, unsigned rng_tensor, float keep,
+    float mix, T* __restrict__ out_nhwc4, float* __restrict__ out_nchw, int Hs, int Ws, int Hc, int Wc, int oy, int ox, int S, int KX,
+    int KY, int band, int max_rows, unsigned magic, const int* __restrict__ taps) {
+  if ((unsigned)taps[0] != magic || taps[1] != Hc || taps[2] != Wc || taps[3] != S || taps[4] != KX || taps[5] != KY) return;
+  if (origin) {
+    const long long n = blockIdx.x / (S / band);
+    oy = origin[2 * n];
+    ox = origin[2 * n + 1];
+  }
+  oy = min(max(oy, 0), Hs - Hc);
+  ox = min(max(ox, 0), Ws - Wc);
+  resize_band<T>(data, idx, flip, noise, rng, rng_tensor, keep, mix, out_nhwc4, out_nchw, Hs, Ws, Hc, Wc, oy, ox, S, KX, KY, band, max_rows, taps);
 }

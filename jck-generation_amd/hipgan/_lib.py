@@ -15,7 +15,8 @@ class StepInputs(C.Structure):
     _fields_ = [("real_nchw", vp), ("noise_real", vp), ("z", vp), ("noise_fake", vp), ("alpha", vp),
                 ("lr", f32), ("grad_scale", f32), ("step", i32), ("labels", vp), ("drop_mask", vp * 4),
                 ("real_u8", vp), ("real_idx", vp),
-                ("real_h", i32), ("real_w", i32), ("real_flip", vp), ("real_taps", vp)]
+                ("real_h", i32), ("real_w", i32), ("real_flip", vp), ("real_taps", vp),
+                ("real_box_h", i32), ("real_box_w", i32), ("real_y0", i32), ("real_x0", i32), ("real_origin", vp)]
 
 
 # name -> (restype, argtypes)      (keep in sync with include/jckgan.h; tests/test_abi.py checks the symbol list)
@@ -73,6 +74,8 @@ PROTOS = {
     "jck_resize_taps_bytes": (i64, [i32, i32, i32]),
     "jck_resize_taps_build": (i32, [i32, i32, i32, vp]),
     "jck_img_prep_u8_any": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "jck_resize_lds_bytes": (i64, [i32, i32, vp, vp]),
+    "jck_img_prep_u8_box": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "jck_nhwc4_to_nchw": (i32, [i32, vp, vp, i32, i32, vp]),
     "jck_axpy_noise": (i32, [i32, vp, vp, f32, f32, vp, i32, i32, vp]),
     "jck_interp": (i32, [i32, vp, vp, vp, vp, i32, i32, vp]),

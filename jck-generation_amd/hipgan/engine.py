@@ -104,9 +104,12 @@ class DeviceBatch:
     preprocess/dcgan_data_preprocessor.py:38-43, bit-exact against Pillow - with no per-step host->device image copy.
     size: the output side, 64 or 128 (a non-square source is resized to size x size).  flip: uint8 [B] or None, non-zero mirrors
     the image left-right before the resize.  A [N,3,32,32] dataset with size 64 and no flips runs jck_img_prep_u8 (the 2x special
-    case, as before); everything else runs jck_img_prep_u8_any with the tap table of its geometry."""
+    case, as before); everything else runs jck_img_prep_u8_any with the tap table of its geometry.
+    box: None, or (Hc, Wc, origin): only that box of Hc x Wc source pixels of every image is resized (PIL's crop(), then Resize;
+    a flip mirrors inside the box).  origin is its top-left corner, (y0, x0) for all images or an int32 [B,2] tensor of (y0, x0)
+    per image, which the kernel clamps into the image.  A box always runs jck_img_prep_u8_box with the table of (Hc, Wc, size)."""
 
-    def __init__(self, data_u8, idx, size=64, flip=None):
+    def __init__(self, data_u8, idx, size=64, flip=None, box=None):
         if data_u8.dtype != torch.uint8 or not data_u8.is_cuda or not data_u8.is_contiguous():
             raise JckError("DeviceBatch: dataset must be a contiguous uint8 CUDA tensor")
         if data_u8.dim() != 4 or data_u8.shape[1] != 3 or not (1 <= data_u8.shape[2] <= RESIZE_MAX_SRC and 1 <= data_u8.shape[3] <= RESIZE_MAX_SRC):
@@ -122,7 +125,25 @@ class DeviceBatch:
             if self.flip.numel() != self.idx.numel():
                 raise JckError(f"DeviceBatch: flip has {self.flip.numel()} entries for {self.idx.numel()} indices")
         h, w = int(data_u8.shape[2]), int(data_u8.shape[3])
-        self.taps = None if (h, w, self.out_size) == (32, 32, 64) and flip is None else resize_taps(h, w, self.out_size, data_u8.device)
+        self.box, self.origin, self.corner = None, None, (0, 0)
+        if box is not None:
+            if not isinstance(box, (tuple, list)) or len(box) != 3:
+                raise JckError("DeviceBatch: box must be (Hc, Wc, (y0, x0)) or (Hc, Wc, int32 [B,2] tensor)")
+            hc, wc, origin = int(box[0]), int(box[1]), box[2]
+            if not (1 <= hc <= h and 1 <= wc <= w):
+                raise JckError(f"DeviceBatch: a box of {hc}x{wc} does not lie in images of {h}x{w}")
+            if isinstance(origin, torch.Tensor):
+                if origin.dtype != torch.int32 or tuple(origin.shape) != (self.idx.numel(), 2):
+                    raise JckError(f"DeviceBatch: box origins must be int32 [{self.idx.numel()},2], got {origin.dtype} {tuple(origin.shape)}")
+                self.origin = origin.to(data_u8.device).contiguous()
+            else:
+                if len(origin) != 2 or not (0 <= int(origin[0]) <= h - hc and 0 <= int(origin[1]) <= w - wc):
+                    raise JckError(f"DeviceBatch: origin {tuple(origin)} puts a box of {hc}x{wc} outside images of {h}x{w}")
+                self.corner = (int(origin[0]), int(origin[1]))
+            self.box = (hc, wc)
+            self.taps = resize_taps(hc, wc, self.out_size, data_u8.device)
+        else:
+            self.taps = None if (h, w, self.out_size) == (32, 32, 64) and flip is None else resize_taps(h, w, self.out_size, data_u8.device)
 
     def size(self, dim=0):
         return (self.idx.numel(), 3, self.out_size, self.out_size)[dim]
@@ -131,7 +152,11 @@ class DeviceBatch:
         """The transformed batch as fp32 NCHW [B,3,size,size] (what the reference's DataLoader would have yielded)."""
         b, s = self.idx.numel(), self.out_size
         out = torch.empty(b, 3, s, s, dtype=torch.float32, device=self.data.device)
-        if self.taps is None:
+        if self.box is not None:
+            lib.jck_img_prep_u8_box(PREC_F32, self.data, self.idx, self.flip, self.origin, None, None, 0, 1.0, 0.0, None, out, b,
+                                    self.data.shape[2], self.data.shape[3], self.box[0], self.box[1], self.corner[0], self.corner[1], s,
+                                    self.taps, cur_stream())
+        elif self.taps is None:
             lib.jck_img_prep_u8(PREC_F32, self.data, self.idx, None, 1.0, 0.0, None, out, b, 32, 32, cur_stream())
         else:
             lib.jck_img_prep_u8_any(PREC_F32, self.data, self.idx, self.flip, None, None, 0, 1.0, 0.0, None, out, b, self.data.shape[2],
@@ -406,6 +431,10 @@ class DcganEngine(EngineInference):
                 keep += [real.taps, real.flip]
                 si.real_h, si.real_w, si.real_taps = real.data.shape[2], real.data.shape[3], real.taps.data_ptr()
                 si.real_flip = real.flip.data_ptr() if real.flip is not None else None
+            if real.box is not None:                # a box of every image: the table is the box's
+                keep += [real.origin]
+                (si.real_box_h, si.real_box_w), (si.real_y0, si.real_x0) = real.box, real.corner
+                si.real_origin = real.origin.data_ptr() if real.origin is not None else None
             real = None
         elif real is not None and (real.shape != (B, 3, S, S) or real.dtype != torch.float32):
             raise JckError(f"real must be float32 [{B},3,{S},{S}], got {tuple(real.shape)} {real.dtype}")
@@ -520,7 +549,7 @@ class DcganEngine(EngineInference):
             sb = {"nbuf": torch.empty(2 * B * 3 * S * S + B * 100, **f32), "alpha": torch.empty(B, 1, 1, 1, **f32),
                   "z": torch.empty(B, 100, 1, 1, **f32),
                   "real": torch.empty(B, 3, S, S, **f32), "idx": torch.empty(B, dtype=torch.int64, device=dev),
-                  "flip": torch.empty(B, dtype=torch.uint8, device=dev)}
+                  "flip": torch.empty(B, dtype=torch.uint8, device=dev), "origin": torch.empty(B, 2, dtype=torch.int32, device=dev)}
             if self.family == 1:
                 sb["labels"] = torch.empty(B, 100, dtype=torch.int64, device=dev)
                 sb["u"] = torch.empty(4, B, 256, **f32)
@@ -567,7 +596,10 @@ class DcganEngine(EngineInference):
             if real.size(0) != B:
                 raise JckError(f"DeviceBatch must index {B} images")
             flip = sb["flip"].copy_(real.flip, non_blocking=True) if real.flip is not None else None
-            real = DeviceBatch(real.data, sb["idx"].copy_(real.idx, non_blocking=True), real.out_size, flip)
+            box = None
+            if real.box is not None:
+                box = (*real.box, sb["origin"].copy_(real.origin, non_blocking=True) if real.origin is not None else real.corner)
+            real = DeviceBatch(real.data, sb["idx"].copy_(real.idx, non_blocking=True), real.out_size, flip, box)
         else:
             if real.shape != (B, 3, S, S) or real.dtype != torch.float32:
                 raise JckError(f"real must be float32 [{B},3,{S},{S}], got {tuple(real.shape)} {real.dtype}")
@@ -597,9 +629,10 @@ class DcganEngine(EngineInference):
                 segs = ([[PHASE_D_LOSS, PHASE_D_GP]], [[PHASE_D_STEP, PHASE_G_LOSS]], [[PHASE_G_STEP]])
             else:
                 segs = ([[PHASE_D_LOSS, PHASE_D_GP, PHASE_D_STEP, PHASE_G_LOSS, PHASE_G_STEP]], [], [])
-            # (a captured graph bakes the dataset's address, its geometry, the tap table and whether a flip vector is read)
+            # (a captured graph bakes the dataset's address, its geometry, the tap table, whether a flip vector is read, and the box:
+            # its size, the scalar corner and whether an origin vector is read)
             kind = (("u8", real.data.data_ptr(), tuple(real.data.shape[2:]), real.out_size, real.taps.data_ptr() if real.taps is not None else 0,
-                     real.flip is not None) if isinstance(real, DeviceBatch) else ("f32",)) + (nz.get("n1") is None, nz.get("z") is None, nz.get("alpha") is None, nz.get("m1") is None)
+                     real.flip is not None, real.box, real.corner, real.origin is not None) if isinstance(real, DeviceBatch) else ("f32",)) + (nz.get("n1") is None, nz.get("z") is None, nz.get("alpha") is None, nz.get("m1") is None)
             handle = None
 
             launched = []

@@ -56,15 +56,23 @@ def get_arg_parse(argv=None):
     p.add_argument("--data", type=str, default=argparse.SUPPRESS, metavar="FILE.npz",
                    help="train on this dataset instead of CIFAR-100: `images` uint8 [N,H,W,3] (any H, W up to 1024; what generate.py "
                         "writes) and `labels` int [N] (CGAN: required, 0..99; DCGAN: optional).  Every image is resized to "
-                        "image_size x image_size exactly as transforms.Resize((S, S)) would: a non-square source is squeezed, so crop "
-                        "first if the aspect matters")
+                        "image_size x image_size exactly as transforms.Resize((S, S)) would: a non-square source is squeezed unless "
+                        "--crop is given")
     p.add_argument("--image_size", type=int, choices=(64, 128), default=argparse.SUPPRESS,
                    help="DCGAN: side of the generated and the training images; 128 builds the nets with one more stride-2 stage "
                         "(absent = 64, the reference)")
     p.add_argument("--mirror", type=int, choices=(0, 1), default=argparse.SUPPRESS,
                    help="1: mirror every training image left-right with probability 1/2, drawn anew each epoch (needs the "
                         "device-resident input pipeline); absent or 0 = the reference, which has no augmentation")
+    p.add_argument("--crop", type=str, choices=("center", "random"), default=argparse.SUPPRESS,
+                   help="resize a square box of every training image instead of the whole image (CenterCrop / RandomCrop in front of "
+                        "the Resize): center = the centred box; random = a box drawn anew per image and epoch (needs the "
+                        "device-resident input pipeline).  Evaluation reads the centred box in both modes")
+    p.add_argument("--crop_size", type=int, default=argparse.SUPPRESS, metavar="K",
+                   help="side of the --crop box in source pixels, 1..min(H, W) (absent = min(H, W), the largest centred square)")
     args = p.parse_args(argv)
+    if hasattr(args, "crop_size") and not hasattr(args, "crop"):
+        p.error("--crop_size K needs --crop center or --crop random")
     if getattr(args, "image_size", 64) != 64 and args.model != ModelEnum.DCGAN:
         p.error("--image_size 128: the 128x128 topology exists for DCGAN only (CGAN's Linear(8392,256) fixes 64x64)")
     return args

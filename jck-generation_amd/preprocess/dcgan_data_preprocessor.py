@@ -16,7 +16,10 @@ host and a torch DataLoader is returned, as in the reference.
 Opt-in (main.py --data / --image_size / --mirror): any uint8 image set from an `images.npz` (`load_npz_dataset`) instead of CIFAR-100,
 resized to 64x64 or 128x128 from any source size with Pillow's general bilinear taps (`resize_pil_u8` on the host,
 jck_img_prep_u8_any in the step; pinned to PIL by tests/golden/resize_any_u8.json), and left-right flips drawn per epoch
-(`DeviceLoader(mirror=True)`, device-resident pipeline only)."""
+(`DeviceLoader(mirror=True)`, device-resident pipeline only).  --crop center|random [--crop_size K] puts CenterCrop(K) / RandomCrop(K) in
+front of the Resize: a K x K box of every image (`center_origin`; random origins drawn per epoch by `DeviceLoader(crop="random")`,
+device-resident pipeline only) is what jck_img_prep_u8_box resizes, pinned to PIL's crop().resize() by tests/golden/crop_resize_u8.json;
+evaluation reads the centre box of the same size."""
 import math
 import os
 import pickle
@@ -99,15 +102,40 @@ def resize_pil_u8(x, size):
     return one_axis(one_axis(x, -1), -2).to(torch.uint8)
 
 
+def center_origin(hs, ws, hc, wc):
+    """Top-left corner (y0, x0) of the centred hc x wc box of an hs x ws image, as torchvision's center_crop places it:
+    int(round(difference / 2.0)) with Python's round-half-to-even (12 for a difference of 25, 4 for 7)."""
+    return int(round((hs - hc) / 2.0)), int(round((ws - wc) / 2.0))
+
+
+def crop_side(crop, crop_size, hs, ws):
+    """The side K of the square box of --crop / --crop_size for hs x ws images: None without a crop, min(hs, ws) - the largest
+    centred square - when no size is given.  ValueError for a mode that does not exist, a size without a mode and a K outside
+    1..min(hs, ws)."""
+    if crop is None:
+        if crop_size is not None:
+            raise ValueError("crop_size needs a crop mode: crop must be 'center' or 'random'")
+        return None
+    if crop not in ("center", "random"):
+        raise ValueError(f"crop must be 'center' or 'random', got {crop!r}")
+    k = min(hs, ws) if crop_size is None else int(crop_size)
+    if not 1 <= k <= min(hs, ws):
+        raise ValueError(f"crop_size {k}: a square crop of {hs}x{ws} images has a side of 1..{min(hs, ws)}")
+    return k
+
+
 class DeviceLoader:
     """Iterable with the DataLoader surface the trainers use (`len()`, iteration over `[images, (labels)]` batches): images
     are `DeviceBatch`es over the uint8 dataset in HBM, labels (CGAN: int64 one-hot [B,100]) are gathered on the device.
     Shuffles every epoch like DataLoader(shuffle=True); under torch.distributed every rank takes a strided share of the same
     permutation (DistributedSampler semantics, padded by wrap-around).
     size: the side the step resizes to (64 or 128).  mirror: every drawn index also draws a left-right flip with probability 1/2
-    (RandomHorizontalFlip) from a SECOND generator, so the index order of a seed is the same with and without it."""
+    (RandomHorizontalFlip) from a SECOND generator, so the index order of a seed is the same with and without it.
+    crop: None, "center" or "random", crop_size: the side K of the square box (None: min(H, W)).  "center" resizes the centred
+    K x K box of every image; "random" draws one origin per drawn index, y0 uniform on 0..H-K and x0 on 0..W-K, anew each epoch
+    from a THIRD generator, so indices and flips of a seed do not depend on it either."""
 
-    def __init__(self, data_u8, batch_size, onehot=None, seed=0, size=64, mirror=False):
+    def __init__(self, data_u8, batch_size, onehot=None, seed=0, size=64, mirror=False, crop=None, crop_size=None):
         from hipgan.engine import DeviceBatch
         self._DeviceBatch = DeviceBatch
         self.data, self.onehot, self.batch_size = data_u8, onehot, batch_size
@@ -118,24 +146,38 @@ class DeviceLoader:
         self.n_local = (data_u8.shape[0] + self.world - 1) // self.world
         self.gen = torch.Generator().manual_seed(seed)
         self.flip_gen = torch.Generator().manual_seed(seed + 0x6d6972) if self.mirror else None
+        self.crop = crop
+        self.crop_size = crop_side(crop, crop_size, int(data_u8.shape[2]), int(data_u8.shape[3]))
+        self.origin_gen = torch.Generator().manual_seed(seed + 0x63726f70) if crop == "random" else None
 
     def __len__(self):
         return (self.n_local + self.batch_size - 1) // self.batch_size
 
-    def __iter__(self):
-        n = self.data.shape[0]
+    def draw_epoch(self):
+        """One epoch's draws of this rank on the host: (indices int64 [n_local], flips uint8 [n_local] or None, box origins int32
+        [n_local,2] = (y0, x0) or None).  Every draw belongs to its position in the permutation, so all three are strided and
+        wrapped alike."""
+        n, (h, w), k = self.data.shape[0], self.data.shape[2:], self.crop_size
         perm = torch.randperm(n, generator=self.gen)
         flips = torch.randint(0, 2, (n,), generator=self.flip_gen, dtype=torch.uint8) if self.mirror else None      # one per drawn index, new every epoch
+        origins = None
+        if self.origin_gen is not None:
+            origins = torch.stack([torch.randint(0, h - k + 1, (n,), generator=self.origin_gen, dtype=torch.int32),
+                                   torch.randint(0, w - k + 1, (n,), generator=self.origin_gen, dtype=torch.int32)], 1)
         if self.world > 1:
             total = self.n_local * self.world
-            perm = torch.cat([perm, perm[:total - n]])[self.rank:total:self.world]
-            if flips is not None:
-                flips = torch.cat([flips, flips[:total - n]])[self.rank:total:self.world]
-        perm = perm.to(self.data.device)
-        flips = flips.to(self.data.device) if flips is not None else None
+            perm, flips, origins = (torch.cat([t, t[:total - n]])[self.rank:total:self.world] if t is not None else None
+                                    for t in (perm, flips, origins))
+        return perm, flips, origins
+
+    def __iter__(self):
+        perm, flips, origins = (t.to(self.data.device) if t is not None else None for t in self.draw_epoch())
+        k = self.crop_size
+        center = (k, k, center_origin(*self.data.shape[2:], k, k)) if self.crop == "center" else None
         for i in range(0, perm.numel(), self.batch_size):
             idx = perm[i:i + self.batch_size]
-            batch = [self._DeviceBatch(self.data, idx, self.size, flips[i:i + self.batch_size] if flips is not None else None)]
+            box = (k, k, origins[i:i + self.batch_size].contiguous()) if origins is not None else center
+            batch = [self._DeviceBatch(self.data, idx, self.size, flips[i:i + self.batch_size] if flips is not None else None, box)]
             if self.onehot is not None:
                 batch.append(self.onehot[idx])
             yield batch
@@ -180,8 +222,14 @@ class DCGANDataPreprocessor:
         self.mirror = bool(int(getattr(args, "mirror", 0)))
         if self.image_size not in (64, 128):
             raise ValueError(f"image_size must be 64 or 128, got {self.image_size}")
+        self.crop, crop_size = getattr(args, "crop", None), getattr(args, "crop_size", None)
         self.metric_cache = None
         self.images, self.targets = self._load(synthetic_size)
+        # the square box of --crop (None without one): checked here, on the host, before anything is allocated on the device
+        self.crop_size = crop_side(self.crop, crop_size, int(self.images.shape[2]), int(self.images.shape[3]))
+        if self.crop is not None:                   # features of the real images are those of ONE box: never another crop's cache
+            base = self.metric_cache or os.path.join(".", "data", "metric_data.pikl")
+            self.metric_cache = f"{os.path.splitext(base)[0]}_crop{self.crop_size}.pikl"
         self._train, self._metric = None, None
         self._logger.debug("data preprocessor init")
 
@@ -217,22 +265,31 @@ class DCGANDataPreprocessor:
         return torch.cuda.is_available() and os.environ.get("JCKGAN_DEVICE_DATA", "1") != "0"
 
     def transform_data(self):
-        self._metric = _TensorSource(self.images, self.targets)                   # 299x299 resize is done lazily by metrics.py
+        center = self.images
+        if self.crop is not None:                                                 # CenterCrop(K); evaluation reads it in both modes
+            k = self.crop_size
+            y0, x0 = center_origin(*self.images.shape[2:], k, k)
+            center = self.images[:, :, y0:y0 + k, x0:x0 + k].contiguous()
+        self._metric = _TensorSource(center, self.targets)                        # 299x299 resize is done lazily by metrics.py
         if self.device_resident():
             self._train = self.images.cuda().contiguous()                         # uint8, transformed inside the step
         else:
             if self.mirror:
                 raise ValueError("--mirror 1 needs the device-resident pipeline (a GPU, JCKGAN_DEVICE_DATA not 0): the host "
                                  "loader transforms the dataset once, before training, and has no per-step flip")
-            if tuple(self.images.shape[2:]) == (32, 32) and self.image_size == 64:
-                up = resize2x_pil_u8(self.images)                                 # Resize(64) on the PIL image (:39)
+            if self.crop == "random":
+                raise ValueError("--crop random needs the device-resident pipeline (a GPU, JCKGAN_DEVICE_DATA not 0): the host "
+                                 "loader transforms the dataset once, before training, and cannot draw a crop per epoch")
+            if tuple(center.shape[2:]) == (32, 32) and self.image_size == 64:
+                up = resize2x_pil_u8(center)                                      # Resize(64) on the PIL image (:39)
             else:
-                up = resize_pil_u8(self.images, self.image_size)                  # Resize((S, S)) of any source size
+                up = resize_pil_u8(center, self.image_size)                       # Resize((S, S)) of any source size, or of its centre box
             self._train = (up.float() / 255.0 - 0.5) / 0.5                        # ToTensor, Normalize(0.5, 0.5)
         self._logger.debug("data transform")
 
     def _device_loader(self, onehot=None):
-        return DeviceLoader(self._train, self.batch_size, onehot=onehot, seed=12345, size=self.image_size, mirror=self.mirror)
+        return DeviceLoader(self._train, self.batch_size, onehot=onehot, seed=12345, size=self.image_size, mirror=self.mirror,
+                            crop=self.crop, crop_size=self.crop_size)
 
     def get_data_loader(self):
         if self._train is None:

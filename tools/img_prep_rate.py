@@ -1,16 +1,19 @@
 """Time of the input transform of the training step - gather by index, Resize, ToTensor, Normalize, instance-noise mix into NHWC4 -
-for the 2x kernel (img_prep_u8_kernel, csrc/ew.hpp) and the any-size kernel (img_prep_u8_any_kernel, csrc/resize.hpp) in one run:
+for the 2x kernel (img_prep_u8_kernel, csrc/ew.hpp), the any-size kernel (img_prep_u8_any_kernel, csrc/resize.hpp) and the box kernel
+beside it (img_prep_u8_box_kernel: the same code with a box's corner added to its addresses) in one run:
 
   old   32x32 -> 64    B 256   jck_img_prep_u8_rng                      (what a CIFAR run launches)
   any   32x32 -> 64    B 256   jck_img_prep_u8_any, the same batch
   any   64x64 -> 64, 218x178 -> 64 at B 256; 128x128 -> 128, 256x256 -> 128 at B 128
+  box   whole-image boxes at 32x32 -> 64, 218x178 -> 64, 256x256 -> 128: the same work as `any` at those shapes
+  box   the crops themselves: the centred 178x178 of 218x178 -> 64, the centred 28x28 of 32x32 -> 64
 
 bf16 NHWC4 output with the in-kernel noise, as the step runs them; the batch is a random index vector into a seeded uint8 dataset
 of --images images.  Every path: untimed launches first, then --rounds rounds in which the paths alternate, each round's call
 `reps` back-to-back launches between two device events, reps chosen so that a call lasts about --window seconds.  One JSON line per
 path with the median time per launch, the bytes the algorithm must move (the batch's source bytes once plus the output) and the
-bandwidth that makes.  Then the DCGAN step at batch 256 (bf16) fed from a 64x64 dataset beside the same step fed from a 32x32 one,
-alternating in blocks of --steps steps.
+bandwidth that makes.  Then the DCGAN step at batch 256 (bf16) fed from a 64x64 dataset beside the same step fed from a 32x32 one, and
+fed from a 218x178 dataset squeezed beside the same dataset's centred 178x178 box, alternating in blocks of --steps steps.
 
     timeout -k 10 300 python tools/img_prep_rate.py
 """
@@ -27,9 +30,13 @@ for p in (ROOT, os.path.join(ROOT, "jck-generation_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-#        name            kernel  Hs   Ws   S    B
-PATHS = (("old_32_64", "old", 32, 32, 64, 256), ("any_32_64", "any", 32, 32, 64, 256), ("any_64_64", "any", 64, 64, 64, 256),
-         ("any_218x178_64", "any", 218, 178, 64, 256), ("any_128_128", "any", 128, 128, 128, 128), ("any_256_128", "any", 256, 256, 128, 128))
+#        name            kernel  Hs   Ws   S    B    box (Hc, Wc, y0, x0) of the box kernel
+PATHS = (("old_32_64", "old", 32, 32, 64, 256, None), ("any_32_64", "any", 32, 32, 64, 256, None), ("any_64_64", "any", 64, 64, 64, 256, None),
+         ("any_218x178_64", "any", 218, 178, 64, 256, None), ("any_128_128", "any", 128, 128, 128, 128, None),
+         ("any_256_128", "any", 256, 256, 128, 128, None),
+         ("box_32_64", "box", 32, 32, 64, 256, (32, 32, 0, 0)), ("box_218x178_64", "box", 218, 178, 64, 256, (218, 178, 0, 0)),
+         ("box_256_128", "box", 256, 256, 128, 128, (256, 256, 0, 0)),
+         ("box_178sq_of_218x178_64", "box", 218, 178, 64, 256, (178, 178, 20, 0)), ("box_28sq_of_32_64", "box", 32, 32, 64, 256, (28, 28, 2, 2)))
 
 
 def timed(fn, reps):
@@ -49,17 +56,22 @@ def kernel_paths(images):
     gen = torch.Generator(device="cuda").manual_seed(1)
     rng = torch.tensor([2024, 0, 1, 0], dtype=torch.int32, device="cuda")
     data, out = {}, {}
-    for name, kind, hs, ws, s, b in PATHS:
+    for name, kind, hs, ws, s, b, box in PATHS:
         if (hs, ws) not in data:
             data[(hs, ws)] = torch.randint(0, 256, (images, 3, hs, ws), dtype=torch.uint8, device="cuda", generator=gen)
         if (b, s) not in out:
             out[(b, s)] = torch.empty(b, s, s, 4, dtype=torch.bfloat16, device="cuda")
     idx = {b: torch.randint(0, images, (b,), device="cuda", generator=gen) for b in (128, 256)}
     fns = {}
-    for name, kind, hs, ws, s, b in PATHS:
+    for name, kind, hs, ws, s, b, box in PATHS:
         d, o, i = data[(hs, ws)], out[(b, s)], idx[b]
         if kind == "old":
             fns[name] = lambda d=d, o=o, i=i, b=b: lib.jck_img_prep_u8_rng(PREC_BF16, d, i, rng, 0, 0.9, 0.1, o, b, 32, 32, cur_stream())
+        elif kind == "box":
+            hc, wc, y0, x0 = box
+            t = resize_taps(hc, wc, s, "cuda")
+            fns[name] = lambda d=d, o=o, i=i, b=b, hs=hs, ws=ws, s=s, t=t, hc=hc, wc=wc, y0=y0, x0=x0: lib.jck_img_prep_u8_box(
+                PREC_BF16, d, i, None, None, None, rng, 0, 0.9, 0.1, o, None, b, hs, ws, hc, wc, y0, x0, s, t, cur_stream())
         else:
             t = resize_taps(hs, ws, s, "cuda")
             fns[name] = lambda d=d, o=o, i=i, b=b, hs=hs, ws=ws, s=s, t=t: lib.jck_img_prep_u8_any(
@@ -72,16 +84,19 @@ def step_paths(images):
     from model import DCGAN
     B = 256
     gen = torch.Generator(device="cuda").manual_seed(2)
-    fns = {}
-    for name, side in (("step_32_data", 32), ("step_64_data", 64)):
+    fns, datasets = {}, {}
+    for name, shape, box in (("step_32_data", (32, 32), None), ("step_64_data", (64, 64), None), ("step_218x178_squeezed", (218, 178), None),
+                             ("step_218x178_center", (218, 178), (178, 178, (20, 0)))):
         eng = DcganEngine(batch=B, prec="bf16")
         torch.manual_seed(12345)
         g, d = DCGAN.Generator(), DCGAN.Discriminator()
         g.apply(DCGAN.weights_init)
         d.apply(DCGAN.weights_init)
         eng.load_state(g.state_dict(), d.state_dict())
-        data = torch.randint(0, 256, (images, 3, side, side), dtype=torch.uint8, device="cuda", generator=gen)
-        batches = [DeviceBatch(data, torch.randint(0, images, (B,), device="cuda", generator=gen)) for _ in range(4)]
+        if shape not in datasets:
+            datasets[shape] = torch.randint(0, 256, (images, 3, *shape), dtype=torch.uint8, device="cuda", generator=gen)
+        data = datasets[shape]
+        batches = [DeviceBatch(data, torch.randint(0, images, (B,), device="cuda", generator=gen), box=box) for _ in range(4)]
         count = [0]
 
         def one(eng=eng, batches=batches, count=count):
@@ -110,10 +125,10 @@ def main(argv=None):
     for _ in range(args.rounds):
         for name, fn in fns.items():
             times[name].append(timed(fn, reps[name]))
-    for name, kind, hs, ws, s, b in PATHS:
+    for name, kind, hs, ws, s, b, box in PATHS:
         t = statistics.median(times[name])
-        nbytes = b * (3 * hs * ws + s * s * 4 * 2)
-        print(json.dumps({"path": name, "B": b, "source": [hs, ws], "size": s, "launches_per_call": reps[name], "rounds": args.rounds,
+        nbytes = b * (3 * (box[0] * box[1] if box else hs * ws) + s * s * 4 * 2)
+        print(json.dumps({"path": name, "B": b, "source": [hs, ws], **({"box": list(box)} if box else {}), "size": s, "launches_per_call": reps[name], "rounds": args.rounds,
                           "us": t * 1e6, "us_min": min(times[name]) * 1e6, "us_max": max(times[name]) * 1e6, "bytes": nbytes,
                           "GBps": nbytes / t * 1e-9}), flush=True)
     if args.steps > 0:
