@@ -417,6 +417,16 @@ int jck_adam(float* p, const float* g, float* m, float* v, long long n, double l
  * untouched.  p, m, v come out bitwise as jck_adam leaves them. */
 int jck_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, double lr, double beta1, double beta2,
                  double eps, int step, float grad_scale, float ema_weight, const unsigned* skip_if, void* stream);
+/* jck_adam (ema != NULL: jck_adam_ema) over the arena AND the packed operands of the conv weights inside it, written by the same
+ * launch from the registers that hold the new weights: what the engine's optimiser phases run.  Job i packs the weight at element
+ * w_off[i] (% 4 == 0; jobs in arena order, the forms of one weight next to each other) into wp[i], element type by prec:
+ * kind 0 = jck_pack_down(Cs = a, Cb = b), 1 = jck_pack_up (Cb > 4), 2 = jck_pack_up (Cb <= 4), 3 = jck_pack_g1(Ci = a, Co = b,
+ * CiPad = a rounded up to 128), 4 = jck_pack_head(C = a).  Padding rows and channels of the operands are not written.  All arenas
+ * 16-byte aligned; at most 12 jobs.  skip_if non-zero leaves arenas and operands untouched.  Every value comes out bitwise as
+ * jck_adam / jck_adam_ema followed by the jck_pack_* calls leave it. */
+int jck_adam_pack(int prec, float* p, const float* g, float* m, float* v, float* ema, long long n, int njobs, const int* kind,
+                  const long long* w_off, void* const* wp, const int* a, const int* b, double lr, double beta1, double beta2, double eps,
+                  int step, float grad_scale, float ema_weight, const unsigned* skip_if, void* stream);
 
 /* ---- whole-step engine (train/dcgan_trainer.py:155-189 as one native schedule) --------------------------- */
 typedef struct jck_engine jck_engine;

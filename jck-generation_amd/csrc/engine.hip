@@ -3,7 +3,7 @@
 // allocates, synchronises or reads back - scalars stay on the device until the trainer logs them.
 #include <cstdlib>
 
-#include "engine_internal.hpp"      // ew_optim.hpp with it: the kernels this file launches itself (pack_multi_kernel, pack_tail_kernel)
+#include "engine_internal.hpp"      // ew_optim.hpp with it: the kernels this file launches itself (pack_multi_kernel, pack_tail_kernel) and the repack table of adam_pack_kernel
 #define JCK_BATCHED_DEFAULT 3
 
 namespace {
@@ -149,6 +149,7 @@ extern "C" int jck_engine_create_ex(jck_engine** out, int family, int prec, int 
   e->real_side = env_on("JCK_REAL_SIDE");
   e->fold_zero = env_on("JCK_FOLD_ZERO");
   e->fuse_tanh = env_on("JCK_FUSE_TANH");
+  e->adam_pack = env_on("JCK_ADAM_PACK");
   if (e->overlap) JCK_TRY(create_side_streams(e));
   *out = e;
   return JCK_OK;
@@ -210,10 +211,9 @@ extern "C" int jck_engine_bind(jck_engine* e, void* workspace, size_t ws_bytes, 
   return JCK_OK;
 }
 
-// all conv operands of one network in one launch (ew_optim.hpp: pack_multi_kernel); the two Linear operands of CGAN's D follow
-// tail (optional): the end-of-step job rides in the same launch (ew_optim.hpp: pack_tail_kernel)
-static int repack_convs(jck_engine* e, int net, void* stream, const TailJobs* tail = nullptr, int tail_x = 0) {
-  PackJobs jobs = {};
+// the repack table of one network: a job per operand form, the forms of one weight next to each other, weights in arena order;
+// returns the workgroups of pack_multi_kernel's grid
+static int pack_jobs(const jck_engine* e, int net, PackJobs& jobs) {
   int n = 0, chunk = 0;
   auto add = [&](int kind, const float* w, void* wp, long long total, int a, int b, int c) {
     PackJob& J = jobs.j[n];
@@ -245,6 +245,13 @@ static int repack_convs(jck_engine* e, int net, void* stream, const TailJobs* ta
   }
   jobs.first_chunk[n] = chunk;
   jobs.n = n;
+  return chunk;
+}
+// all conv operands of one network in one launch (ew_optim.hpp: pack_multi_kernel); the two Linear operands of CGAN's D follow
+// tail (optional): the end-of-step job rides in the same launch (ew_optim.hpp: pack_tail_kernel)
+static int repack_convs(jck_engine* e, int net, void* stream, const TailJobs* tail = nullptr, int tail_x = 0) {
+  PackJobs jobs = {};
+  const int chunk = pack_jobs(e, net, jobs);
   if (net == 1) e->d_packed = true;
   if (tail) {
     const int nblk = chunk + tail_x * (tail->nl + 1);
@@ -802,6 +809,21 @@ static int adam_net(jck_engine* e, int net, long long first, long long count, fl
   return jck_adam_hp(p + first, g + first, m + first, v + first, count, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale, hp, st, zero_other,
                      zero_other ? (net ? e->LG : e->LD).n_params : 0, jck_grid_sync_error_word(e->gsync), ema);
 }
+// adam_net and repack_convs for the conv weights inside the range as ONE launch (ew_optim.hpp: adam_pack_kernel), same values;
+// JCK_ADAM_PACK=0, or an arena that is not 16-byte aligned: the two launches
+static int adam_repack_net(jck_engine* e, int net, long long first, long long count, float grad_scale, const float* hp, hipStream_t st,
+                           float* zero_other = nullptr, float* ema = nullptr, const TailJobs* tail = nullptr, int tail_x = 0) {
+  float *p = net ? e->dp : e->gp, *g = net ? e->dg : e->gg, *m = net ? e->dm : e->gm, *v = net ? e->dv : e->gv;
+  if (!e->adam_pack || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15)) {
+    JCK_TRY(adam_net(e, net, first, count, grad_scale, hp, st, zero_other, ema));
+    return repack_convs(e, net, st, tail, tail_x);
+  }
+  PackJobs jobs = {};
+  pack_jobs(e, net, jobs);
+  if (net == 1) e->d_packed = true;
+  return jck_adam_pack_hp(e->prec, p, g, m, v, ema, first, count, jobs, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale, hp, 0.f, 1.f, 1.f, st, zero_other,
+                          zero_other ? (net ? e->LG : e->LD).n_params : 0, jck_grid_sync_error_word(e->gsync), tail, tail_x);
+}
 // `p` (and `p2`) cleared by a neighbour launch for this step - `clean_step`, a promise that is consumed here - else by a memset
 // (captured steps, a phase called twice)
 static int clear_or_memset(jck_engine* e, int& clean_step, int step, hipStream_t st, void* p, size_t bytes, void* p2 = nullptr, size_t bytes2 = 0) {
@@ -1065,15 +1087,15 @@ static int phase_d_step(jck_engine* e, const PhaseCtx& c) {                     
     const TensorInfo* c1 = find(e->LD, CWN[0]);
     const long long cut = c1->offset + c1->numel;
     HIPCHK(hipStreamWaitEvent(c.st, e->ss.mid_recorded ? e->evWmid : e->evWdone, 0));
-    JCK_TRY(adam_net(e, 1, cut, e->LD.n_params - cut, c.in->grad_scale, hp, c.st, zg));
+    if (e->adam_pack) JCK_TRY(adam_repack_net(e, 1, cut, e->LD.n_params - cut, c.in->grad_scale, hp, c.st, zg));      // each range packs what it updates
+    else JCK_TRY(adam_net(e, 1, cut, e->LD.n_params - cut, c.in->grad_scale, hp, c.st, zg));
     JCK_TRY(repack_linear(e, c.st));
     if (e->ss.mid_recorded) HIPCHK(hipStreamWaitEvent(c.st, e->evWdone, 0));
     e->ss.join_pending = e->ss.mid_recorded = false;
-    JCK_TRY(adam_net(e, 1, 0, cut, c.in->grad_scale, hp, c.st));
-    return repack_convs(e, 1, c.st);
+    return adam_repack_net(e, 1, 0, cut, c.in->grad_scale, hp, c.st);
   }
-  JCK_TRY(adam_net(e, 1, 0, e->LD.n_params, c.in->grad_scale, hp, c.st, zg));
-  return jck_engine_repack(e, 1, c.st);
+  JCK_TRY(adam_repack_net(e, 1, 0, e->LD.n_params, c.in->grad_scale, hp, c.st, zg));
+  return e->family == 1 ? repack_linear(e, c.st) : JCK_OK;
 }
 
 static int phase_g_loss(jck_engine* e, const PhaseCtx& c) {                                       // :182-188
@@ -1097,9 +1119,8 @@ static int phase_g_loss(jck_engine* e, const PhaseCtx& c) {                     
 
 static int phase_g_step(jck_engine* e, const PhaseCtx& c) {                                       // :189
   if (!e->hp_holds(c.in->step, c.in->lr) && !e->capturing) JCK_TRY(refresh_adam_scalars(e, c.in->step, c.in->lr, c.st));
-  // ... and the moving average of G's weights, when one is bound, in the same launch (its weight is hp[2] of the step)
-  JCK_TRY(adam_net(e, 0, 0, e->LG.n_params, c.in->grad_scale, e->hp2 + 8 * e->parity, c.st, nullptr, e->gema));
-  // G's repack, the four D passes' BatchNorm records in the reference's order and the logged scalars: one launch
+  // Adam(G) with the moving average of G's weights, when one is bound (its weight is hp[2] of the step), G's repack, the four D
+  // passes' BatchNorm records in the reference's order and the logged scalars: one launch
   TailJobs t = {};
   for (int i = 0; i < TT.NS; ++i) {
     const int cs = TT.D_CS[i];
@@ -1110,7 +1131,7 @@ static int phase_g_step(jck_engine* e, const PhaseCtx& c) {                     
     t.l[i].C = cs;
   }
   t.nl = TT.NS; t.npass = 4; t.momentum = BN_MOM; t.acc = e->acc; t.acc_ld = e->acc_ld; t.B = c.B; t.invB = 1.0f / (float)c.B; t.lambda_gp = 10.0f; t.out = e->scal_out;
-  return repack_convs(e, 0, c.st, &t, cdiv(TT.G_C1, 256));
+  return adam_repack_net(e, 0, 0, e->LG.n_params, c.in->grad_scale, e->hp2 + 8 * e->parity, c.st, nullptr, e->gema, &t, cdiv(TT.G_C1, 256));
 }
 
 // What every phase call does first, in this order: the engine's own draws for inputs left NULL, the wait for a join left open,

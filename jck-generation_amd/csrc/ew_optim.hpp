@@ -84,6 +84,33 @@ __device__ __forceinline__ void adam_one(float& pi, float gi_raw, float& mi_io, 
 // Exponential moving average of the parameters, updated from the new parameter while it is still in a register: ATen's lerp
 // (the same two branches adam_one takes for exp_avg), so w = 1 gives e = p exactly
 __device__ __forceinline__ float ema_one(float e, float pn, float w) { return (w < 0.5f) ? e + w * (pn - e) : pn - (pn - e) * (1.f - w); }
+// Adam's constants and the step's scalars as every element sees them
+struct AdamScal { float w1 /*1-beta1*/, beta2, omb2 /*1-beta2*/, eps, step_size, bc2_sqrt, grad_scale, ema_w; };
+// elements [4i, 4i + 4) of 16-byte aligned arenas; pn (optional): the four new parameters, for a caller that goes on with them
+template <bool EMA>
+__device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                          float* __restrict__ ema, long long i, const AdamScal& s, float* pn = nullptr) {
+  f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+  const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+  f32x4 ev;
+  if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float pk = pv[k], mk = mv[k], vk = vv[k];
+    adam_one(pk, gv[k], mk, vk, s.w1, s.beta2, s.omb2, s.eps, s.step_size, s.bc2_sqrt, s.grad_scale);
+    pv[k] = pk; mv[k] = mk; vv[k] = vk;
+    if (EMA) ev[k] = ema_one(ev[k], pk, s.ema_w);
+    if (pn) pn[k] = pk;
+  }
+  reinterpret_cast<f32x4*>(p)[i] = pv; reinterpret_cast<f32x4*>(m)[i] = mv; reinterpret_cast<f32x4*>(v)[i] = vv;
+  if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
+}
+template <bool EMA>
+__device__ __forceinline__ void adam_single(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                            float* __restrict__ ema, long long i, const AdamScal& s) {
+  adam_one(p[i], g[i], m[i], v[i], s.w1, s.beta2, s.omb2, s.eps, s.step_size, s.bc2_sqrt, s.grad_scale);
+  if (EMA) ema[i] = ema_one(ema[i], p[i], s.ema_w);
+}
 // four elements per thread (16-byte loads and stores: the arenas are 16-byte aligned); the last n % 4 elements one by one
 // EMA = true: `ema` is a fifth arena of n floats (16-byte aligned like the others when vec = 1), weight ema_w - or hp[2] when the
 // per-step scalars come from device memory; EMA = false is the kernel without any of it
@@ -104,26 +131,12 @@ static __global__ void adam_kernel(float* __restrict__ p, const float* __restric
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nzero4; i += (long long)gridDim.x * blockDim.x)
     reinterpret_cast<f32x4*>(zero)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (skip) return;
+  const AdamScal s = {w1, beta2, omb2, eps, step_size, bc2_sqrt, grad_scale, ema_w};
   const long long n4 = vec ? (n >> 2) : 0;                 // vec = 0: a pointer is not 16-byte aligned -> element by element
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 ev;
-    if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float pk = pv[k], mk = mv[k], vk = vv[k];
-      adam_one(pk, gv[k], mk, vk, w1, beta2, omb2, eps, step_size, bc2_sqrt, grad_scale);
-      pv[k] = pk; mv[k] = mk; vv[k] = vk;
-      if (EMA) ev[k] = ema_one(ev[k], pk, ema_w);
-    }
-    reinterpret_cast<f32x4*>(p)[i] = pv; reinterpret_cast<f32x4*>(m)[i] = mv; reinterpret_cast<f32x4*>(v)[i] = vv;
-    if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
-  }
-  for (long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    adam_one(p[i], g[i], m[i], v[i], w1, beta2, omb2, eps, step_size, bc2_sqrt, grad_scale);
-    if (EMA) ema[i] = ema_one(ema[i], p[i], ema_w);
-  }
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x)
+    adam_quad<EMA>(p, g, m, v, ema, i, s);
+  for (long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    adam_single<EMA>(p, g, m, v, ema, i, s);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -214,45 +227,30 @@ static __global__ void pack_head_kernel(const float* __restrict__ w, int C, floa
 #define PACK_CHUNK 256
 struct PackJob { const float* w; void* wp; long long total; int kind, a, b, c; };   // kind: 0 down 1 up 2 up16 3 g1 4 head
 struct PackJobs { PackJob j[PACK_MAX_JOBS]; int first_chunk[PACK_MAX_JOBS + 1]; int n; };
+// the operand elements of one pair (x, y) of a conv weight [A][Bc][4][4] from its 16 taps v: x is the weight's outer channel index
+// (Cs, G.conv1's Ci, the head's C), y the inner one (Cb, Co).  One copy for the repack kernels and for Adam's launch below
 template <typename W>
-__device__ __forceinline__ void pack_multi_block(const PackJobs& jobs, int bx) {
-  int ji = 0;
-  while (ji + 1 < jobs.n && bx >= jobs.first_chunk[ji + 1]) ++ji;
-  const PackJob& J = jobs.j[ji];
-  const long long u = (long long)(bx - jobs.first_chunk[ji]) * PACK_CHUNK + threadIdx.x;
-  if (u >= J.total) return;
+__device__ __forceinline__ void pack_store_pair(const PackJob& J, int x, int y, const float* v) {
   W* wp = reinterpret_cast<W*>(J.wp);
-  float v[16];
-  auto load16 = [&](const float* src) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(src + 4 * q);
-      v[4 * q] = t[0]; v[4 * q + 1] = t[1]; v[4 * q + 2] = t[2]; v[4 * q + 3] = t[3];
-    }
-  };
   switch (J.kind) {
-    case 0: {   // down: a = Cs, b = Cb, c = logCbPad; unit = (cs, cb), cb fastest; wp[cs][t*CbPad + cb]
-      const int Cb = J.b, cs = (int)(u / Cb), cb = (int)(u % Cb);
-      load16(J.w + ((long long)cs * Cb + cb) * 16);
-      W* d = wp + (((long long)cs * 16) << J.c) + cb;
+    case 0: {   // down: a = Cs, b = Cb, c = logCbPad; wp[cs][t*CbPad + cb]
+      W* d = wp + (((long long)x * 16) << J.c) + y;
 #pragma unroll
       for (int t = 0; t < 16; ++t) stf(d + ((long long)t << J.c), v[t]);
     } break;
-    case 1: {   // up: a = Cs, b = Cb, c = CbPad; unit = (cb, cs), cs fastest; wp[phase][cb][t4*Cs + cs]
-      const int Cs = J.a, Cb = J.b, cb = (int)(u / Cs), cs = (int)(u % Cs);
-      load16(J.w + ((long long)cs * Cb + cb) * 16);
+    case 1: {   // up: a = Cs, b = Cb, c = CbPad; wp[phase][cb][t4*Cs + cs]
+      const int Cs = J.a;
       const long long K = 4ll * Cs, per = (long long)J.c * K;
 #pragma unroll
       for (int phase = 0; phase < 4; ++phase)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int kh = c_up_k[phase >> 1][t >> 1], kw = c_up_k[phase & 1][t & 1];
-          stf(wp + phase * per + (long long)cb * K + (long long)t * Cs + cs, v[kh * 4 + kw]);
+          stf(wp + phase * per + (long long)y * K + (long long)t * Cs + x, v[kh * 4 + kw]);
         }
     } break;
-    case 2: {   // up16: a = Cs, b = Cb; unit = (c, cs), cs fastest; wp[phase*4 + c][t9*Cs + cs], unused (phase, offset) pairs stay 0
-      const int Cs = J.a, Cb = J.b, c = (int)(u / Cs), cs = (int)(u % Cs);
-      load16(J.w + ((long long)cs * Cb + c) * 16);
+    case 2: {   // up16: a = Cs, b = Cb; wp[phase*4 + c][t9*Cs + cs], unused (phase, offset) pairs stay 0
+      const int Cs = J.a;
       const long long K = 9ll * Cs;
 #pragma unroll
       for (int phase = 0; phase < 4; ++phase)
@@ -261,22 +259,39 @@ __device__ __forceinline__ void pack_multi_block(const PackJobs& jobs, int bx) {
           const int dy = t9 / 3 - 1, dx = t9 % 3 - 1, ph = phase >> 1, pw = phase & 1;
           const int kh = ph == 0 ? (dy == 0 ? 1 : (dy == -1 ? 3 : -1)) : (dy == 1 ? 0 : (dy == 0 ? 2 : -1));
           const int kw = pw == 0 ? (dx == 0 ? 1 : (dx == -1 ? 3 : -1)) : (dx == 1 ? 0 : (dx == 0 ? 2 : -1));
-          if (kh >= 0 && kw >= 0) stf(wp + (long long)(phase * 4 + c) * K + (long long)t9 * Cs + cs, v[kh * 4 + kw]);
+          if (kh >= 0 && kw >= 0) stf(wp + (long long)(phase * 4 + y) * K + (long long)t9 * Cs + x, v[kh * 4 + kw]);
         }
     } break;
-    case 3: {   // g1: a = Ci, b = Co, c = CiPad; unit = (co, ci), ci fastest; wp[(t*Co + co)][ci]
-      const int Ci = J.a, Co = J.b, co = (int)(u / Ci), ci = (int)(u % Ci);
-      load16(J.w + ((long long)ci * Co + co) * 16);
+    case 3: {   // g1: a = Ci, b = Co, c = CiPad; wp[(t*Co + co)][ci]
 #pragma unroll
-      for (int t = 0; t < 16; ++t) stf(wp + ((long long)t * Co + co) * J.c + ci, v[t]);
+      for (int t = 0; t < 16; ++t) stf(wp + ((long long)t * J.b + y) * J.c + x, v[t]);
     } break;
-    default: {  // head: a = C; unit = c; wp[t*C + c] fp32
-      const int c = (int)u;
-      load16(J.w + (long long)c * 16);
+    default: {  // head: a = C; wp[t*C + c] fp32
 #pragma unroll
-      for (int t = 0; t < 16; ++t) reinterpret_cast<float*>(J.wp)[(long long)t * J.a + c] = v[t];
+      for (int t = 0; t < 16; ++t) reinterpret_cast<float*>(J.wp)[(long long)t * J.a + x] = v[t];
     } break;
   }
+}
+// the repack: thread u of a job owns one pair, the lane-fastest index chosen per layout (down: cb; up, up16: cs; g1: ci; head: c)
+template <typename W>
+__device__ __forceinline__ void pack_multi_block(const PackJobs& jobs, int bx) {
+  int ji = 0;
+  while (ji + 1 < jobs.n && bx >= jobs.first_chunk[ji + 1]) ++ji;
+  const PackJob& J = jobs.j[ji];
+  const long long u = (long long)(bx - jobs.first_chunk[ji]) * PACK_CHUNK + threadIdx.x;
+  if (u >= J.total) return;
+  int x, y, Bc = J.b;
+  if (J.kind == 0) { x = (int)(u / J.b); y = (int)(u % J.b); }
+  else if (J.kind == 4) { x = (int)u; y = 0; Bc = 1; }
+  else { y = (int)(u / J.a); x = (int)(u % J.a); }
+  const float* src = J.w + ((long long)x * Bc + y) * 16;
+  float v[16];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(src + 4 * q);
+    v[4 * q] = t[0]; v[4 * q + 1] = t[1]; v[4 * q + 2] = t[2]; v[4 * q + 3] = t[3];
+  }
+  pack_store_pair<W>(J, x, y, v);
 }
 template <typename W>
 __global__ __launch_bounds__(256) void pack_multi_kernel(const PackJobs jobs) { pack_multi_block<W>(jobs, (int)blockIdx.x); }
@@ -354,4 +369,85 @@ __global__ __launch_bounds__(256) void pack_tail_kernel(const PackJobs jobs, int
   if ((int)blockIdx.x < pack_chunks) { pack_multi_block<W>(jobs, (int)blockIdx.x); return; }
   const int q = (int)blockIdx.x - pack_chunks;
   step_tail_block(t, q % tail_x, q / tail_x);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Adam and the repack of one network as ONE launch: the operands are written from the registers that hold the new weights
+// ------------------------------------------------------------------------------------------------------
+// The repack read, once per operand form, the fp32 weights Adam had written a launch earlier.  Here a conv weight [A][Bc][4][4] at
+// arena offset `off` is a group of the jobs [j0, j0 + nj) that pack it, cut into tiles of 16 x 16 pairs, one workgroup each.  The
+// update streams like adam_kernel: a wave takes one outer channel of the tile per turn, its 64 lanes the 64 consecutive quads of
+// that row's 16 pairs (1 KB of each arena per instruction; a thread that owned a pair's 64 bytes would load 16 bytes at a stride of
+// 64 and made the step 2.3 % slower than the two launches).  The new weights go to LDS, and every form is written from there with
+// pack_store_pair by the thread that owns the pair: (tid >> 4, tid & 15) for `down`, whose inner channel is fastest, (tid & 15,
+// tid >> 4) for the forms with the outer channel fastest - 16 lanes to a contiguous run either way.  LDS slots are 20 floats per
+// pair, 17 slots per row: both readers' 16-byte reads fall on distinct banks.  Every arena range [fa, fb) between the conv weights
+// (BatchNorm weights and biases, CGAN's embedding and Linear layers) goes four elements per thread as in adam_kernel, 1024 per
+// workgroup.  Values are those of adam_kernel followed by pack_multi_kernel bit for bit: the same adam_one per element, the same
+// stf per operand element.
+#define ADAM_MAX_FLAT 8
+struct AdamGroup { long long off; int A, Bc, j0, nj; };
+struct AdamPlan {
+  AdamGroup g[PACK_MAX_JOBS]; int first_blk[PACK_MAX_JOBS + 1]; int ng;
+  long long fa[ADAM_MAX_FLAT], fb[ADAM_MAX_FLAT]; int first_fblk[ADAM_MAX_FLAT + 1]; int nf;
+};
+struct AdamArenas { float* p; const float* g; float *m, *v, *ema; const float* hp; float* zero; long long nzero4; const unsigned* skip_if; };
+template <typename W, bool EMA>
+__device__ __forceinline__ void adam_pair_block(const PackJobs& jobs, const AdamGroup& G, int tile, const AdamArenas& a, const AdamScal& s) {
+  __shared__ __attribute__((aligned(16))) float sm[16 * 17 * 20];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int ty = (G.Bc + 15) >> 4, x0 = tile / ty * 16, y0 = tile % ty * 16;
+  const int nq = min(64, (G.Bc - y0) * 4);                       // quads of a row inside the tile
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int xr = 4 * k + wv;
+    if (x0 + xr < G.A && lane < nq) {
+      float pn[4];
+      adam_quad<EMA>(a.p, a.g, a.m, a.v, a.ema, (G.off >> 2) + ((long long)(x0 + xr) * G.Bc + y0) * 4 + lane, s, pn);
+      *reinterpret_cast<f32x4*>(sm + (xr * 17 + (lane >> 2)) * 20 + (lane & 3) * 4) = f32x4{pn[0], pn[1], pn[2], pn[3]};
+    }
+  }
+  __syncthreads();
+  for (int f = G.j0; f < G.j0 + G.nj; ++f) {
+    const PackJob& J = jobs.j[f];
+    const int xl = J.kind == 0 ? tid >> 4 : tid & 15, yl = J.kind == 0 ? tid & 15 : tid >> 4;
+    if (x0 + xl >= G.A || y0 + yl >= G.Bc) continue;
+    float r[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(sm + (xl * 17 + yl) * 20 + 4 * q);
+      r[4 * q] = t[0]; r[4 * q + 1] = t[1]; r[4 * q + 2] = t[2]; r[4 * q + 3] = t[3];
+    }
+    pack_store_pair<W>(J, x0 + xl, y0 + yl, r);
+  }
+}
+// workgroups [0, pair_blks): tiles of the conv weights; the next flat_blks: the ranges between them; then (G's launch) the end-of-step
+// job's tail_x * (nl + 1) as in pack_tail_kernel.  zero / skip_if / hp as in adam_kernel: a set error word leaves parameters,
+// moments AND operands as they are - the operands come from registers here, and those would hold the weights Adam did not write
+template <typename W, bool EMA>
+__global__ __launch_bounds__(256) void adam_pack_kernel(const PackJobs jobs, const AdamPlan plan, const AdamArenas a, AdamScal s, int pair_blks,
+                                                        int flat_blks, const TailJobs t, int tail_x) {
+  const int bx = (int)blockIdx.x, nb = pair_blks + flat_blks;
+  if (bx >= nb) { step_tail_block(t, (bx - nb) % tail_x, (bx - nb) / tail_x); return; }
+  for (long long i = bx * 256ll + threadIdx.x; i < a.nzero4; i += nb * 256ll) reinterpret_cast<f32x4*>(a.zero)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (a.skip_if && *a.skip_if != 0u) return;
+  if (a.hp) { s.step_size = a.hp[0]; s.bc2_sqrt = a.hp[1]; if (EMA) s.ema_w = a.hp[2]; }
+  if (bx < pair_blks) {
+    int gi = 0;
+    while (gi + 1 < plan.ng && bx >= plan.first_blk[gi + 1]) ++gi;
+    adam_pair_block<W, EMA>(jobs, plan.g[gi], bx - plan.first_blk[gi], a, s);
+    return;
+  }
+  const int fx = bx - pair_blks;
+  int fi = 0;
+  while (fi + 1 < plan.nf && fx >= plan.first_fblk[fi + 1]) ++fi;
+  // [fa, fb) = unaligned head | whole quads [a4, b4) | tail; the range's first workgroup takes head and tail one by one
+  const long long fa = plan.fa[fi], fb = plan.fb[fi], a4 = min((fa + 3) & ~3ll, fb), b4 = max(fb & ~3ll, a4);
+  const int k = fx - plan.first_fblk[fi];
+  const long long i = (a4 >> 2) + k * 256ll + threadIdx.x;
+  if (i < (b4 >> 2)) adam_quad<EMA>(a.p, a.g, a.m, a.v, a.ema, i, s);
+  if (k == 0) {
+    const int nh = (int)(a4 - fa), nt = (int)(fb - b4);
+    if ((int)threadIdx.x < nh + nt) adam_single<EMA>(a.p, a.g, a.m, a.v, a.ema, (int)threadIdx.x < nh ? fa + threadIdx.x : b4 + (threadIdx.x - nh), s);
+  }
 }

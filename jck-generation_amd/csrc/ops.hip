@@ -635,6 +635,91 @@ int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, doubl
   return JCK_OK;
 }
 
+int jck_adam_pack_hp(int prec, float* p, const float* g, float* m, float* v, float* ema, long long first, long long count, const PackJobs& jobs,
+                     double beta1, double beta2, double eps, float grad_scale, const float* hp, float step_size, float bc2_sqrt, float ema_w,
+                     hipStream_t st, float* zero, long long nzero, const unsigned* skip_if, const TailJobs* tail, int tail_x) {
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) JCK_FAIL(JCK_E_ARG, "adam_pack: the arenas must be 16-byte aligned");
+  if (zero && (((uintptr_t)zero & 15) || (nzero & 3))) JCK_FAIL(JCK_E_ARG, "adam: the zero range must be 16-byte aligned, count % 4 == 0");
+  if (first < 0 || count < 0) JCK_FAIL(JCK_E_ARG, "adam_pack: bad range");
+  // the jobs of the weights inside the range, grouped per weight (the forms of one weight are neighbours in the table) ...
+  PackJobs sel = {};
+  AdamPlan plan = {};
+  int blk = 0;
+  for (int i = 0; i < jobs.n; ++i) {
+    const PackJob& J = jobs.j[i];
+    const int A = J.a, Bc = J.kind == 4 ? 1 : J.b;
+    const long long off = J.w - p, numel = 16ll * A * Bc;
+    if (off + numel <= first || off >= first + count) continue;
+    if (off < first || off + numel > first + count || (off & 3)) JCK_FAIL(JCK_E_ARG, "adam_pack: a conv weight straddles the range or is not 16-byte aligned");
+    if (plan.ng && plan.g[plan.ng - 1].off == off) ++plan.g[plan.ng - 1].nj;
+    else {
+      if (plan.ng && off < plan.g[plan.ng - 1].off + 16ll * plan.g[plan.ng - 1].A * plan.g[plan.ng - 1].Bc) JCK_FAIL(JCK_E_ARG, "adam_pack: conv weights must come in arena order, without overlap");
+      plan.g[plan.ng] = AdamGroup{off, A, Bc, sel.n, 1};
+      plan.first_blk[plan.ng++] = blk;
+      blk += cdiv(A, 16) * cdiv(Bc, 16);
+    }
+    sel.j[sel.n++] = J;
+  }
+  plan.first_blk[plan.ng] = blk;
+  const int pair_blks = blk;
+  // ... and what lies between them
+  int fblk = 0;
+  auto flat = [&](long long a, long long b) {
+    if (a >= b) return true;
+    if (plan.nf == ADAM_MAX_FLAT) return false;
+    plan.fa[plan.nf] = a; plan.fb[plan.nf] = b;
+    plan.first_fblk[plan.nf++] = fblk;
+    const long long a4 = std::min((a + 3) & ~3ll, b), b4 = std::max(b & ~3ll, a4);
+    fblk += (int)std::max<long long>(1, ((b4 - a4) / 4 + 255) / 256);
+    return true;
+  };
+  long long at = first;
+  bool fits = true;
+  for (int i = 0; i < plan.ng; ++i) {
+    fits = fits && flat(at, plan.g[i].off);
+    at = plan.g[i].off + 16ll * plan.g[i].A * plan.g[i].Bc;
+  }
+  fits = fits && flat(at, first + count);
+  if (!fits) JCK_FAIL(JCK_E_ARG, "adam_pack: more than ADAM_MAX_FLAT ranges between the conv weights");
+  plan.first_fblk[plan.nf] = fblk;
+  const int nb = pair_blks + fblk;
+  const TailJobs no_tail = {};
+  const int tail_blks = tail ? tail_x * (tail->nl + 1) : 0;
+  if (nb + tail_blks == 0) return JCK_OK;
+  const AdamArenas a = {p, g, m, v, ema, hp, zero, zero ? nzero / 4 : 0, skip_if};
+  const AdamScal s = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, step_size, bc2_sqrt, grad_scale, ema_w};
+#define ADAM_PACK_LAUNCH(W, EMA) \
+  hipLaunchKernelGGL((adam_pack_kernel<W, EMA>), dim3(nb + tail_blks), dim3(256), 0, st, sel, plan, a, s, pair_blks, fblk, tail ? *tail : no_tail, tail ? tail_x : 1)
+  if (prec == JCK_PREC_BF16) { if (ema) ADAM_PACK_LAUNCH(bf16_t, true); else ADAM_PACK_LAUNCH(bf16_t, false); }
+  else if (ema) ADAM_PACK_LAUNCH(float, true);
+  else ADAM_PACK_LAUNCH(float, false);
+#undef ADAM_PACK_LAUNCH
+  HIPCHK(hipGetLastError());
+  return JCK_OK;
+}
+extern "C" int jck_adam_pack(int prec, float* p, const float* g, float* m, float* v, float* ema, long long n, int njobs, const int* kind,
+                             const long long* w_off, void* const* wp, const int* a, const int* b, double lr, double beta1, double beta2, double eps,
+                             int step, float grad_scale, float ema_weight, const unsigned* skip_if, void* stream) {
+  if (step < 1) JCK_FAIL(JCK_E_ARG, "adam: step is 1-based");
+  if (njobs < 0 || njobs > PACK_MAX_JOBS || (njobs && (!kind || !w_off || !wp || !a || !b))) JCK_FAIL(JCK_E_ARG, "adam_pack: 0..12 jobs, every table given");
+  if (prec != JCK_PREC_BF16 && !prec_f32_storage(prec)) JCK_FAIL(JCK_E_ARG, "bad prec");
+  PackJobs jobs = {};
+  for (int i = 0; i < njobs; ++i) {
+    PackJob& J = jobs.j[i];
+    if (kind[i] < 0 || kind[i] > 4 || a[i] < 1 || (kind[i] != 4 && b[i] < 1) || !wp[i]) JCK_FAIL(JCK_E_ARG, "adam_pack: bad job");
+    J.w = p + w_off[i]; J.wp = wp[i]; J.kind = kind[i]; J.a = a[i]; J.b = kind[i] == 4 ? 0 : b[i];
+    J.total = (long long)a[i] * (kind[i] == 4 ? 1 : b[i]);
+    // the third size of each layout follows from the two channel counts, as in the engine's table
+    J.c = kind[i] == 0 ? ilog2(jck_pad_chan(b[i])) : kind[i] == 1 ? jck_pad_rows(b[i]) : kind[i] == 3 ? (a[i] + 127) / 128 * 128 : 0;
+    if (kind[i] == 0 && (1 << J.c) != jck_pad_chan(b[i])) JCK_FAIL(JCK_E_ARG, "adam_pack: down needs a power-of-two (padded) Cb");
+    if (kind[i] == 2 && b[i] > 4) JCK_FAIL(JCK_E_ARG, "adam_pack: up16 packs at most 4 channels");
+  }
+  jobs.n = njobs;
+  const double bc1 = 1.0 - std::pow(beta1, step), bc2 = 1.0 - std::pow(beta2, step);
+  return jck_adam_pack_hp(prec, p, g, m, v, ema, 0, n, jobs, beta1, beta2, eps, grad_scale, nullptr, (float)(lr / bc1), (float)std::sqrt(bc2),
+                          ema_weight, (hipStream_t)stream, nullptr, 0, skip_if, nullptr, 0);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // latent projection (latent.hpp)
 // ---------------------------------------------------------------------------------------------------------

@@ -132,6 +132,14 @@ int jck_adam_hp(float* p, const float* g, float* m, float* v, long long n, doubl
                 float grad_scale, const float* hp, hipStream_t st, float* zero = nullptr, long long nzero = 0,
                 const unsigned* skip_if = nullptr,       // skip_if: device word; non-zero = leave p, m, v untouched (a grid barrier of the step timed out)
                 float* ema = nullptr);                   // ema: moving average of p, advanced in the same launch with the weight in hp[2]
+// jck_adam_hp on elements [first, first + count) of the arenas p, g, m, v (ema) AND the repack of every conv weight inside that range, one
+// launch (ew_optim.hpp: adam_pack_kernel): `jobs` is the network's repack table (weights that lie outside the range are left out),
+// tail (optional) the end-of-step job that rides along.  All arenas 16-byte aligned.
+struct PackJobs;
+struct TailJobs;
+int jck_adam_pack_hp(int prec, float* p, const float* g, float* m, float* v, float* ema, long long first, long long count, const PackJobs& jobs,
+                     double beta1, double beta2, double eps, float grad_scale, const float* hp, float step_size, float bc2_sqrt, float ema_w,
+                     hipStream_t st, float* zero, long long nzero, const unsigned* skip_if, const TailJobs* tail, int tail_x);
 const unsigned* jck_grid_sync_error_word(const void* sync_ws);      // (ops_bn.hip)
 // BatchNorm finalize + apply as one launch where the statistics rows are few (ops_bn.hip); *fused = false: nothing was launched
 int bn_fwd_fused(int prec, const void* y, const float* stats, int slots_per_group, float count, const float* gamma, const float* beta,

@@ -114,6 +114,8 @@ PROTOS = {
     "jck_head_bwd_conv2": (i32, [i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "jck_adam": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, i32, f32, vp]),
     "jck_adam_ema": (i32, [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, i32, f32, f32, vp, vp]),
+    "jck_adam_pack": (i32, [i32, vp, vp, vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32),
+                            f64, f64, f64, f64, i32, f32, f32, vp, vp]),
     "jck_engine_create": (i32, [C.POINTER(vp), i32, i32, i32]),
     "jck_engine_create_sized": (i32, [C.POINTER(vp), i32, i32, i32, i32]),
     "jck_engine_create_ex": (i32, [C.POINTER(vp), i32, i32, i32, i32, C.c_uint]),

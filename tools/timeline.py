@@ -1,5 +1,5 @@
 """One traced step of a rocprofv3 kernel trace as a timeline (development aid): python tools/timeline.py <kernel_trace.csv> [out.txt]
-start offset us | duration us | HIP stream | kernel | grid, between the last-but-two and last-but-one end-of-step (pack_tail) launches."""
+start offset us | duration us | HIP stream | kernel | grid, between the last-but-two and last-but-one end-of-step (pack_tail) launches, or set-step launches where the trace has no pack_tail."""
 import csv
 import re
 import sys
@@ -10,6 +10,8 @@ def main():
           for r in csv.DictReader(open(sys.argv[1]))]
     tr.sort()
     marks = [e[0] for e in tr if "step_tail" in e[3] or "pack_tail" in e[3]]
+    if not marks:      # Adam(G)'s launch carries the end-of-step job: a step starts at its set-step launch
+        marks = [e[0] - 1 for e in tr if "adam_hp_kernel" in e[3]]
     a, b = marks[-3], marks[-2]
     lines = [f"# one traced step ({(b - a) / 1e3:.1f} us under rocprofv3): start us | duration us | HIP stream | kernel | grid"]
     for st, en, sid, name, grid in tr:
