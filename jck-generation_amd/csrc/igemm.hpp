@@ -24,6 +24,20 @@
 
 #include "common.hpp"
 
+// The epilogue of a launch: a compile-time tag of the kernels that end in igemm_epilogue (never the persistent ones).  The fused forms
+// work on the fp32 accumulators before the one rounding of the store, c = channel & (cstat - 1): no statistics, bias, tanh or split-K.
+enum class Epi {
+  Plain,        // training: optional BatchNorm partial statistics, bias, tanh
+  ReluAffine,   // G's inference (jck_conv_up_affine, jck_g1_fwd_affine): t = aff_scale[c] * acc + aff_shift[c], a folded eval-mode BatchNorm; v = relu(t), NaN passes
+  LeakyAffine,  // D's inference (jck_conv_down_affine): the same t, v = t > 0 ? t : t * aff_slope (ATen's LeakyReLU: NaN passes, -0 stays -0)
+  ReluMask,     // latent projection (jck_conv_down_mask), the gradient through a folded ReLU stage a: v = a[pixel][c] > 0 ? mask_scale[c] * acc : +0 (a NaN masks)
+  LeakyMask     // the critic's latent gradient (jck_conv_up_mask), through a = leaky(scale[c] * y + shift[c]): t = mask_scale[c] * acc,
+                // v = a[pixel][c] > 0 ? t : t * aff_slope (ATen's leaky_relu_backward: +-0 and NaN activations take the slope); a is mask_act
+};
+constexpr bool epi_affine(Epi e) { return e == Epi::ReluAffine || e == Epi::LeakyAffine; }
+constexpr bool epi_mask(Epi e) { return e == Epi::ReluMask || e == Epi::LeakyMask; }
+constexpr bool epi_leaky(Epi e) { return e == Epi::LeakyAffine || e == Epi::LeakyMask; }
+
 struct IgemmParams {
   const void* act;        // gathered NHWC tensor, element type T
   const void* w;          // packed weights [Z][NchPad][K]  (K contiguous, K % 64 == 0), bf16 or fp32
@@ -60,18 +74,11 @@ struct IgemmParams {
   // instead of one row per (tile, wave); set by the launcher for the *_grouped entry points
   int stat_accum;
   double flops;           // algorithmic FLOPs of this launch (profiling only)
-  // AFFINE instantiations only (inference: BatchNorm with the running statistics folded into the product's epilogue):
-  // v = relu(aff_scale[c] * acc + aff_shift[c]), c = channel & (cstat - 1); 16-byte aligned, cstat floats each
-  const float* aff_scale;
-  const float* aff_shift;
-  // MASK instantiations only (latent projection: the backward of a folded BatchNorm + ReLU in a dgrad's epilogue):
-  // v = mask_act[pixel][c] > 0 ? mask_scale[c] * acc : +0, c = channel & (cstat - 1); mask_act has the output's layout and type
-  const void* mask_act;
-  const float* mask_scale;
-  // LEAKY form of the AFFINE instantiations (discriminator inference, jck_conv_down_affine): t = aff_scale[c] * acc + aff_shift[c],
-  // v = t > 0 ? t : t * aff_slope.  LEAKY form of the MASK instantiations (the critic's latent gradient, jck_conv_up_mask): the backward of
-  // a folded BatchNorm + LeakyReLU, t = mask_scale[c] * acc, v = mask_act[pixel][c] > 0 ? t : t * aff_slope
-  float aff_slope;
+  const float* aff_scale;  // the fused epilogues' operands (enum Epi above).  ReluAffine, LeakyAffine: scale[c] and ...
+  const float* aff_shift;  // ... shift[c]; 16-byte aligned, cstat floats each
+  const void* mask_act;    // ReluMask, LeakyMask: the stored activation, in the output's layout and type, and ...
+  const float* mask_scale; // ... scale[c]; 16-byte aligned, cstat floats
+  float aff_slope;         // LeakyAffine, LeakyMask: the LeakyReLU's slope
 };
 
 #define IG_BK 64
@@ -107,22 +114,15 @@ __device__ __forceinline__ void igemm_pixel_offsets(const IgemmParams& p, int la
   }
 }
 
-// Shared epilogue: optional BatchNorm partial statistics, bias, tanh, NHWC store of 4 consecutive channels per lane.
-// AFFINE (compile time, the inference entry points alone): the per-channel affine of an eval-mode BatchNorm and the ReLU are applied
-// to the fp32 accumulators before the one rounding of the store - no statistics, no pre-activation tensor.  NaN passes (torch.relu).
-// MASK (compile time, jck_conv_down_mask alone): the gradient through a folded stage a = relu(scale[c] * y + shift[c]) - scale[c]
-// where the stored activation is > 0, else +0 (a NaN activation masks: torch.relu's backward) - on the fp32 accumulators.
-// LEAKY (compile time, with AFFINE; jck_conv_down_affine alone): LeakyReLU in the ReLU's place, t > 0 ? t : t * aff_slope - ATen's
-// form: NaN passes, -0 stays -0.  With MASK (jck_conv_up_mask alone): the gradient through a = leaky(scale[c] * y + shift[c]) - scale[c]
-// where the stored activation is > 0, else scale[c] * aff_slope (ATen's leaky_relu_backward on the result: +-0 and NaN take the slope).
-template <class P, int BCH, int BPIX, int FM, int FN, int WPIXN, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
+// Shared epilogue: optional BatchNorm partial statistics, bias, tanh, E's fused form (enum Epi), NHWC store of 4 consecutive channels per lane.
+template <class P, int BCH, int BPIX, int FM, int FN, int WPIXN, Epi E = Epi::Plain>
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc)[FM][FN], int lane, int wch, int wpix, int z, int zraw,
                                                int bidx, int bidy, int m0, int ch0) {
   typedef typename P::T T;
   // ---- epilogue --------------------------------------------------------------------------------------
   long long poff[FN];                                               // output offset of this lane's pixel in tile column j (-1: past M)
   igemm_pixel_offsets<FN>(p, lane, wpix, m0, poff);
-  if (!AFFINE && p.stats) {
+  if (!epi_affine(E) && p.stats) {
     // slot = one (pixel tile, phase, channel-set replica, pixel-wave); every (slot, channel) is written exactly once
     const int yrep = bidy / p.ytiles_per_cset, nyrep = p.gy / p.ytiles_per_cset;
     // pixel tile slowest, so that the slots of consecutive pixel ranges (BatchNorm groups) are consecutive too
@@ -166,23 +166,23 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]);
       }
-      if constexpr (AFFINE) {
+      if constexpr (epi_affine(E)) {
         const int cc = ch & (p.cstat - 1);
         const f32x4 sc = *reinterpret_cast<const f32x4*>(p.aff_scale + cc), sh = *reinterpret_cast<const f32x4*>(p.aff_shift + cc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float t = fmaf(sc[r], v[r], sh[r]);
-          if constexpr (LEAKY) v[r] = t > 0.f ? t : t * p.aff_slope;
+          if constexpr (epi_leaky(E)) v[r] = t > 0.f ? t : t * p.aff_slope;
           else v[r] = t < 0.f ? 0.f : t;
         }
       }
-      if constexpr (MASK) {
+      if constexpr (epi_mask(E)) {
         const f32x4 sc = *reinterpret_cast<const f32x4*>(p.mask_scale + (ch & (p.cstat - 1)));
         float a[4];
         ld4(reinterpret_cast<const T*>(p.mask_act) + off + ch, a);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          if constexpr (LEAKY) { const float t = sc[r] * v[r]; v[r] = a[r] > 0.f ? t : t * p.aff_slope; }
+          if constexpr (epi_leaky(E)) { const float t = sc[r] * v[r]; v[r] = a[r] > 0.f ? t : t * p.aff_slope; }
           else v[r] = a[r] > 0.f ? sc[r] * v[r] : 0.f;
         }
       }
@@ -192,8 +192,8 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
   }
 }
 
-// NSUB: 1 - >= 64 gathered channels, 2 - exactly 4, 0 - 8..32 (ReLU AFFINE and MASK launches only: small generators at inference / projection)
-template <class P, int BCH, int BPIX, int NSUB, int NST = 2, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
+// NSUB: 1 - >= 64 gathered channels, 2 - exactly 4, 0 - 8..32 (Epi::ReluAffine and Epi::ReluMask launches only: small generators at inference / projection)
+template <class P, int BCH, int BPIX, int NSUB, int NST = 2, Epi E = Epi::Plain>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   typedef typename P::T T;        // activation storage type
   typedef typename P::W W;        // packed-weight element type (bf16_t or float)
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     }
   }
 
-  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK, LEAKY>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, E>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -443,7 +443,7 @@ static __device__ __attribute__((aligned(16))) unsigned int g_jck_zero_page[64];
 // about one workgroup per CU, where a 4-wave workgroup would serialise DMA issue and MFMA in every wave.
 // NCW = 8 (768 threads) with a 128 x 256 tile: the weight tile is filled once for twice the pixels - 85 instead of 64 FLOP
 // per filled byte (the kernels are bound by the LDS fill rate).
-template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
+template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, Epi E = Epi::Plain>
 __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(const IgemmParams p) {
   static_assert(!WS || NSTG == 3, "wave specialisation uses 3 LDS stages");
   static_assert(NCW == 4 || (WS && NCW == 8), "8 consumer waves exist in the wave-specialised form only");
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(co
       compute(slot);
       slot = slot == 2 ? 0 : slot + 1;
     }
-    igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK, LEAKY>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+    igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, E>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
     return;
   }
   // prologue: NSTG-1 stages in flight
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(WS ? (NCW + 4) * 64 : 256) void igemm_dma_kernel(co
     st_i = (st_i + 1 == NSTG) ? 0 : st_i + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // drain the dead tail loads before the epilogue reuses nothing of LDS
-  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, AFFINE, MASK, LEAKY>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
+  igemm_epilogue<P, BCH, BPIX, FM, FN, C::WPIX, E>(p, acc, lane, wch, wpix, z, zraw, bidx, bidy, m0, ch0);
 }
 
 // Epilogue of the persistent kernel: 16-byte stores.  The loader fills LDS weight row r of every 32-row block with output

@@ -1,6 +1,6 @@
 // Latent projection (fit z to given images through the frozen eval-mode generator): the image loss with its gradient at the pre-tanh
 // product, and Adam on z fused with the split-K slab sum of the dz product.  Memory-bound, one launch each; the third piece - the
-// backward of a folded BatchNorm + ReLU - is the MASK option of the gather-GEMM epilogue (igemm.hpp).
+// backward of a folded BatchNorm + ReLU - is the Epi::ReluMask form of the gather-GEMM epilogue (igemm.hpp).
 #pragma once
 #include "common.hpp"
 

@@ -43,7 +43,7 @@ static void igemm_tile_stats(IgemmParams& q, const dim3& grid, int BCH, int rows
   if (slots) *slots = (int)(grid.x * grid.z * (grid.y / q.ytiles_per_cset) * rows_per_tile);
 }
 
-template <class P, int BCH, int BPIX, int NSUB, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
+template <class P, int BCH, int BPIX, int NSUB, Epi E = Epi::Plain>
 static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   typedef IgemmCfg<P, BCH, BPIX> C;
   constexpr KernelId id = kid_igemm<P, BCH, BPIX, NSUB>();
@@ -55,10 +55,10 @@ static int launch_igemm_t(const IgemmParams& p, int nch_pad, int phases, hipStre
     if (q.cstat % BCH != 0 && BCH % q.cstat != 0) JCK_FAIL(JCK_E_ARG, "igemm: stats channel count incompatible with the tile");
     igemm_tile_stats(q, grid, BCH, C::WPIX, slots);
   }
-  return launch_lds<igemm_kernel<P, BCH, BPIX, NSUB, 2, AFFINE, MASK, LEAKY>>(dim3(grid.x * grid.y * grid.z), dim3(256), C::LDS_BYTES, st, q);
+  return launch_lds<igemm_kernel<P, BCH, BPIX, NSUB, 2, E>>(dim3(grid.x * grid.y * grid.z), dim3(256), C::LDS_BYTES, st, q);
 }
 
-template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, bool AFFINE = false, bool MASK = false, bool LEAKY = false>
+template <int BCH, int BPIX, int NSTG, bool WS = false, int NCW = 4, Epi E = Epi::Plain>
 static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
   constexpr int LDSB = NSTG * (BCH + BPIX) * IG_BK * 2;
   ProfScope prof(kid_igemm_dma(K_IGEMM_DMA, BCH, BPIX), p.flops, st);
@@ -66,7 +66,7 @@ static int launch_igemm_dma(const IgemmParams& p, int nch_pad, int phases, hipSt
   IgemmParams q;
   const dim3 grid = igemm_grid(p, nch_pad, phases, BCH, BPIX, q);
   if (q.stats) igemm_tile_stats(q, grid, BCH, IgemmCfg<PrecBf16, BCH, BPIX, NCW>::WPIX, slots);
-  return launch_lds<igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW, AFFINE, MASK, LEAKY>>(dim3(grid.x * grid.y * grid.z), dim3(WS ? (NCW + 4) * 64 : 256), LDSB, st, q);
+  return launch_lds<igemm_dma_kernel<BCH, BPIX, NSTG, WS, NCW, E>>(dim3(grid.x * grid.y * grid.z), dim3(WS ? (NCW + 4) * 64 : 256), LDSB, st, q);
 }
 
 // persistent wave-specialised form: at most `cap` workgroups (what the chip holds at this tile's LDS footprint) walk the tiles
@@ -102,6 +102,14 @@ constexpr int IGEMM_256_MIN_TILES = 250;
 // (D.conv3's forward at 3 x 256 images 60.6 -> 55.3 us against 128 x 256 tiles)
 constexpr int IGEMM_128_MIN_TILES = 200;
 
+// >= 128 channel rows on the register-staged kernel: keep >= ~256 workgroups in flight - halve the pixel tile for small pixel counts
+template <class P, Epi E = Epi::Plain>
+static int launch_igemm_t128(const IgemmParams& p, int nch_pad, int phases, hipStream_t st, int* slots) {
+  const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
+  if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, E>(p, nch_pad, phases, st, slots);
+  return launch_igemm_t<P, 128, 64, 1, E>(p, nch_pad, phases, st, slots);
+}
+
 template <class P>
 static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st, int* slots) {
   // bf16 tiles with >= 128 channel rows run on the LDS-DMA kernels: 128x128 tiles with 2 LDS stages (64 KB -> 2-3 workgroups per
@@ -131,10 +139,7 @@ static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsu
   }
   if (nch_pad % 128 == 0) {
     if (nsub != 1) JCK_FAIL(JCK_E_ARG, "igemm: 4-channel gather with >=128 output rows unsupported");
-    // keep >= ~256 workgroups in flight: halve the pixel tile for small pixel counts
-    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
-    if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1>(p, nch_pad, phases, st, slots);
-    return launch_igemm_t<P, 128, 64, 1>(p, nch_pad, phases, st, slots);
+    return launch_igemm_t128<P>(p, nch_pad, phases, st, slots);
   }
   if (nch_pad == 64) {
     if (nsub == 2) return launch_igemm_t<P, 64, 128, 2>(p, nch_pad, phases, st, slots);
@@ -156,109 +161,58 @@ static int launch_igemm_p(const IgemmParams& p, int nch_pad, int phases, int nsu
   JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
 }
 
-// Inference launches (p.aff_scale set): the kernels that end in the shared epilogue, in its AFFINE instantiation - never the persistent
-// ones.  Tile choice as launch_igemm_p's non-persistent branches; 8..32 gathered channels (nsub 0) take 16-row tiles whatever the row count.
-// LEAKY (jck_conv_down_affine: D's stages): the same tiles in the epilogue's leaky form for >= 64 output rows; nsub 2 - the image-side
-// layer, 4 gathered channels - on the register-staged 64 x 128 tile in every precision, as launch_igemm_mask_p does.
-template <class P, bool LEAKY = false>
-static int launch_igemm_affine_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st) {
-  if constexpr (LEAKY) {
+// what launch_igemm_fused_p says when it refuses
+constexpr const char* epi_built_for(Epi e) {
+  return e == Epi::ReluAffine ? "igemm: the ReLU affine epilogue is built for 8..32 gathered channels, or >= 64 and 16, 64 or a multiple of 128 output rows"
+       : e == Epi::LeakyAffine ? "igemm: the leaky affine epilogue is built for 4 gathered channels and 64 output rows, or >= 64 and 64 or a multiple of 128"
+       : e == Epi::ReluMask ? "igemm: the ReLU mask epilogue is built for 4..32 gathered channels and 64 output rows, or >= 64 and 64 or a multiple of 128"
+                            : "igemm: the leaky mask epilogue is built for >= 64 gathered channels and 64 or a multiple of 128 output rows";
+}
+// Fused-epilogue launches (E != Epi::Plain, igemm.hpp): the kernels that end in the shared epilogue, never the persistent ones, and no
+// statistics.  First what E alone has or refuses, then the one tile ladder - launch_igemm_p's non-persistent choices, `phases`
+// counted into the workgroups.  No tile is built for an epilogue that does not launch it.
+template <class P, Epi E>
+static int launch_igemm_fused_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st) {
+  static_assert(E != Epi::Plain, "the plain epilogue launches through launch_igemm_p");
+  if constexpr (E == Epi::LeakyAffine || E == Epi::ReluMask) {         // nsub 2, the image-side layer: register-staged in every precision
     if (nsub == 2) {
       if (nch_pad != 64) JCK_FAIL(JCK_E_ARG, "igemm: a 4-channel gather is built for 64 output rows");
-      return launch_igemm_t<P, 64, 128, 2, true, false, true>(p, nch_pad, phases, st, nullptr);
+      return launch_igemm_t<P, 64, 128, 2, E>(p, nch_pad, phases, st, nullptr);
     }
-    if (nsub != 1 || (nch_pad != 64 && nch_pad % 128)) JCK_FAIL(JCK_E_ARG, "igemm: the leaky affine epilogue is built for 4 or >= 64 gathered channels and >= 64 output rows");
+  }
+  if constexpr (E == Epi::ReluAffine) {                                // nsub 0, small generators: 16-row tiles whatever the row count
+    if (nsub == 0 && nch_pad % 16 == 0) return launch_igemm_t<P, 16, 256, 0, E>(p, nch_pad, phases, st, nullptr);
+    if (nsub == 1 && nch_pad == 16) return launch_igemm_t<P, 16, 256, 1, E>(p, nch_pad, phases, st, nullptr);
+  }
+  if constexpr (E == Epi::ReluMask) {                                  // nsub 0, small generators: 64 output rows alone
+    if (nsub == 0 && nch_pad == 64) return launch_igemm_t<P, 64, 128, 0, E>(p, nch_pad, phases, st, nullptr);
+  }
+  if (nsub != 1 || (nch_pad != 64 && nch_pad % 128)) JCK_FAIL(JCK_E_ARG, std::string(epi_built_for(E)) + ", got " + std::to_string(nch_pad));
+  // the ladder: >= 64 gathered channels, 64 or a multiple of 128 channel rows
+  if (nch_pad == 64) {
+    if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, E>(p, nch_pad, phases, st, nullptr);
+    else return launch_igemm_t<P, 64, 128, 1, E>(p, nch_pad, phases, st, nullptr);
+  }
+  if constexpr (!P::IS_F32) {
+    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
+    const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128) * phases;
+    if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, E>(p, nch_pad, phases, st, nullptr);
+    if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, E>(p, nch_pad, phases, st, nullptr);
+    return launch_igemm_dma<128, 64, 3, true, 4, E>(p, nch_pad, phases, st, nullptr);
   } else {
-    if (nsub == 0) {
-      if (nch_pad % 16) JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
-      return launch_igemm_t<P, 16, 256, 0, true>(p, nch_pad, phases, st, nullptr);
-    }
-    if (nsub != 1) JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue is built for >= 8 gathered channels");
+    return launch_igemm_t128<P, E>(p, nch_pad, phases, st, nullptr);
   }
-  if (nch_pad % 128 == 0) {
-    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
-    if constexpr (!P::IS_F32) {
-      const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128) * phases;
-      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
-      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
-      return launch_igemm_dma<128, 64, 3, true, 4, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
-    } else {
-      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
-      return launch_igemm_t<P, 128, 64, 1, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
-    }
-  }
-  if (nch_pad == 64) {
-    if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
-    else return launch_igemm_t<P, 64, 128, 1, true, false, LEAKY>(p, nch_pad, phases, st, nullptr);
-  }
-  if constexpr (!LEAKY) {
-    if (nch_pad == 16) return launch_igemm_t<P, 16, 256, 1, true>(p, nch_pad, phases, st, nullptr);
-  }
-  JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
-}
-
-// Masked dgrad launches (p.mask_act set: jck_conv_down_mask): the same kernels in the epilogue's MASK instantiation, tile choice as
-// launch_igemm_affine_p's.  nsub 2: the image-side layer (4 gathered channels) on the register-staged 64 x 128 tile in every precision.
-template <class P>
-static int launch_igemm_mask_p(const IgemmParams& p, int nch_pad, int nsub, hipStream_t st) {
-  if (nsub == 2) {
-    if (nch_pad != 64) JCK_FAIL(JCK_E_ARG, "igemm: a 4-channel gather is built for 64 output rows");
-    return launch_igemm_t<P, 64, 128, 2, false, true>(p, nch_pad, 1, st, nullptr);
-  }
-  if (nsub == 0) {                                                     // 8..32 gathered channels: small generators
-    if (nch_pad == 64) return launch_igemm_t<P, 64, 128, 0, false, true>(p, nch_pad, 1, st, nullptr);
-    JCK_FAIL(JCK_E_ARG, "igemm: 8..32 gathered channels are built for 64 output rows");
-  }
-  if (nch_pad % 128 == 0) {
-    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128);
-    if constexpr (!P::IS_F32) {
-      const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128);
-      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, false, true>(p, nch_pad, 1, st, nullptr);
-      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, false, true>(p, nch_pad, 1, st, nullptr);
-      return launch_igemm_dma<128, 64, 3, true, 4, false, true>(p, nch_pad, 1, st, nullptr);
-    } else {
-      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, false, true>(p, nch_pad, 1, st, nullptr);
-      return launch_igemm_t<P, 128, 64, 1, false, true>(p, nch_pad, 1, st, nullptr);
-    }
-  }
-  if (nch_pad == 64) {
-    if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, false, true>(p, nch_pad, 1, st, nullptr);
-    else return launch_igemm_t<P, 64, 128, 1, false, true>(p, nch_pad, 1, st, nullptr);
-  }
-  JCK_FAIL(JCK_E_ARG, "igemm: unsupported padded row count " + std::to_string(nch_pad));
-}
-
-// Leaky masked dgrad launches (jck_conv_up_mask: a Conv2d's input gradient through a folded BatchNorm + LeakyReLU stage, 4 output
-// parities as phases): the epilogue's MASK + LEAKY instantiation on launch_igemm_affine_p's tiles, `phases` counted into the tile
-// choice.  >= 64 gathered channels and >= 64 output rows alone; never the persistent kernels.
-template <class P>
-static int launch_igemm_mask_leaky_p(const IgemmParams& p, int nch_pad, int phases, int nsub, hipStream_t st) {
-  if (nsub != 1 || (nch_pad != 64 && nch_pad % 128)) JCK_FAIL(JCK_E_ARG, "igemm: the leaky mask epilogue is built for >= 64 gathered channels and >= 64 output rows");
-  if (nch_pad % 128 == 0) {
-    const long long wgs = (long long)cdiv(p.M, 128) * (nch_pad / 128) * phases;
-    if constexpr (!P::IS_F32) {
-      const long long wgs256 = (long long)cdiv(p.M, 256) * (nch_pad / 128) * phases;
-      if (wgs256 >= IGEMM_256_MIN_TILES && p.M % 256 == 0) return launch_igemm_dma<128, 256, 3, true, 8, false, true, true>(p, nch_pad, phases, st, nullptr);
-      if (wgs >= 512) return launch_igemm_dma<128, 128, 2, false, 4, false, true, true>(p, nch_pad, phases, st, nullptr);
-      return launch_igemm_dma<128, 64, 3, true, 4, false, true, true>(p, nch_pad, phases, st, nullptr);
-    } else {
-      if (wgs >= 256) return launch_igemm_t<P, 128, 128, 1, false, true, true>(p, nch_pad, phases, st, nullptr);
-      return launch_igemm_t<P, 128, 64, 1, false, true, true>(p, nch_pad, phases, st, nullptr);
-    }
-  }
-  if constexpr (!P::IS_F32) return launch_igemm_dma<64, 128, 2, false, 4, false, true, true>(p, nch_pad, phases, st, nullptr);
-  else return launch_igemm_t<P, 64, 128, 1, false, true, true>(p, nch_pad, phases, st, nullptr);
 }
 
 static int launch_wgrad_reduce(const float* ws, int Z, int CsRows, int ncols, int Cs, int Cb, int logCbPad, float* grad,
                                int accumulate, hipStream_t st);
-// leaky: with p0.aff_scale, the LeakyReLU form of the affine epilogue (slope p0.aff_slope); with p0.mask_act, that of the mask epilogue
-static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int nsub, hipStream_t st, int* slots, bool leaky = false) {
+// e: the epilogue (igemm.hpp); a fused one finds its operands in p0, where set_epilogue put them
+static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases, int nsub, hipStream_t st, int* slots, Epi e = Epi::Plain) {
   IgemmParams p = p0;
   for (int zz = 0; zz < 4; ++zz)
     for (int t = 0; t < 16; ++t) p.tap[zz][t] = ((int)p.dy[zz][t] << 16) | ((int)p.dx[zz][t] & 0xffff);
   const long long esz = prec_f32_storage(prec) ? 4 : 2;
-  if (nsub == 0 && (p.logC < 3 || p.logC > 5 || !(p.aff_scale || p.mask_act))) JCK_FAIL(JCK_E_ARG, "igemm: 8..32 gathered channels are built for the affine and mask epilogues alone");
+  if (nsub == 0 && (p.logC < 3 || p.logC > 5 || e == Epi::Plain)) JCK_FAIL(JCK_E_ARG, "igemm: 8..32 gathered channels are built for the affine and mask epilogues alone");
   if (nsub == 1 && p.logC < 6 && !p.act_row_elems) JCK_FAIL(JCK_E_ARG, "igemm: the gathered tensor needs >= 64 channels (or exactly 4)");
   {
     // extent of the gathered tensor: rows (n, oy, ox) span N = M / (OH*OW) images of H x W x C
@@ -271,24 +225,22 @@ static int launch_igemm(int prec, const IgemmParams& p0, int nch_pad, int phases
   if (p.K % IG_BK != 0) JCK_FAIL(JCK_E_ARG, "igemm: K must be a multiple of 64, got " + std::to_string(p.K));
   if (p.M <= 0) JCK_FAIL(JCK_E_ARG, "igemm: empty problem");
   if (p.stats && !slots) JCK_FAIL(JCK_E_ARG, "igemm: stats requested without a slot-count output");
-  if (p.aff_scale) {
-    if (!p.aff_shift || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || !is_pow2(p.cstat) || p.cstat % 4 ||
-        ((uintptr_t)p.aff_scale | (uintptr_t)p.aff_shift) % 16)
-      JCK_FAIL(JCK_E_ARG, "igemm: the affine epilogue takes 16-byte aligned scale and shift, a power-of-two channel count and no other option");
-    if (leaky) DISPATCH_P(prec, (launch_igemm_affine_p<P, true>(p, nch_pad, phases, nsub, st)));
-    DISPATCH_P(prec, launch_igemm_affine_p<P>(p, nch_pad, phases, nsub, st));
-  }
-  if (p.mask_act && leaky) {
-    if (!p.mask_scale || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || !is_pow2(p.cstat) || p.cstat % 4 ||
-        (uintptr_t)p.mask_scale % 16 || (uintptr_t)p.mask_act % 16)
-      JCK_FAIL(JCK_E_ARG, "igemm: the mask epilogue takes a 16-byte aligned scale and activation, a power-of-two channel count and no other option");
-    DISPATCH_P(prec, launch_igemm_mask_leaky_p<P>(p, nch_pad, phases, nsub, st));
-  }
-  if (p.mask_act) {
-    if (!p.mask_scale || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || phases != 1 || !is_pow2(p.cstat) || p.cstat % 4 ||
-        (uintptr_t)p.mask_scale % 16 || (uintptr_t)p.mask_act % 16)
-      JCK_FAIL(JCK_E_ARG, "igemm: the mask epilogue takes a 16-byte aligned scale and activation, a power-of-two channel count and no other option");
-    DISPATCH_P(prec, launch_igemm_mask_p<P>(p, nch_pad, nsub, st));
+  if (e != Epi::Plain) {
+    // the two operands of the variant: scale and shift, or scale and the stored activation
+    const void* a = epi_affine(e) ? (const void*)p.aff_scale : (const void*)p.mask_scale;
+    const void* b = epi_affine(e) ? (const void*)p.aff_shift : p.mask_act;
+    if (!a || !b || p.stats || p.bias || p.epi || p.ksplit > 1 || p.rows_are_phases || (e == Epi::ReluMask && phases != 1) ||
+        !is_pow2(p.cstat) || p.cstat % 4 || ((uintptr_t)a | (uintptr_t)b) % 16)
+      JCK_FAIL(JCK_E_ARG, std::string("igemm: the ") + (epi_affine(e) ? "affine epilogue takes 16-byte aligned scale and shift" :
+               "mask epilogue takes a 16-byte aligned scale and activation") + ", a power-of-two channel count and no other option" +
+               (e == Epi::ReluMask ? ", in one phase" : ""));
+    switch (e) {
+      case Epi::ReluAffine: DISPATCH_P(prec, (launch_igemm_fused_p<P, Epi::ReluAffine>(p, nch_pad, phases, nsub, st)));
+      case Epi::LeakyAffine: DISPATCH_P(prec, (launch_igemm_fused_p<P, Epi::LeakyAffine>(p, nch_pad, phases, nsub, st)));
+      case Epi::ReluMask: DISPATCH_P(prec, (launch_igemm_fused_p<P, Epi::ReluMask>(p, nch_pad, phases, nsub, st)));
+      case Epi::LeakyMask: DISPATCH_P(prec, (launch_igemm_fused_p<P, Epi::LeakyMask>(p, nch_pad, phases, nsub, st)));
+      case Epi::Plain: break;
+    }
   }
   DISPATCH_P(prec, launch_igemm_p<P>(p, nch_pad, phases, nsub, st, slots));
 }
@@ -327,10 +279,23 @@ static int launch_img_up(const void* a, const void* w, void* out, int epi_tanh, 
   return JCK_OK;
 }
 
-static int conv_down_impl(int prec, const void* big, const void* w, void* small_out, float* stats, int* stats_slots,
-                          int N, int Hb, int Wb, int Cb, int Cs, void* stream, int fwd_group_images = 0,
-                          const void* mask_act = nullptr, const float* mask_scale = nullptr, const float* aff_scale = nullptr,
-                          const float* aff_shift = nullptr, float aff_slope = 0.f) {
+// The fused epilogue of an _impl call (enum Epi, igemm.hpp), filled in by name; a default-constructed one is the plain epilogue.
+struct IgemmEpiArgs {
+  Epi kind = Epi::Plain;
+  const float* scale = nullptr;    // every fused kind
+  const float* shift = nullptr;    // the affine kinds
+  const void* act = nullptr;       // the mask kinds: the stored activation, in the output's layout and type
+  float slope = 0.f;               // the leaky kinds
+};
+// ... and where IgemmParams keeps it: the leaky mask's slope travels in aff_slope
+static void set_epilogue(IgemmParams& p, const IgemmEpiArgs& e) {
+  if (epi_affine(e.kind)) { p.aff_scale = e.scale; p.aff_shift = e.shift; }
+  if (epi_mask(e.kind)) { p.mask_scale = e.scale; p.mask_act = e.act; }
+  if (epi_leaky(e.kind)) p.aff_slope = e.slope;
+}
+
+static int conv_down_impl(int prec, const void* big, const void* w, void* small_out, int N, int Hb, int Wb, int Cb, int Cs, void* stream,
+                          const IgemmEpiArgs& e = {}, float* stats = nullptr, int* stats_slots = nullptr, int fwd_group_images = 0) {
   const int cbp = jck_pad_chan(Cb);
   if (!is_pow2(cbp) || !is_pow2(Hb) || !is_pow2(Wb) || Hb < 2 || Wb < 2 || Cs % 4 != 0)
     JCK_FAIL(JCK_E_ARG, "conv_down: shapes must be powers of two (Hb,Wb,Cb) and Cs % 4 == 0");
@@ -346,12 +311,11 @@ static int conv_down_impl(int prec, const void* big, const void* w, void* small_
   if (stats && !is_pow2(Cs)) JCK_FAIL(JCK_E_ARG, "conv_down: BN statistics need a power-of-two channel count");
   p.flops = 2.0 * p.M * Cs * 16.0 * Cb;
   if (stats && fwd_group_images > 0) { p.bn_group_rows = fwd_group_images * OH * OW; p.stat_accum = 1; }
-  p.mask_act = mask_act; p.mask_scale = mask_scale;
-  p.aff_scale = aff_scale; p.aff_shift = aff_shift; p.aff_slope = aff_slope;
-  if (aff_scale) return launch_igemm(prec, p, jck_pad_rows(Cs), 1, cbp == 4 ? 2 : 1, (hipStream_t)stream, nullptr, true);
-  if (!mask_act && prec == JCK_PREC_BF16 && cbp == 4 && Cs == 64 && OW % 16 == 0 && is_pow2(OH))
+  set_epilogue(p, e);
+  if (e.kind == Epi::Plain && prec == JCK_PREC_BF16 && cbp == 4 && Cs == 64 && OW % 16 == 0 && is_pow2(OH))
     return launch_img_down(big, w, small_out, stats, stats_slots, N, Hb, Wb, p.flops, (hipStream_t)stream);
-  return launch_igemm(prec, p, jck_pad_rows(Cs), 1, cbp == 4 ? 2 : (mask_act && cbp < 64 ? 0 : 1), (hipStream_t)stream, stats_slots);
+  const int nsub = cbp == 4 ? 2 : (e.kind == Epi::ReluMask && cbp < 64 ? 0 : 1);
+  return launch_igemm(prec, p, jck_pad_rows(Cs), 1, nsub, (hipStream_t)stream, stats_slots, e.kind);
 }
 // Input gradient of a ConvTranspose2d whose INPUT is a folded eval-mode stage a = relu(scale[c] * y + shift[c]) (latent projection):
 // jck_conv_down with v = a_small[m, c] > 0 ? scale[c] * acc : +0 applied to the fp32 accumulators before the one rounding of the store.
@@ -360,7 +324,9 @@ extern "C" int jck_conv_down_mask(int prec, const void* big, const void* w, cons
                                   int N, int Hb, int Wb, int Cb, int Cs, void* stream) {
   if (!a_small || !scale) JCK_FAIL(JCK_E_ARG, "conv_down_mask: the activation and the scale are required");
   if (!is_pow2(Cs)) JCK_FAIL(JCK_E_ARG, "conv_down_mask: Cs must be a power of two");
-  return conv_down_impl(prec, big, w, small_out, nullptr, nullptr, N, Hb, Wb, Cb, Cs, stream, 0, a_small, scale);
+  IgemmEpiArgs e;
+  e.kind = Epi::ReluMask; e.act = a_small; e.scale = scale;
+  return conv_down_impl(prec, big, w, small_out, N, Hb, Wb, Cb, Cs, stream, e);
 }
 // D's stage at inference: jck_conv_down with an eval-mode BatchNorm (folded by jck_bn_eval_aux) and the LeakyReLU applied to the fp32
 // accumulators, t = fmaf(scale[c], acc, shift[c]), out = t > 0 ? t : t * slope, before the one rounding of the store.  Never the persistent
@@ -375,11 +341,13 @@ extern "C" int jck_conv_down_affine(int prec, const void* big, const void* w, co
   } else if (Cb < 64 || !is_pow2(Cb)) {
     JCK_FAIL(JCK_E_ARG, "conv_down_affine: Cb must be 3, 4 or a power of two >= 64");
   }
-  return conv_down_impl(prec, big, w, small_out, nullptr, nullptr, N, Hb, Wb, Cb, Cs, stream, 0, nullptr, nullptr, scale, shift, slope);
+  IgemmEpiArgs e;
+  e.kind = Epi::LeakyAffine; e.scale = scale; e.shift = shift; e.slope = slope;
+  return conv_down_impl(prec, big, w, small_out, N, Hb, Wb, Cb, Cs, stream, e);
 }
 extern "C" int jck_conv_down(int prec, const void* big, const void* w, void* small_out, float* stats, int* stats_slots,
                              int N, int Hb, int Wb, int Cb, int Cs, void* stream) {
-  return conv_down_impl(prec, big, w, small_out, stats, stats_slots, N, Hb, Wb, Cb, Cs, stream);
+  return conv_down_impl(prec, big, w, small_out, N, Hb, Wb, Cb, Cs, stream, {}, stats, stats_slots);
 }
 // Forward statistics per BatchNorm group of `group_images` images (N % group_images == 0): *stats_slots rows, the first
 // *stats_slots / (N / group_images) of them belong to group 0, and so on - the layout jck_bn_finalize_grouped reads.  Large
@@ -387,15 +355,13 @@ extern "C" int jck_conv_down(int prec, const void* big, const void* w, void* sma
 extern "C" int jck_conv_down_grouped(int prec, const void* big, const void* w, void* small_out, float* stats, int* stats_slots,
                                      int N, int Hb, int Wb, int Cb, int Cs, int group_images, void* stream) {
   if (group_images < 1 || N % group_images) JCK_FAIL(JCK_E_ARG, "conv_down_grouped: N must be a multiple of group_images >= 1");
-  return conv_down_impl(prec, big, w, small_out, stats, stats_slots, N, Hb, Wb, Cb, Cs, stream, group_images);
+  return conv_down_impl(prec, big, w, small_out, N, Hb, Wb, Cb, Cs, stream, {}, stats, stats_slots, group_images);
 }
-static int conv_up_impl(int prec, const void* small_in, const void* w, void* big_out, float* stats, int* stats_slots,
-                        int epi_tanh, int N, int Hs, int Ws, int Cs, int Cb, void* stream, int fwd_group_images = 0,
-                        const float* aff_scale = nullptr, const float* aff_shift = nullptr, const void* mask_act = nullptr,
-                        const float* mask_scale = nullptr, float mask_slope = 0.f) {
+static int conv_up_impl(int prec, const void* small_in, const void* w, void* big_out, int epi_tanh, int N, int Hs, int Ws, int Cs, int Cb,
+                        void* stream, const IgemmEpiArgs& e = {}, float* stats = nullptr, int* stats_slots = nullptr, int fwd_group_images = 0) {
   const int cbp = jck_pad_chan(Cb);
   // (<= 4 output channels run as rows-are-phases tiles or on the image-side kernel below, neither of which has the affine)
-  if (aff_scale && (Cb < 8 || !is_pow2(Cb))) JCK_FAIL(JCK_E_ARG, "conv_up_affine: Cb must be a power of two >= 8");
+  if (epi_affine(e.kind) && (Cb < 8 || !is_pow2(Cb))) JCK_FAIL(JCK_E_ARG, "conv_up_affine: Cb must be a power of two >= 8");
   if (!is_pow2(Cs) || Cs < 16 || !is_pow2(Hs) || !is_pow2(Ws) || cbp % 4 != 0)
     JCK_FAIL(JCK_E_ARG, "conv_up: shapes must be powers of two (Hs,Ws,Cs>=16)");
   if ((long long)N * Hs * Ws * 4 * cbp >= (1ll << 31)) JCK_FAIL(JCK_E_ARG, "conv_up: tensor exceeds 2^31 elements");
@@ -434,10 +400,8 @@ static int conv_up_impl(int prec, const void* small_in, const void* w, void* big
   if (p.K % 64 != 0) JCK_FAIL(JCK_E_ARG, "conv_up: 4*Cs must be a multiple of 64");
   p.flops = 2.0 * p.M * 4.0 * Cb * 4.0 * Cs;
   if (stats && fwd_group_images > 0) { p.bn_group_rows = fwd_group_images * Hs * Ws; p.stat_accum = 1; }
-  p.aff_scale = aff_scale; p.aff_shift = aff_shift;
-  p.mask_act = mask_act; p.mask_scale = mask_scale;
-  if (mask_act) { p.aff_slope = mask_slope; return launch_igemm(prec, p, rows, 4, 1, (hipStream_t)stream, nullptr, true); }
-  return launch_igemm(prec, p, rows, 4, aff_scale && Cs < 64 ? 0 : 1, (hipStream_t)stream, stats_slots);
+  set_epilogue(p, e);
+  return launch_igemm(prec, p, rows, 4, e.kind == Epi::ReluAffine && Cs < 64 ? 0 : 1, (hipStream_t)stream, stats_slots, e.kind);
 }
 // D.conv1's input gradient with the tanh + instance-noise-mix backward of G's output in its epilogue (thin.hpp: ImgUpParams::mul_t):
 // out = scale * bf16(convT(small_in)) * (1 - tanh_y^2), bit for bit jck_conv_up followed by tanh_bwd_ev.  *fused = false (and
@@ -451,7 +415,7 @@ int conv_up_tanh_bwd_ev(int prec, const void* small_in, const void* w, const voi
 }
 extern "C" int jck_conv_up(int prec, const void* small_in, const void* w, void* big_out, float* stats, int* stats_slots,
                            int epi_tanh, int N, int Hs, int Ws, int Cs, int Cb, void* stream) {
-  return conv_up_impl(prec, small_in, w, big_out, stats, stats_slots, epi_tanh, N, Hs, Ws, Cs, Cb, stream);
+  return conv_up_impl(prec, small_in, w, big_out, epi_tanh, N, Hs, Ws, Cs, Cb, stream, {}, stats, stats_slots);
 }
 // Input gradient of a Conv2d(k4, s2, p1) whose INPUT is a folded eval-mode stage a = leaky(scale[c] * y + shift[c]) (the critic's latent
 // gradient): jck_conv_up with t = scale[c] * acc, v = a_big[m, c] > 0 ? t : t * slope applied to the fp32 accumulators before the one
@@ -463,15 +427,17 @@ extern "C" int jck_conv_up_mask(int prec, const void* small_in, const void* w, c
   if (N < 1) JCK_FAIL(JCK_E_ARG, "conv_up_mask: N must be >= 1");
   if (!is_pow2(Cs) || Cs < 64 || !is_pow2(Cb) || Cb < 64) JCK_FAIL(JCK_E_ARG, "conv_up_mask: Cs and Cb must be powers of two >= 64");
   if ((uintptr_t)scale % 16 || (uintptr_t)a_big % 16) JCK_FAIL(JCK_E_ARG, "conv_up_mask: the scale and the activation must be 16-byte aligned");
-  return conv_up_impl(prec, small_in, w, big_out, nullptr, nullptr, 0, N, Hs, Ws, Cs, Cb, stream, 0, nullptr, nullptr, a_big, scale, slope);
+  IgemmEpiArgs e;
+  e.kind = Epi::LeakyMask; e.act = a_big; e.scale = scale; e.slope = slope;
+  return conv_up_impl(prec, small_in, w, big_out, 0, N, Hs, Ws, Cs, Cb, stream, e);
 }
 extern "C" int jck_conv_up_grouped(int prec, const void* small_in, const void* w, void* big_out, float* stats, int* stats_slots,
                                    int N, int Hs, int Ws, int Cs, int Cb, int group_images, void* stream) {
   if (group_images < 1 || N % group_images) JCK_FAIL(JCK_E_ARG, "conv_up_grouped: N must be a multiple of group_images >= 1");
-  return conv_up_impl(prec, small_in, w, big_out, stats, stats_slots, 0, N, Hs, Ws, Cs, Cb, stream, group_images);
+  return conv_up_impl(prec, small_in, w, big_out, 0, N, Hs, Ws, Cs, Cb, stream, {}, stats, stats_slots, group_images);
 }
-static int g1_fwd_impl(int prec, const void* z, const void* w, void* out, float* stats, int* stats_slots, int B,
-                       int CiPad, int Co, void* stream, const float* aff_scale = nullptr, const float* aff_shift = nullptr) {
+static int g1_fwd_impl(int prec, const void* z, const void* w, void* out, int B, int CiPad, int Co, void* stream,
+                       const IgemmEpiArgs& e = {}, float* stats = nullptr, int* stats_slots = nullptr) {
   if (!is_pow2(CiPad) || CiPad < 64 || !is_pow2(Co) || (16 * Co) % 128 != 0)
     JCK_FAIL(JCK_E_ARG, "g1_fwd: CiPad must be a power of two >= 64, Co a power of two");
   IgemmParams p = {};
@@ -481,26 +447,30 @@ static int g1_fwd_impl(int prec, const void* z, const void* w, void* out, float*
   p.dy[0][0] = 0; p.dx[0][0] = 0;
   p.osN = (long long)16 * Co; p.osY = 0; p.osX = 0; p.obase[0] = 0;
   p.cstat = Co; p.ytiles_per_cset = 1; p.epi = 0; p.w_phase_stride = 0;
-  if (Co < 128 && !aff_scale) JCK_FAIL(JCK_E_ARG, "g1_fwd: Co must be >= 128");      // (statistics: a channel set must fill a tile)
+  if (Co < 128 && e.kind == Epi::Plain) JCK_FAIL(JCK_E_ARG, "g1_fwd: Co must be >= 128");      // (statistics: a channel set must fill a tile)
   p.flops = 2.0 * B * 16.0 * Co * CiPad;
-  p.aff_scale = aff_scale; p.aff_shift = aff_shift;
-  return launch_igemm(prec, p, 16 * Co, 1, 1, (hipStream_t)stream, stats_slots);
+  set_epilogue(p, e);
+  return launch_igemm(prec, p, 16 * Co, 1, 1, (hipStream_t)stream, stats_slots, e.kind);
 }
 extern "C" int jck_g1_fwd(int prec, const void* z, const void* w, void* out, float* stats, int* stats_slots, int B,
                           int CiPad, int Co, void* stream) {
-  return g1_fwd_impl(prec, z, w, out, stats, stats_slots, B, CiPad, Co, stream);
+  return g1_fwd_impl(prec, z, w, out, B, CiPad, Co, stream, {}, stats, stats_slots);
 }
 // inference: the product with relu(scale[c] * y + shift[c]) - an eval-mode BatchNorm folded by jck_bn_eval_aux - in its epilogue
 extern "C" int jck_conv_up_affine(int prec, const void* small_in, const void* w, const float* scale, const float* shift, void* big_out,
                                   int N, int Hs, int Ws, int Cs, int Cb, void* stream) {
   if (!scale || !shift) JCK_FAIL(JCK_E_ARG, "conv_up_affine: scale and shift are required");
-  return conv_up_impl(prec, small_in, w, big_out, nullptr, nullptr, 0, N, Hs, Ws, Cs, Cb, stream, 0, scale, shift);
+  IgemmEpiArgs e;
+  e.kind = Epi::ReluAffine; e.scale = scale; e.shift = shift;
+  return conv_up_impl(prec, small_in, w, big_out, 0, N, Hs, Ws, Cs, Cb, stream, e);
 }
 extern "C" int jck_g1_fwd_affine(int prec, const void* z, const void* w, const float* scale, const float* shift, void* out, int B,
                                  int CiPad, int Co, void* stream) {
   if (!scale || !shift) JCK_FAIL(JCK_E_ARG, "g1_fwd_affine: scale and shift are required");
   if (Co < 4) JCK_FAIL(JCK_E_ARG, "g1_fwd_affine: Co must be >= 4");
-  return g1_fwd_impl(prec, z, w, out, nullptr, nullptr, B, CiPad, Co, stream, scale, shift);
+  IgemmEpiArgs e;
+  e.kind = Epi::ReluAffine; e.scale = scale; e.shift = shift;
+  return g1_fwd_impl(prec, z, w, out, B, CiPad, Co, stream, e);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -86,7 +86,7 @@ enum KernelId : int {
   K_COUNT
 };
 template <class P> constexpr int kid_prec() { return P::SPLIT ? 2 : P::IS_F32 ? 1 : 0; }
-// register-staged gather-GEMM (AFFINE instantiations report the id of their tile: it says which kernel form and tile ran, not which
+// register-staged gather-GEMM (the fused-epilogue instantiations, enum Epi, report the id of their tile: it says which kernel form and tile ran, not which
 // of the epilogue's options - statistics, bias, tanh, the inference affine - it applied)
 template <class P, int BCH, int BPIX, int NSUB> constexpr KernelId kid_igemm() {
   static_assert(P::IS_F32 || !(BCH == 64 && NSUB == 1), "bf16 has no register-staged 64 x 128 tile (and no name for one)");

@@ -59,7 +59,7 @@ def _nhwc(x, prec):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# jck_conv_up_mask, exact.  Tile branches of launch_igemm_mask_leaky_p (rows = Cb, M = N * Hs^2 pixel rows, 4 phases):
+# jck_conv_up_mask, exact.  Tile branches of launch_igemm_fused_p<P, Epi::LeakyMask> (rows = Cb, M = N * Hs^2 pixel rows, 4 phases):
 #   Cb = 64                                              -> 64 x 128      (1, 4, 128, 64): 16 rows, far below one tile
 #   Cb % 128 == 0, few workgroups                        -> 128 x 64      (3, 4, 128, 128): M = 48, ragged
 #   ceil(M / 128) * Cb / 128 * 4 >= 256 (f32) / 512 (bf16) -> 128 x 128   (31, 8, 128, 1024): M = 1984 = 15.5 tiles, 512 workgroups

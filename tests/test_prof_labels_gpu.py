@@ -65,7 +65,7 @@ CASES += [
     ("wgrad", (9, 16, 32, 64), {}, 0, "wgrad<bf16,128,64>", "wgrad<bf16,128,64>"),
     ("wgrad", (3, 64, 3, 64), {}, 0, "wgrad<bf16,64,64,img>", "wgrad<bf16,64,64,img>"),
     ("linw", (40, 64, 190, 192, 64, 0, 0), {}, 0, "wgrad<bf16,64,64>", "wgrad<bf16,64,64>"),
-    # inference (the AFFINE instantiations): the name and label of their tile; Cs = 32 is the gather form of the 16 x 256 tile alone
+    # inference (the Epi::ReluAffine instantiations): the name and label of their tile; Cs = 32 is the gather form of the 16 x 256 tile alone
     ("upa", (1, 4, 64, 32), {}, 0, "igemm_dma<64,128,2>", "igemm<bf16,64,128>"),
     ("upa", (1, 4, 64, 32), {}, 1, "igemm<f32,64,128>", "igemm<f32,64,128>"),
     ("upa", (2, 8, 32, 16), {}, 0, "igemm<bf16,16,256>", "igemm<bf16,16,256>"),

@@ -3,7 +3,8 @@ DcganEngine.latent_grad / .project and Sampler.project.
 
 Per op, exact (the integer-data pattern of tests/test_exact_gpu.py and tests/test_sample_eval_gpu.py): gradients 0..15 and weights
 in {-1, 0, 1} - every partial sum is an integer below 2^24, exact in fp32 in any order and exact as bf16 operands - and
-scale[c] = 2^(c - Cs/2), so scale * sum is exact and the stored value is its ONE rounding to the element type, which fp64 -> fp32
+scale[c] = 2^(c - Cs/2) (Cs > 128: the exponents -64 .. 63 repeat every 128 channels, so that no product leaves the normal range of
+fp32), so scale * sum is exact and the stored value is its ONE rounding to the element type, which fp64 -> fp32
 -> bf16 reproduces (the fp32 step is exact: the sums have at most 14 significant bits).  Masked elements must be +0 bit for bit.
 
 Per op, real valued: fp64 references from the same (rounded) inputs, bounds gpu_util.TOL relative to the reference (3e-6 f32,
@@ -50,16 +51,28 @@ def _bits(t):
 # ---------------------------------------------------------------------------------------------------------------------
 # jck_conv_down_mask, exact
 # ---------------------------------------------------------------------------------------------------------------------
-MASK_SHAPES = [(1, 8, 32, 64), (3, 8, 64, 128), (2, 16, 4, 64)]                       # (N, Hb, Cb, Cs)
+# (N, Hb, Cb, Cs).  (1, 8, 64, 64): the 64-row tile at >= 64 gathered channels.  BIG / BIG1 - 256 / 257 images of 16 x 16 x 64 into 512
+# channels - reach the tiles the dispatch takes only at >= 250 / 512 / 256 workgroups: 128x256 wave-specialised (bf16, M % 256 == 0),
+# 128x128 LDS-DMA (bf16, 257 images: M % 256 != 0), 128x128 register-staged (f32, bf16x3); None: not run
+BIG, BIG1 = (256, 16, 64, 512), (257, 16, 64, 512)
 MASK_KERNEL = {(1, 8, 32, 64): ("", "igemm<f32,64,128>", "igemm<bf16x3,64,128>"),    # (bf16's register-staged 64 x 128 tile has no name)
                (3, 8, 64, 128): ("igemm_dma<128,64,3,ws>", "igemm<f32,128,64>", "igemm<bf16x3,128,64>"),
-               (2, 16, 4, 64): ("igemm<bf16,64,128,img>", "igemm<f32,64,128,img>", "igemm<bf16x3,64,128,img>")}
+               (2, 16, 4, 64): ("igemm<bf16,64,128,img>", "igemm<f32,64,128,img>", "igemm<bf16x3,64,128,img>"),
+               (1, 8, 64, 64): ("igemm_dma<64,128,2>", "igemm<f32,64,128>", "igemm<bf16x3,64,128>"),
+               BIG: ("igemm_dma<128,256,3,ws,8>", "igemm<f32,128,128>", "igemm<bf16x3,128,128>"),
+               BIG1: ("igemm_dma<128,128,2>", None, None)}
+MASK_EXACT = [pytest.param(s, p, id="x".join(map(str, s)) + "-" + PREC_NAME[p]) for s in MASK_KERNEL for p in (0, 1, 2)
+              if MASK_KERNEL[s][p] is not None]
 _mask_cache = {}
 
 
 def _mask_data(shape):
     if shape not in _mask_cache:
         n, hb, cb, cs = shape
+        if shape == BIG:                        # the first 256 images of the 257-image case: one CPU reference for both
+            g, w, a, scale, ref = _mask_data(BIG1)
+            _mask_cache[shape] = (g[:256], w, a[:256], scale, ref[:256])
+            return _mask_cache[shape]
         g = torch.randint(0, 16, (n, cb, hb, hb), generator=_gen(31)).float()
         u = torch.rand((cs, cb, 4, 4), generator=_gen(32))
         w = (u < 0.6).float() - (u > 0.8).float()
@@ -73,15 +86,15 @@ def _mask_data(shape):
         flat[idx[:k]] = 0.0                                          # exact zeros: masked (torch.relu's convention at 0)
         flat[idx[k:2 * k]] = -0.0
         flat[idx[2 * k:3 * k]] = float("nan")                       # NaN activations mask as well
-        scale = torch.pow(2.0, (torch.arange(cs) - cs // 2).double())
+        # exponents -64 .. 63 at the most: |scale * sum| stays between 2^-64 and 2^77, a normal number in fp32 and bf16
+        scale = torch.pow(2.0, (torch.arange(cs) % 128 - min(cs, 128) // 2).double())
         ref = torch.where(a.double() > 0, y * scale.view(1, -1, 1, 1), torch.zeros_like(y))
         assert float((a > 0).double().mean()) > 0.2 and float((a < 0).double().mean()) > 0.2
         _mask_cache[shape] = (g, w, a, scale.float(), ref)
     return _mask_cache[shape]
 
 
-@pytest.mark.parametrize("prec", [0, 1, 2], ids=PREC_NAME.get)
-@pytest.mark.parametrize("shape", MASK_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape,prec", MASK_EXACT)
 def test_conv_down_mask_exact(G, shape, prec):
     n, hb, cb, cs = shape
     g, w, a, scale, ref = _mask_data(shape)

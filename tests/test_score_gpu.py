@@ -78,6 +78,7 @@ BIG, BIG1 = (256, 16, 64, 512), (257, 16, 64, 512)
 IMG = ("igemm<bf16,64,128,img>", "igemm<f32,64,128,img>", "igemm<bf16x3,64,128,img>")
 SMALL = ("igemm_dma<128,64,3,ws>", "igemm<f32,128,64>", "igemm<bf16x3,128,64>")
 DOWN_KERNEL = {(1, 8, 4, 64): IMG, (3, 16, 3, 64): IMG, (1, 8, 64, 128): SMALL, (3, 8, 128, 256): SMALL, (2, 8, 256, 512): SMALL,
+               (1, 8, 64, 64): ("igemm_dma<64,128,2>", "igemm<f32,64,128>", "igemm<bf16x3,64,128>"),       # the 64-row tile at >= 64 gathered channels
                BIG: ("igemm_dma<128,256,3,ws,8>", "igemm<f32,128,128>", "igemm<bf16x3,128,128>"),
                BIG1: ("igemm_dma<128,128,2>", None, None)}
 DOWN_EXACT = [pytest.param(s, p, id="x".join(map(str, s)) + "-" + PREC_NAME[p]) for s in DOWN_KERNEL for p in (0, 1, 2) if DOWN_KERNEL[s][p]]
@@ -184,7 +185,7 @@ def test_conv_down_affine_refuses_what_it_was_not_built_for(G):
 
 @pytest.mark.parametrize("prec", [0, 1, 2], ids=PREC_NAME.get)
 def test_relu_affine_is_untouched(G, prec):
-    """the generator's AFFINE instantiations keep t < 0 ? 0 : t: jck_conv_up_affine still equals the exact reference"""
+    """the generator's Epi::ReluAffine instantiations keep t < 0 ? 0 : t: jck_conv_up_affine still equals the exact reference"""
     shape = (1, 4, 64, 32)
     n, hs, cs, cb = shape
     x, w, y = _up_exact_data(shape)
