@@ -709,6 +709,28 @@ size_t jck_knn_index_ws_bytes(int M, int N);
 int jck_knn_index_f32(const float* q, int M, const float* ref, int N, int D, int k, long long q_base, long long ref_base,
                       int exclude_self, int merge, long long* idx, float* d2, void* ws, void* stream);
 
+/* Per-cluster sums and means of feature rows (csrc/cluster.hip): the update half of a Lloyd iteration of k-means; the assignment
+ * half is jck_knn_index_f32 with k = 1, whose idx[M][1] is `label` as it stands (int64).
+ *   sum[c][j]    = the sum over the rows i of x[N][D] with label[i] == c of x[i][j]; count[c] = their number.  Both are always
+ *                  written; an empty cluster gets zeros.  Rows with label[i] < 0 or >= K are skipped and counted nowhere
+ *                  (jck_knn_index_f32 gives -1 to a non-finite row).
+ *   centre[c][j] = __fdiv_rn(sum[c][j], (float)count[c]) for every c with count[c] > 0 (a correctly rounded division); rows of
+ *                  empty clusters are not touched.  NULL: no centres.
+ * Deterministic, and more: no floating-point atomics.  The row indices are grouped by label with a stable counting sort in ws,
+ * every cluster's list is cut from its own start into pieces of R = jck_segment_chunk_rows() rows, a piece is summed row after row
+ * from zero, and a cluster's pieces are added in ascending order: sum[c] = ((p_0 + p_1) + p_2) + ..., p_j = (((0 + r_jR) + r_jR+1)
+ * + ...).  The bits of sum[c] therefore depend on the sequence of rows labelled c, in ascending row index, and on nothing else -
+ * not on N, K, the other rows, the launch grid or the scheduling - and |sum - exact| <= gamma_(n_c - 1) sum |x_ij|.
+ * Every element of x is read once.  16-byte loads when D % 4 == 0 and x, sum, centre and ws lie on 16-byte boundaries, scalar
+ * loads otherwise, with the same results.  Limits: 1 <= K <= 1024, 1 <= N <= 2^30, 1 <= D <= 65535 * 256; these, or a NULL x, label,
+ * sum, count or ws: JCK_E_ARG from the host, nothing launched.
+ * jck_segment_ws_bytes: bytes of ws (host only; 0 for sizes the entry point refuses; grows with N).  jck_segment_chunk_rows: R
+ * (host only). */
+size_t jck_segment_ws_bytes(int N, int D, int K);
+int jck_segment_chunk_rows(void);
+int jck_segment_mean_f32(const float* x, int N, int D, const long long* label, int K, float* sum, int* count, float* centre, void* ws,
+                         void* stream);
+
 /* Per-step optimiser scalars into device memory (so that a captured graph of the step has no per-step kernel argument), and
  * hipGraph capture of a sequence of jck_engine_phase calls: begin -> phases on `stream` (not the default stream) -> end
  * returns an executable graph; launch replays it.  The jck_step_inputs pointers are baked: keep the buffers in place,

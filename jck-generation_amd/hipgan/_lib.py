@@ -164,6 +164,9 @@ PROTOS = {
     "jck_manifold_hit_u8": (i32, [vp, i32, vp, vp, i32, i32, vp, vp]),
     "jck_knn_index_ws_bytes": (sz, [i32, i32]),
     "jck_knn_index_f32": (i32, [vp, i32, vp, i32, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
+    "jck_segment_ws_bytes": (sz, [i32, i32, i32]),
+    "jck_segment_chunk_rows": (i32, []),
+    "jck_segment_mean_f32": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
     "jck_engine_set_step": (i32, [vp, i32, f32, vp]),
     "jck_engine_bind_ema": (i32, [vp, vp]),
     "jck_engine_set_ema": (i32, [vp, f64, i32]),
@@ -245,7 +248,7 @@ class _Lib:
                     if not a.is_contiguous():
                         raise JckError(f"{name}: non-contiguous tensor argument")
             r = fn(*[_arg(a) for a in args])
-            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_comm_world", "jck_engine_graph_nodes") \
+            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_comm_world", "jck_engine_graph_nodes", "jck_segment_chunk_rows") \
                     and r != 0:
                 raise JckError(f"{name} failed ({r}): {dll.jck_last_error().decode()}")
             return r

@@ -8,6 +8,8 @@
     z2, before, after = s.refine(z, steps=10)                  # latents moved along the discriminator's gradient
     f = s.features(u8)                                         # D's pooled conv activations, fp32 [n,15360] (hipgan.probe)
     r = s.knn_probe(train_u8, train_labels, test_u8, test_labels)    # what D learned about the classes: r["accuracy"]
+    c = s.cluster(train_u8, 100)                               # k-means of the training set on D's features: c["labels"], c["centres"]
+    m = s.modes(train_u8, n=10000, k=100)                      # mode coverage (hipgan.cluster): m["covered"], m["kl"], m["missing"]
 
 Sampling runs with bn="running" by default (DcganEngine.sample): BatchNorm on the running statistics, every image a function of
 its own z, any n.  The running statistics of an AVERAGED generator were never fitted to its weights - they are the live ones at
@@ -489,6 +491,62 @@ class Sampler:
         from .probe import knn_probe
         self._needs_d("knn_probe")
         return knn_probe(self.engine, train_u8, train_labels, test_u8, test_labels, **kw)
+
+    def _cluster_rows(self, images_u8, space, grid, pool, what):
+        """fp32 [n,D] on the device, the rows a clustering works on: space="d": the discriminator's block-normalised features
+        (hipgan.probe.extract); space="pixel": u8 / 127.5 - 1 flattened, 32 x 32 data upscaled as `neighbours` does"""
+        if space not in ("pixel", "d"):
+            raise JckError(f"{what}: space must be 'pixel' or 'd', got {space!r}")
+        if space == "d":
+            from .probe import extract
+            self._needs_d(f"{what}(space='d')")
+            return extract(self.engine, images_u8, grid, pool)
+        from .neighbours import _check_u8, _rows, upscale_steps
+        x = _check_u8(images_u8, "images")
+        return _rows(x, upscale_steps(x.shape[1], self.engine.size, "training"), self.engine.device)
+
+    def cluster(self, train_u8, k, space="d", seed=0, iters=50, grid=4, pool="max"):
+        """k-means (hipgan.cluster.kmeans, on the device) of the training pictures (uint8 NHWC) in the discriminator's block-normalised
+        feature space (space="d"; grid, pool as hipgan.probe.extract takes them; needs from_checkpoint(..., with_d=True)) or in pixel
+        space -> kmeans' dict of device tensors: "centres" [k,D], "labels" [N], "count" [k], "d2", "inertia", "iters", "history".
+        "labels" are the usual pseudo-labels of unlabelled pictures."""
+        from .cluster import kmeans
+        return kmeans(self._cluster_rows(train_u8, space, grid, pool, "cluster"), k, iters=iters, seed=seed)
+
+    def modes(self, train_u8, n=10000, k=100, seed=0, truncation=None, labels=None, clusters=None, min_count=1, space="d", grid=4,
+              pool="max", **cluster_kw):
+        """Mode coverage: did the generator collapse?  The training pictures are clustered (cluster(train_u8, k, space, seed, grid=, pool=,
+        **cluster_kw), unless `clusters` is a dict from cluster() in the same space), n images are drawn from latents(n, seed, truncation)
+        with bn="running" (labels: a CGAN's class ids [n] or one-hot rows), a chunk at a time, their rows are made the same way and
+        assigned to the nearest centre (metrics.nearest) -> hipgan.cluster.coverage(count, sample clusters, min_count) - "k", "k_real",
+        "covered", "expected_covered", "kl", "hist_real", "hist_fake", "missing" - plus, as host arrays, "sample_cluster" int64 [n],
+        "sample_d2" fp32 [n], "train_labels" int64 [N], "train_d2" fp32 [N], "centres" fp32 [k,D], "z" fp32 [n,100], and "inertia" and
+        "iters" of the clustering."""
+        from metrics import nearest
+        from .cluster import coverage
+        n = int(n)
+        if n < 1:
+            raise JckError(f"modes: n = {n} must be >= 1")
+        cl = clusters if clusters is not None else self.cluster(train_u8, k, space=space, seed=seed, grid=grid, pool=pool, **cluster_kw)
+        centres = torch.as_tensor(cl["centres"]).to(device=self.engine.device, dtype=torch.float32).contiguous()
+        z = latents(n, seed, truncation)
+        lab = self._labels(labels, n)
+        step = max(self.engine.batch, 1024)
+        which, dist = [], []
+        for lo in range(0, n, step):
+            u8 = self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step])
+            rows = self._cluster_rows(u8, space, grid, pool, "modes")
+            if rows.shape[1] != centres.shape[1]:
+                raise JckError(f"modes: the clusters' centres have {centres.shape[1]} columns, the samples' rows {rows.shape[1]}")
+            idx, d2 = nearest(rows, centres, 1)
+            which.append(idx[:, 0].cpu())
+            dist.append(d2[:, 0].cpu())
+        which, dist = torch.cat(which).numpy(), torch.cat(dist).numpy()
+        host = lambda v: torch.as_tensor(v).cpu().numpy()
+        out = coverage(host(cl["count"]), which, min_count)
+        out.update(sample_cluster=which, sample_d2=dist, train_labels=host(cl["labels"]).astype("int64"), train_d2=host(cl["d2"]),
+                   centres=host(centres), z=z.numpy(), inertia=float(cl["inertia"]), iters=int(cl["iters"]))
+        return out
 
     def calibrate(self, batches, seed=0):
         """`batches` train-mode sampling batches (full engine batches of fresh z, uniform random classes for a CGAN) through the

@@ -9,7 +9,8 @@ missing, construction raises MetricsUnavailable and the trainer carries on witho
 formed in fp64 on the device (jck_mean_cov_f64) when the features live there; the matrix square root stays on the host
 (scipy), as in the reference.  Beyond the reference (opt-in in the trainers): KID, intra-KID and improved precision / recall
 from pairwise kernels over the feature matrices (csrc/pairstat.hip; numpy fp64 for host arrays), and the nearest real rows of
-given rows with their indices (csrc/knnindex.hip).  Fixes the reference's `.targets` defect for DCGAN (its loader has none): targets are optional."""
+given rows with their indices (csrc/knnindex.hip), and per-cluster sums and means of rows (csrc/cluster.hip; with `nearest` the two
+halves of a k-means iteration, hipgan/cluster.py).  Fixes the reference's `.targets` defect for DCGAN (its loader has none): targets are optional."""
 import os
 import pickle
 
@@ -254,6 +255,52 @@ def nearest_chunk(q, ref, k, idx, d2, q_base=0, ref_base=0, exclude_self=False, 
         raise JckError(f"nearest: {m} x {n} rows are outside what jck_knn_index_f32 takes")
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
     lib.jck_knn_index_f32(q, m, ref, n, d, k, int(q_base), int(ref_base), int(bool(exclude_self)), int(bool(merge)), idx, d2, ws, cur_stream())
+
+
+def segment_mean(x, labels, k, centre=None):
+    """(sum fp32 [k,D], count int32 [k], centre fp32 [k,D]): per-cluster sums, sizes and means of the rows of x [N,D] under int64
+    labels [N] (nearest's idx[:, 0:1] goes in as it is) - the update half of a Lloyd iteration.  Rows labelled outside 0..k-1 are
+    skipped (nearest gives -1 to a non-finite row); an empty cluster has sum 0 and count 0 and keeps its row of `centre` (zeros
+    where none was given); a non-empty one gets fp32 sum / fp32 count, correctly rounded.  centre is not modified: a new array leaves.
+    CUDA (any argument a CUDA tensor): device tensors from jck_segment_mean_f32 (1 <= k <= 1024; no float atomics: the bits of
+    sum[c] depend only on the rows labelled c, in ascending index); else numpy, the sums in fp64 and rounded to fp32 once - the
+    same bits wherever the fp32 sums are exact."""
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError(f"segment_mean: k = {k} needs 1 <= k <= 1024")
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"segment_mean: x must be a non-empty [rows, D] matrix, got {tuple(x.shape)}")
+    n, d = x.shape
+    if labels.ndim not in (1, 2) or labels.shape[0] != n or (labels.ndim == 2 and labels.shape[1] != 1):
+        raise ValueError(f"segment_mean: labels must be [{n}] or [{n}, 1], got {tuple(labels.shape)}")
+    if centre is not None and tuple(centre.shape) != (k, d):
+        raise ValueError(f"segment_mean: centre must be [{k}, {d}], got {tuple(centre.shape)}")
+    dev = _pair_device(x, labels, centre)
+    if dev is not None:
+        from hipgan._lib import JckError, cur_stream, lib, load_library
+        x = _dev32(x, dev)
+        lab = labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels, dtype=np.int64))
+        lab = lab.detach().to(device=dev, dtype=torch.int64).contiguous()
+        total = torch.empty(k, d, dtype=torch.float32, device=dev)
+        count = torch.empty(k, dtype=torch.int32, device=dev)
+        out = torch.zeros(k, d, dtype=torch.float32, device=dev) if centre is None else _dev32(centre, dev).clone()
+        nbytes = load_library().jck_segment_ws_bytes(n, d, k)
+        if nbytes == 0:
+            raise JckError(f"segment_mean: {n} x {d} rows in {k} clusters are outside what jck_segment_mean_f32 takes")
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        lib.jck_segment_mean_f32(x, n, d, lab, k, total, count, out, ws, cur_stream())
+        return total, count, out
+    x = _np64(x)
+    lab = np.asarray(_host(labels), dtype=np.int64).reshape(-1)
+    ok = (lab >= 0) & (lab < k)
+    acc = np.zeros((k, d))
+    np.add.at(acc, lab[ok], x[ok])
+    total = acc.astype(np.float32)
+    count = np.bincount(lab[ok], minlength=k).astype(np.int32)
+    out = np.zeros((k, d), np.float32) if centre is None else np.array(_host(centre), dtype=np.float32)
+    full = count > 0
+    out[full] = total[full] / count[full].astype(np.float32)[:, None]
+    return total, count, out
 
 
 def _scalar(v):
