@@ -731,6 +731,25 @@ int jck_segment_chunk_rows(void);
 int jck_segment_mean_f32(const float* x, int N, int D, const long long* label, int K, float* sum, int* count, float* centre, void* ws,
                          void* stream);
 
+/* Structural similarity of pairs of uint8 NHWC pictures [n][S][S][3] (csrc/ssim.hip; the definition: DESIGN.md 5.16).  Pair p is
+ * (a[ia[p]], b[ib[p]]); b may equal a; the index lists are device int64 [P].  11 <= S <= 128; L levels, L >= 1, S % 2^(L-1) == 0 and
+ * S >> (L-1) >= 11 (so L <= 4).
+ *   ssim[p]     the mean over the channels of the mean SSIM map at level 0 (11-tap Gaussian window, sigma 1.5, valid region)
+ *   ms_ssim[p]  the mean over the channels of prod_{l<L-1} max(cs[c][l], 0)^w_l * max(ss[c][L-1], 0)^w_(L-1), w = the first L of
+ *               (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) over their sum; the next level is the 2 x 2 mean of both planes
+ *   sq_err[p]   sum (a - b)^2 over the 3 S^2 bytes, an exact integer
+ *   terms       [P][3][L][2] = (cs[c][l], ss[c][l]), the means of the two maps per channel and level; NULL: not written
+ * A pair with an index outside 0 .. na-1 / 0 .. nb-1 gets NaN, NaN, -1 (and NaN terms); nothing else of it is touched.
+ * One workgroup per pair: every byte of the two pictures is read once, at any byte alignment, and planes, filter passes and levels
+ * stay in LDS and registers.  No floating-point atomics and no contraction in the map formulas: a map's mean is added in an order
+ * fixed by S and the level, the bits of a pair's outputs depend on its two pictures, S and L alone (not on P, its place, the other
+ * pairs or the grid), they are equal when the two pictures are swapped, and equal pictures give exactly 1.0f, 1.0f, 0.
+ * NULL a, b, ia, ib, ssim, ms_ssim or sq_err, S or L outside the above, P < 1, P > 2^24, na or nb < 1: JCK_E_ARG from the host before
+ * any HIP call.  jck_ssim_max_levels: the largest admissible L for S, 0 when S is out of range (host only). */
+int jck_ssim_pairs_u8(const unsigned char* a, long long na, const unsigned char* b, long long nb, int S, const long long* ia,
+                      const long long* ib, int P, int L, float* ssim, float* ms_ssim, long long* sq_err, float* terms, void* stream);
+int jck_ssim_max_levels(int S);
+
 /* Per-step optimiser scalars into device memory (so that a captured graph of the step has no per-step kernel argument), and
  * hipGraph capture of a sequence of jck_engine_phase calls: begin -> phases on `stream` (not the default stream) -> end
  * returns an executable graph; launch replays it.  The jck_step_inputs pointers are baked: keep the buffers in place,

@@ -167,6 +167,8 @@ PROTOS = {
     "jck_segment_ws_bytes": (sz, [i32, i32, i32]),
     "jck_segment_chunk_rows": (i32, []),
     "jck_segment_mean_f32": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "jck_ssim_pairs_u8": (i32, [vp, i64, vp, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "jck_ssim_max_levels": (i32, [i32]),
     "jck_engine_set_step": (i32, [vp, i32, f32, vp]),
     "jck_engine_bind_ema": (i32, [vp, vp]),
     "jck_engine_set_ema": (i32, [vp, f64, i32]),
@@ -248,7 +250,7 @@ class _Lib:
                     if not a.is_contiguous():
                         raise JckError(f"{name}: non-contiguous tensor argument")
             r = fn(*[_arg(a) for a in args])
-            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_comm_world", "jck_engine_graph_nodes", "jck_segment_chunk_rows") \
+            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_comm_world", "jck_engine_graph_nodes", "jck_segment_chunk_rows", "jck_ssim_max_levels") \
                     and r != 0:
                 raise JckError(f"{name} failed ({r}): {dll.jck_last_error().decode()}")
             return r

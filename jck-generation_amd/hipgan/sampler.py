@@ -10,6 +10,7 @@
     r = s.knn_probe(train_u8, train_labels, test_u8, test_labels)    # what D learned about the classes: r["accuracy"]
     c = s.cluster(train_u8, 100)                               # k-means of the training set on D's features: c["labels"], c["centres"]
     m = s.modes(train_u8, n=10000, k=100)                      # mode coverage (hipgan.cluster): m["covered"], m["kl"], m["missing"]
+    v = s.diversity(2000, pairs=1000, train_u8=train_u8)       # mean MS-SSIM of random pairs against the training set's (hipgan.diversity)
 
 Sampling runs with bn="running" by default (DcganEngine.sample): BatchNorm on the running statistics, every image a function of
 its own z, any n.  The running statistics of an AVERAGED generator were never fitted to its weights - they are the live ones at
@@ -546,6 +547,37 @@ class Sampler:
         out = coverage(host(cl["count"]), which, min_count)
         out.update(sample_cluster=which, sample_d2=dist, train_labels=host(cl["labels"]).astype("int64"), train_d2=host(cl["d2"]),
                    centres=host(centres), z=z.numpy(), inertia=float(cl["inertia"]), iters=int(cl["iters"]))
+        return out
+
+    def diversity(self, n, pairs=1000, seed=0, labels=None, train_u8=None, train_labels=None, levels=None, truncation=None, top=16):
+        """Sample diversity (hipgan.diversity): does every sample (of a class) look the same?  n images are drawn from latents(n, seed,
+        truncation) with bn="running" (labels: a CGAN's class ids [n] or one-hot rows), a chunk at a time, and kept as uint8 on the
+        device; `pairs` random pairs (per class; draw_pairs(n, pairs, seed, class ids)) go through metrics.ssim_pairs at `levels`
+        (None: default_levels of the networks' size).  train_u8 (uint8 NHWC, 32 x 32 data upscaled as the trainers do) with
+        train_labels (class ids, for a CGAN) gets the same treatment, and the two are compared class by class ->
+          "levels", "images" (uint8 [n,S,S,3], device), "z" fp32 [n,100], "pairs" (draw_pairs' dict), "ssim", "ms_ssim", "sq_err"
+          (host arrays [P]), "summary": {"ms_ssim", "ssim": hipgan.diversity.summarise}, "dropped", "top": the indices of the `top`
+          pairs with the highest MS-SSIM (near-duplicate samples; ties to the lower pair index), and with training pictures "train":
+          the same keys for them (but "images", "z", "top") and "comparison": hipgan.diversity.compare of the two MS-SSIM summaries.
+        Without labels all pictures are one class 0."""
+        from .diversity import compare, default_levels, pair_diversity, top_pairs
+        from .probe import _to_size
+        n = int(n)
+        if n < 2:
+            raise JckError(f"diversity: n = {n} must be >= 2")
+        L = default_levels(self.engine.size) if levels is None else int(levels)
+        z = latents(n, seed, truncation)
+        lab = self._labels(labels, n)
+        step = max(self.engine.batch, 1024)
+        u8 = torch.cat([self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step]) for lo in range(0, n, step)])
+        ids = None if lab is None else lab.argmax(1).numpy()
+        out = pair_diversity(u8, pairs, seed, ids, L)
+        out.update(levels=L, images=u8, z=z.numpy(), top=top_pairs(out["ms_ssim"], top))
+        if train_u8 is not None:
+            t = _to_size(train_u8, self.engine.size, "training images").to(self.engine.device).contiguous()
+            tl = train_labels if self.conditional else None                  # an unconditional generator has one class, so has its data
+            out["train"] = pair_diversity(t, pairs, seed, None if tl is None else torch.as_tensor(tl).cpu().numpy(), L)
+            out["comparison"] = compare(out["summary"]["ms_ssim"], out["train"]["summary"]["ms_ssim"])
         return out
 
     def calibrate(self, batches, seed=0):

@@ -303,6 +303,115 @@ def segment_mean(x, labels, k, centre=None):
     return total, count, out
 
 
+# ---- structural similarity of picture pairs (csrc/ssim.hip; the definition: DESIGN.md 5.16) -----------------------------------------
+SSIM_C1, SSIM_C2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def _ssim_window():
+    j = np.arange(11, dtype=np.float64)
+    g = np.exp(-(j - 5.0) ** 2 / 4.5)
+    return g / g.sum()
+
+
+def _ssim_filter(p, g):
+    """the separable 11-tap window over the valid region of the last two axes: [..., s, s] -> [..., s - 10, s - 10]"""
+    m = p.shape[-1] - 10
+    v = sum(g[j] * p[..., j:j + m, :] for j in range(11))
+    return sum(g[j] * v[..., :, j:j + m] for j in range(11))
+
+
+def _ssim_check(a, b, ia, ib, levels):
+    from hipgan.diversity import default_levels, max_levels
+    for name, x in (("a", a), ("b", b)):
+        if x.ndim != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2] or x.shape[0] < 1 or not 11 <= x.shape[1] <= 128:
+            raise ValueError(f"ssim_pairs: {name} must be uint8 [n,S,S,3] with n >= 1 and 11 <= S <= 128, got {tuple(x.shape)}")
+        if x.dtype not in (torch.uint8, np.uint8):
+            raise ValueError(f"ssim_pairs: {name} must be uint8, got {x.dtype}")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"ssim_pairs: a is {a.shape[1]}x{a.shape[1]}, b is {b.shape[1]}x{b.shape[1]}")
+    if ia.ndim != 1 or ib.ndim != 1 or ia.shape[0] != ib.shape[0] or not 1 <= ia.shape[0] <= 1 << 24:
+        raise ValueError(f"ssim_pairs: ia and ib must be two index lists of one length 1..2^24, got {tuple(ia.shape)} and {tuple(ib.shape)}")
+    S = int(a.shape[1])
+    L = default_levels(S) if levels is None else int(levels)
+    if not 1 <= L <= max_levels(S):
+        raise ValueError(f"ssim_pairs: levels = {L} needs L >= 1, S % 2^(L-1) == 0 and S >> (L-1) >= 11 at S = {S}")
+    return S, L
+
+
+def ssim_pairs(a, b, ia, ib, levels=None, terms=False):
+    """SSIM, multi-scale SSIM and squared error of the pairs (a[ia[p]], b[ib[p]]) of uint8 NHWC pictures [n,S,S,3], 11 <= S <= 128 (b may
+    be a) -> {"ssim" [P], "ms_ssim" [P], "sq_err" int64 [P]} and, with terms, "terms" [P,3,L,2] = the means of the cs and ss maps per
+    channel and level.  levels: L >= 1 with S % 2^(L-1) == 0 and S >> (L-1) >= 11; None: hipgan.diversity.default_levels(S).  A pair
+    with an index outside its array gets NaN, NaN, -1.  CUDA (any argument a CUDA tensor): fp32 device tensors from jck_ssim_pairs_u8
+    (one workgroup per pair, no float atomics; equal bits for swapped pictures, exactly 1, 1, 0 for equal ones); else numpy fp64."""
+    as_np = lambda v: v if torch.is_tensor(v) else np.asarray(v)
+    a, b, ia, ib = as_np(a), as_np(b), as_np(ia), as_np(ib)
+    S, L = _ssim_check(a, b, ia, ib, levels)
+    P = int(ia.shape[0])
+    dev = _pair_device(a, b, ia, ib)
+    if dev is not None:
+        from hipgan._lib import cur_stream, lib
+        u8 = lambda v: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))).detach().to(dev).contiguous()
+        ix = lambda v: (v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, dtype=np.int64))).detach().to(device=dev, dtype=torch.int64).contiguous()
+        same = a is b
+        a = u8(a)
+        b = a if same else u8(b)
+        out = {"ssim": torch.empty(P, dtype=torch.float32, device=dev), "ms_ssim": torch.empty(P, dtype=torch.float32, device=dev),
+               "sq_err": torch.empty(P, dtype=torch.int64, device=dev)}
+        if terms:
+            out["terms"] = torch.empty(P, 3, L, 2, dtype=torch.float32, device=dev)
+        lib.jck_ssim_pairs_u8(a, a.shape[0], b, b.shape[0], S, ix(ia), ix(ib), P, L, out["ssim"], out["ms_ssim"], out["sq_err"],
+                              out.get("terms"), cur_stream())
+        return out
+    a, b = _host(a), _host(b)
+    ia, ib = _host(ia).astype(np.int64), _host(ib).astype(np.int64)
+    ok = (ia >= 0) & (ia < a.shape[0]) & (ib >= 0) & (ib < b.shape[0])
+    g = _ssim_window()
+    w = np.asarray(MS_SSIM_WEIGHTS[:L], dtype=np.float64)
+    w = w / w.sum()
+    t = np.full((P, 3, L, 2), np.nan)
+    sq = np.full(P, -1, dtype=np.int64)
+    rows = np.flatnonzero(ok)
+    for lo in range(0, rows.shape[0], 64):                              # 64 pairs at a time: [64,3,S,S] fp64 planes
+        r = rows[lo:lo + 64]
+        xa, xb = a[ia[r]].astype(np.int64), b[ib[r]].astype(np.int64)
+        sq[r] = ((xa - xb) ** 2).reshape(r.shape[0], -1).sum(axis=1)
+        x, y = (np.moveaxis(v, 3, 1).astype(np.float64) for v in (xa, xb))
+        for l in range(L):
+            mx, my = _ssim_filter(x, g), _ssim_filter(y, g)
+            vx, vy, vxy = _ssim_filter(x * x, g) - mx * mx, _ssim_filter(y * y, g) - my * my, _ssim_filter(x * y, g) - mx * my
+            cs = (2.0 * vxy + SSIM_C2) / (vx + vy + SSIM_C2)
+            ss = (2.0 * mx * my + SSIM_C1) / (mx * mx + my * my + SSIM_C1) * cs
+            t[r, :, l, 0], t[r, :, l, 1] = cs.mean(axis=(2, 3)), ss.mean(axis=(2, 3))
+            if l + 1 < L:
+                x, y = (0.25 * (v[..., 0::2, 0::2] + v[..., 0::2, 1::2] + v[..., 1::2, 0::2] + v[..., 1::2, 1::2]) for v in (x, y))
+    out = {"ssim": t[:, :, 0, 1].mean(axis=1), "ms_ssim": ms_ssim_from_terms(t), "sq_err": sq}
+    if terms:
+        out["terms"] = t
+    return out
+
+
+def ms_ssim_from_terms(t):
+    """[P] from terms [P,3,L,2] (fp64 on the host): mean_c prod_{l<L-1} max(cs[c][l], 0)^w_l * max(ss[c][L-1], 0)^w_(L-1), w the first L
+    of MS_SSIM_WEIGHTS over their sum"""
+    t = _np64(t)
+    L = t.shape[2]
+    w = np.asarray(MS_SSIM_WEIGHTS[:L], dtype=np.float64)
+    w = w / w.sum()
+    with np.errstate(invalid="ignore"):
+        f = np.concatenate([np.maximum(t[:, :, :L - 1, 0], 0.0), np.maximum(t[:, :, L - 1:, 1], 0.0)], axis=2) ** w
+    return np.where(np.isnan(t).any(axis=(1, 2, 3)), np.nan, f.prod(axis=2).mean(axis=1))
+
+
+def psnr(sq_err, S):
+    """10 log10(255^2 * 3 S^2 / sq_err) in dB per pair, fp64 on the host: inf at 0, NaN for the -1 of a pair that was not compared"""
+    e = _np64(sq_err)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = 10.0 * np.log10(255.0 ** 2 * 3 * int(S) ** 2 / e)
+    return np.where(e < 0, np.nan, out)
+
+
 def _scalar(v):
     v = v.detach().cpu().numpy() if torch.is_tensor(v) else v
     return float(np.asarray(v, dtype=np.float64).reshape(-1)[0])
