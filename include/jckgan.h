@@ -204,6 +204,11 @@ int jck_grid_sync_error(const void* sync_ws);
 int jck_bn_act_bwd_res(int prec, const void* g_a, const void* y, const float* aux, float slope, float* sums, void* g_y,
                        float* dgamma, float* dbeta, long long rows_per_group, int C, int groups, int grad_groups, void* sync_ws,
                        void* stream);
+/* The plan jck_bn_act_bwd_res follows for these arguments when it is given a sync_ws (host only, no launch): returns 1 and fills
+ * nch (16-byte chunks per thread and group: 1, 2, 4, 8 or 16), ng (groups resident together; groups > ng go through several
+ * passes and barrier generations) and nb (workgroups; a pass covers nb / (C / 64) * 64 rows per chunk), each pointer optional; returns
+ * 0 where that call falls back to jck_bn_act_bwd_grouped.  Follows jck_tune("bn_res", ...) / JCK_BN_RES. */
+int jck_bn_res_plan(int prec, long long rows_per_group, int C, int groups, int* nch, int* ng, int* nb);
 /* jck_conv_down / jck_conv_up with the forward statistics laid out per BatchNorm group of `group_images` images
  * (N % group_images == 0): *stats_slots rows, the first *stats_slots / (N / group_images) of them belong to group 0, and so
  * on - what jck_bn_finalize_grouped reads.  Large launches write one row per (workgroup, group) instead of one per (tile, wave). */

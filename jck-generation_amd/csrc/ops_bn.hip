@@ -203,8 +203,8 @@ extern "C" int jck_grid_sync_error(const void* sync_ws) {
 }
 // multi-group passes take the resident form above this many MB of (g_a, y): below it their second read comes out of the Infinity Cache
 constexpr int BN_RES_MIN_MB = 120;
-// nb workgroups (all co-resident), nsl channel slices, chunks per thread; 0 = does not fit
-static int bnres_plan(int prec, long long rows, int C, int groups, int* nb_out, int* nsl_out) {
+// nb workgroups (all co-resident), nsl channel slices, ng groups resident together, chunks per thread; 0 = does not fit
+static int bnres_plan(int prec, long long rows, int C, int groups, int* nb_out, int* nsl_out, int* ng_out) {
   if (!g_bn_res || prec != JCK_PREC_BF16 || !is_pow2(C) || C < 64 || groups < 1 || rows < 1) return 0;
   // Several groups in one pass (the batched D pass): the three-launch form's second read of (g_a, y) comes out of the
   // Infinity Cache while all groups fit it, and then it is as fast or faster in the step (measured, DESIGN.md section 5.3:
@@ -219,8 +219,22 @@ static int bnres_plan(int prec, long long rows, int C, int groups, int* nb_out, 
   const long long per_iter = (long long)(nb / nsl) * BNRES_ROWS;
   const long long need = (rows + per_iter - 1) / per_iter;
   if (need > 16) return 0;
+  const int nch = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
   *nb_out = nb; *nsl_out = nsl;
-  return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
+  // groups resident together (one barrier for all of them) while their chunks fit the register file
+  *ng_out = (groups >= 3 && 3 * nch <= 16) ? 3 : (groups >= 2 && 2 * nch <= 16) ? 2 : 1;
+  return nch;
+}
+// the plan of jck_bn_act_bwd_res for these arguments, given a barrier workspace: 1 and (chunks, resident groups, workgroups), or 0
+// where that call takes the three-launch form.  Host only (the CU count is asked of the runtime once).
+extern "C" int jck_bn_res_plan(int prec, long long rows_per_group, int C, int groups, int* nch, int* ng, int* nb) {
+  int b = 0, sl = 0, g = 0;
+  const int ch = bnres_plan(prec, rows_per_group, C, groups, &b, &sl, &g);
+  if (!ch) return 0;
+  if (nch) *nch = ch;
+  if (ng) *ng = g;
+  if (nb) *nb = b;
+  return 1;
 }
 extern "C" int jck_bn_act_bwd_res(int prec, const void* g_a, const void* y, const float* aux, float slope, float* sums, void* g_y,
                                   float* dgamma, float* dbeta, long long rows_per_group, int C, int groups, int grad_groups,
@@ -231,8 +245,8 @@ extern "C" int jck_bn_act_bwd_res(int prec, const void* g_a, const void* y, cons
 int bn_act_bwd_res_ev(int prec, const void* g_a, const void* y, const float* aux, float slope, float* sums, void* g_y, float* dgamma,
                       float* dbeta, long long rows_per_group, int C, int groups, int grad_groups, void* sync_ws, hipStream_t stream,
                       hipEvent_t done) {
-  int nb = 0, nsl = 0;
-  const int nch = sync_ws ? bnres_plan(prec, rows_per_group, C, groups, &nb, &nsl) : 0;
+  int nb = 0, nsl = 0, ng = 0;
+  const int nch = sync_ws ? bnres_plan(prec, rows_per_group, C, groups, &nb, &nsl, &ng) : 0;
   if (!nch) return bn_act_bwd_grouped_ev(prec, g_a, y, aux, slope, sums, g_y, dgamma, dbeta, rows_per_group, C, groups, grad_groups, stream, done);
   BnResParams p;
   p.ga = (const bf16_t*)g_a; p.y = (const bf16_t*)y; p.gy = (bf16_t*)g_y; p.aux = aux;
@@ -242,8 +256,6 @@ int bn_act_bwd_res_ev(int prec, const void* g_a, const void* y, const float* aux
   p.slope = slope; p.inv_count = 1.0f / (float)rows_per_group;
   const dim3 grid(nb), block(BNRES_THREADS);
   ProfScope prof(K_BN_BWD_RES, 0.0, stream, 3.0 * groups * rows_per_group * C * 2);
-  // groups resident together (one barrier for all of them) while their chunks fit the register file
-  const int ng = (groups >= 3 && 3 * nch <= 16) ? 3 : (groups >= 2 && 2 * nch <= 16) ? 2 : 1;
 #define BNRES_CASE(NCH_, NG_) case NCH_ * 4 + NG_: LAUNCH_EV((bn_bwd_res_kernel<NCH_, NG_>), grid, block, 0, stream, done, p); break
   switch (nch * 4 + ng) {
     BNRES_CASE(1, 1); BNRES_CASE(2, 1); BNRES_CASE(4, 1); BNRES_CASE(8, 1); BNRES_CASE(16, 1);

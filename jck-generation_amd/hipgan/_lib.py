@@ -68,6 +68,7 @@ PROTOS = {
     "jck_grid_sync_bytes": (sz, []),
     "jck_grid_sync_error": (i32, [vp]),
     "jck_bn_act_bwd_res": (i32, [i32, vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]),
+    "jck_bn_res_plan": (i32, [i32, i64, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "jck_img_prep": (i32, [i32, vp, vp, f32, f32, vp, i32, i32, vp]),
     "jck_resize_norm": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp]),
     "jck_img_prep_u8": (i32, [i32, vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
@@ -250,7 +251,7 @@ class _Lib:
                     if not a.is_contiguous():
                         raise JckError(f"{name}: non-contiguous tensor argument")
             r = fn(*[_arg(a) for a in args])
-            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_comm_world", "jck_engine_graph_nodes", "jck_segment_chunk_rows", "jck_ssim_max_levels") \
+            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_bn_res_plan", "jck_comm_world", "jck_engine_graph_nodes", "jck_segment_chunk_rows", "jck_ssim_max_levels") \
                     and r != 0:
                 raise JckError(f"{name} failed ({r}): {dll.jck_last_error().decode()}")
             return r
