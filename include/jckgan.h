@@ -755,6 +755,36 @@ int jck_ssim_pairs_u8(const unsigned char* a, long long na, const unsigned char*
                       const long long* ib, int P, int L, float* ssim, float* ms_ssim, long long* sq_err, float* terms, void* stream);
 int jck_ssim_max_levels(int S);
 
+/* Sliced Wasserstein distance on Laplacian-pyramid patches of uint8 NHWC pictures [n][S][S][3] (csrc/swd.hip; the definition:
+ * DESIGN.md 5.17).  S is 32, 64 or 128; level l has side S >> l, 1 <= L <= jck_swd_max_levels(S) (the levels with side >= 16:
+ * 2, 3, 4; 0 for another S; host only).  pos: device int32 [n][L][P][2], the (y, x) top-left corners of P 7 x 7 patches per picture
+ * and level, each in [0, (S >> l) - 7].  A descriptor is the 147 Laplacian values of a patch in the order [c][dy][dx]; every one is
+ * the fp64 value of the definition rounded once to fp32 (the pyramid is exact fixed point).
+ *   jck_swd_patch_stats_u8   sum[l][c], sumsq[l][c] (fp64 [L][3]) of the descriptor components over the n P 49 of a level and
+ *                            channel.  part: fp64 workspace [n][L][3][2], one row per picture (kept: a caller may inspect it).  fp64
+ *                            accumulation in an order fixed by n and P: two calls give the same bits.
+ *   jck_swd_project_u8       proj[(l D + d) ld + i P + p] = sum_j fmul(fsub(x_j, mean[l][c(j)]), rstd[l][c(j)]) dirs[d][j], dirs
+ *                            fp32 [D][147], mean / rstd fp32 [L][3], ld >= n P the length of a row (a chunk of pictures passes proj +
+ *                            its first column).  fp32, one fmaf per product, per channel from zero in ascending j, the three
+ *                            channels added in ascending order: |proj - exact| <= 53 2^-24 sum_j |(x_j - mean) rstd dirs[d][j]|.
+ * A picture with a corner out of range: its part[] row / its P entries of every proj row are NaN, nothing else of it is written.
+ * One workgroup per picture; descriptors stay in LDS.
+ *   jck_sort_rows_f32        out[r] = x[r] sorted ascending, rows of M >= 1 keys, by the sign-flip order of the bit patterns (total:
+ *                            -0 < +0; NaNs at the two ends by their bits).  ws: jck_sort_rows_ws_bytes(Rows, M) bytes (0 when M <=
+ *                            jck_sort_rows_tile(); may then be NULL); ws_bytes is what the caller has.  out may equal x.
+ *   jck_swd_rows             w[r] = mean_j |sa[r][j] - sb[r][j]| in fp64, an order fixed by M.
+ * NULL pointers, S, L, P, D, n, Rows, M out of range, ld < n P, a workspace that is too small: JCK_E_ARG from the host before any
+ * HIP call.  jck_sort_rows_ws_bytes returns 0 for sizes the entry point refuses too. */
+int jck_swd_max_levels(int S);
+int jck_swd_patch_stats_u8(const unsigned char* images, int n, int S, int L, const int* pos, int P, double* part, double* sum,
+                           double* sumsq, void* stream);
+int jck_swd_project_u8(const unsigned char* images, int n, int S, int L, const int* pos, int P, const float* dirs, int D,
+                       const float* mean, const float* rstd, float* proj, long long ld, void* stream);
+size_t jck_sort_rows_ws_bytes(int Rows, long long M);
+int jck_sort_rows_tile(void);
+int jck_sort_rows_f32(const float* x, int Rows, long long M, float* out, void* ws, size_t ws_bytes, void* stream);
+int jck_swd_rows(const float* sa, const float* sb, int Rows, long long M, double* w, void* stream);
+
 /* Per-step optimiser scalars into device memory (so that a captured graph of the step has no per-step kernel argument), and
  * hipGraph capture of a sequence of jck_engine_phase calls: begin -> phases on `stream` (not the default stream) -> end
  * returns an executable graph; launch replays it.  The jck_step_inputs pointers are baked: keep the buffers in place,

@@ -11,6 +11,7 @@
     c = s.cluster(train_u8, 100)                               # k-means of the training set on D's features: c["labels"], c["centres"]
     m = s.modes(train_u8, n=10000, k=100)                      # mode coverage (hipgan.cluster): m["covered"], m["kl"], m["missing"]
     v = s.diversity(2000, pairs=1000, train_u8=train_u8)       # mean MS-SSIM of random pairs against the training set's (hipgan.diversity)
+    w = s.swd(train_u8, n=8192)                                # sliced Wasserstein distance per pyramid level (hipgan.swd): w["swd"], w["mean"]
 
 Sampling runs with bn="running" by default (DcganEngine.sample): BatchNorm on the running statistics, every image a function of
 its own z, any n.  The running statistics of an AVERAGED generator were never fitted to its weights - they are the live ones at
@@ -578,6 +579,49 @@ class Sampler:
             tl = train_labels if self.conditional else None                  # an unconditional generator has one class, so has its data
             out["train"] = pair_diversity(t, pairs, seed, None if tl is None else torch.as_tensor(tl).cpu().numpy(), L)
             out["comparison"] = compare(out["summary"]["ms_ssim"], out["train"]["summary"]["ms_ssim"])
+        return out
+
+    def swd(self, train_u8, n=8192, seed=0, labels=None, train_labels=None, truncation=None, classes=None, **kw):
+        """Sliced Wasserstein distance of the samples' Laplacian-pyramid patch statistics to the training set's, level by level
+        (hipgan.swd, metrics.swd; no metric network).  n images are drawn from latents(n, seed, truncation) with bn="running" (labels:
+        a CGAN's class ids [n] or one-hot rows), a chunk at a time, and kept as uint8 on the device; of the training pictures (uint8
+        NHWC, 32 x 32 data upscaled as `neighbours` does) the first n after numpy.random.default_rng(seed).permutation are taken.  kw
+        goes to metrics.swd (levels, patches, dirs, repeats, chunk) -> its dict ("swd" x 1e3 per level, "mean", "sides", "per_repeat")
+        plus "n", "n_train", "seed" and, with classes (ids; needs labels and train_labels), "per_class": {id: the same dict for the
+        samples and the training pictures of that class, as many of each as the smaller side has, "n" among its keys}."""
+        import numpy as np
+
+        from metrics import swd as metric
+        from .probe import _to_size
+        n = int(n)
+        if n < 1:
+            raise JckError(f"swd: n = {n} must be >= 1")
+        t = _to_size(train_u8, self.engine.size, "training images")
+        if t.shape[0] < n:
+            raise JckError(f"swd: {t.shape[0]} training pictures are fewer than the n = {n} samples they are compared with")
+        order = np.random.default_rng(int(seed)).permutation(int(t.shape[0]))
+        pick = torch.from_numpy(order[:n])
+        z = latents(n, seed, truncation)
+        lab = self._labels(labels, n)
+        step = max(self.engine.batch, 1024)
+        u8 = torch.cat([self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step]) for lo in range(0, n, step)])
+        real = t[pick].to(self.engine.device).contiguous()
+        out = metric(u8, real, seed=seed, **kw)
+        out.update(n=n, n_train=int(t.shape[0]), seed=int(seed))
+        if classes is not None:
+            if lab is None or train_labels is None:
+                raise JckError("swd: per-class reports need the samples' labels and train_labels")
+            ids = lab.argmax(1)
+            tl = torch.as_tensor(train_labels).cpu().view(-1).to(torch.int64)[torch.from_numpy(order)]
+            out["per_class"] = {}
+            for c in classes:
+                mine, theirs = torch.nonzero(ids.cpu() == int(c)).view(-1), torch.from_numpy(order)[tl == int(c)]
+                k = min(int(mine.shape[0]), int(theirs.shape[0]))
+                if k < 1:
+                    raise JckError(f"swd: class {c} has {mine.shape[0]} samples and {theirs.shape[0]} training pictures")
+                r = metric(u8[mine[:k].to(u8.device)].contiguous(), t[theirs[:k]].to(self.engine.device).contiguous(), seed=seed, **kw)
+                r.update(n=k)
+                out["per_class"][int(c)] = r
         return out
 
     def calibrate(self, batches, seed=0):

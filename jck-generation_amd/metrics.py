@@ -412,6 +412,102 @@ def psnr(sq_err, S):
     return np.where(e < 0, np.nan, out)
 
 
+# ---- sliced Wasserstein distance on Laplacian-pyramid patches (csrc/swd.hip; the definition: DESIGN.md 5.17) ------------------------
+SWD_CHUNK = 4096        # pictures per launch of the device path: bounds the uint8 staging of host pictures (48 KB each at S = 128) and
+#                         the fp64 partial rows of the statistics; the [L][D][n P] projection rows are whole whatever the chunk
+
+
+def _swd_check(a, b, levels, patches, dirs, repeats):
+    from hipgan.swd import SIZES, max_levels
+    for name, x in (("a", a), ("b", b)):
+        if x.ndim != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2] or x.shape[0] < 1 or x.shape[1] not in SIZES:
+            raise ValueError(f"swd: {name} must be uint8 [n,S,S,3] with n >= 1 and S in {SIZES}, got {tuple(x.shape)}")
+        if x.dtype not in (torch.uint8, np.uint8):
+            raise ValueError(f"swd: {name} must be uint8, got {x.dtype} {tuple(x.shape)}")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"swd: the two sets must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    S = int(a.shape[1])
+    L = max_levels(S) if levels is None else int(levels)
+    if not 1 <= L <= max_levels(S):
+        raise ValueError(f"swd: levels = {L} must lie in 1..{max_levels(S)} at {tuple(a.shape)} (sides down to 16)")
+    if int(patches) < 1 or int(dirs) < 1 or int(repeats) < 1:
+        raise ValueError(f"swd: patches = {patches}, dirs = {dirs}, repeats = {repeats} must be >= 1 (pictures {tuple(a.shape)})")
+    if int(a.shape[0]) * int(patches) >= 1 << 31:
+        raise ValueError(f"swd: n * patches = {int(a.shape[0]) * int(patches)} keys a row must stay below 2^31 (pictures {tuple(a.shape)})")
+    return S, L
+
+
+def swd(a, b, levels=None, patches=128, dirs=128, repeats=4, seed=0, chunk=None):
+    """Sliced Wasserstein distance between the Laplacian-pyramid patch statistics of two sets of uint8 NHWC pictures [n,S,S,3] of one
+    shape, S in (32, 64, 128) -> {"swd" fp64 [L] (x 1e3, one number per level, finest first), "mean", "sides" [s_0 .. s_(L-1)],
+    "per_repeat" fp64 [R][L]}.  levels: None = every level with side >= 16.  Per picture and level `patches` 7 x 7 x 3 patches, their
+    corners and the `repeats` x `dirs` unit directions from hipgan.swd.draw(seed) - the same for both sets and for both paths.  CUDA (an
+    argument a CUDA tensor): jck_swd_patch_stats_u8 / jck_swd_project_u8 / jck_sort_rows_f32 / jck_swd_rows, a repeat at a time with
+    one [L][D][n P] fp32 projection buffer per set (sorted in place) and one sort workspace of that size, the pictures in chunks of
+    `chunk` (None: SWD_CHUNK) whose rows go to the chunk's offset; else numpy fp64.  Equal sets give exactly 0, swapped sets equal
+    bits, on both paths."""
+    from hipgan import swd as H
+    as_np = lambda v: v if torch.is_tensor(v) else np.asarray(v)
+    a, b = as_np(a), as_np(b)
+    S, L = _swd_check(a, b, levels, patches, dirs, repeats)
+    n, P, D, R = int(a.shape[0]), int(patches), int(dirs), int(repeats)
+    step = SWD_CHUNK if chunk is None else int(chunk)
+    if step < 1:
+        raise ValueError(f"swd: chunk = {step} must be >= 1")
+    pos, directions = H.draw(n, S, L, P, D, R, seed)
+    M = n * P
+    dev = _pair_device(a, b)
+    per_repeat = np.zeros((R, L))
+    if dev is not None:
+        from hipgan._lib import cur_stream, lib, load_library
+        same = a is b
+        piece = lambda x, lo: (x[lo:lo + step] if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x[lo:lo + step]))).detach().to(dev).contiguous()
+        pos_t = torch.from_numpy(pos).to(dev)
+        count = float(M * 49)
+        norm = []
+        for x in ((a,) if same else (a, b)):
+            part = torch.empty(min(step, n), L, 3, 2, dtype=torch.float64, device=dev)
+            tot, tot_sq = np.zeros((L, 3)), np.zeros((L, 3))
+            for lo in range(0, n, step):                                           # the chunks' sums add on the host, in chunk order
+                s1, s2 = torch.empty(L, 3, dtype=torch.float64, device=dev), torch.empty(L, 3, dtype=torch.float64, device=dev)
+                xs = piece(x, lo)
+                lib.jck_swd_patch_stats_u8(xs, xs.shape[0], S, L, pos_t[lo:lo + step], P, part, s1, s2, cur_stream())
+                tot += s1.cpu().numpy()
+                tot_sq += s2.cpu().numpy()
+            mean, rstd = H.moments_from_sums(tot, tot_sq, count)
+            norm.append((torch.from_numpy(mean.astype(np.float32)).to(dev), torch.from_numpy(rstd.astype(np.float32)).to(dev)))
+        if same:
+            norm.append(norm[0])
+        rows = L * D
+        ws_bytes = load_library().jck_sort_rows_ws_bytes(rows, M)
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+        bufs = [torch.empty(rows, M, dtype=torch.float32, device=dev) for _ in range(2)]
+        w = torch.empty(rows, dtype=torch.float64, device=dev)
+        for r in range(R):
+            d_t = torch.from_numpy(directions[r]).to(dev)
+            for x, (mean_t, rstd_t), buf in zip((a, b), norm, bufs):
+                for lo in range(0, n, step):
+                    xs = piece(x, lo)
+                    lib.jck_swd_project_u8(xs, xs.shape[0], S, L, pos_t[lo:lo + step], P, d_t, D, mean_t, rstd_t, buf.data_ptr() + 4 * lo * P, M, cur_stream())
+                lib.jck_sort_rows_f32(buf, rows, M, buf, ws, ws_bytes, cur_stream())
+            lib.jck_swd_rows(bufs[0], bufs[1], rows, M, w, cur_stream())
+            per_repeat[r] = 1e3 * w.cpu().numpy().reshape(L, D).mean(axis=1)
+    else:
+        a, b = _host(a), _host(b)
+        la, lb = H.pyramid(a, L)[1], H.pyramid(b, L)[1]
+        for l in range(L):
+            xn = []
+            for plane in (la[l], lb[l]):
+                d = H.descriptors(plane, pos[:, l])
+                mean, rstd = H.moments(d)
+                xn.append(((d - mean[None, :, None]) * rstd[None, :, None]).reshape(M, H.DESC))
+            for r in range(R):
+                dr = directions[r].astype(np.float64).T
+                sa, sb = np.sort(xn[0] @ dr, axis=0), np.sort(xn[1] @ dr, axis=0)
+                per_repeat[r, l] = 1e3 * np.abs(sa - sb).mean(axis=0).mean()
+    return H.report(per_repeat, S)
+
+
 def _scalar(v):
     v = v.detach().cpu().numpy() if torch.is_tensor(v) else v
     return float(np.asarray(v, dtype=np.float64).reshape(-1)[0])
