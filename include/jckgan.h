@@ -462,6 +462,12 @@ size_t jck_engine_workspace_bytes(const jck_engine*);
 /* arenas: params/grads/m/v are flat fp32 of jck_engine_arena_numel(net, 0); bn = running stats arena (kind 1,2);
  * nbt = int64[4] per net */
 long long jck_engine_arena_numel(int family, int net, int which /*0 params, 1 bn buffers*/);
+/* workspace: jck_engine_workspace_bytes(e) bytes of device memory, 256-byte aligned.  The workspace's contents on entry do not
+ * matter; bind clears it (all of it, synchronously, once per call - no step pays for it); between bind and destroy it belongs to
+ * the engine: the kernels rely on the zeros bind left wherever they write only part of a buffer (padding rows / columns of the
+ * packed operands, of G.conv1's operand rows and of CGAN's concat buffers, the grid-barrier words), so a caller reads it
+ * (jck_engine_tensor, jck_engine_scalars) and never writes it.  Binding a bound engine again is allowed (no step in flight): the
+ * workspace is cleared again - call jck_engine_repack for both networks afterwards -, the arenas are not touched. */
 int jck_engine_bind(jck_engine*, void* workspace, size_t ws_bytes, float* g_params, float* g_grads, float* g_m, float* g_v,
                     float* g_bn, int64_t* g_nbt, float* d_params, float* d_grads, float* d_m, float* d_v, float* d_bn,
                     int64_t* d_nbt);

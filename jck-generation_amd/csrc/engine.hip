@@ -197,14 +197,18 @@ extern "C" int jck_engine_bind(jck_engine* e, void* workspace, size_t ws_bytes, 
   if (ws_bytes < e->ws_bytes) JCK_FAIL(JCK_E_WS, "workspace too small: need " + std::to_string(e->ws_bytes));
   if (((uintptr_t)workspace) % 256) JCK_FAIL(JCK_E_ARG, "workspace must be 256-byte aligned");
   e->carve(reinterpret_cast<unsigned char*>(workspace));
-  // the repack kernel writes only real (channel, channel) pairs: the padding rows / channels of the packed operands must
-  // read as zero -> clear that region once (from the first packed operand up to the first activation buffer)
-  {
-    unsigned char* p0 = reinterpret_cast<unsigned char*>(e->d_down[0]);
-    unsigned char* p1 = reinterpret_cast<unsigned char*>(e->dset[0].y[0]);
-    HIPCHK(hipMemset(p0, 0, (size_t)(p1 - p0)));
-  }
-  HIPCHK(hipMemset(e->gsync, 0, jck_grid_sync_bytes()));
+  // Bind owns the workspace's zero contract: whatever the caller's memory held, everything the engine carves reads as zero from
+  // here on.  The kernels rely on it where they write only part of a buffer - the repack kernels write real (channel, channel)
+  // pairs and leave the padding rows / channels of the packed operands alone, the set-step launch and the label embedding leave
+  // the padding columns of g_z / cbuf / cbuf2 alone - and the grid-barrier words (gsync) start at generation 0 with no error.
+  // One clear of all of it, once per bind, in no step - finished when bind returns, so that the first launch may come on any stream.
+  HIPCHK(hipMemset(workspace, 0, e->ws_bytes));
+  HIPCHK(hipStreamSynchronize(nullptr));
+  // ... which also took the device copies of the step scalars and the packed operands of an engine that is bound again
+  e->hp_step[0] = e->hp_step[1] = 0;
+  e->hp_lr[0] = e->hp_lr[1] = -1.f;
+  e->ss = StepState();
+  e->d_packed = false;
   e->gp = g_params; e->gg = g_grads; e->gm = g_m; e->gv = g_v; e->gbn = g_bn; e->gnbt = g_nbt;
   e->dp = d_params; e->dg = d_grads; e->dm = d_m; e->dv = d_v; e->dbn = d_bn; e->dnbt = d_nbt;
   e->bound = true;
@@ -623,7 +627,7 @@ static int gp_double_backward(jck_engine* e, const DActs& P, const void* xhat, i
     if (side) (void)hipStreamWaitEvent(st, e->evGP, 0);
   } else {
     // head: gc[:, :8192] = gh W1 -> adj(gh) = [u4 | 0] W1^T, dW1 += gh^T [u4 | 0]; gh = gh' * m/(1-p); gh' = ds w2; ds = p(1-p)
-    JCK_TRY(jck_concat_rows(e->prec, e->d_v[TT.NS - 1], TT.FEAT, e->cbuf2, L1_KPAD, B, st));          // tail columns of cbuf2 stay zero
+    JCK_TRY(jck_concat_rows(e->prec, e->d_v[TT.NS - 1], TT.FEAT, e->cbuf2, L1_KPAD, B, st));          // tail columns of cbuf2: the zeros of jck_engine_bind
     JCK_TRY(fork(0));
     JCK_TRY(jck_linear_wgrad(e->prec, gh1, L1_OUT, e->cbuf2, L1_KPAD, e->wg_ws, e->wg_ws_bytes, e->gw1p, 1, B, L1_OUT, ws));
     // What the reverse sweep must wait for are the v-chain's products (they read the v_i it overwrites): the weight-gradient stream is

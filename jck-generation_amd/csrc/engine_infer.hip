@@ -18,19 +18,20 @@ extern "C" int jck_engine_sample(jck_engine* e, const float* z, const int64_t* l
 }
 
 // One of the engine's inference buffer groups (LatentBufs, ScoreBufs, CriticBufs, FeatBufs), allocated by the first call that needs it:
-// `carve` takes the group's buffers from a Carver and runs twice - without memory for the size, then on the allocation.  `clear`: the
-// group must read as zero from the start, and the call waits on that stream for the clear (score_alloc says why).
+// `carve` takes the group's buffers from a Carver and runs twice - without memory for the size, then on the allocation.  Every group
+// reads as zero from the start, as the workspace does after jck_engine_bind: the call clears it on `st` and waits for the clear
+// (score_alloc says why) - once per group and engine, next to a hipMalloc that synchronises anyway.
 template <typename Bufs, typename Carve>
-static int infer_alloc(Bufs& group, Carve carve, const hipStream_t* clear = nullptr) {
+static int infer_alloc(Bufs& group, Carve carve, hipStream_t st) {
   if (group.base) return JCK_OK;
   Carver c;
   Bufs b;
   carve(c, b);                                                       // sizes
   void* base = nullptr;
   HIPCHK(hipMalloc(&base, c.off));
-  if (clear && (hipMemsetAsync(base, 0, c.off, *clear) != hipSuccess || hipStreamSynchronize(*clear) != hipSuccess)) {
+  if (hipMemsetAsync(base, 0, c.off, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     (void)hipFree(base);
-    JCK_FAIL(JCK_E_HIP, "score: clearing the buffers failed");
+    JCK_FAIL(JCK_E_HIP, "clearing an inference buffer group failed");
   }
   c = Carver{0, reinterpret_cast<unsigned char*>(base)};
   carve(c, b);
@@ -57,7 +58,7 @@ static int latent_begin(jck_engine* e, const float* z, const int64_t* labels, in
     b.w = c.take<unsigned char>((size_t)LAT_LD * K * e->esz);
     b.slab = c.take<float>((size_t)LAT_KSPLIT * e->B * LAT_LD);
     b.loss = c.take<float>(e->B);
-  }));
+  }, st));
   if (e->family == 1) JCK_TRY(jck_cgan_z(e->prec, z, labels, n, 100, N_CLASS, zp, e->g_z, st));
   else {
     e->ss.gz_step = -1;                        // the operand rows now hold somebody else's z
@@ -108,7 +109,7 @@ static int score_alloc(jck_engine* e, hipStream_t st) {
       b.slab = c.take<float>((size_t)L1_KSPLIT * e->B * L1_OUT);
       b.h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
     }
-  }, &st);
+  }, st);
 }
 // the fold of D's BatchNorm layers (gamma, beta and the running statistics) into the stages' aux tables: one launch ...
 static int score_fold(jck_engine* e, hipStream_t st) {
@@ -220,7 +221,7 @@ extern "C" int jck_engine_features(jck_engine* e, const float* images_nchw, int 
 // and the plain one of stage 0 into an image gradient that jck_latent_loss_ex adds in front of the tanh.  Nothing of D's training
 // buffers (DActs, real_noisy, the head's cbuf, any gradient arena) is read or written.
 // ---------------------------------------------------------------------------------------------------------
-static int critic_alloc(jck_engine* e) {
+static int critic_alloc(jck_engine* e, hipStream_t st) {
   return infer_alloc(e->cr, [&](Carver& c, jck_engine::CriticBufs& b) {
     for (int i = 0; i < TT.NS; ++i) b.g[i] = c.take<unsigned char>((size_t)e->B * (TT.D_HB[i] / 2) * (TT.D_HB[i] / 2) * TT.D_CS[i] * e->esz);
     b.gx = c.take<unsigned char>((size_t)e->B * TT.HW * 4 * e->esz);
@@ -229,7 +230,7 @@ static int critic_alloc(jck_engine* e) {
       b.g_h = c.take<unsigned char>((size_t)e->B * L1_OUT * e->esz);
       b.gc = c.take<unsigned char>((size_t)e->B * L1_KPAD * e->esz);
     }
-  });
+  }, st);
 }
 // The objective of a latent call, as the six entry points build it: the image loss on `target` under the per-pixel `weight` (either may be
 // null), the critic's term (mode 0: none) at weight cw, and
@@ -272,11 +273,11 @@ static long long feat_elems(const jck_engine* e, int k) { return (long long)(TT.
 static int latent_ex_begin(jck_engine* e, const LatentEx& o, int n, hipStream_t st) {
   if (!o.mode && !o.fm()) return JCK_OK;
   JCK_TRY(score_alloc(e, st));
-  JCK_TRY(critic_alloc(e));
+  JCK_TRY(critic_alloc(e, st));
   if (o.fm()) JCK_TRY(infer_alloc(e->fm, [&](Carver& c, jck_engine::FeatBufs& b) {
     b.fa = c.take<unsigned char>((size_t)e->B * feat_elems(e, 0) * e->esz);
     b.term = c.take<float>(e->B);
-  }));
+  }, st));
   JCK_TRY(score_fold(e, st));
   if (!o.fm()) return JCK_OK;
   const int k = feat_stage_of(e, o);

@@ -617,7 +617,8 @@ __global__ __launch_bounds__(256) void label_embed_bwd_kernel(const T* __restric
   }
 }
 
-// cbuf[b][0..K0) = a4[b][0..K0)  (columns [K0, ld) are written by the label embedding / stay zero)
+// cbuf[b][0..K0) = a4[b][0..K0)  (columns [K0, ld) are written by the label embedding / keep the zeros of the buffer's owner: jck_engine_bind
+// for the engine's cbuf / cbuf2, infer_alloc for the scoring group's)
 template <typename T>
 __global__ void concat_rows_kernel(const T* __restrict__ a4, int K0, T* __restrict__ cbuf, int ld, long long total8) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {

@@ -49,7 +49,7 @@ static __global__ void adam_hp_kernel(float* __restrict__ hp, float step_size, f
         if (i * 4 + k < r.nz) {
           r.z[i * 4 + k] = v[k];
           // ... and, in the same launch, into G.conv1's operand rows (what pad_rows_kernel would copy a launch later; the padding
-          // columns [zd, zp) are never written by anybody: they keep the zeros of the zero-initialised workspace)
+          // columns [zd, zp) are never written by anybody: they keep the zeros jck_engine_bind cleared the workspace to)
           if (r.zpad) {
             const long long e = i * 4 + k, b = e / r.zd;
             const int c = (int)(e - b * r.zd);
@@ -222,7 +222,7 @@ static __global__ void pack_head_kernel(const float* __restrict__ w, int C, floa
 // their ~4.5 us floor each left the GPU idle for ~45 us twice per step).  A thread owns one (output channel, input channel)
 // pair of a conv weight: it reads the pair's 16 taps (64 contiguous bytes) once and writes the 16 operand elements, with
 // the lane-fastest index chosen per layout so that every store instruction covers contiguous elements.  Padding rows and
-// channels are never written: they stay zero from the zero-initialised workspace.  256 pairs per workgroup.
+// channels are never written: they stay zero from jck_engine_bind's clear of the workspace.  256 pairs per workgroup.
 #define PACK_MAX_JOBS 12
 #define PACK_CHUNK 256
 struct PackJob { const float* w; void* wp; long long total; int kind, a, b, c; };   // kind: 0 down 1 up 2 up16 3 g1 4 head

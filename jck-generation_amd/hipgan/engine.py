@@ -246,21 +246,12 @@ class DcganEngine(EngineInference):
         self.ws_bytes = dll.jck_engine_workspace_bytes(h)
         self.workspace = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=self.device)
         a = self.arenas
-        if self.ema_sampler:
-            # G's forward reads the average where a training engine reads the parameters; everything else is the same engine
-            if not self._shared.get("ema_bn_seeded"):
-                share.join()
-                a["g_ema_bn"].copy_(a["g_bn"])
-                a["g_ema_nbt"].copy_(a["g_nbt"])
-                self._shared["ema_bn_seeded"] = True
-            lib.jck_engine_bind(h, self.workspace, self.ws_bytes, a["g_ema"], a["g_grads"], a["g_m"], a["g_v"], a["g_ema_bn"],
-                                a["g_ema_nbt"], a["d_params"], a["d_grads"], a["d_m"], a["d_v"], a["d_bn"], a["d_nbt"])
-        else:
-            lib.jck_engine_bind(h, self.workspace, self.ws_bytes, a["g_params"], a["g_grads"], a["g_m"], a["g_v"], a["g_bn"],
-                                a["g_nbt"], a["d_params"], a["d_grads"], a["d_m"], a["d_v"], a["d_bn"], a["d_nbt"])
-            if self.ema_decay is not None:
-                lib.jck_engine_bind_ema(h, a["g_ema"])
-                lib.jck_engine_set_ema(h, self.ema_decay, self.ema_start)
+        if self.ema_sampler and not self._shared.get("ema_bn_seeded"):
+            share.join()
+            a["g_ema_bn"].copy_(a["g_bn"])
+            a["g_ema_nbt"].copy_(a["g_nbt"])
+            self._shared["ema_bn_seeded"] = True
+        self._bind()
         self.layout = {"g": _layout(h, 0), "d": _layout(h, 1)}
         # the step's own draws (Philox: z, alpha, instance noise, dropout masks) follow torch's seed unless the caller sets one
         self.set_noise_seed(int(torch.initial_seed()) + 0x6a636b67)
@@ -271,6 +262,23 @@ class DcganEngine(EngineInference):
                     a[f"{tag}_bn"][off:off + numel].fill_(1.0)
         if share is None and self.ema_decay is not None:
             self.reset_ema()
+
+    def _bind(self):
+        """Binds the arenas and self.workspace (jck_engine_bind, and the average's arena of an engine that keeps one).  Bind clears the
+        workspace whatever it held, so this engine's operand copies are gone afterwards: they are re-derived before its next use.
+        The constructor's call; calling it again on an idle engine is ordinary use of the ABI."""
+        h, a = self._h, self.arenas
+        if self.ema_sampler:
+            # G's forward reads the average where a training engine reads the parameters; everything else is the same engine
+            lib.jck_engine_bind(h, self.workspace, self.ws_bytes, a["g_ema"], a["g_grads"], a["g_m"], a["g_v"], a["g_ema_bn"],
+                                a["g_ema_nbt"], a["d_params"], a["d_grads"], a["d_m"], a["d_v"], a["d_bn"], a["d_nbt"])
+        else:
+            lib.jck_engine_bind(h, self.workspace, self.ws_bytes, a["g_params"], a["g_grads"], a["g_m"], a["g_v"], a["g_bn"],
+                                a["g_nbt"], a["d_params"], a["d_grads"], a["d_m"], a["d_v"], a["d_bn"], a["d_nbt"])
+            if self.ema_decay is not None:
+                lib.jck_engine_bind_ema(h, a["g_ema"])
+                lib.jck_engine_set_ema(h, self.ema_decay, self.ema_start)
+        self._packed_version = -1
 
     # optimiser step count and weight version are shared by engines bound to the same arenas
     @property
