@@ -4,10 +4,10 @@
 //   jck_knn_index_ws_bytes  its workspace (host only)
 //
 // Two stages, two launches, both on the device:
-//   candidates  knn_cand_kernel: the Gram-tile core of pairstat.hip (64 x 64 tile, v_mfma_f32_16x16x4_f32, fmaf-chain norms, the
-//               staging of pairtile.hpp) with the queries as the workgroup's own block (tile columns) and the references walked
-//               (tile rows).  d = max(0, (|ref|^2 + |q|^2) - 2 G) in fp32.  A lane keeps, for each of its two query columns, the 8
-//               smallest (d, reference row) pairs in lexicographic order; the 8 lanes that share a column merge once through LDS.
+//   candidates  knn_cand_kernel: the Gram-tile core of pairtile.hpp with the queries as the workgroup's own block (tile columns) and
+//               the references walked (tile rows).  d = max(0, (|ref|^2 + |q|^2) - 2 G) in fp32.  A lane keeps, for each of its two
+//               query columns, the 8 smallest (d, reference row) pairs in lexicographic order; the 8 lanes that share a column
+//               merge once through LDS.
 //               The walk is split: the grid is (query tiles x strips of reference tiles), every workgroup writes its 64 x 8 partial
 //               lists to the workspace.  No atomics: the partial lists have fixed places, every merge compares (d, index) pairs,
 //               whose order is total, so the 8 survivors do not depend on the order in which anything ran.
@@ -26,7 +26,6 @@ namespace {
 
 constexpr int KNN_WGS = 768;              // workgroups the candidate walk is split into at least (3 per CU of 256) where the tiles allow
 constexpr int KSUB = 4;                   // 16-column steps of the tile core staged per barrier pair
-constexpr int KNN_IPAD = 0x7fffffff;      // index of a list's padding entry (d = +inf): sorts after every real entry
 
 struct KnnCandP {
   const float* q; const float* ref;
@@ -43,29 +42,6 @@ struct KnnRankP {
   long long* idx; float* d2;
 };
 
-__device__ __forceinline__ bool kv_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
-
-// keeps the PKMAX smallest (value, index) pairs seen, ascending in lexicographic order (v is not NaN)
-__device__ __forceinline__ void keep_smallest_kv(float (&L)[PKMAX], int (&I)[PKMAX], float v, int vi) {
-#pragma unroll
-  for (int t = 0; t < PKMAX; ++t) {
-    const bool lt = kv_less(v, vi, L[t], I[t]);
-    const float lo = lt ? v : L[t], hi = lt ? L[t] : v;
-    const int loi = lt ? vi : I[t], hii = lt ? I[t] : vi;
-    L[t] = lo; I[t] = loi;
-    v = hi; vi = hii;
-  }
-}
-
-// stage_tile's 16-byte load alone: this thread's float4 of rows r0 .. r0+63, columns k0 .. k0+15 of p[R][D], zero outside the
-// matrix.  The load itself is unconditional (from p when outside: D % 4 == 0 makes p[0..3] readable), so that several can be in flight.
-__device__ __forceinline__ f32x4 load_tile_vec(const float* __restrict__ p, int R, int D, int r0, int k0, int tid) {
-  const int gr = r0 + (tid >> 2), c = k0 + (tid & 3) * 4;
-  const bool in = gr < R && c < D;
-  const f32x4 v = *reinterpret_cast<const f32x4*>(p + (in ? (long long)gr * D + c : 0));
-  return in ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
 __global__ __launch_bounds__(256) void knn_cand_kernel(const KnnCandP p) {
   // KSUB staged steps of the tile core per barrier pair: their global loads are in flight together.  After the walk the same
   // memory holds the lists that the lanes of a column merge (8 lanes x 8 entries x 64 columns of distances, then of indices).
@@ -76,120 +52,47 @@ __global__ __launch_bounds__(256) void knn_cand_kernel(const KnnCandP p) {
   float* candD = smem;
   int* candI = reinterpret_cast<int*>(smem + PT * 8 * PKMAX);
   static_assert(2 * PT * 8 * PKMAX <= 2 * KSUB * PT * PLD, "the merge lists fit the staging memory");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;               // this wave's 32 x 32 part of the tile
+  const TilePos t(threadIdx.x);
+  const int tid = t.tid;
   const int b0 = (int)blockIdx.x * PT;                                  // the query block
   const long long tilesA = ((long long)p.N + PT - 1) / PT;
   const long long t0 = (long long)blockIdx.y * p.strip, t1 = t0 + p.strip < tilesA ? t0 + p.strip : tilesA;
-  float L[2][PKMAX];
-  int I[2][PKMAX], self[2];
+  TopK<true> L[2];
+  int self[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-#pragma unroll
-    for (int t = 0; t < PKMAX; ++t) { L[j][t] = INFINITY; I[j][t] = KNN_IPAD; }
-    const long long s = (long long)(b0 + wn + j * 16 + (lane & 15)) + p.self_off;
+    L[j].clear();
+    const long long s = (long long)(b0 + t.col(j)) + p.self_off;
     self[j] = (p.exclude && s >= 0 && s < p.N) ? (int)s : -1;
   }
 
   for (long long ta = t0; ta < t1; ++ta) {
     const int a0 = (int)(ta * PT);
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float nrm = 0.f;
-    for (int k0 = 0; k0 < p.D; k0 += KSUB * PK) {
-      if (p.vec) {                                                      // every load of the KSUB steps leaves before the first store waits
-        f32x4 ra[KSUB], rb[KSUB];
-#pragma unroll
-        for (int s = 0; s < KSUB; ++s) {
-          ra[s] = load_tile_vec(p.ref, p.N, p.D, a0, k0 + s * PK, tid);
-          rb[s] = load_tile_vec(p.q, p.M, p.D, b0, k0 + s * PK, tid);
-        }
-#pragma unroll
-        for (int s = 0; s < KSUB; ++s) {
-          *reinterpret_cast<f32x4*>(&As[s][tid >> 2][(tid & 3) * 4]) = ra[s];
-          *reinterpret_cast<f32x4*>(&Bs[s][tid >> 2][(tid & 3) * 4]) = rb[s];
-        }
-      } else {
-#pragma unroll
-        for (int s = 0; s < KSUB; ++s)
-          if (k0 + s * PK < p.D) {
-            stage_tile(As[s], p.ref, p.N, p.D, a0, k0 + s * PK, 0, tid);
-            stage_tile(Bs[s], p.q, p.M, p.D, b0, k0 + s * PK, 0, tid);
-          }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int s = 0; s < KSUB; ++s)
-        if (k0 + s * PK < p.D) {
-          if (wave == 0) {                                              // squared norms: wave 0 the walked rows, wave 1 the own block (once)
-#pragma unroll
-            for (int k = 0; k < PK; ++k) { const float v = As[s][lane][k]; nrm = fmaf(v, v, nrm); }
-          } else if (wave == 1 && ta == t0) {
-#pragma unroll
-            for (int k = 0; k < PK; ++k) { const float v = Bs[s][lane][k]; nrm = fmaf(v, v, nrm); }
-          }
-#pragma unroll
-          for (int kk = 0; kk < PK; kk += 4) {
-            // v_mfma_f32_16x16x4_f32: lane l holds A[row l&15][k = l>>4], B[k = l>>4][col l&15]
-            float a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = As[s][wm + i * 16 + (lane & 15)][kk + (lane >> 4)];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = Bs[s][wn + j * 16 + (lane & 15)][kk + (lane >> 4)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-              for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-          }
-        }
-      __syncthreads();
-    }
-    if (wave == 0) nA[lane] = nrm;
-    else if (wave == 1 && ta == t0) nB[lane] = nrm;
+    gram_tile<KSUB, true>(acc, As, Bs, nA, nB, p.ref, p.N, a0, p.q, p.M, b0, p.D, p.vec, ta == t0, t);
     __syncthreads();
-    // C/D: row (reference) = 4*(l>>4) + reg, col (query) = l & 15.  A lane meets its references in ascending order.
+    // a lane meets its references in ascending order
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const float nb = nB[wn + j * 16 + (lane & 15)];
+      const float nb = nB[t.col(j)];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int ra = wm + i * 16 + (lane >> 4) * 4 + r, ga = a0 + ra;
+          const int ra = t.row(i, r), ga = a0 + ra;
           float d = (nA[ra] + nb) - 2.f * acc[i][j][r];
           d = d < 0.f ? 0.f : d;                                        // NaN stays NaN and is never kept
-          if (ga < p.N && ga != self[j] && kv_less(d, ga, L[j][PKMAX - 1], I[j][PKMAX - 1])) keep_smallest_kv(L[j], I[j], d, ga);
+          if (ga < p.N && ga != self[j]) L[j].offer(d, ga);
         }
     }
   }
 
-  // the 8 lanes that share a query column (4 per wave, 2 waves) merge their lists once
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int cb = wn + j * 16 + (lane & 15), sh = (wave >> 1) * 4 + (lane >> 4);
-#pragma unroll
-    for (int t = 0; t < PKMAX; ++t) {
-      candD[(cb * 8 + sh) * PKMAX + t] = L[j][t];
-      candI[(cb * 8 + sh) * PKMAX + t] = I[j][t];
-    }
-  }
-  __syncthreads();
+  TopK<true> M;
+  merge_columns(M, L, candD, candI, t);
   if (tid < PT && b0 + tid < p.M) {
-    float Md[PKMAX];
-    int Mi[PKMAX];
-#pragma unroll
-    for (int t = 0; t < PKMAX; ++t) { Md[t] = INFINITY; Mi[t] = KNN_IPAD; }
-    for (int s = 0; s < 8 * PKMAX; ++s) {
-      const float v = candD[tid * 8 * PKMAX + s];
-      const int vi = candI[tid * 8 * PKMAX + s];
-      if (kv_less(v, vi, Md[PKMAX - 1], Mi[PKMAX - 1])) keep_smallest_kv(Md, Mi, v, vi);
-    }
     const long long o = ((long long)(b0 + tid) * p.nstrips + blockIdx.y) * PKMAX;
 #pragma unroll
-    for (int t = 0; t < PKMAX; ++t) { p.cd[o + t] = Md[t]; p.ci[o + t] = Mi[t]; }
+    for (int e = 0; e < PKMAX; ++e) { p.cd[o + e] = M.v[e]; p.ci[o + e] = M.i[e]; }
     if (blockIdx.y == 0) p.qn[b0 + tid] = nB[tid];
   }
 }
@@ -205,39 +108,29 @@ __global__ __launch_bounds__(256) void knn_rank_kernel(const KnnRankP p) {
   const int lane = threadIdx.x & 63;
   const long long qrow = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (qrow >= p.M) return;                                              // wave-uniform; no workgroup barrier below
-  float L[PKMAX];
-  int I[PKMAX];
-#pragma unroll
-  for (int t = 0; t < PKMAX; ++t) { L[t] = INFINITY; I[t] = KNN_IPAD; }
+  TopK<true> L;
+  L.clear();
   const long long base = qrow * p.nstrips * PKMAX;
   const int n = p.nstrips * PKMAX;
-  for (int e = lane; e < n; e += 64) {
-    const float v = p.cd[base + e];
-    const int vi = p.ci[base + e];
-    if (kv_less(v, vi, L[PKMAX - 1], I[PKMAX - 1])) keep_smallest_kv(L, I, v, vi);
-  }
+  for (int e = lane; e < n; e += 64) L.offer(p.cd[base + e], p.ci[base + e]);
   // 8 rounds: the smallest head of the 64 sorted lists leaves its list.  Real entries are distinct (one per reference row); padding
   // entries are all alike, and a list that pops one only shifts in another.
   float C[PKMAX];
   int CI[PKMAX];
 #pragma unroll
   for (int t = 0; t < PKMAX; ++t) {
-    float hd = L[0];
-    int hi = I[0];
+    float hd = L.v[0];
+    int hi = L.i[0];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float od = __shfl_xor(hd, o, 64);
       const int oi = __shfl_xor(hi, o, 64);
-      const bool lt = kv_less(od, oi, hd, hi);
+      const bool lt = TopK<true>::less(od, oi, hd, hi);
       hd = lt ? od : hd;
       hi = lt ? oi : hi;
     }
     C[t] = hd; CI[t] = hi;
-    if (L[0] == hd && I[0] == hi) {
-#pragma unroll
-      for (int u = 0; u + 1 < PKMAX; ++u) { L[u] = L[u + 1]; I[u] = I[u + 1]; }
-      L[PKMAX - 1] = INFINITY; I[PKMAX - 1] = KNN_IPAD;
-    }
+    if (L.v[0] == hd && L.i[0] == hi) L.pop();
   }
   // distances from differences; a padding candidate reads reference row 0 and is dropped below
   const float* __restrict__ qr = p.q + qrow * p.D;
@@ -289,7 +182,7 @@ __global__ __launch_bounds__(256) void knn_rank_kernel(const KnnRankP p) {
   if (lane < 2 * PKMAX && rank < p.k) {
     const bool qok = finite_f(p.qn[qrow]);
     p.idx[qrow * p.k + rank] = (qok && kd < INFINITY) ? ki : -1;
-    p.d2[qrow * p.k + rank] = qok ? kd : __uint_as_float(0x7fc00000u);
+    p.d2[qrow * p.k + rank] = qok ? kd : qnan_f();
   }
 }
 

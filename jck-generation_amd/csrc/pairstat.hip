@@ -7,17 +7,9 @@
 //   jck_manifold_hit_u8   hit[i] = 1 when q_i lies inside the k-NN ball of some reference row
 //   jck_pairstat_ws_bytes workspace of the first (host only)
 //
-// (The nearest rows WITH their indices, jck_knn_index_f32, live in knnindex.hip over the same tile geometry, pairtile.hpp.)
-//
-// One Gram-tile core serves the three: G[i][j] = sum_c a[i][c] * b[j][c] on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32,
-// bitwise an fmaf chain - the convolutions of infer.hip use it for the same reason), 64 x 64 per 256-thread workgroup, each
-// wave a 32 x 32 quarter as 2 x 2 accumulator fragments, c in steps of 16 through LDS rows of 20 floats ((20 m + k) % 64 is
-// conflict-free for the fragment reads).  Rows past the matrix and columns past D are zero-filled; D % 4 != 0 or a base
-// pointer off a 16-byte boundary stages with scalar loads instead of 16-byte ones.  A workgroup owns one 64-row block of `b`
-// (the tile's columns) and walks 64-row tiles of `a` (the tile's rows): a lane then holds, per accumulator fragment, ONE
-// column and four rows, so the per-column state of the k-NN and manifold epilogues (the k smallest, the hit flag) is two
-// columns per lane.  Squared row norms are an fp32 fmaf chain over c in order, taken from the staged tiles: the block's own
-// once, a walked tile's when it passes.  d^2 = max(0, (|a|^2 + |b|^2) - 2 G) in fp32, in that association.
+// The three are epilogues of one Gram-tile walk (pairtile.hpp: the tile, its staging, the norms and the k-smallest list; the nearest
+// rows WITH their indices, jck_knn_index_f32, live in knnindex.hip over the same core).  A workgroup owns one 64-row block of `b`
+// and walks 64-row tiles of `a`; d^2 = max(0, (|a|^2 + |b|^2) - 2 G) in fp32, in that association.
 //
 // Determinism: no float atomics.  The polynomial sum is fp64 per lane in a fixed order, wave and workgroup sums in
 // a fixed order, one partial per workgroup into the caller's workspace, and a second one-workgroup launch adds the partials
@@ -37,16 +29,6 @@ struct PairP {
   double* ws; float* r2out; const float* r2in; unsigned char* hit;
 };
 
-// keeps the PKMAX smallest values seen, ascending (v is not NaN)
-__device__ __forceinline__ void keep_smallest(float (&L)[PKMAX], float v) {
-#pragma unroll
-  for (int t = 0; t < PKMAX; ++t) {
-    const float lo = v < L[t] ? v : L[t], hi = v < L[t] ? L[t] : v;
-    L[t] = lo;
-    v = hi;
-  }
-}
-
 template <int EPI>
 __global__ __launch_bounds__(256) void pair_kernel(const PairP p) {
   __shared__ __attribute__((aligned(16))) float As[PT][PLD];
@@ -55,72 +37,35 @@ __global__ __launch_bounds__(256) void pair_kernel(const PairP p) {
   __shared__ int hitf[PT];
   __shared__ float cand[EPI == EPI_KNN ? PT * 8 * PKMAX : 1];
   __shared__ double wsum[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;               // this wave's 32 x 32 part of the tile
+  const TilePos t(threadIdx.x);
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
   const int b0 = (int)blockIdx.x * PT;
   const long long tilesA = ((long long)p.Ma + PT - 1) / PT;
   const long long t0 = (long long)blockIdx.y * p.strip, t1 = t0 + p.strip < tilesA ? t0 + p.strip : tilesA;
   double psum = 0.0;
-  float L[2][PKMAX];
+  TopK<false> L[2];
   bool h[2] = {false, false};
 #pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int t = 0; t < PKMAX; ++t) L[j][t] = INFINITY;
+  for (int j = 0; j < 2; ++j) L[j].clear();
   if (EPI == EPI_HIT && tid < PT) hitf[tid] = 0;
 
   for (long long ta = t0; ta < t1; ++ta) {
     const int a0 = (int)(ta * PT);
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float nrm = 0.f;
-    for (int k0 = 0; k0 < p.D; k0 += PK) {
-      stage_tile(As, p.a, p.Ma, p.D, a0, k0, p.vec, tid);
-      stage_tile(Bs, p.b, p.Nb, p.D, b0, k0, p.vec, tid);
-      __syncthreads();
-      if (EPI != EPI_POLY3) {                                           // squared norms: wave 0 the walked rows, wave 1 the own block (once)
-        if (wave == 0) {
-#pragma unroll
-          for (int k = 0; k < PK; ++k) { const float v = As[lane][k]; nrm = fmaf(v, v, nrm); }
-        } else if (wave == 1 && ta == t0) {
-#pragma unroll
-          for (int k = 0; k < PK; ++k) { const float v = Bs[lane][k]; nrm = fmaf(v, v, nrm); }
-        }
-      }
-#pragma unroll
-      for (int kk = 0; kk < PK; kk += 4) {
-        // v_mfma_f32_16x16x4_f32: lane l holds A[row l&15][k = l>>4], B[k = l>>4][col l&15]
-        float a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = As[wm + i * 16 + (lane & 15)][kk + (lane >> 4)];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b[j] = Bs[wn + j * 16 + (lane & 15)][kk + (lane >> 4)];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
+    gram_tile<1, EPI != EPI_POLY3>(acc, &As, &Bs, nA, nB, p.a, p.Ma, a0, p.b, p.Nb, b0, p.D, p.vec, ta == t0, t);
     if (EPI != EPI_POLY3) {
-      if (wave == 0) nA[lane] = nrm;
-      else if (wave == 1 && ta == t0) nB[lane] = nrm;
-      if (EPI == EPI_HIT && wave == 2) r2s[lane] = (a0 + lane < p.Ma) ? p.r2in[a0 + lane] : __uint_as_float(0x7fc00000u);
+      if (EPI == EPI_HIT && wave == 2) r2s[lane] = (a0 + lane < p.Ma) ? p.r2in[a0 + lane] : qnan_f();
       __syncthreads();
     }
-    // C/D: row (a) = 4*(l>>4) + reg, col (b) = l & 15
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int cb = wn + j * 16 + (lane & 15), gb = b0 + cb;
+      const int cb = t.col(j), gb = b0 + cb;
       const float nb = EPI != EPI_POLY3 ? nB[cb] : 0.f;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int ra = wm + i * 16 + (lane >> 4) * 4 + r, ga = a0 + ra;
+          const int ra = t.row(i, r), ga = a0 + ra;
           const float g = acc[i][j][r];
           if (EPI == EPI_POLY3) {
             if (ga < p.Ma && gb < p.Nb && !(p.skip_diag && ga == gb)) {
@@ -131,7 +76,7 @@ __global__ __launch_bounds__(256) void pair_kernel(const PairP p) {
             float d = (nA[ra] + nb) - 2.f * g;
             d = d < 0.f ? 0.f : d;                                      // NaN stays NaN
             if (EPI == EPI_KNN) {
-              if (ga < p.Ma && ga != gb && d < L[j][PKMAX - 1]) keep_smallest(L[j], d);
+              if (ga < p.Ma && ga != gb) L[j].offer(d);
             } else {
               h[j] = h[j] || (d <= r2s[ra]);                            // rows past Ma carry a NaN radius
             }
@@ -141,7 +86,7 @@ __global__ __launch_bounds__(256) void pair_kernel(const PairP p) {
     if (EPI == EPI_HIT) {                                               // leave the walk once every row of the block is decided
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        if (h[j]) hitf[wn + j * 16 + (lane & 15)] = 1;
+        if (h[j]) hitf[t.col(j)] = 1;
       __syncthreads();
       const int decided = hitf[lane] | (b0 + lane >= p.Nb) | !finite_f(nB[lane]);
       if (__syncthreads_and(decided)) break;
@@ -154,26 +99,13 @@ __global__ __launch_bounds__(256) void pair_kernel(const PairP p) {
     __syncthreads();
     if (tid == 0) p.ws[(long long)blockIdx.y * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
   } else if (EPI == EPI_KNN) {
-    // the 8 lanes that share a column (4 per wave, 2 waves) merge their lists once
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int cb = wn + j * 16 + (lane & 15), sh = (wave >> 1) * 4 + (lane >> 4);
-#pragma unroll
-      for (int t = 0; t < PKMAX; ++t) cand[(cb * 8 + sh) * PKMAX + t] = L[j][t];
-    }
-    __syncthreads();
+    TopK<false> M;
+    merge_columns(M, L, cand, nullptr, t);
     if (tid < PT && b0 + tid < p.Nb) {
-      float M[PKMAX];
+      float res = M.v[0];
 #pragma unroll
-      for (int t = 0; t < PKMAX; ++t) M[t] = INFINITY;
-      for (int s = 0; s < 8 * PKMAX; ++s) {
-        const float v = cand[tid * 8 * PKMAX + s];
-        if (v < M[PKMAX - 1]) keep_smallest(M, v);
-      }
-      float res = M[0];
-#pragma unroll
-      for (int t = 1; t < PKMAX; ++t) res = (t == p.k - 1) ? M[t] : res;
-      p.r2out[b0 + tid] = finite_f(nB[tid]) ? res : __uint_as_float(0x7fc00000u);
+      for (int e = 1; e < PKMAX; ++e) res = (e == p.k - 1) ? M.v[e] : res;
+      p.r2out[b0 + tid] = finite_f(nB[tid]) ? res : qnan_f();
     }
   } else {
     if (tid < PT && b0 + tid < p.Nb) p.hit[b0 + tid] = finite_f(nB[tid]) ? (unsigned char)(hitf[tid] != 0) : (unsigned char)255;

@@ -146,6 +146,35 @@ def test_manifold_hits_are_bit_exact_on_integer_features_with_ties():
     assert 0 < (d2 <= r2[None, :].astype(np.int64)).any(1).sum() < 131 and (d2 == r2[None, :].astype(np.int64)).any()
 
 
+@pytest.mark.parametrize("D,offset", [(5, False), (20, False), (64, True)])
+def test_all_three_are_bit_exact_at_ragged_depth_and_off_alignment(D, offset):
+    """the exact tests above stage with 16-byte loads only (D = 64, aligned).  D = 5 is scalar staging inside one 16-column step,
+    D = 20 is 16-byte staging with a partly filled second step, D = 64 one float off the boundary is scalar staging over whole steps.
+    Entries in -3..3 at D <= 64 keep every product, norm and partial sum exact."""
+    put = dev_offset if offset else dev
+    base, other = int_features(129, D, seed=11), int_features(65, D, seed=12)
+    base[1] = base[0]
+    g = np.random.default_rng(13)
+    q = base[g.integers(0, 63, size=65)].copy()
+    q[np.arange(65), g.integers(0, D, size=65)] += 2                 # near a reference row
+    q[::3] = int_features(65, D, seed=14)[::3]                        # ... or nowhere near one
+    for n in (63, 64, 65, 129):
+        x = base[:n]
+        xd, od, qd = put(x), put(other), put(q)
+        for skip in (0, 1):
+            assert poly3(xd, xd, 1.0 / 64, 1.0, skip).item() == poly3_ref(x, x, bool(skip), 1.0 / 64, 1.0), (n, skip)
+            assert poly3(xd, od, 1.0 / 64, 1.0, skip).item() == poly3_ref(x, other, bool(skip), 1.0 / 64, 1.0), (n, skip)
+            assert poly3(od, xd, 1.0 / 64, 1.0, skip).item() == poly3_ref(other, x, bool(skip), 1.0 / 64, 1.0), (n, skip)
+        d2 = d2_int(q, x)
+        for k in (1, 3, 8):
+            r2 = radii_int(x, k)
+            got = knn(xd, k)
+            assert np.array_equal(got.cpu().numpy(), r2), (n, k)
+            want = (d2 <= r2[None, :].astype(np.int64)).any(1).astype(np.uint8)
+            assert np.array_equal(hits(qd, xd, got).cpu().numpy(), want), (n, k)
+            assert np.array_equal(hits(xd, xd, got).cpu().numpy(), np.ones(n, np.uint8)), (n, k)      # d2 = 0 to itself
+
+
 def _check_side(q, ref, k, name):
     """one side of precision / recall by the margin rule: queries whose fp64 decision margin is below MARGIN are set aside (at
     most 2 %), the others' hits must be identical, the device radii within the same bound"""
