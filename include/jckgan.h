@@ -791,6 +791,28 @@ int jck_sort_rows_tile(void);
 int jck_sort_rows_f32(const float* x, int Rows, long long M, float* out, void* ws, size_t ws_bytes, void* stream);
 int jck_swd_rows(const float* sa, const float* sb, int Rows, long long M, double* w, void* stream);
 
+/* Power spectra of uint8 NHWC pictures [n][S][S][3], S in 32, 64, 128 (csrc/spectrum.hip; the definition: DESIGN.md 5.18).  plane: 0, 1, 2
+ * = a channel (Y = 256 * byte), 3 = luma (Y = 77 R + 150 G + 29 B).  Per picture T = sum Y, mean[i] = T / (256 S^2) (exact), the plane
+ * c = S^2 Y - T converted to fp32 once, scaled by 1 / (256 S^2) and, with win (device fp32 [S], or NULL), multiplied by win[y] then win[x];
+ * F its two-dimensional DFT (fp32, in LDS, twiddles rounded from fp64), P = |F|^2 / (S^2 win_power) in fp64.
+ *   jck_spectrum_bins      R = 24 / 46 / 92 radial bins of S = 32 / 64 / 128 (bin r of (u, v): r^2 - r < fu^2 + fv^2 <= r^2 + r with fu =
+ *                          min(u, S - u), fv likewise); JCK_E_ARG for another S.  Host only.
+ *   jck_spectrum_grid      G, the workgroups of a launch that forms the mean plane (JCK_E_ARG for another S).  Host only.
+ *   jck_spectrum_ws_bytes  bytes of the partial planes: min(n, G) S (S / 2 + 1) 8 with the mean plane, 0 without it or for sizes the
+ *                          entry point refuses.  Host only.
+ *   jck_spectrum_u8        prof[i][r] (device fp64 [n][R]) = the mean of P_i over bin r; mean (device fp64 [n]); mean2d (device fp64
+ *                          [S][S], or NULL) = (1/n) sum_i P_i[u][v], (u, v) and (-u, -v) holding equal bits; ws / ws_bytes: what
+ *                          jck_spectrum_ws_bytes(n, S, 1) asks for, 8-byte aligned (unused when mean2d is NULL).
+ * A picture's prof row and mean depend on that picture alone (equal bits at n = 1 and inside any batch); every sum runs in an order
+ * fixed by S, the mean plane's by S and n.  x may start at any byte address.  sum |P^ - P| <= B(S) sum P with B = 8.5e-6, 1.01e-5,
+ * 1.16e-5 (derived in csrc/spectrum.hip).  n = 0: JCK_OK, nothing launched.  S, plane, n < 0, a win_power that is not finite and
+ * positive, a NULL x / prof / mean, a workspace that is too small: JCK_E_ARG from the host before any HIP call. */
+int jck_spectrum_bins(int S);
+int jck_spectrum_grid(int S);
+size_t jck_spectrum_ws_bytes(int n, int S, int want_mean2d);
+int jck_spectrum_u8(const unsigned char* x, int n, int S, int plane, const float* win, double win_power, double* prof, double* mean,
+                    double* mean2d, void* ws, size_t ws_bytes, void* stream);
+
 /* Per-step optimiser scalars into device memory (so that a captured graph of the step has no per-step kernel argument), and
  * hipGraph capture of a sequence of jck_engine_phase calls: begin -> phases on `stream` (not the default stream) -> end
  * returns an executable graph; launch replays it.  The jck_step_inputs pointers are baked: keep the buffers in place,

@@ -177,6 +177,10 @@ PROTOS = {
     "jck_sort_rows_tile": (i32, []),
     "jck_sort_rows_f32": (i32, [vp, i32, i64, vp, vp, sz, vp]),
     "jck_swd_rows": (i32, [vp, vp, i32, i64, vp, vp]),
+    "jck_spectrum_bins": (i32, [i32]),
+    "jck_spectrum_grid": (i32, [i32]),
+    "jck_spectrum_ws_bytes": (sz, [i32, i32, i32]),
+    "jck_spectrum_u8": (i32, [vp, i32, i32, i32, vp, f64, vp, vp, vp, vp, sz, vp]),
     "jck_engine_set_step": (i32, [vp, i32, f32, vp]),
     "jck_engine_bind_ema": (i32, [vp, vp]),
     "jck_engine_set_ema": (i32, [vp, f64, i32]),
@@ -258,7 +262,7 @@ class _Lib:
                     if not a.is_contiguous():
                         raise JckError(f"{name}: non-contiguous tensor argument")
             r = fn(*[_arg(a) for a in args])
-            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_bn_res_plan", "jck_comm_world", "jck_engine_graph_nodes", "jck_segment_chunk_rows", "jck_ssim_max_levels", "jck_swd_max_levels", "jck_sort_rows_tile") \
+            if fn.restype is i32 and name not in ("jck_version", "jck_pad_rows", "jck_pad_chan", "jck_engine_num_tensors", "jck_prof_collect", "jck_grid_sync_error", "jck_bn_res_plan", "jck_comm_world", "jck_engine_graph_nodes", "jck_segment_chunk_rows", "jck_ssim_max_levels", "jck_swd_max_levels", "jck_sort_rows_tile", "jck_spectrum_bins", "jck_spectrum_grid") \
                     and r != 0:
                 raise JckError(f"{name} failed ({r}): {dll.jck_last_error().decode()}")
             return r

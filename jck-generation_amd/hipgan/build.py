@@ -8,7 +8,7 @@ PKG = os.path.dirname(HERE)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libjckgan_hip.so")
-SOURCES = ["ops.hip", "ops_bn.hip", "ops_gemm.hip", "engine.hip", "engine_infer.hip", "infer.hip", "pairstat.hip", "knnindex.hip", "cluster.hip", "ssim.hip", "comm.hip", "swd.hip"]
+SOURCES = ["ops.hip", "ops_bn.hip", "ops_gemm.hip", "engine.hip", "engine_infer.hip", "infer.hip", "pairstat.hip", "knnindex.hip", "cluster.hip", "ssim.hip", "comm.hip", "swd.hip", "spectrum.hip"]
 
 
 def source_id():

@@ -12,6 +12,7 @@
     m = s.modes(train_u8, n=10000, k=100)                      # mode coverage (hipgan.cluster): m["covered"], m["kl"], m["missing"]
     v = s.diversity(2000, pairs=1000, train_u8=train_u8)       # mean MS-SSIM of random pairs against the training set's (hipgan.diversity)
     w = s.swd(train_u8, n=8192)                                # sliced Wasserstein distance per pyramid level (hipgan.swd): w["swd"], w["mean"]
+    f = s.spectrum(train_u8, n=8192)                           # power spectra against the training set's (hipgan.spectrum): f["gap_db"], f["checkerboard_db"]
 
 Sampling runs with bn="running" by default (DcganEngine.sample): BatchNorm on the running statistics, every image a function of
 its own z, any n.  The running statistics of an AVERAGED generator were never fitted to its weights - they are the live ones at
@@ -620,6 +621,53 @@ class Sampler:
                 if k < 1:
                     raise JckError(f"swd: class {c} has {mine.shape[0]} samples and {theirs.shape[0]} training pictures")
                 r = metric(u8[mine[:k].to(u8.device)].contiguous(), t[theirs[:k]].to(self.engine.device).contiguous(), seed=seed, **kw)
+                r.update(n=k)
+                out["per_class"][int(c)] = r
+        return out
+
+    def spectrum(self, train_u8, n=8192, seed=0, labels=None, train_labels=None, truncation=None, classes=None, **kw):
+        """Power spectra of the samples against the training set's (hipgan.spectrum, metrics.spectrum / spectrum_report):
+        the radial profiles' gap in dB per bin, the lattice peaks that stride-2 transposed convolutions leave (checkerboard_db), and
+        how well a linear rule on the profile tells the sets apart (separability).  The samples and the training pictures are taken
+        exactly as `swd` takes them: n images from latents(n, seed, truncation) with bn="running" (labels: a CGAN's class ids [n] or
+        one-hot rows), a chunk at a time, kept as uint8 on the device; the first n training pictures (uint8 NHWC, 32 x 32 data upscaled
+        as `neighbours` does) after numpy.random.default_rng(seed).permutation.  kw goes to metrics.spectrum (plane, window, chunk; the
+        mean planes are always formed) -> the report dict plus "n", "n_train", "seed" and, with classes (ids; needs labels and
+        train_labels), "per_class": {id: the same report for that class's samples and training pictures, as many of each as the smaller
+        side has, "n" among its keys}."""
+        import numpy as np
+
+        from metrics import spectrum as metric
+        from metrics import spectrum_report
+        from .probe import _to_size
+        n = int(n)
+        if n < 1:
+            raise JckError(f"spectrum: n = {n} must be >= 1")
+        t = _to_size(train_u8, self.engine.size, "training images")
+        if t.shape[0] < n:
+            raise JckError(f"spectrum: {t.shape[0]} training pictures are fewer than the n = {n} samples they are compared with")
+        kw = {**kw, "mean2d": True}
+        order = np.random.default_rng(int(seed)).permutation(int(t.shape[0]))
+        pick = torch.from_numpy(order[:n])
+        z = latents(n, seed, truncation)
+        lab = self._labels(labels, n)
+        step = max(self.engine.batch, 1024)
+        u8 = torch.cat([self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step]) for lo in range(0, n, step)])
+        real = t[pick].to(self.engine.device).contiguous()
+        out = spectrum_report(metric(u8, **kw), metric(real, **kw))
+        out.update(n=n, n_train=int(t.shape[0]), seed=int(seed))
+        if classes is not None:
+            if lab is None or train_labels is None:
+                raise JckError("spectrum: per-class reports need the samples' labels and train_labels")
+            ids = lab.argmax(1)
+            tl = torch.as_tensor(train_labels).cpu().view(-1).to(torch.int64)[torch.from_numpy(order)]
+            out["per_class"] = {}
+            for c in classes:
+                mine, theirs = torch.nonzero(ids.cpu() == int(c)).view(-1), torch.from_numpy(order)[tl == int(c)]
+                k = min(int(mine.shape[0]), int(theirs.shape[0]))
+                if k < 1:
+                    raise JckError(f"spectrum: class {c} has {mine.shape[0]} samples and {theirs.shape[0]} training pictures")
+                r = spectrum_report(metric(u8[mine[:k].to(u8.device)].contiguous(), **kw), metric(t[theirs[:k]].to(self.engine.device).contiguous(), **kw))
                 r.update(n=k)
                 out["per_class"][int(c)] = r
         return out

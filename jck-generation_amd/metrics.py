@@ -508,6 +508,59 @@ def swd(a, b, levels=None, patches=128, dirs=128, repeats=4, seed=0, chunk=None)
     return H.report(per_repeat, S)
 
 
+# ---- power spectra of pictures (csrc/spectrum.hip; the definition: DESIGN.md 5.18) -----------------------------------------------------
+SPECTRUM_CHUNK = 4096   # pictures per launch of the device path: bounds the uint8 staging of host pictures; the derived bound of the mean
+#                         plane counts on at most 2^12 pictures a launch
+
+
+def spectrum(x, plane="luma", window=None, mean2d=False, chunk=None):
+    """Power spectra of uint8 NHWC pictures [n,S,S,3], S in (32, 64, 128), n >= 0 -> {"profile" fp64 [n][R] (the azimuthally averaged
+    power per radial bin, byte levels squared; R = 24 / 46 / 92), "mean" fp64 [n] (the plane's mean in byte levels), "radius" [R],
+    "count" [R], "mean2d" fp64 [S][S] (the mean power plane; None unless asked for), "S", "plane", "window"}.  plane: "r", "g", "b",
+    "luma" (or 0..3); window: None or "hann" (periodic; removes the leakage of the picture's borders).  A CUDA tensor runs
+    jck_spectrum_u8, `chunk` pictures (None: SPECTRUM_CHUNK) a launch - profiles are bit-equal whatever the chunking, the chunks' plane
+    sums add on the host in chunk order; anything else runs numpy fp64 (hipgan.spectrum.host_spectrum)."""
+    from hipgan import spectrum as H
+    x = x if torch.is_tensor(x) else np.asarray(x)
+    if x.ndim != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2] or x.shape[1] not in H.SIZES:
+        raise ValueError(f"spectrum: x must be uint8 [n,S,S,3] with S in {H.SIZES}, got {tuple(x.shape)}")
+    if x.dtype not in (torch.uint8, np.uint8):
+        raise ValueError(f"spectrum: x must be uint8, got {x.dtype} {tuple(x.shape)}")
+    pl, window = H.plane_index(plane), H.check_window(window)
+    step = SPECTRUM_CHUNK if chunk is None else int(chunk)
+    if step < 1:
+        raise ValueError(f"spectrum: chunk = {step} must be >= 1")
+    n, S = int(x.shape[0]), int(x.shape[1])
+    dev = _pair_device(x)
+    if dev is None:
+        return H.host_spectrum(_host(x), pl, window, bool(mean2d), step)
+    from hipgan._lib import cur_stream, lib, load_library
+    R = H.bins(S)
+    w, W = H.window_table(S, window)
+    w_t = None if w is None else torch.from_numpy(w).to(dev)
+    prof, mean = torch.empty(n, R, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    total = np.zeros((S, S))
+    ws_bytes = load_library().jck_spectrum_ws_bytes(min(step, n), S, 1) if mean2d else 0
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+    plane_t = torch.empty(S, S, dtype=torch.float64, device=dev) if mean2d else None
+    with torch.cuda.device(dev):
+        for lo in range(0, n, step):
+            xs = x[lo:lo + step].detach().contiguous()
+            k = int(xs.shape[0])
+            lib.jck_spectrum_u8(xs, k, S, pl, w_t, float(W), prof[lo:lo + k], mean[lo:lo + k], plane_t, ws if mean2d else None, ws_bytes, cur_stream())
+            if mean2d:                                                             # one chunk: the kernel's plane as it is
+                total = plane_t.cpu().numpy() if k == n else total + k * plane_t.cpu().numpy()
+    return H.result(prof.cpu().numpy(), mean.cpu().numpy(), S, pl, window, (total if n <= step else total / n) if mean2d else None)
+
+
+def spectrum_report(a, b):
+    """two spectrum() dicts (a: samples, b: training pictures; their n may differ) -> the report of hipgan.spectrum.report: per radial bin
+    mean_db / std_db of both sets, gap_db, z; rms_gap_db, high_gap_db, worst; with both mean planes the 15 lattice peaks and
+    checkerboard_db; separability"""
+    from hipgan.spectrum import report
+    return report(a, b)
+
+
 def _scalar(v):
     v = v.detach().cpu().numpy() if torch.is_tensor(v) else v
     return float(np.asarray(v, dtype=np.float64).reshape(-1)[0])
