@@ -28,75 +28,31 @@ import sys
 import numpy as np
 import torch
 
+from evalcli import add_common_options, check_common, load_u8, open_run, split_key  # noqa: F401  (split_key: part of this module's interface)
+
 PAIRS_A_ROW = 4
 COMPARE_CHUNK = 4096
-
-
-def split_key(spec):
-    """'file.npz:key' -> (file.npz, key); the key is `images` when none is given"""
-    path, sep, key = spec.rpartition(":")
-    if sep and path and key and not key.endswith(".npz") and "/" not in key and "\\" not in key:
-        return path, key
-    return spec, "images"
 
 
 def get_arg_parse(argv=None):
     p = argparse.ArgumentParser(description="sample diversity (MS-SSIM of random pairs) of a trained DCGAN / CGAN generator; SSIM / PSNR of two files",
                                 formatter_class=argparse.RawDescriptionHelpFormatter, epilog=__doc__)
-    p.add_argument("-m", "--model", choices=["DCGAN", "CGAN"], default="DCGAN")
-    p.add_argument("--checkpoint", default=None, help="a checkpoint written by the trainers (or the reference's)")
-    p.add_argument("--compare", nargs=2, default=None, metavar=("A.npz[:key]", "B.npz[:key]"), help="score row i of A against row i of B")
-    p.add_argument("--train", default=None, metavar="TRAIN.npz", help="the training pictures: uint8 `images` [N,S,S,3] (and `labels`)")
-    p.add_argument("--num", type=int, default=2000, help="samples")
+    add_common_options(p, 2000, "samples", compare_help="score row i of A against row i of B",
+                       classes_help="CGAN: comma-separated class ids, cycled over the samples")
     p.add_argument("--pairs", type=int, default=1000, help="random pairs (per class)")
-    p.add_argument("--classes", default=None, help="CGAN: comma-separated class ids, cycled over the samples")
     p.add_argument("--levels", type=int, default=None, help="MS-SSIM levels, 1..4 (default: by the picture size)")
     p.add_argument("--top", type=int, default=16, help="most similar pairs on the sheet")
-    p.add_argument("--out", required=True, help="output directory")
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--which", choices=["auto", "live", "ema"], default="auto")
-    p.add_argument("-b", "--batch_size", type=int, default=64, help="images per launch sequence")
-    p.add_argument("--truncation", type=float, default=None, help="draw z from a normal truncated to [-T, T]")
-    p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     a = p.parse_args(argv)
     if a.levels is not None and not 1 <= a.levels <= 4:
         p.error("--levels must lie in 1..4")
+    check_common(p, a, num_min=2)
     if a.compare:
-        if a.checkpoint or a.train or a.classes:
-            p.error("--compare scores two files: --checkpoint, --train and --classes do not go with it")
-        a.compare = [split_key(s) for s in a.compare]
         return a
-    if not a.checkpoint:
-        p.error("--checkpoint is required (or --compare A.npz B.npz)")
-    if a.num < 2 or a.pairs < 1 or a.top < 0 or a.batch_size < 1:
-        p.error("--num must be >= 2, --pairs >= 1, --top >= 0, -b >= 1")
-    if a.truncation is not None and not a.truncation > 0:
-        p.error("--truncation must be > 0")
-    if a.classes is not None:
-        if a.model != "CGAN":
-            p.error("--classes goes with -m CGAN")
-        try:
-            a.classes = [int(c) for c in a.classes.split(",")]
-        except ValueError:
-            p.error("--classes takes comma-separated integers")
-        if not a.classes or min(a.classes) < 0 or max(a.classes) > 99:
-            p.error("--classes must lie in 0..99")
-    elif a.model == "CGAN" and not a.train:
+    if a.pairs < 1 or a.top < 0:
+        p.error("--pairs must be >= 1, --top >= 0")
+    if a.classes is None and a.model == "CGAN" and not a.train:
         p.error("a CGAN's samples take their classes from --classes or from the `labels` of --train")
-    # to generate.check_checkpoint this is a plain sampling run without a discriminator
-    a.mode, a.score, a.select, a.refine, a.space = "sample", False, None, None, None
     return a
-
-
-def load_u8(path, key):
-    from hipgan._lib import JckError
-    with np.load(path) as f:
-        if key not in f.files:
-            raise JckError(f"{path}: no '{key}' array (found {sorted(f.files)})")
-        x = f[key]
-    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2] or x.shape[0] < 1 or not 11 <= x.shape[1] <= 128:
-        raise JckError(f"{path}: '{key}' must be uint8 [n,S,S,3] with 11 <= S <= 128, got {x.dtype} {tuple(x.shape)}")
-    return np.ascontiguousarray(x)
 
 
 def run_compare(args):
@@ -104,7 +60,7 @@ def run_compare(args):
     from generate import write_outputs
     from hipgan._lib import JckError
     (pa, ka), (pb, kb) = args.compare
-    a, b = load_u8(pa, ka), load_u8(pb, kb)
+    a, b = load_u8(pa, ka, range(11, 129)), load_u8(pb, kb, range(11, 129))
     if a.shape != b.shape:
         raise JckError(f"--compare: {pa} holds {a.shape}, {pb} holds {b.shape}")
     on_dev = torch.cuda.is_available()
@@ -134,18 +90,8 @@ def main(argv=None):
     args = get_arg_parse(argv)
     if args.compare:
         return run_compare(args)
-    from generate import check_checkpoint, write_outputs
-    from hipgan.probe import load_images
-    from hipgan.sampler import Sampler
-    from modes import sample_classes
-    train_u8, train_labels = load_images(args.train) if args.train else (None, None)      # a bad file ends the run before a checkpoint is read
-    if args.classes:
-        cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(args.num)])
-    else:
-        cls = sample_classes(args, train_labels, args.num)
-    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
-    check_checkpoint(args, ckpt)
-    s = Sampler.from_checkpoint(ckpt, args.model, which=args.which, prec=args.prec, batch=args.batch_size)
+    from generate import write_outputs
+    s, train_u8, train_labels, cls = open_run(args, False)
     r = s.diversity(args.num, pairs=args.pairs, seed=args.seed, labels=cls, train_u8=train_u8, train_labels=train_labels, levels=args.levels,
                     truncation=args.truncation, top=args.top)
     group = lambda pr: pr["group"] if pr["group"] is not None else np.zeros(pr["i"].shape[0], np.int64)

@@ -568,10 +568,7 @@ class Sampler:
         if n < 2:
             raise JckError(f"diversity: n = {n} must be >= 2")
         L = default_levels(self.engine.size) if levels is None else int(levels)
-        z = latents(n, seed, truncation)
-        lab = self._labels(labels, n)
-        step = max(self.engine.batch, 1024)
-        u8 = torch.cat([self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step]) for lo in range(0, n, step)])
+        z, lab, u8 = self._draw_u8(n, seed, truncation, labels)
         ids = None if lab is None else lab.argmax(1).numpy()
         out = pair_diversity(u8, pairs, seed, ids, L)
         out.update(levels=L, images=u8, z=z.numpy(), top=top_pairs(out["ms_ssim"], top))
@@ -582,6 +579,51 @@ class Sampler:
             out["comparison"] = compare(out["summary"]["ms_ssim"], out["train"]["summary"]["ms_ssim"])
         return out
 
+    def _draw_u8(self, n, seed, truncation, labels):
+        """(z fp32 [n,100], the one-hot labels or None, uint8 [n,S,S,3] on the device): n images from latents(n, seed, truncation) with
+        bn="running", drawn a chunk at a time"""
+        z = latents(n, seed, truncation)
+        lab = self._labels(labels, n)
+        step = max(self.engine.batch, 1024)
+        u8 = torch.cat([self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step]) for lo in range(0, n, step)])
+        return z, lab, u8
+
+    def _against_training(self, what, train_u8, n, seed, labels, train_labels, truncation, classes, compare):
+        """The samples-against-training-set driver of `swd` and `spectrum`: n images from _draw_u8 against the first n training pictures
+        (uint8 NHWC, 32 x 32 data upscaled as `neighbours` does) after numpy.random.default_rng(seed).permutation, both uint8 on the
+        device.  compare(samples, training pictures) -> the report dict, to which "n", "n_train" and "seed" are added and, with classes
+        (ids; needs labels and train_labels), "per_class": {id: compare's dict for the samples and the training pictures of that class,
+        as many of each as the smaller side has, "n" among its keys}."""
+        import numpy as np
+
+        from .probe import _to_size
+        n = int(n)
+        if n < 1:
+            raise JckError(f"{what}: n = {n} must be >= 1")
+        t = _to_size(train_u8, self.engine.size, "training images")
+        if t.shape[0] < n:
+            raise JckError(f"{what}: {t.shape[0]} training pictures are fewer than the n = {n} samples they are compared with")
+        order = np.random.default_rng(int(seed)).permutation(int(t.shape[0]))
+        pick = torch.from_numpy(order[:n])
+        _, lab, u8 = self._draw_u8(n, seed, truncation, labels)
+        out = compare(u8, t[pick].to(self.engine.device).contiguous())
+        out.update(n=n, n_train=int(t.shape[0]), seed=int(seed))
+        if classes is not None:
+            if lab is None or train_labels is None:
+                raise JckError(f"{what}: per-class reports need the samples' labels and train_labels")
+            ids = lab.argmax(1)
+            tl = torch.as_tensor(train_labels).cpu().view(-1).to(torch.int64)[torch.from_numpy(order)]
+            out["per_class"] = {}
+            for c in classes:
+                mine, theirs = torch.nonzero(ids.cpu() == int(c)).view(-1), torch.from_numpy(order)[tl == int(c)]
+                k = min(int(mine.shape[0]), int(theirs.shape[0]))
+                if k < 1:
+                    raise JckError(f"{what}: class {c} has {mine.shape[0]} samples and {theirs.shape[0]} training pictures")
+                r = compare(u8[mine[:k].to(u8.device)].contiguous(), t[theirs[:k]].to(self.engine.device).contiguous())
+                r.update(n=k)
+                out["per_class"][int(c)] = r
+        return out
+
     def swd(self, train_u8, n=8192, seed=0, labels=None, train_labels=None, truncation=None, classes=None, **kw):
         """Sliced Wasserstein distance of the samples' Laplacian-pyramid patch statistics to the training set's, level by level
         (hipgan.swd, metrics.swd; no metric network).  n images are drawn from latents(n, seed, truncation) with bn="running" (labels:
@@ -590,40 +632,9 @@ class Sampler:
         goes to metrics.swd (levels, patches, dirs, repeats, chunk) -> its dict ("swd" x 1e3 per level, "mean", "sides", "per_repeat")
         plus "n", "n_train", "seed" and, with classes (ids; needs labels and train_labels), "per_class": {id: the same dict for the
         samples and the training pictures of that class, as many of each as the smaller side has, "n" among its keys}."""
-        import numpy as np
-
         from metrics import swd as metric
-        from .probe import _to_size
-        n = int(n)
-        if n < 1:
-            raise JckError(f"swd: n = {n} must be >= 1")
-        t = _to_size(train_u8, self.engine.size, "training images")
-        if t.shape[0] < n:
-            raise JckError(f"swd: {t.shape[0]} training pictures are fewer than the n = {n} samples they are compared with")
-        order = np.random.default_rng(int(seed)).permutation(int(t.shape[0]))
-        pick = torch.from_numpy(order[:n])
-        z = latents(n, seed, truncation)
-        lab = self._labels(labels, n)
-        step = max(self.engine.batch, 1024)
-        u8 = torch.cat([self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step]) for lo in range(0, n, step)])
-        real = t[pick].to(self.engine.device).contiguous()
-        out = metric(u8, real, seed=seed, **kw)
-        out.update(n=n, n_train=int(t.shape[0]), seed=int(seed))
-        if classes is not None:
-            if lab is None or train_labels is None:
-                raise JckError("swd: per-class reports need the samples' labels and train_labels")
-            ids = lab.argmax(1)
-            tl = torch.as_tensor(train_labels).cpu().view(-1).to(torch.int64)[torch.from_numpy(order)]
-            out["per_class"] = {}
-            for c in classes:
-                mine, theirs = torch.nonzero(ids.cpu() == int(c)).view(-1), torch.from_numpy(order)[tl == int(c)]
-                k = min(int(mine.shape[0]), int(theirs.shape[0]))
-                if k < 1:
-                    raise JckError(f"swd: class {c} has {mine.shape[0]} samples and {theirs.shape[0]} training pictures")
-                r = metric(u8[mine[:k].to(u8.device)].contiguous(), t[theirs[:k]].to(self.engine.device).contiguous(), seed=seed, **kw)
-                r.update(n=k)
-                out["per_class"][int(c)] = r
-        return out
+        return self._against_training("swd", train_u8, n, seed, labels, train_labels, truncation, classes,
+                                      lambda a, b: metric(a, b, seed=seed, **kw))
 
     def spectrum(self, train_u8, n=8192, seed=0, labels=None, train_labels=None, truncation=None, classes=None, **kw):
         """Power spectra of the samples against the training set's (hipgan.spectrum, metrics.spectrum / spectrum_report):
@@ -635,42 +646,11 @@ class Sampler:
         mean planes are always formed) -> the report dict plus "n", "n_train", "seed" and, with classes (ids; needs labels and
         train_labels), "per_class": {id: the same report for that class's samples and training pictures, as many of each as the smaller
         side has, "n" among its keys}."""
-        import numpy as np
-
         from metrics import spectrum as metric
         from metrics import spectrum_report
-        from .probe import _to_size
-        n = int(n)
-        if n < 1:
-            raise JckError(f"spectrum: n = {n} must be >= 1")
-        t = _to_size(train_u8, self.engine.size, "training images")
-        if t.shape[0] < n:
-            raise JckError(f"spectrum: {t.shape[0]} training pictures are fewer than the n = {n} samples they are compared with")
         kw = {**kw, "mean2d": True}
-        order = np.random.default_rng(int(seed)).permutation(int(t.shape[0]))
-        pick = torch.from_numpy(order[:n])
-        z = latents(n, seed, truncation)
-        lab = self._labels(labels, n)
-        step = max(self.engine.batch, 1024)
-        u8 = torch.cat([self.from_latents(z[lo:lo + step], None if lab is None else lab[lo:lo + step]) for lo in range(0, n, step)])
-        real = t[pick].to(self.engine.device).contiguous()
-        out = spectrum_report(metric(u8, **kw), metric(real, **kw))
-        out.update(n=n, n_train=int(t.shape[0]), seed=int(seed))
-        if classes is not None:
-            if lab is None or train_labels is None:
-                raise JckError("spectrum: per-class reports need the samples' labels and train_labels")
-            ids = lab.argmax(1)
-            tl = torch.as_tensor(train_labels).cpu().view(-1).to(torch.int64)[torch.from_numpy(order)]
-            out["per_class"] = {}
-            for c in classes:
-                mine, theirs = torch.nonzero(ids.cpu() == int(c)).view(-1), torch.from_numpy(order)[tl == int(c)]
-                k = min(int(mine.shape[0]), int(theirs.shape[0]))
-                if k < 1:
-                    raise JckError(f"spectrum: class {c} has {mine.shape[0]} samples and {theirs.shape[0]} training pictures")
-                r = spectrum_report(metric(u8[mine[:k].to(u8.device)].contiguous(), **kw), metric(t[theirs[:k]].to(self.engine.device).contiguous(), **kw))
-                r.update(n=k)
-                out["per_class"][int(c)] = r
-        return out
+        return self._against_training("spectrum", train_u8, n, seed, labels, train_labels, truncation, classes,
+                                      lambda a, b: spectrum_report(metric(a, **kw), metric(b, **kw)))
 
     def calibrate(self, batches, seed=0):
         """`batches` train-mode sampling batches (full engine batches of fresh z, uniform random classes for a CGAN) through the

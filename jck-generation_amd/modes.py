@@ -28,29 +28,23 @@ import sys
 import numpy as np
 import torch
 
+import evalcli
+
 SHEET_ROWS, SHEET_SIDE = 16, 8
 
 
 def get_arg_parse(argv=None):
     p = argparse.ArgumentParser(description="mode coverage of a trained DCGAN / CGAN generator", formatter_class=argparse.RawDescriptionHelpFormatter,
                                 epilog=__doc__)
-    p.add_argument("-m", "--model", choices=["DCGAN", "CGAN"], default="DCGAN")
-    p.add_argument("--checkpoint", required=True, help="a checkpoint written by the trainers (or the reference's)")
-    p.add_argument("--train", required=True, metavar="TRAIN.npz", help="the training pictures: uint8 `images` [N,S,S,3]")
+    evalcli.add_common_options(p, 10000, "samples (0 with --labels_out: cluster only)", train_help="the training pictures: uint8 `images` [N,S,S,3]",
+                               train_required=True)
     p.add_argument("--k", type=int, default=100, help="clusters, 1..1024")
-    p.add_argument("--num", type=int, default=10000, help="samples (0 with --labels_out: cluster only)")
-    p.add_argument("--out", required=True, help="output directory")
     p.add_argument("--space", choices=["d", "pixel"], default="d", help="the discriminator's features, or pixels")
     p.add_argument("--grid", type=int, choices=[1, 2, 4], default=4, help="--space d: the pooling raster")
     p.add_argument("--pool", choices=["max", "mean"], default="max", help="--space d")
-    p.add_argument("--seed", type=int, default=0)
     p.add_argument("--iters", type=int, default=50, help="Lloyd updates at most")
-    p.add_argument("--which", choices=["auto", "live", "ema"], default="auto")
-    p.add_argument("-b", "--batch_size", type=int, default=64, help="images per launch sequence")
-    p.add_argument("--truncation", type=float, default=None, help="draw z from a normal truncated to [-T, T]")
     p.add_argument("--min_count", type=int, default=1, help="samples a cluster needs to count as covered")
     p.add_argument("--labels_out", default=None, metavar="FILE.npz", help="the training pictures with their cluster ids as `labels`")
-    p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     a = p.parse_args(argv)
     if not 1 <= a.k <= 1024:
         p.error("--k must lie in 1..1024")
@@ -60,11 +54,7 @@ def get_arg_parse(argv=None):
         p.error("--num must be >= 1 (0 only with --labels_out: cluster and stop)")
     if a.iters < 0 or a.min_count < 1 or a.batch_size < 1:
         p.error("--iters must be >= 0, --min_count >= 1, -b >= 1")
-    if a.truncation is not None and not a.truncation > 0:
-        p.error("--truncation must be > 0")
-    # to generate.check_checkpoint this is a plain sampling run whose --space says whether the discriminator is needed
-    a.mode, a.score, a.select, a.refine = "sample", False, None, None
-    return a
+    return evalcli.check_common(p, a, train_required=True, num_min=0)
 
 
 def write_labels(path, images_u8, labels):
@@ -75,16 +65,10 @@ def write_labels(path, images_u8, labels):
     return path
 
 
-def sample_classes(args, train_labels, n):
-    """class ids [n] of a CGAN's samples (None for a DCGAN): drawn with the seed from the training file's labels"""
+def check_k(args, train_u8):
     from hipgan._lib import JckError
-    if args.model != "CGAN":
-        return None
-    if train_labels is None:
-        raise JckError(f"{args.train} has no 'labels' array: a CGAN's samples take their classes from it")
-    if train_labels.min() < 0 or train_labels.max() > 99:
-        raise JckError(f"{args.train}: 'labels' must lie in 0..99")
-    return torch.as_tensor(train_labels[np.random.default_rng(args.seed + 1).integers(0, train_labels.shape[0], size=n)])
+    if args.k > train_u8.shape[0]:
+        raise JckError(f"--k {args.k} clusters of the {train_u8.shape[0]} pictures of {args.train}")
 
 
 def least_covered(r, rows=SHEET_ROWS):
@@ -124,17 +108,8 @@ def sheet(s, train_u8, r, cls):
 
 def main(argv=None):
     args = get_arg_parse(argv)
-    from generate import check_checkpoint, write_outputs
-    from hipgan._lib import JckError
-    from hipgan.probe import load_images
-    from hipgan.sampler import Sampler
-    train_u8, train_labels = load_images(args.train)              # a bad file ends the run before a checkpoint is read
-    if args.k > train_u8.shape[0]:
-        raise JckError(f"--k {args.k} clusters of the {train_u8.shape[0]} pictures of {args.train}")
-    cls = sample_classes(args, train_labels, args.num) if args.num else None
-    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
-    check_checkpoint(args, ckpt)
-    s = Sampler.from_checkpoint(ckpt, args.model, which=args.which, prec=args.prec, batch=args.batch_size, **({"with_d": True} if args.space == "d" else {}))
+    from generate import write_outputs
+    s, train_u8, _, cls = evalcli.open_run(args, args.space == "d", check_train=lambda t: check_k(args, t))
     cl = s.cluster(train_u8, args.k, space=args.space, seed=args.seed, iters=args.iters, grid=args.grid, pool=args.pool)
     if args.labels_out:
         path = write_labels(args.labels_out, train_u8.numpy(), cl["labels"].cpu().numpy())

@@ -26,58 +26,25 @@ swd.npz of A against B.  Where there is a GPU the run goes through the kernels (
 import argparse
 import sys
 
-import numpy as np
-import torch
+import evalcli
 
 
 def get_arg_parse(argv=None):
-    from diversity import split_key
     p = argparse.ArgumentParser(description="sliced Wasserstein distance on Laplacian-pyramid patches: a trained DCGAN / CGAN generator against its "
                                             "training set, or two picture files", formatter_class=argparse.RawDescriptionHelpFormatter, epilog=__doc__)
-    p.add_argument("-m", "--model", choices=["DCGAN", "CGAN"], default="DCGAN")
-    p.add_argument("--checkpoint", default=None, help="a checkpoint written by the trainers (or the reference's)")
-    p.add_argument("--compare", nargs=2, default=None, metavar=("A.npz[:key]", "B.npz[:key]"), help="the pictures of A against those of B")
-    p.add_argument("--train", default=None, metavar="TRAIN.npz", help="the training pictures: uint8 `images` [N,S,S,3] (and `labels`)")
-    p.add_argument("--num", type=int, default=8192, help="samples, and training pictures they are compared with")
-    p.add_argument("--classes", default=None, help="CGAN: comma-separated class ids, cycled over the samples; one report per class plus the pooled one")
+    evalcli.add_common_options(p, 8192, "samples, and training pictures they are compared with", train_required=True,
+                               compare_help="the pictures of A against those of B",
+                               classes_help="CGAN: comma-separated class ids, cycled over the samples; one report per class plus the pooled one")
     p.add_argument("--levels", type=int, default=None, help="pyramid levels, finest first (default: every level down to 16 x 16)")
     p.add_argument("--patches", type=int, default=128, help="7 x 7 patches per picture and level")
     p.add_argument("--dirs", type=int, default=128, help="directions per repeat")
     p.add_argument("--repeats", type=int, default=4, help="repeats (fresh directions each)")
-    p.add_argument("--out", required=True, help="output directory")
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--which", choices=["auto", "live", "ema"], default="auto")
-    p.add_argument("-b", "--batch_size", type=int, default=64, help="images per launch sequence")
-    p.add_argument("--truncation", type=float, default=None, help="draw z from a normal truncated to [-T, T]")
-    p.add_argument("--prec", choices=["bf16", "f32", "bf16x3"], default="bf16")
     a = p.parse_args(argv)
     if a.levels is not None and not 1 <= a.levels <= 4:
         p.error("--levels must lie in 1..4")
     if a.patches < 1 or a.dirs < 1 or a.repeats < 1:
         p.error("--patches, --dirs and --repeats must be >= 1")
-    if a.compare:
-        if a.checkpoint or a.train or a.classes:
-            p.error("--compare takes two files: --checkpoint, --train and --classes do not go with it")
-        a.compare = [split_key(s) for s in a.compare]
-        return a
-    if not a.checkpoint or not a.train:
-        p.error("--checkpoint and --train are required (or --compare A.npz B.npz)")
-    if a.num < 1 or a.batch_size < 1:
-        p.error("--num and -b must be >= 1")
-    if a.truncation is not None and not a.truncation > 0:
-        p.error("--truncation must be > 0")
-    if a.classes is not None:
-        if a.model != "CGAN":
-            p.error("--classes goes with -m CGAN")
-        try:
-            a.classes = [int(c) for c in a.classes.split(",")]
-        except ValueError:
-            p.error("--classes takes comma-separated integers")
-        if not a.classes or min(a.classes) < 0 or max(a.classes) > 99:
-            p.error("--classes must lie in 0..99")
-    # to generate.check_checkpoint this is a plain sampling run without a discriminator
-    a.mode, a.score, a.select, a.refine, a.space = "sample", False, None, None, None
-    return a
+    return evalcli.check_common(p, a, train_required=True)
 
 
 def settings_of(args):
@@ -85,33 +52,19 @@ def settings_of(args):
 
 
 def write(args, r, line):
-    from generate import write_outputs
     from hipgan.swd import format_report, to_json
-    record = {**to_json(r), "settings": settings_of(args), "seed": args.seed}
-    arrays = {"per_repeat": r["per_repeat"]}
-    if "per_class" in r:
-        record["per_class"] = {str(c): to_json(v) for c, v in r["per_class"].items()}
-        arrays.update({f"per_repeat_{c}": v["per_repeat"] for c, v in r["per_class"].items()})
-    write_outputs(args.out, "swd.npz", arrays, record=("swd.json", record))
-    print(f"swd: {format_report(r)} ({line}) -> {args.out}/swd.json, swd.npz")
-    return 0
+    return evalcli.write_report(args, r, line, "swd", to_json, lambda v, suffix: {f"per_repeat{suffix}": v["per_repeat"]}, format_report,
+                                extra={"settings": settings_of(args), "seed": args.seed})
 
 
 def run_compare(args):
+    import torch
+
     import metrics
     from hipgan._lib import JckError
     from hipgan.swd import SIZES
     (pa, ka), (pb, kb) = args.compare
-    sets = []
-    for path, key in ((pa, ka), (pb, kb)):
-        with np.load(path) as f:
-            if key not in f.files:
-                raise JckError(f"{path}: no '{key}' array (found {sorted(f.files)})")
-            x = f[key]
-        if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2] or x.shape[0] < 1 or x.shape[1] not in SIZES:
-            raise JckError(f"{path}: '{key}' must be uint8 [n,S,S,3] with S in {SIZES}, got {x.dtype} {tuple(x.shape)}")
-        sets.append(np.ascontiguousarray(x))
-    a, b = sets
+    a, b = evalcli.load_u8(pa, ka, SIZES), evalcli.load_u8(pb, kb, SIZES)
     if a.shape != b.shape:
         raise JckError(f"--compare: {pa} holds {a.shape}, {pb} holds {b.shape}")
     if torch.cuda.is_available():
@@ -125,18 +78,7 @@ def main(argv=None):
     args = get_arg_parse(argv)
     if args.compare:
         return run_compare(args)
-    from generate import check_checkpoint
-    from hipgan.probe import load_images
-    from hipgan.sampler import Sampler
-    from modes import sample_classes
-    train_u8, train_labels = load_images(args.train)                     # a bad file ends the run before a checkpoint is read
-    if args.classes:
-        cls = torch.tensor([args.classes[k % len(args.classes)] for k in range(args.num)])
-    else:
-        cls = sample_classes(args, train_labels, args.num)
-    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
-    check_checkpoint(args, ckpt)
-    s = Sampler.from_checkpoint(ckpt, args.model, which=args.which, prec=args.prec, batch=args.batch_size)
+    s, train_u8, train_labels, cls = evalcli.open_run(args, False)
     r = s.swd(train_u8, n=args.num, seed=args.seed, labels=cls, train_labels=train_labels if args.classes else None, truncation=args.truncation,
               classes=args.classes, levels=args.levels, **settings_of(args))
     return write(args, r, f"{r['n']} samples against {r['n']} of {r['n_train']} training pictures")

@@ -161,8 +161,8 @@ def test_coverage_against_values_worked_out_by_hand():
     assert abs(got["expected_covered"] - want["expected_covered"]) <= 1e-12
 
 
-def test_modes_parser_defaults_refusals_and_help(capsys):
-    import generate
+def test_modes_parser_defaults_refusals_and_help(capsys, tmp_path, monkeypatch):
+    import evalcli
     import modes
     from hipgan._lib import JckError
     base = ["--checkpoint", "c.pt", "--train", "t.npz", "--out", "o"]
@@ -184,14 +184,23 @@ def test_modes_parser_defaults_refusals_and_help(capsys):
     assert e.value.code == 0
     text = capsys.readouterr().out
     assert "--labels_out" in text and "modes.json" in text and "KL(samples || train)" in text
-    # the discriminator's feature space needs the checkpoint's discriminator; pixel space does not
+    # the discriminator's feature space needs the checkpoint's discriminator; pixel space does not: the run opener refuses the checkpoint
+    # before any engine exists (Sampler.from_checkpoint is stood in for: it needs a GPU)
+    from hipgan.sampler import Sampler
+    monkeypatch.setattr(Sampler, "from_checkpoint", classmethod(lambda cls, ckpt, model, with_d=False, **kw: ("sampler", with_d)))
+    np.savez(str(tmp_path / "t.npz"), images=np.zeros((4, 32, 32, 3), np.uint8))
     g_only = {"model_g": {"conv1.weight": torch.zeros(1)}}
+
+    def open_with(ckpt, extra=()):
+        torch.save(ckpt, str(tmp_path / "c.pt"))
+        a = modes.get_arg_parse(["--checkpoint", str(tmp_path / "c.pt"), "--train", str(tmp_path / "t.npz"), "--out", "o", "--k", "2"] + list(extra))
+        return evalcli.open_run(a, a.space == "d")[0]
     with pytest.raises(JckError):
-        generate.check_checkpoint(modes.get_arg_parse(base), g_only)
+        open_with(g_only)
     with pytest.raises(JckError):
-        generate.check_checkpoint(modes.get_arg_parse(base), {**g_only, "model_d": {}})
-    generate.check_checkpoint(modes.get_arg_parse(base + ["--space", "pixel"]), g_only)
-    generate.check_checkpoint(modes.get_arg_parse(base), {**g_only, "model_d": {"conv1.weight": torch.zeros(1)}})
+        open_with({**g_only, "model_d": {}})
+    assert open_with(g_only, ["--space", "pixel"]) == ("sampler", False)
+    assert open_with({**g_only, "model_d": {"conv1.weight": torch.zeros(1)}}) == ("sampler", True)
 
 
 def test_labels_file_loads_as_a_conditional_training_set(tmp_path):

@@ -185,14 +185,12 @@ def test_ssim_entry_points_check_their_arguments_on_the_host():
 
 def test_diversity_parser_defaults_refusals_and_help(capsys):
     import diversity
-    import generate
     base = ["--checkpoint", "c.pt", "--out", "o"]
     a = diversity.get_arg_parse(base)
     assert (a.model, a.num, a.pairs, a.top, a.seed, a.which, a.batch_size, a.prec) == ("DCGAN", 2000, 1000, 16, 0, "auto", 64, "bf16")
     assert a.levels is None and a.train is None and a.classes is None and a.compare is None and a.truncation is None
     a = diversity.get_arg_parse(base + ["-m", "CGAN", "--classes", "3,17,42", "--num", "200", "--pairs", "50", "--train", "t.npz", "--levels", "2"])
     assert (a.model, a.classes, a.num, a.pairs, a.train, a.levels) == ("CGAN", [3, 17, 42], 200, 50, "t.npz", 2)
-    generate.check_checkpoint(a, {"model_g": {"conv1.weight": torch.zeros(1)}})            # no discriminator is needed
     a = diversity.get_arg_parse(["--compare", "a.npz:recon", "dir.x/b.npz", "--out", "o"])
     assert a.compare == [("a.npz", "recon"), ("dir.x/b.npz", "images")]
     assert diversity.split_key("C:/x/a.npz") == ("C:/x/a.npz", "images") and diversity.split_key("a.npz:z") == ("a.npz", "z")
