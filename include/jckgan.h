@@ -507,7 +507,8 @@ int jck_engine_repack(jck_engine*, int net, void* stream);
  * [B,3,S,S] fp32 taken as they are, alpha [B] (CGAN: labels, drop_mask[2]).  Afterwards jck_engine_tensor("norms") holds the
  * per-image gradient norms - the penalty is mean((norm - 1)^2) - and, CGAN, D's gradient arena holds d(penalty)/d(theta_D)
  * (cleared first; lambda = 1): the double backward the reference obtains with create_graph=True, in closed form
- * (hipgan/functional.py: gradient_penalty). */
+ * (hipgan/functional.py: gradient_penalty).  It overwrites real_noisy: a PHASE_D_REAL_FWD enqueued ahead for the next step is
+ * waited for and abandoned first (jck_engine_drop_prefetch), and that step's D phase computes D(real) itself. */
 #define JCK_PHASE_GP_ONLY 10
 /* OR-ed into PHASE_D_LOSS / PHASE_D_GP (CGAN): the caller reads nothing of D's gradient arena before PHASE_D_STEP (no
  * all-reduce in between), so the phase need not wait for the weight-gradient stream before it returns.  PHASE_D_STEP then

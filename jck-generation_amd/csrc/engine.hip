@@ -1036,6 +1036,15 @@ static int phase_d_real_fwd(jck_engine* e, const PhaseCtx& c) {
   return JCK_OK;
 }
 
+// A PHASE_D_REAL_FWD already enqueued for the next step is abandoned: `st` waits for it where it ran on the weight-gradient stream
+// (it may still be reading D's packed operands and writing real_noisy there), and the next D phase computes D(real) itself.
+static int drop_prefetch(jck_engine* e, hipStream_t st) {
+  if (e->ss.real_fwd_step >= 0 && e->ss.pre_on_side && e->evReal) HIPCHK(hipStreamWaitEvent(st, e->evReal, 0));
+  e->ss.real_fwd_step = -1;
+  e->ss.pre_on_side = false;
+  return JCK_OK;
+}
+
 // The stand-alone gradient penalty of the module path (train/dcgan_trainer.py:110-127, train/cgan_trainer.py:114-131 called
 // outside this engine's step): real_nchw = real_data, noise_real = fake_data - both [B,3,S,S] fp32, taken as they are -, alpha
 // (CGAN: labels, drop_mask[2]).  Leaves the per-image gradient norms in "norms" (the caller forms mean((n - 1)^2)) and, CGAN
@@ -1045,6 +1054,9 @@ static int phase_gp_only(jck_engine* e, const PhaseCtx& c) {
   if (!c.in->real_nchw || !c.in->noise_real || !c.given->alpha) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY needs real_nchw (real), noise_real (fake) and alpha");
   if (e->capturing) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY: not inside a capture");
   if (c.cg && !c.given->drop_mask[2]) JCK_FAIL(JCK_E_ARG, "PHASE_GP_ONLY (CGAN) needs drop_mask[2]");
+  // a D(real) forward enqueued ahead of the next step owns real_noisy (and may still be writing it on the weight-gradient stream):
+  // it is abandoned before the first write here, and that step's D phase computes D(real) itself
+  JCK_TRY(drop_prefetch(e, c.st));
   HIPCHK(hipMemsetAsync(e->acc, 0, (size_t)8 * e->acc_ld * sizeof(float), c.st));
   HIPCHK(hipMemsetAsync(e->dg, 0, e->LD.n_params * sizeof(float), c.st));
   if (c.cg) HIPCHK(hipMemsetAsync(e->gw1p, 0, (size_t)L1_OUT * L1_KPAD * sizeof(float), c.st));
@@ -1371,15 +1383,11 @@ extern "C" int jck_engine_order_after_tail(jck_engine* e, void* stream) {
   HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->evTail, 0));
   return JCK_OK;
 }
-// A PHASE_D_REAL_FWD already enqueued for the next step is abandoned (its weights are about to change: a re-broadcast of the
-// replica guard, load_model): `stream` waits for it - it may still be reading D's packed operands on the weight-gradient stream -
-// and the next D phase computes D(real) itself.
+// drop_prefetch for a caller whose weights are about to change (a re-broadcast of the replica guard, load_model, another engine's
+// step on the same arenas): `stream`, the one the change is made on - NULL is the default stream, which waits like any other.
 extern "C" int jck_engine_drop_prefetch(jck_engine* e, void* stream) {
   if (!e || !e->bound) JCK_FAIL(JCK_E_ARG, "engine not bound");
-  if (e->ss.real_fwd_step >= 0 && e->ss.pre_on_side && e->evReal && stream) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->evReal, 0));
-  e->ss.real_fwd_step = -1;
-  e->ss.pre_on_side = false;
-  return JCK_OK;
+  return drop_prefetch(e, (hipStream_t)stream);
 }
 extern "C" long long jck_engine_grad_tail(const jck_engine* e, int net) {
   if (!e || !e->bound || net != 1 || e->family != 0 || e->batched != 3 || e->gp_bwd) return -1;

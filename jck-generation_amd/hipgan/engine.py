@@ -712,6 +712,11 @@ class DcganEngine(EngineInference):
         self._training_only("step_async")
         self._shared["d_loaded"] = True             # a trained discriminator is a discriminator to score with
         if self._packed_version != self._shared["version"]:
+            if getattr(self, "_prefetched_real", None) is not None:
+                # the weights moved through another engine on the same arenas (its step, its mark_weights_changed) after this one
+                # enqueued its next D(real) forward: that pass used the old operands, so it is abandoned before they are re-derived.
+                # self._prefetched_real stays until the check below: the announced batch is still this step's, which runs eagerly
+                lib.jck_engine_drop_prefetch(self._h, torch.cuda.current_stream().cuda_stream)
             self.join()
             self.repack()
         use_graph = (self.graphs if graph is None else graph) and self._eager_steps >= 1 and lr_g is None
@@ -866,8 +871,12 @@ class DcganEngine(EngineInference):
             keep.append(lab)
             si.labels = lab.data_ptr()
             si.drop_mask[2] = f32(drop_mask, B * 256, "drop_mask")
+        # A D(real) forward already enqueued for the next step (step_async(next_real=...)) is abandoned by the phase: it waits for it
+        # before it overwrites real_noisy, and the next step's D phase computes D(real) itself.  self._prefetched_real stays as it
+        # is: the announced batch is still the one the next step_async must be given, and that step still runs eagerly.
         lib.jck_engine_phase(self._h, PHASE_GP_ONLY, C.byref(si), torch.cuda.current_stream().cuda_stream)
-        self._keep = keep
+        # a slot of its own: self._keep holds what the step in flight still reads (and the module path calls this without ever stepping)
+        self._keep_gp = keep
         n = C.c_longlong()
         p = load_library().jck_engine_tensor(self._h, b"norms", C.byref(n))
         return self._ws_view(p, n.value, torch.float32)[:B]
